@@ -1,6 +1,7 @@
 """bench.py -- decode-steps/s of the caption-decoder hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N --steps K --warmup W] [--mode train|forward|greedy|beam] [--config cfg2] [--no-modes]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (`python bench.py --gpus N` with N > 1 and no WORLD_SIZE starts that torch.distributed.run line itself, as a child
 process, and relays rank 0's JSON line; `ranks_seen` in the line is what the probe all-reduce returned.)
@@ -14,8 +15,19 @@ per step and per GPU (weak scaling: every rank owns its own 64-sample shard, SUR
   --mode forward          Encoder.conv1 + teacher-forced forward only (validate(), no collective)
   --mode greedy           Encoder.conv1 + predict() greedy decode, KV-cached (eval.py path; cfg5)
   --mode beam             Encoder.conv1 + predict_beam() (beam 5, batch 32: north_star cfg5; parity-unpinned)
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both sides (max
-over ranks); blocks are repeated until 2 s of timed device work and the MEDIAN block is reported (`repeats`).
+Timing: W warm-up steps, then ONE block of EXACTLY K steps, bracketed by barrier + synchronize on both sides (max over
+ranks); ms_per_step = that block / K.  --min-seconds S repeats the K-step block until S s of timed work and reports the
+MEDIAN block (`repeats`).
+--dump-outputs DIR: after the timed block, rank 0 writes what the timed path returned in its LAST step as DIR/<name>.npy
+(floating arrays float32, integer ones float64; inputs are seeded, so equal arguments give equal inputs every run):
+  train    loss (the token-mean loss the step returns) and params (every decoder parameter after that step's update,
+           flattened in named_parameters() order)
+  forward  scores, captions (length-sorted), decode_lengths
+  greedy / beam  sequences (max_pred_len, B)
+The train outputs differ in their last bits from run to run (the backward pass's scatter-adds and column sums are float
+atomics, amplified by Adam) unless ICK_DETERMINISTIC=1 (bit-reproducible, slower).
+When the arrays exceed 64 MB in all, every array above 2M elements is replaced by <name>_sample.npy: the elements at
+2M fixed indices (torch.randperm with seed 0, sorted).
 Rank 0 prints ONE JSON line with the whole-job rate plus
   roofline      by_kernel: every kernel class of the step (launches per step, mean duration from HIP events on
                 the launch stream in an eager single-stream pass, algorithmic FLOP or bytes, fraction of the fp32
@@ -48,6 +60,8 @@ sys.path.insert(0, ROOT)
 # but the line says so (`in_step_stale` / `traffic_stale`).
 def _table(kind, mode, cfgname):
     return os.path.join(ROOT, "profiles", "r05_%s_%s_%s.json" % (kind, mode, cfgname))
+DUMP_BYTES = 64 << 20
+DUMP_SAMPLE = 2 << 20
 PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32, 64 FLOP/clk/SIMD
 PEAK_HBM_GBS = 8000.0
 BEAM = 5
@@ -73,7 +87,10 @@ def parse():
     ap.add_argument("--no-profile", action="store_true", help="skip the eager per-kernel pass (roofline.by_kernel)")
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--no-modes", action="store_true", help="headline only: skip the forward / greedy / beam / cfg4 legs")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the K-step block until this much timed work")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step block until this much timed work (default: one block of exactly K steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
 
 
@@ -292,8 +309,37 @@ class Workload:
         return bool(self.dec.use_hip_graphs and self.dec.__dict__.get("_graphs"))
 
 
-def run_workload(wl, steps, warmup, min_seconds, world, profile_steps, max_repeats=400):
-    """-> dict(ms_per_step, value, repeats, timed_region_s, graph, by_kernel)."""
+def step_outputs(wl, out):
+    """name -> host tensor: what a caller of the timed path holds after the step that returned `out`."""
+    if wl.mode == "train":
+        params = torch.cat([p.detach().reshape(-1) for _, p in wl.dec.named_parameters()])
+        return {"loss": out.detach().cpu(), "params": params.cpu()}
+    if wl.mode == "forward":
+        scores, captions, decode_lengths = out
+        return {"scores": scores.detach().cpu(), "captions": captions.cpu(), "decode_lengths": torch.tensor(decode_lengths)}
+    return {"sequences": out.cpu()}
+
+
+def dump_outputs(dirname, arrays):
+    """Write name -> tensor as dirname/<name>.npy: float32 (float64 stays float64), integers as float64; at most
+    DUMP_BYTES in all (above that, a fixed sample of every array with more than DUMP_SAMPLE elements)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.reshape(-1) if v.dim() == 0 else v for k, v in arrays.items()}
+    arrays = {k: v.double() if (not v.is_floating_point() or v.dtype == torch.float64) else v.float()
+              for k, v in arrays.items()}
+    if sum(v.numel() * v.element_size() for v in arrays.values()) > DUMP_BYTES:
+        for k in [k for k, v in arrays.items() if v.numel() > DUMP_SAMPLE]:
+            v = arrays.pop(k).reshape(-1)
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            arrays[k + "_sample"] = v[idx]
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v.numpy())
+
+
+def run_workload(wl, steps, warmup, min_seconds, world, profile_steps, max_repeats=400, dump_dir=None):
+    """-> dict(ms_per_step, value, repeats, timed_region_s, graph, by_kernel).  dump_dir: rank 0 writes the outputs of
+    the last timed step there (dump_outputs) before anything else runs on the device."""
     import torch.distributed as dist
     import ick_amd.profiling as prof
 
@@ -307,12 +353,14 @@ def run_workload(wl, steps, warmup, min_seconds, world, profile_steps, max_repea
         if wl.train_step is not None:
             wl.train_step.flush()          # (lazy_update) the last step's optimizer update
 
+    last = {}
+
     def block(step):
         flush()
         fence()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            last["out"] = step()
         flush()
         fence()
         dt = torch.tensor([time.perf_counter() - t0], device="cuda", dtype=torch.float64)
@@ -330,6 +378,9 @@ def run_workload(wl, steps, warmup, min_seconds, world, profile_steps, max_repea
         times.append(block(step))
     dt = statistics.median(times)
     graph = wl.graph_in_use()
+    if dump_dir is not None and wl.rank == 0:
+        # the graphs' output buffers are overwritten by the passes below: copy them out first
+        dump_outputs(dump_dir, step_outputs(wl, last["out"]))
     # The timed steps above find their batch in the graph's own input buffers (where a loader's host-to-device copy puts
     # it: eval.py / train.py do).  A caller that hands over OTHER device tensors pays a device-to-device copy of the
     # inputs in front of every replay (103 MB of features at B = 64): that number too, one block, not the headline.
@@ -436,7 +487,8 @@ def main():
 
     cfgname = args.config or ("cfg5" if args.mode in ("greedy", "beam") else "cfg2")
     wl = Workload(args.mode, cfgname, rank)
-    res = run_workload(wl, args.steps, args.warmup, args.min_seconds, world, 0 if args.no_profile else args.profile_steps)
+    res = run_workload(wl, args.steps, args.warmup, args.min_seconds, world, 0 if args.no_profile else args.profile_steps,
+                       dump_dir=args.dump_outputs)
     cfg, seed = wl.cfg, wl.seed
     B, L = cfg["B"], cfg["L"]
 

@@ -28,10 +28,10 @@ import ick_amd.synth as synth  # noqa: E402
 REF_DIRS = {"geo": "geo-aware", "knowledge": "knowledge-aware", "news": "news-knowledge-aware"}
 
 
-def load_reference(variant):
+def load_reference(variant, module_name=None):
     sys.modules.setdefault("torchvision", types.ModuleType("torchvision"))
     path = os.path.join("/root/reference", REF_DIRS[variant], "models.py")
-    spec = importlib.util.spec_from_file_location("ref_models_" + variant, path)
+    spec = importlib.util.spec_from_file_location(module_name or "ref_models_" + variant, path)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
@@ -268,9 +268,42 @@ def round4_cases():
     big_vocab_digest("digest_cfg2_b64", c["variant"], c["B"], c["L"], c["K"], c["V"], c["F"], seed=44, conv1=True)
 
 
+def checkpoint_case(variant, V=40):
+    """checkpoint_<variant>.pt: a whole-object checkpoint pickled by the REAL reference (utils.save_checkpoint's dict,
+    classes recorded as models.<Name>) plus the reference decoder's state_dict.  To keep the file a few KB, every
+    parameter and buffer is a one-element storage expanded to its full shape, holding its position in the state_dict
+    (1, 2, ...; a tensor two modules share -- the predicate embedding of the fact encoder -- keeps one number): shapes,
+    names, sharing and which tensor sits where survive the pickle, the values of the seeded weights do not (unpickling
+    does not look at them)."""
+    ref = load_reference(variant, "models")
+    saved = sys.modules.get("models")
+    sys.modules["models"] = ref                      # the reference pickles its classes as models.<Name>
+    try:
+        dec = ref.DecoderTransformer(word_map=synth.make_word_map(V), emb_dim=300, decoder_dim=512, encoder_dim=512,
+                                     num_heads=10, num_layers=3)
+        tensors = list({id(t): t for t in dec.state_dict(keep_vars=True).values()}.values())
+        for i, t in enumerate(tensors):
+            t.data = torch.full((1,) * t.dim(), float(i + 1), dtype=t.dtype).expand(t.shape)
+        opt = torch.optim.Adam(dec.parameters(), lr=4e-4)
+        state = {"epoch": 3, "epochs_since_improvement": 1, "loss": 2.5, "encoder": None, "decoder": dec,
+                 "encoder_optimizer": None, "decoder_optimizer": opt}
+        name = "checkpoint_" + variant
+        torch.save({"checkpoint": state, "state_dict": dec.state_dict()}, os.path.join(HERE, name + ".pt"))
+    finally:
+        if saved is None:
+            sys.modules.pop("models", None)
+        else:
+            sys.modules["models"] = saved
+    print("wrote", name, os.path.getsize(os.path.join(HERE, name + ".pt")), "bytes")
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     torch.set_num_threads(4)
+    if "--checkpoints" in sys.argv:
+        for v in synth.VARIANTS:
+            checkpoint_case(v)
+        sys.exit(0)
     if "--round4" in sys.argv:
         round4_cases()
         sys.exit(0)

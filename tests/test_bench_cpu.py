@@ -52,3 +52,26 @@ def test_main_routes_to_the_launcher_only_without_world_size():
     body = src[src.index("def main():"):]
     assert body.index('"WORLD_SIZE" not in os.environ and args.gpus > 1') < body.index("torch.cuda.set_device")
     assert "os.exec" not in src
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(monkeypatch, tmp_path):
+    """--dump-outputs: floating arrays as float32, integer ones as float64, whole while they fit the budget; above it a
+    fixed sample of every large array (the same elements every run)."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    loss, seq = torch.tensor([2.5]), torch.arange(12).view(3, 4)
+    big = torch.randn(5000, generator=torch.Generator().manual_seed(1))
+    bench.dump_outputs(str(tmp_path / "a"), {"loss": loss, "sequences": seq, "params": big})
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("loss", "sequences", "params")}
+    assert a["loss"].dtype == np.float32 and a["loss"].tolist() == [2.5]
+    assert a["sequences"].dtype == np.float64 and a["sequences"].shape == (3, 4)
+    assert np.array_equal(a["sequences"], seq.numpy()) and np.array_equal(a["params"], big.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"loss": loss, "params": big})
+    assert sorted(os.listdir(str(tmp_path / "b"))) == ["loss.npy", "params_sample.npy"]
+    b, c = (np.load(str(tmp_path / d / "params_sample.npy")) for d in ("b", "c"))
+    assert b.shape == (100,) and np.array_equal(b, c) and np.isin(b, big.numpy()).all()
