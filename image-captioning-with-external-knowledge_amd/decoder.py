@@ -14,6 +14,7 @@ in libick_amd.so (HIP, gfx950) through ops.py.  There is no CPU / PyTorch fallba
 """
 import math
 import os
+import struct
 
 import torch
 from torch import nn
@@ -1103,6 +1104,84 @@ class DecoderTransformer(nn.Module):
             res = self._predict_beam_device(enc_tok, entities, facts, max_pred_len, beam_size)
         out = res[0].t().contiguous()
         return (out, res[1], res[2], res[3]) if return_all else out
+
+    def _predict_sample_device(self, enc_tok, entities, facts, knobs, max_pred_len, n):
+        """Sampled decode on the fused decode kernels: R = B * n rows, the n samples of a caption share its cross K/V
+        and keep their own self-attention caches.  knobs: int64 (3) device tensor [seed, temperature | top_p << 32
+        (two fp32 words), top_k] -- read by the selection kernel, so a replay sees whatever was copied into it.
+        Returns (tokens (R, max_len), log-probabilities (R, max_len))."""
+        from . import lib as L
+        dev = enc_tok.device
+        V, K = self.vocab_size, entities.shape[1]
+        ee, fe, kv, _, side = self._encode_context(enc_tok, entities, facts, None)
+        side.join()
+        c, t = self._decode_ctx(kv, ee, fe, n, max_pred_len, kv.shape[3], want_scores=True)
+        log_prob = torch.zeros(c.R, max_pred_len, device=dev, dtype=torch.float32)
+        facts_r = facts.repeat_interleave(n, dim=0).contiguous() if self.has_facts else None
+        st = L.SampleState()
+        base = knobs.data_ptr()
+        st.seed, st.temp_top_p, st.top_k, st.log_prob = base, base + 8, base + 16, log_prob.data_ptr()
+        for i in range(max_pred_len):
+            if self.has_facts:
+                ops.context_indicators(t["cap_buf"], facts_r, K, V, self._pred_wt(), self.fc_predicate.bias.detach(),
+                                       mode=1, eib=t["eib"], gate=t["gate"])
+            ops.decode_layers(c, i)
+            ops.decode_select_sample(c, st, i)
+        return t["output"], log_prob
+
+    @torch.no_grad()
+    def predict_sample(self, encoder_out, max_pred_len, entities, facts=None, num_samples=1, temperature=1.0, top_k=0,
+                       top_p=1.0, seed=None, return_log_probs=False):
+        """Stochastic decode: `num_samples` captions per image drawn from the model's distribution, with temperature,
+        top-k and nucleus (top-p) truncation.  Per row and step over the V+K+F raw scores s: z = s / temperature;
+        top-k keeps s >= the k-th largest s (ties at the boundary all kept); top-p then keeps the tokens whose
+        strictly-greater mass (weights exp(z - max z) over the kept set) is < top_p of the kept mass; the token is
+        argmax(z + Gumbel noise) over the kept set, the noise drawn by Philox-4x32-10 from (seed, caption, sample, step,
+        column) -- so the samples of a caption do not depend on the rest of the batch (csrc/sample.hip).
+        The reference's repeated n-gram clean-up (a greedy heuristic on the runner-up token) is NOT applied: top_k=1 is
+        plain argmax decoding and differs from predict() wherever that clean-up fires.
+
+        Returns LongTensor (max_pred_len, B * num_samples), column b * num_samples + j = sample j of caption b, <pad>
+        after <end>; with return_log_probs also a float tensor of the same shape: the model's log-probability
+        (log_softmax of the raw scores, T = 1, untruncated) of every generated token, 0 after <end>.  seed=None draws a
+        63-bit seed from torch's default CPU generator; an integer seed makes the call bit-reproducible.  The knobs
+        and the seed are inputs of the captured decode graph: changing them replays it without a new capture."""
+        if not (isinstance(num_samples, int) and num_samples >= 1):
+            raise IckError("predict_sample needs num_samples >= 1")
+        if not (math.isfinite(temperature) and temperature > 0):
+            raise IckError("predict_sample needs a finite temperature > 0")
+        if not (isinstance(top_k, int) and top_k >= 0):
+            raise IckError("predict_sample needs an integer top_k >= 0 (0 = off)")
+        if not (0 < top_p <= 1):
+            raise IckError("predict_sample needs 0 < top_p <= 1")
+        encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
+        entities = entities.contiguous()
+        enc_tok, P = self._image_input(encoder_out)
+        enc_tok = enc_tok.contiguous()
+        B = enc_tok.shape[0]
+        FF = self.transformer_decoder.layers[0].linear1.out_features
+        S_all = P + entities.shape[1] + (facts.shape[1] if facts is not None else 0)
+        Vx = self.vocab_size + S_all - P
+        if B * num_samples > 65535 or not ops.decode_supported(self.emb_dim, self.num_heads, FF, S_all, max_pred_len) \
+                or not ops.decode_sample_supported(Vx, num_samples):
+            raise IckError("predict_sample needs B * num_samples <= 65535, V+K+F <= 65536 and sizes the fused decode "
+                           "kernels support")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (), dtype=torch.int64))
+        seed = int(seed) & (2 ** 64 - 1)
+        seed = seed - 2 ** 64 if seed >= 2 ** 63 else seed          # the same 64 bits as an int64
+        tp = struct.unpack("<q", struct.pack("<ff", temperature, top_p))[0]
+        knobs = torch.tensor([seed, tp, min(top_k, 2 ** 31 - 1)], dtype=torch.int64).to(enc_tok.device)
+        if self.use_hip_graphs:
+            key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
+                   max_pred_len, num_samples) + self._enc_key(enc_tok)
+            tok, lp = self._graphed("sample", key,
+                                    lambda t, e, f, k: self._predict_sample_device(t, e, f, k, max_pred_len, num_samples),
+                                    [enc_tok, entities, facts, knobs])
+        else:
+            tok, lp = self._predict_sample_device(enc_tok, entities, facts, knobs, max_pred_len, num_samples)
+        out = tok.t().contiguous()
+        return (out, lp.t().contiguous()) if return_log_probs else out
 
     def _predict_device(self, enc_tok, entities, facts, max_pred_len):
         """Whole greedy decode on the device: every step's token choice, clean-up and stop flag are computed

@@ -37,16 +37,21 @@ def detokenize(seq, word_map, rev_word_map, entity_names, fact_names=None):
 
 
 @torch.no_grad()
-def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="generated_captions.csv", device="cuda"):
+def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="generated_captions.csv", device="cuda",
+             sample=None):
+    """sample=None: greedy decode (predict), one CSV row per image.  sample = a dict of predict_sample keyword arguments
+    (num_samples, temperature, top_k, top_p, seed): sampled decode, one CSV row per (image, sample) with the columns
+    image (running index over the loader), sample, generated_caption; an explicit seed is advanced by one per batch."""
     decoder.eval()
     encoder.eval()
     rev = {v: k for k, v in word_map.items()}
-    captions, sequences = [], []
+    captions, sequences, rows = [], [], []
+    n = int(sample.get("num_samples", 1)) if sample is not None else 1
     # precomputed feature maps go to predict() as they are: Encoder.conv1 then runs inside the captured decode graph
     # beside the context encoders (decoder.attach_encoder); raw images go through the encoder's trunk first
     decoder.attach_encoder(encoder)
     img_buf = None
-    for batch in loader:                                      # any batch size: captions decode independently
+    for bi, batch in enumerate(loader):                       # any batch size: captions decode independently
         ent, names = batch[4], batch[5]
         has_facts = len(batch) > 6
         extra = (batch[6].to(device),) if has_facts else ()
@@ -58,13 +63,26 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
             image = img_buf
         else:
             image = batch[0].to(device)
-        seq = decoder.predict(image if feature_map else encoder(image), max_caption_len, ent, *extra)   # (max_len, B)
+        enc_in = image if feature_map else encoder(image)
+        if sample is None:
+            seq = decoder.predict(enc_in, max_caption_len, ent, *extra)                     # (max_len, B)
+        else:
+            kw = dict(sample)
+            if kw.get("seed") is not None:       # a batch's caption b would otherwise reuse the noise of every other batch's b
+                kw["seed"] = int(kw["seed"]) + bi
+            seq = decoder.predict_sample(enc_in, max_caption_len, ent, *extra, **kw)   # (max_len, B * n)
         bufs = decoder.input_buffers() if feature_map else None
         img_buf = bufs[0] if bufs is not None and bufs[0] is not None and bufs[0].dim() == 4 else None
         for b in range(seq.shape[1]):
             ids = seq[:, b].tolist()
             sequences.append(ids)
-            captions.append(detokenize(ids, word_map, rev, names[b], batch[7][b] if has_facts else None))
+            k = b // n
+            captions.append(detokenize(ids, word_map, rev, names[k], batch[7][k] if has_facts else None))
+            rows.append((len(rows) // n, b % n))
     if out_csv:
-        pd.DataFrame({"generated_caption": captions}).to_csv(out_csv, index=False)
+        if sample is None:
+            pd.DataFrame({"generated_caption": captions}).to_csv(out_csv, index=False)
+        else:
+            pd.DataFrame({"image": [r[0] for r in rows], "sample": [r[1] for r in rows],
+                          "generated_caption": captions}).to_csv(out_csv, index=False)
     return captions, sequences

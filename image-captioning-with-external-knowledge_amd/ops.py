@@ -600,6 +600,10 @@ def decode_beam_supported(Vx, beam):
     return bool(L.load().ick_decode_beam_supported(Vx, beam))
 
 
+def decode_sample_supported(Vx, rows_per_sample):
+    return bool(L.load().ick_decode_sample_supported(Vx, rows_per_sample))
+
+
 def decode_layers(ctx, pos):
     """Decoder stack + score head of one KV-cached decode step (ick_decode_layers); ctx: lib.DecodeCtx."""
     L.check(L.load().ick_decode_layers(C.byref(ctx), pos, _stream()), "ick_decode_layers")
@@ -621,6 +625,12 @@ def decode_select_greedy(ctx, pos):
 
 def decode_select_beam(ctx, beam_state, pos):
     L.check(L.load().ick_decode_select_beam(C.byref(ctx), C.byref(beam_state), pos, _stream()), "ick_decode_select_beam")
+
+
+def decode_select_sample(ctx, sample_state, pos):
+    """Sampled token of step `pos` for every live row (ick_decode_select_sample); sample_state: lib.SampleState."""
+    L.check(L.load().ick_decode_select_sample(C.byref(ctx), C.byref(sample_state), pos, _stream()),
+            "ick_decode_select_sample")
 
 
 def packed_ce(scores, captions_sorted, decode_len, pad_token, want_grad=False, out_sum=None, out_count=None):

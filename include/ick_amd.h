@@ -405,6 +405,25 @@ int ick_decode_select_beam(const ick_decode_ctx* ctx, const ick_beam_state* beam
  * beam^2 * ceil(Vx / 1024) <= 4096 candidates); callers check this BEFORE capturing a decode graph. */
 int ick_decode_beam_supported(int32_t Vx, int32_t beam);
 
+/* Sampled selection of one step (csrc/sample.hip; DecoderTransformer.predict_sample): every live row draws its token
+ * from the V+K+F scores (ctx->scores + ctx->ptr) -- temperature, top-k (ties at the boundary kept), top-p (smallest
+ * prefix by strictly-greater mass), Gumbel-max with Philox-4x32-10 noise keyed by the seed, counter (c >> 2, step,
+ * sample j = r % rows_per_sample, caption b = r / rows_per_sample) -- then does predict()'s bookkeeping (<end>,
+ * finished / n_done, next token / mask, caption buffer, embedding of the next token into x0) WITHOUT the repeated
+ * n-gram clean-up.  The knobs live in device memory (read with scalar loads), so a captured decode graph replays with
+ * a new seed / temperature / top-k / top-p.  Rows of a caption share its cross K/V (rows_per_sample = samples,
+ * anc = NULL: every row keeps its own self-attention cache).  Needs ctx->scores. */
+typedef struct {
+    const int64_t* seed;          /* (1) */
+    const float* temp_top_p;      /* (2) temperature > 0, top_p in (0, 1] */
+    const int32_t* top_k;         /* (1) 0 = off */
+    float* log_prob;              /* optional (R, max_len): log_softmax(scores)[token] at T = 1; the caller zeroes it */
+} ick_sample_state;
+int ick_decode_select_sample(const ick_decode_ctx* ctx, const ick_sample_state* s, int32_t pos, void* stream);
+/* 1 when ick_decode_select_sample handles Vx = V+K+F scores per row (Vx <= 65536) and rows_per_sample samples per
+ * caption (<= 65535); host-only, callers check it BEFORE capturing a decode graph. */
+int ick_decode_sample_supported(int32_t Vx, int32_t rows_per_sample);
+
 /* fused token-mean cross entropy over the packed rows of train.py
  * (pack_padded_sequence + CrossEntropyLoss(ignore_index=<pad>), geo-aware/train.py:275-281):
  * rows (b,t) with t < decode_len[b] and target != pad contribute.  Writes loss_sum[0] (sum of
