@@ -80,6 +80,38 @@ def copy_inputs(static, inputs):
             d.copy_(s, non_blocking=True)
 
 
+class DropSites:
+    """Hands out (p, seed, site) triples: one site id per dropout call site of a step, so the backward
+    kernels regenerate exactly the masks the forward used (ick_dropout_mask in include/ick_amd.h)."""
+
+    def __init__(self, seed, enabled, epoch=None):
+        self.seed, self.enabled, self.next, self.epoch = seed, enabled, 0, epoch
+
+    def site(self, p):
+        if not self.enabled or p <= 0.0:
+            return None
+        self.next += 1
+        return (float(p), self.seed, self.next, self.epoch) if self.epoch is not None else \
+            (float(p), self.seed, self.next)
+
+
+_NO_DROPOUT = DropSites(0, False)
+
+
+def _wb(linear):
+    return linear.weight.detach(), linear.bias.detach()
+
+
+def _ln(norm):
+    """The (gamma, beta, eps) arguments of ops.add_layernorm / ops.rowchain_fwd."""
+    return norm.weight.detach(), norm.bias.detach(), norm.eps
+
+
+def _with_stats(r, save):
+    """ops.add_layernorm's result as (out, mean, rstd); the statistics are None unless save_stats was set."""
+    return r if save else (r, None, None)
+
+
 class PositionEncoder(nn.Module):
     """Holds the sinusoid buffer `pe` and the dropout rate; applied inside ick_caption_embed."""
 
@@ -404,7 +436,10 @@ class DecoderTransformer(nn.Module):
             wkv.data_ptr(), self.__dict__.get("_param_epoch", 0))
         return ops.presplit_cached(self, "wkv", wkv, key)
 
-    def _vocab_presplit(self):
+    def _vocab_presplit(self, rows):
+        """Pre-split copy of fc_vocab's weight for the vocabulary GEMM over `rows` rows (None below 256 rows)."""
+        if rows < 256:
+            return None
         w = self.fc_vocab.weight
         return ops.presplit_cached(self, "vocab", w.detach(), (w._version, w.data_ptr(), self.__dict__.get("_param_epoch", 0)))
 
@@ -514,51 +549,6 @@ class DecoderTransformer(nn.Module):
             self.__dict__["_pred_wt_cache"] = cache
         return cache[1]
 
-    def _context_encoder(self, stack, x, tag="e", out=None, slim=False):
-        """Post-LN encoder stack on x (B, T, d); `out` (optional (B, T, d) view, e.g. rows of the memory buffer)
-        receives the last layer's output."""
-        H = self.num_heads
-        d = self.emb_dim
-        B, T, _ = x.shape
-        chain = self.chain_supported()
-        pk = self._chain_pack() if chain else None
-        n = len(stack.layers)
-        qkv = None
-        for li, layer in enumerate(stack.layers):
-            if qkv is None:
-                qkv = ops.project_heads(x, layer.self_attn.in_proj_weight.detach(), layer.self_attn.in_proj_bias.detach(),
-                                        3, H, T)
-            sa = torch.empty_like(x)
-            ops.attention_heads(qkv, qkv, sa, H, d // H, T, T, q_seg=0, k_seg=1, v_seg=2)
-            qkv = None
-            last = li == n - 1
-            if chain:
-                x1 = torch.empty_like(x)
-                f = torch.empty(B, T, layer.linear1.out_features, device=x.device, dtype=torch.float32)
-                ops.rowchain_fwd(sa, pk[(tag, li, "so")], layer.self_attn.out_proj.bias.detach(), x,
-                                 layer.norm1.weight.detach(), layer.norm1.bias.detach(), layer.norm1.eps, x1,
-                                 w2p=pk[(tag, li, "l1")], b2=layer.linear1.bias.detach(), y2=f, relu=True, slim=slim)
-                x2 = out if (last and out is not None) else torch.empty_like(x)
-                nxt = None if last else stack.layers[li + 1]
-                if nxt is not None:
-                    qkv = torch.empty(B, 3, H, T, ops.DHP, device=x.device, dtype=torch.float32)
-                ops.rowchain_fwd(f, pk[(tag, li, "l2")], layer.linear2.bias.detach(), x1, layer.norm2.weight.detach(),
-                                 layer.norm2.bias.detach(), layer.norm2.eps, x2,
-                                 w2p=None if nxt is None else pk[(tag, li + 1, "si")],
-                                 b2=None if nxt is None else nxt.self_attn.in_proj_bias.detach(), y2=qkv,
-                                 heads=None if nxt is None else (3, H, T, 0, T), slim=slim)
-                x = x2
-                continue
-            o = ops.linear(sa, layer.self_attn.out_proj.weight.detach(), layer.self_attn.out_proj.bias.detach())
-            x = ops.add_layernorm(o, x, layer.norm1.weight.detach(), layer.norm1.bias.detach(), layer.norm1.eps)
-            f = ops.linear(x, layer.linear1.weight.detach(), layer.linear1.bias.detach(), relu=True)
-            o = ops.linear(f, layer.linear2.weight.detach(), layer.linear2.bias.detach())
-            x = ops.add_layernorm(o, x, layer.norm2.weight.detach(), layer.norm2.bias.detach(), layer.norm2.eps)
-            if last and out is not None:
-                out.copy_(x)
-                x = out
-        return x
-
     def _encode_context(self, enc_tok, entities, facts, gmap):
         """Entity / fact encoders, context transformers and the all-layer cross K/V projection.
         Returns (entities_encoded, facts_encoded, kv, contexts); kv is head-major
@@ -576,18 +566,12 @@ class DecoderTransformer(nn.Module):
         else:
             B, P, _ = enc_tok.shape
         K = entities.shape[1]
-        ee = ops.entity_encode(self.variant, entities, self.entity_encoder.type_embedding.weight.detach(), d,
-                               facts=facts if self.has_facts else None,
-                               word_emb=self.word_embedding.weight.detach() if self.variant == "news" else None)
-        fe = None
-        Fn = 0
-        if self.has_facts:
-            Fn = facts.shape[1]
-            fe = ops.fact_encode(facts, ee, self.predicate_embedding.weight.detach())
+        Fn = facts.shape[1] if self.has_facts else 0
+        ee, fe = self._encode_entities(entities, facts)
         wkv, bkv = self._packed_cross_kv()
         wkv_ps = self._cross_kv_presplit(wkv)
-        if self.chain_supported():
-            self._chain_pack()      # refreshed (if stale) on the main stream, before the side stream forks
+        # refreshed (if stale) on the main stream, before the side stream forks
+        pk = self._chain_pack() if self.chain_supported() else None
         nseg = wkv.shape[0] // d
         S = P + K + Fn
         kv = torch.empty(B, nseg, H, S, ops.DHP, device=enc_tok.device, dtype=torch.float32)
@@ -604,13 +588,13 @@ class DecoderTransformer(nn.Module):
             ops.stamp("side: context chain starts")
             # beside Encoder.conv1 / the image K/V projection: the 8-wave form finds room on a CU that hosts bulk GEMM
             # workgroups (as in the training step)
-            ctx[0] = self._context_encoder(self.transformer_encoder_entities, ee, slim=True)
+            ctx[0] = self._context_stack(self.transformer_encoder_entities, ee, pk, "e", slim=True)
             ops.project_heads(ctx[0], wkv, bkv, nseg, H, S, out=kv, s0=P, grp=K)
             side.signal("ctx")
             ops.stamp("side: context chain done")
 
         def fact_chain():
-            ctx[1] = self._context_encoder(self.transformer_encoder_facts, fe, tag="f")
+            ctx[1] = self._context_stack(self.transformer_encoder_facts, fe, pk, "f")
             ops.project_heads(ctx[1], wkv, bkv, nseg, H, S, out=kv, s0=P + K, grp=Fn)
 
         # dependency point now, enqueued after the main stream's next kernel: in a captured graph the main chain
@@ -643,81 +627,161 @@ class DecoderTransformer(nn.Module):
         ctx_e, ctx_f = ctx
         return ee, fe, kv, (ctx_e, ctx_f), side
 
-    def _decoder_layer(self, li, layer, x, kv, S, qkv_buf=None, pos=None, side=None, qkv=None, want_next=False):
-        """One post-LN decoder layer on x (B, T, d).  With qkv_buf (B, 3, H, max_len, 32) the layer runs
-        one KV-cached decode step: the new q|k|v row is written at position `pos` and attends to [0, pos].
-        qkv: this layer's head-major q|k|v when the previous layer's last launch already projected it (row chains);
-        want_next: return (x, next layer's qkv) -- the in_proj of layer li + 1 rides on this layer's linear2 + norm3."""
+    # ------------------------------------------------------------------ layer forward (inference and training.py)
+    # Shared by the inference forward and training.forward_with_tape.  pk: the packed row-chain weights (_chain_pack) ->
+    # each out-projection / linear2 runs in one ops.rowchain_fwd launch together with its add & norm and the next
+    # projection; pk None -> the separate GEMM / add & norm kernels.  ds hands out the dropout sites (training only).
+    # save: keep what the backward pass needs -- o_out, the norm statistics and the attention lse -- in the layer's dict.
+    def _encode_entities(self, entities, facts):
+        """-> (entities_encoded (B, K, d), facts_encoded (B, F, d) or None)."""
+        ee = ops.entity_encode(self.variant, entities, self.entity_encoder.type_embedding.weight.detach(), self.emb_dim,
+                               facts=facts if self.has_facts else None,
+                               word_emb=self.word_embedding.weight.detach() if self.variant == "news" else None)
+        fe = ops.fact_encode(facts, ee, self.predicate_embedding.weight.detach()) if self.has_facts else None
+        return ee, fe
+
+    def _context_stack(self, stack, x, pk, tag, out=None, slim=False, ds=_NO_DROPOUT, tape=None):
+        """Post-LN encoder stack (entities: tag "e", facts: "f") on x (B, T, d).  With pk, two row-chain launches per
+        layer: out-projection + norm1 + linear1, linear2 + norm2 + the next layer's in_proj.  `out`: (B, T, d) view (rows
+        of the memory buffer) that receives the last layer's output.  slim: the chains' 8-wave form.  tape: a list ->
+        each layer's dict is appended to it."""
+        H, d = self.num_heads, self.emb_dim
+        B, T, _ = x.shape
+        save = tape is not None
+        n = len(stack.layers)
+        qkv = None
+        for li, layer in enumerate(stack.layers):
+            t = {"x": x, "d_att": ds.site(layer.self_attn.dropout), "d1": ds.site(layer.dropout1.p),
+                 "d_ff": ds.site(layer.dropout.p), "d2": ds.site(layer.dropout2.p)}
+            if qkv is None:
+                qkv = ops.project_heads(x, layer.self_attn.in_proj_weight.detach(), layer.self_attn.in_proj_bias.detach(),
+                                        3, H, T)
+            t["qkv"], qkv = qkv, None
+            t["sa"] = torch.empty_like(x)
+            t["lse"] = torch.empty(B * H * T, device=x.device, dtype=torch.float32) if save else None
+            ops.attention_heads(t["qkv"], t["qkv"], t["sa"], H, d // H, T, T, 0, 1, 2, lse=t["lse"], drop=t["d_att"])
+            last = li == n - 1
+            if pk is not None:
+                t["x1"] = torch.empty_like(x)
+                t["o1"], t["o2"] = (torch.empty_like(x), torch.empty_like(x)) if save else (None, None)
+                t["f"] = torch.empty(B, T, layer.linear1.out_features, device=x.device, dtype=torch.float32)
+                t["m1"], t["r1"] = ops.rowchain_fwd(
+                    t["sa"], pk[(tag, li, "so")], layer.self_attn.out_proj.bias.detach(), x, *_ln(layer.norm1), t["x1"],
+                    drop1=t["d1"], o_out=t["o1"], save_stats=save, w2p=pk[(tag, li, "l1")],
+                    b2=layer.linear1.bias.detach(), y2=t["f"], relu=True, drop2=t["d_ff"], slim=slim)
+                x2 = out if (last and out is not None) else torch.empty_like(x)
+                nxt = None if last else stack.layers[li + 1]
+                if nxt is not None:
+                    qkv = torch.empty(B, 3, H, T, ops.DHP, device=x.device, dtype=torch.float32)
+                t["m2"], t["r2"] = ops.rowchain_fwd(
+                    t["f"], pk[(tag, li, "l2")], layer.linear2.bias.detach(), t["x1"], *_ln(layer.norm2), x2,
+                    drop1=t["d2"], o_out=t["o2"], save_stats=save, w2p=None if nxt is None else pk[(tag, li + 1, "si")],
+                    b2=None if nxt is None else nxt.self_attn.in_proj_bias.detach(), y2=qkv,
+                    heads=None if nxt is None else (3, H, T, 0, T), slim=slim)
+            else:
+                t["o1"] = ops.linear(t["sa"], *_wb(layer.self_attn.out_proj))
+                t["x1"], t["m1"], t["r1"] = _with_stats(ops.add_layernorm(
+                    t["o1"], x, *_ln(layer.norm1), save_stats=save, drop=t["d1"]), save)
+                t["f"] = ops.linear(t["x1"], *_wb(layer.linear1), relu=True, drop=t["d_ff"])
+                t["o2"] = ops.linear(t["f"], *_wb(layer.linear2))
+                x2, t["m2"], t["r2"] = _with_stats(ops.add_layernorm(
+                    t["o2"], t["x1"], *_ln(layer.norm2), save_stats=save, drop=t["d2"]), save)
+                if last and out is not None:
+                    out.copy_(x2)
+                    x2 = out
+            x = x2
+            if save:
+                tape.append(t)
+        return x
+
+    def _decoder_self_block(self, li, layer, x, pk, qkv=None, ds=_NO_DROPOUT, save=False, qkv_buf=None, pos=None):
+        """Self-attention block of decoder layer li on x (B, T, d), up to the cross-attention query: in_proj (unless
+        qkv, this layer's head-major q|k|v, came with the previous layer's last launch), causal attention, out-projection
+        + norm1 + q-projection (with pk: one row-chain launch).  Nothing here reads the memory.  With qkv_buf
+        (B, 3, H, max_len, 32) and no pk it is one KV-cached decode step: the new q|k|v row is written at position `pos`
+        and attends to [0, pos].  ds hands out the six dropout sites of the layer.  Returns the layer's dict."""
         H, d = self.num_heads, self.emb_dim
         dh = d // H
         B, T, _ = x.shape
         sa_w, sa_b = layer.self_attn.in_proj_weight.detach(), layer.self_attn.in_proj_bias.detach()
-        sa = torch.empty_like(x)
-        chain = qkv_buf is None and self.chain_supported()
+        t = {"x": x, "d_sa": ds.site(layer.self_attn.dropout), "d1": ds.site(layer.dropout1.p),
+             "d_ca": ds.site(layer.multihead_attn.dropout), "d2": ds.site(layer.dropout2.p),
+             "d_ff": ds.site(layer.dropout.p), "d3": ds.site(layer.dropout3.p)}
+        t["sa"] = torch.empty_like(x)
         if qkv_buf is None:
-            if qkv is None:
-                qkv = ops.project_heads(x, sa_w, sa_b, 3, H, T)
-            ops.attention_heads(qkv, qkv, sa, H, dh, T, T, q_seg=0, k_seg=1, v_seg=2, causal=True)
+            t["qkv"] = qkv if qkv is not None else ops.project_heads(x, sa_w, sa_b, 3, H, T)
+            t["lse_s"] = torch.empty(B * H * T, device=x.device, dtype=torch.float32) if save else None
+            ops.attention_heads(t["qkv"], t["qkv"], t["sa"], H, dh, T, T, 0, 1, 2, causal=True, lse=t["lse_s"],
+                                drop=t["d_sa"])
         else:
-            ML = qkv_buf.shape[3]
-            ops.project_heads(x, sa_w, sa_b, 3, H, ML, out=qkv_buf, s0=pos, grp=1)
-            ops.attention_heads(qkv_buf, qkv_buf, sa, H, dh, 1, pos + 1, q_seg=0, k_seg=1, v_seg=2, q_t0=pos)
+            ops.project_heads(x, sa_w, sa_b, 3, H, qkv_buf.shape[3], out=qkv_buf, s0=pos, grp=1)
+            ops.attention_heads(qkv_buf, qkv_buf, t["sa"], H, dh, 1, pos + 1, 0, 1, 2, q_t0=pos)
         ca_w, ca_b = layer.multihead_attn.in_proj_weight.detach(), layer.multihead_attn.in_proj_bias.detach()
-        if chain:
-            pk = self._chain_pack()
-            x1 = torch.empty_like(x)
-            q = torch.empty(B, 1, H, T, ops.DHP, device=x.device, dtype=torch.float32)
-            ops.rowchain_fwd(sa, pk[("d", li, "so")], layer.self_attn.out_proj.bias.detach(), x, layer.norm1.weight.detach(),
-                             layer.norm1.bias.detach(), layer.norm1.eps, x1, w2p=pk[("d", li, "cq")], b2=ca_b[:d], y2=q,
-                             heads=(1, H, T, 0, T))
-            ca = torch.empty_like(x)
-            if side is not None:
-                side.join()       # entity / fact rows of kv come from the side stream
-            ops.attention_heads(q, kv, ca, H, dh, T, S, q_seg=0, k_seg=2 * li, v_seg=2 * li + 1)
-            x2 = torch.empty_like(x)
-            f = torch.empty(B, T, layer.linear1.out_features, device=x.device, dtype=torch.float32)
-            ops.rowchain_fwd(ca, pk[("d", li, "co")], layer.multihead_attn.out_proj.bias.detach(), x1,
-                             layer.norm2.weight.detach(), layer.norm2.bias.detach(), layer.norm2.eps, x2,
-                             w2p=pk[("d", li, "l1")], b2=layer.linear1.bias.detach(), y2=f, relu=True)
-            layers = self.transformer_decoder.layers
-            nxt = layers[li + 1] if (want_next and li + 1 < len(layers)) else None
-            x3 = torch.empty_like(x)
-            qkv_n = None if nxt is None else torch.empty(B, 3, H, T, ops.DHP, device=x.device, dtype=torch.float32)
-            ops.rowchain_fwd(f, pk[("d", li, "l2")], layer.linear2.bias.detach(), x2, layer.norm3.weight.detach(),
-                             layer.norm3.bias.detach(), layer.norm3.eps, x3,
-                             w2p=None if nxt is None else pk[("d", li + 1, "si")],
-                             b2=None if nxt is None else nxt.self_attn.in_proj_bias.detach(), y2=qkv_n,
-                             heads=None if nxt is None else (3, H, T, 0, T))
-            return (x3, qkv_n) if want_next else x3
-        o = ops.linear(sa, layer.self_attn.out_proj.weight.detach(), layer.self_attn.out_proj.bias.detach())
-        x = ops.add_layernorm(o, x, layer.norm1.weight.detach(), layer.norm1.bias.detach(), layer.norm1.eps)
-        q = ops.project_heads(x, ca_w[:d], ca_b[:d], 1, H, T)
-        ca = torch.empty_like(x)
-        if side is not None:
-            side.join()    # entity / fact rows of kv come from the side stream
-        ops.attention_heads(q, kv, ca, H, dh, T, S, q_seg=0, k_seg=2 * li, v_seg=2 * li + 1)
-        o = ops.linear(ca, layer.multihead_attn.out_proj.weight.detach(), layer.multihead_attn.out_proj.bias.detach())
-        x = ops.add_layernorm(o, x, layer.norm2.weight.detach(), layer.norm2.bias.detach(), layer.norm2.eps)
-        f = ops.linear(x, layer.linear1.weight.detach(), layer.linear1.bias.detach(), relu=True)
-        o = ops.linear(f, layer.linear2.weight.detach(), layer.linear2.bias.detach())
-        x = ops.add_layernorm(o, x, layer.norm3.weight.detach(), layer.norm3.bias.detach(), layer.norm3.eps)
-        return (x, None) if want_next else x
+        if pk is not None:
+            t["x1"] = torch.empty_like(x)
+            t["o1"] = torch.empty_like(x) if save else None
+            t["qc"] = torch.empty(B, 1, H, T, ops.DHP, device=x.device, dtype=torch.float32)
+            t["m1"], t["r1"] = ops.rowchain_fwd(
+                t["sa"], pk[("d", li, "so")], layer.self_attn.out_proj.bias.detach(), x, *_ln(layer.norm1), t["x1"],
+                drop1=t["d1"], o_out=t["o1"], save_stats=save, w2p=pk[("d", li, "cq")], b2=ca_b[:d], y2=t["qc"],
+                heads=(1, H, T, 0, T))
+        else:
+            t["o1"] = ops.linear(t["sa"], *_wb(layer.self_attn.out_proj))
+            t["x1"], t["m1"], t["r1"] = _with_stats(ops.add_layernorm(
+                t["o1"], x, *_ln(layer.norm1), save_stats=save, drop=t["d1"]), save)
+            t["qc"] = ops.project_heads(t["x1"], ca_w[:d], ca_b[:d], 1, H, T)
+        return t
 
-    def _score_head(self, h, ee, fe, eib, gate, out=None):
-        """get_scores: vocabulary logits and pointer scores written into one (B, T, V+K[+F]) buffer."""
+    def _decoder_cross_block(self, li, layer, t, kv, S, pk, save=False):
+        """The rest of decoder layer li after _decoder_self_block returned t: cross-attention over the S memory rows of
+        kv (head-major keys / values of layer li in segments 2li, 2li+1), out-projection + norm2 + linear1, linear2 +
+        norm3 (with pk: two row-chain launches, the second also projecting the next layer's q|k|v).  The caller makes
+        the main stream wait for the side stream's rows of kv first.  Returns (x, that q|k|v or None)."""
+        H, d = self.num_heads, self.emb_dim
+        dh = d // H
+        x = t["x"]
+        B, T, _ = x.shape
+        t["ca"] = torch.empty_like(x)
+        t["lse_c"] = torch.empty(B * H * T, device=x.device, dtype=torch.float32) if save else None
+        ops.attention_heads(t["qc"], kv, t["ca"], H, dh, T, S, 0, 2 * li, 2 * li + 1, lse=t["lse_c"], drop=t["d_ca"])
+        if pk is None:
+            t["o2"] = ops.linear(t["ca"], *_wb(layer.multihead_attn.out_proj))
+            t["x2"], t["m2"], t["r2"] = _with_stats(ops.add_layernorm(
+                t["o2"], t["x1"], *_ln(layer.norm2), save_stats=save, drop=t["d2"]), save)
+            t["f"] = ops.linear(t["x2"], *_wb(layer.linear1), relu=True, drop=t["d_ff"])
+            t["o3"] = ops.linear(t["f"], *_wb(layer.linear2))
+            x3, t["m3"], t["r3"] = _with_stats(ops.add_layernorm(
+                t["o3"], t["x2"], *_ln(layer.norm3), save_stats=save, drop=t["d3"]), save)
+            return x3, None
+        t["x2"] = torch.empty_like(x)
+        t["o2"], t["o3"] = (torch.empty_like(x), torch.empty_like(x)) if save else (None, None)
+        t["f"] = torch.empty(B, T, layer.linear1.out_features, device=x.device, dtype=torch.float32)
+        t["m2"], t["r2"] = ops.rowchain_fwd(
+            t["ca"], pk[("d", li, "co")], layer.multihead_attn.out_proj.bias.detach(), t["x1"], *_ln(layer.norm2),
+            t["x2"], drop1=t["d2"], o_out=t["o2"], save_stats=save, w2p=pk[("d", li, "l1")],
+            b2=layer.linear1.bias.detach(), y2=t["f"], relu=True, drop2=t["d_ff"])
+        layers = self.transformer_decoder.layers
+        nxt = layers[li + 1] if li + 1 < len(layers) else None
+        x3 = torch.empty_like(x)
+        qkv_n = None if nxt is None else torch.empty(B, 3, H, T, ops.DHP, device=x.device, dtype=torch.float32)
+        t["m3"], t["r3"] = ops.rowchain_fwd(
+            t["f"], pk[("d", li, "l2")], layer.linear2.bias.detach(), t["x2"], *_ln(layer.norm3), x3, drop1=t["d3"],
+            o_out=t["o3"], save_stats=save, w2p=None if nxt is None else pk[("d", li + 1, "si")],
+            b2=None if nxt is None else nxt.self_attn.in_proj_bias.detach(), y2=qkv_n,
+            heads=None if nxt is None else (3, H, T, 0, T))
+        return x3, qkv_n
+
+    def _score_head(self, h, ee, fe, eib, hv, out, vocab_ps=None):
+        """get_scores into `out`, a (B, T, V+K[+F]) view with any row stride: the vocabulary logits of hv (facts
+        variants: h times the predicate gate; None: h) through fc_vocab (vocab_ps: its pre-split copy) and the pointer
+        scores of h."""
         B, T, d = h.shape
         V, K = self.vocab_size, ee.shape[1]
-        Fn = fe.shape[1] if fe is not None else 0
-        Vx = V + K + Fn
-        if out is None:
-            out = torch.empty(B, T, Vx, device=h.device, dtype=torch.float32)
-        hv = ops.mul(h, gate) if self.has_facts else h
-        ops.gemm_raw(hv, self.fc_vocab.weight.detach(), out, B * T, V, d, d, 1, d, 1, Vx,
-                     bias=self.fc_vocab.bias.detach(), b_ps=self._vocab_presplit() if B * T >= 256 else None)
-        ops.pointer_scores(h, ee, self.fc_entity.weight.detach(), self.fc_entity.bias.detach(), out, V)
+        ops.gemm_raw(h if hv is None else hv, self.fc_vocab.weight.detach(), out, B * T, V, d, d, 1, d, 1, out.stride(1),
+                     bias=self.fc_vocab.bias.detach(), b_ps=vocab_ps)
+        ops.pointer_scores(h, ee, *_wb(self.fc_entity), out, V)
         if self.has_facts:
-            ops.pointer_scores(h, fe, self.fc_fact.weight.detach(), self.fc_fact.bias.detach(), out, V + K, ind=eib)
-        return out
+            ops.pointer_scores(h, fe, *_wb(self.fc_fact), out, V + K, ind=eib)
 
     # ------------------------------------------------------------------ public score-head methods
     @torch.no_grad()
@@ -750,17 +814,21 @@ class DecoderTransformer(nn.Module):
         dev = self.fc_vocab.weight.device
         hb = h.detach().to(dev, torch.float32).permute(1, 0, 2).contiguous()           # (B, L, d) rows
         ee = entities_encoded.detach().to(dev, torch.float32).contiguous()
-        fe = eib = gate = None
+        B, T, d = hb.shape
+        fe = eib = hv = None
         if self.has_facts:
             if facts_encoded is None or entity_idx_before is None or predicate_indicator is None:
                 raise IckError("%s variant: get_scores(h, entities_encoded, facts_encoded, entity_idx_before, "
                                "predicate_indicator)" % self.variant)
-            B, T, d = hb.shape
             fe = facts_encoded.detach().to(dev, torch.float32).contiguous()
             eib = entity_idx_before.detach().to(dev, torch.float32).reshape(B, T, fe.shape[1]).contiguous()
             pi = predicate_indicator.detach().to(dev, torch.float32).reshape(B * T, self.num_predicates).contiguous()
             gate = ops.linear(pi, self.fc_predicate.weight.detach(), self.fc_predicate.bias.detach()).view(B, T, d)
-        return self._score_head(hb, ee, fe, eib, gate).permute(1, 0, 2)
+            hv = ops.mul(hb, gate)
+        out = torch.empty(B, T, self.vocab_size + ee.shape[1] + (0 if fe is None else fe.shape[1]), device=dev,
+                          dtype=torch.float32)
+        self._score_head(hb, ee, fe, eib, hv, out, self._vocab_presplit(B * T))
+        return out.permute(1, 0, 2)
 
     def _prepare_inputs(self, encoder_out, entities, facts):
         dev = self.fc_vocab.weight.device
@@ -789,17 +857,24 @@ class DecoderTransformer(nn.Module):
         # the context chain, which is what the first cross-attention waits for: forward 0.694 -> 0.715 ms.)
         ee, fe, kv, ctx, side = self._encode_context(enc_tok, entities, facts, gmap)
         x, emb = embed(ee, fe)
+        pk = self._chain_pack() if self.chain_supported() else None     # as _encode_context refreshed it
         qkv = None
         S = kv.shape[3]
         for li, layer in enumerate(self.transformer_decoder.layers):
-            x, qkv = self._decoder_layer(li, layer, x, kv, S, qkv=qkv, want_next=True, side=side if li == 0 else None)
+            t = self._decoder_self_block(li, layer, x, pk, qkv=qkv)
+            if li == 0:
+                side.join()       # entity / fact rows of kv come from the side stream
+            x, qkv = self._decoder_cross_block(li, layer, t, kv, S, pk)
             ops.stamp("main: decoder layer %d done" % li)
         side.join()
-        eib = gate = None
+        B, T, _ = x.shape
+        eib = gate = hv = None
         if self.has_facts:
             eib, gate = ops.context_indicators(captions, facts, K, V, self._pred_wt(),
                                                self.fc_predicate.bias.detach(), mode=0)
-        scores = self._score_head(x, ee, fe, eib, gate)
+            hv = ops.mul(x, gate)
+        scores = torch.empty(B, T, V + K + (0 if fe is None else fe.shape[1]), device=x.device, dtype=torch.float32)
+        self._score_head(x, ee, fe, eib, hv, scores, self._vocab_presplit(B * T))
         ops.stamp("forward: scores done")
         if stages is not None:
             stages.update(entities_encoded=ee, facts_encoded=fe, embeddings=emb, entity_context=ctx[0],
@@ -1213,12 +1288,14 @@ class DecoderTransformer(nn.Module):
         for i in range(max_pred_len):
             x = ops.caption_embed(tok, msk, wemb, ee, fe, pe, V, self.word_map["<pad>"], math.sqrt(d), pos0=i)
             for li, layer in enumerate(self.transformer_decoder.layers):
-                x = self._decoder_layer(li, layer, x, kv, S, qkv_buf=qkv_cache[li], pos=i)
-            eib = gate = None
+                t = self._decoder_self_block(li, layer, x, None, qkv_buf=qkv_cache[li], pos=i)
+                x, _ = self._decoder_cross_block(li, layer, t, kv, S, None)
+            eib = hv = None
             if self.has_facts:
                 eib, gate = ops.context_indicators(cap_buf, facts, K, V, self._pred_wt(),
                                                    self.fc_predicate.bias.detach(), mode=1)
-            self._score_head(x, ee, fe, eib, gate, out=scores)
+                hv = ops.mul(x, gate)
+            self._score_head(x, ee, fe, eib, hv, scores, self._vocab_presplit(B))
             ops.greedy_select(scores.view(B, -1), output, hist, finished, tok.view(-1), msk.view(-1), i, V, K,
                               self.has_facts, self.word_map["<end>"])
             if self.has_facts and i + 1 < max_pred_len:

@@ -304,7 +304,7 @@ def rowchain_fwd(a, w1p, b1, res, gamma, beta, eps, x_out, drop1=None, o_out=Non
     (d, K1) and (N2, d) nn.Linear weights; b2 gives N2; x_out (..., d) may be a (B, T, d) view with a sample stride
     (rows inside the memory buffer); heads = (nseg, H, S, s0, grp): y2 is the head-major buffer (B, nseg, H, S, DHP)
     of project_heads.  slim: 8-wave workgroups (ICK_CHAIN_SLIM), for chains that run beside bulk GEMMs on another
-    stream.  Returns (mean, rstd) when save_stats."""
+    stream.  Returns (mean, rstd) -- (None, None) without save_stats."""
     K1, d = a.shape[-1], gamma.shape[0]
     a2 = a.reshape(-1, K1)
     if a2.stride(1) != 1:
@@ -350,7 +350,7 @@ def rowchain_fwd(a, w1p, b1, res, gamma, beta, eps, x_out, drop1=None, o_out=Non
     if slim:
         g.flags |= 256
     L.check(L.load().ick_rowchain_fwd(C.byref(g), _stream()), "ick_rowchain_fwd")
-    return (mean, rstd) if save_stats else None
+    return mean, rstd
 
 
 def rowchain_bwd_supported(K0, d, N1=0):

@@ -23,6 +23,7 @@ import os
 import torch
 
 from . import dp, ops
+from .decoder import DropSites
 from .lib import IckError
 from .weights import DerivedWeights      # noqa: F401  (the optimizer-maintained weight images; also imported from here)
 
@@ -36,21 +37,6 @@ class Tape:
         self.misc = {}
 
 
-class DropSites:
-    """Hands out (p, seed, site) triples: one site id per dropout call site of a step, so the backward
-    kernels regenerate exactly the masks the forward used (ick_dropout_mask in include/ick_amd.h)."""
-
-    def __init__(self, seed, enabled, epoch=None):
-        self.seed, self.enabled, self.next, self.epoch = seed, enabled, 0, epoch
-
-    def site(self, p):
-        if not self.enabled or p <= 0.0:
-            return None
-        self.next += 1
-        return (float(p), self.seed, self.next, self.epoch) if self.epoch is not None else \
-            (float(p), self.seed, self.next)
-
-
 def _p(x):
     return x.detach()
 
@@ -58,146 +44,6 @@ def _p(x):
 # ----------------------------------------------------------------------------------------------
 # forward with saved activations
 # ----------------------------------------------------------------------------------------------
-def _context_encoder_fwd(dec, stack, x, tape_list, ds, pk=None, tag="e", out=None, slim=False):
-    """pk: packed weights (dec._chain_pack) -> the row-chain launches (out-projection + norm1 + linear1, linear2 + norm2
-    + the next layer's in_proj) replace the separate GEMM / add & norm kernels; `out`: (B, T, d) view that receives
-    the stack's output (its rows of the memory buffer)."""
-    H, d = dec.num_heads, dec.emb_dim
-    B, T, _ = x.shape
-    n = len(stack.layers)
-    qkv = None
-    for li, layer in enumerate(stack.layers):
-        p = layer.dropout.p
-        last = li == n - 1
-        t = {"x": x, "d_att": ds.site(layer.self_attn.dropout), "d1": ds.site(layer.dropout1.p), "d_ff": ds.site(p),
-             "d2": ds.site(layer.dropout2.p)}
-        if qkv is not None:
-            t["qkv"] = qkv
-        else:
-            t["qkv"] = ops.project_heads(x, _p(layer.self_attn.in_proj_weight), _p(layer.self_attn.in_proj_bias), 3, H, T)
-        qkv = None
-        t["sa"] = torch.empty_like(x)
-        t["lse"] = torch.empty(B * H * T, device=x.device, dtype=torch.float32)
-        ops.attention_heads(t["qkv"], t["qkv"], t["sa"], H, d // H, T, T, 0, 1, 2, lse=t["lse"], drop=t["d_att"])
-        x2 = out if (last and out is not None) else torch.empty_like(x)
-        if pk is not None:
-            t["o1"], t["x1"], t["o2"] = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-            t["f"] = torch.empty(B, T, layer.linear1.out_features, device=x.device, dtype=torch.float32)
-            t["m1"], t["r1"] = ops.rowchain_fwd(
-                t["sa"], pk[(tag, li, "so")], _p(layer.self_attn.out_proj.bias), x, _p(layer.norm1.weight),
-                _p(layer.norm1.bias), layer.norm1.eps, t["x1"], drop1=t["d1"], o_out=t["o1"], save_stats=True,
-                w2p=pk[(tag, li, "l1")], b2=_p(layer.linear1.bias), y2=t["f"], relu=True, drop2=t["d_ff"], slim=slim)
-            nxt = None if last else stack.layers[li + 1]
-            if nxt is not None:
-                qkv = torch.empty(B, 3, H, T, ops.DHP, device=x.device, dtype=torch.float32)
-            t["m2"], t["r2"] = ops.rowchain_fwd(
-                t["f"], pk[(tag, li, "l2")], _p(layer.linear2.bias), t["x1"], _p(layer.norm2.weight),
-                _p(layer.norm2.bias), layer.norm2.eps, x2, drop1=t["d2"], o_out=t["o2"], save_stats=True,
-                w2p=None if nxt is None else pk[(tag, li + 1, "si")],
-                b2=None if nxt is None else _p(nxt.self_attn.in_proj_bias), y2=qkv,
-                heads=None if nxt is None else (3, H, T, 0, T), slim=slim)
-        else:
-            t["o1"] = ops.linear(t["sa"], _p(layer.self_attn.out_proj.weight), _p(layer.self_attn.out_proj.bias))
-            t["x1"], t["m1"], t["r1"] = ops.add_layernorm(t["o1"], x, _p(layer.norm1.weight), _p(layer.norm1.bias),
-                                                          layer.norm1.eps, save_stats=True, drop=t["d1"])
-            t["f"] = ops.linear(t["x1"], _p(layer.linear1.weight), _p(layer.linear1.bias), relu=True, drop=t["d_ff"])
-            t["o2"] = ops.linear(t["f"], _p(layer.linear2.weight), _p(layer.linear2.bias))
-            y, t["m2"], t["r2"] = ops.add_layernorm(t["o2"], t["x1"], _p(layer.norm2.weight), _p(layer.norm2.bias),
-                                                    layer.norm2.eps, save_stats=True, drop=t["d2"])
-            if last and out is not None:
-                out.copy_(y)
-            else:
-                x2 = y
-        x = x2
-        tape_list.append(t)
-    return x
-
-
-def _decoder_self_block(dec, li, layer, x, ds, pk=None, qkv=None):
-    """Self-attention block of decoder layer li up to the cross-attention query: in_proj (unless qkv came with the
-    previous layer's last launch), causal attention, out-projection + norm1 + q-projection.  Nothing here reads the
-    memory, so layer 0's block can run beside Encoder.conv1 / the K/V projection.  Returns the layer's tape dict."""
-    H, d = dec.num_heads, dec.emb_dim
-    dh = d // H
-    B, T, _ = x.shape
-    t = {"x": x, "d_sa": ds.site(layer.self_attn.dropout), "d1": ds.site(layer.dropout1.p),
-         "d_ca": ds.site(layer.multihead_attn.dropout), "d2": ds.site(layer.dropout2.p),
-         "d_ff": ds.site(layer.dropout.p), "d3": ds.site(layer.dropout3.p)}
-    if qkv is not None:
-        t["qkv"] = qkv
-    else:
-        t["qkv"] = ops.project_heads(x, _p(layer.self_attn.in_proj_weight), _p(layer.self_attn.in_proj_bias), 3, H, T)
-    t["sa"] = torch.empty_like(x)
-    t["lse_s"] = torch.empty(B * H * T, device=x.device, dtype=torch.float32)
-    ops.attention_heads(t["qkv"], t["qkv"], t["sa"], H, dh, T, T, 0, 1, 2, causal=True, lse=t["lse_s"],
-                        drop=t["d_sa"])
-    ca_w, ca_b = _p(layer.multihead_attn.in_proj_weight), _p(layer.multihead_attn.in_proj_bias)
-    if pk is not None:
-        for k in ("o1", "x1"):
-            t[k] = torch.empty_like(x)
-        t["qc"] = torch.empty(B, 1, H, T, ops.DHP, device=x.device, dtype=torch.float32)
-        t["m1"], t["r1"] = ops.rowchain_fwd(
-            t["sa"], pk[("d", li, "so")], _p(layer.self_attn.out_proj.bias), x, _p(layer.norm1.weight),
-            _p(layer.norm1.bias), layer.norm1.eps, t["x1"], drop1=t["d1"], o_out=t["o1"], save_stats=True,
-            w2p=pk[("d", li, "cq")], b2=ca_b[:d], y2=t["qc"], heads=(1, H, T, 0, T))
-    else:
-        t["o1"] = ops.linear(t["sa"], _p(layer.self_attn.out_proj.weight), _p(layer.self_attn.out_proj.bias))
-        t["x1"], t["m1"], t["r1"] = ops.add_layernorm(t["o1"], x, _p(layer.norm1.weight), _p(layer.norm1.bias),
-                                                      layer.norm1.eps, save_stats=True, drop=t["d1"])
-        t["qc"] = ops.project_heads(t["x1"], ca_w[:d], ca_b[:d], 1, H, T)
-    return t
-
-
-def _decoder_layer_fwd(dec, li, layer, x, kv, S, tape_list, ds, side=None, pk=None, qkv=None, t=None):
-    """Returns (x, qkv of the next layer or None).  pk: packed weights -> row-chain launches (see above); then the
-    in_proj of layer li + 1 rides on this layer's linear2 + norm3 launch.  t: the tape dict of a self-attention block
-    that already ran."""
-    H, d = dec.num_heads, dec.emb_dim
-    dh = d // H
-    B, T, _ = x.shape
-    if t is None:
-        t = _decoder_self_block(dec, li, layer, x, ds, pk, qkv)
-    t["ca"] = torch.empty_like(x)
-    t["lse_c"] = torch.empty(B * H * T, device=x.device, dtype=torch.float32)
-    if pk is not None:
-        for k in ("o2", "x2", "o3"):
-            t[k] = torch.empty_like(x)
-        ops.stamp("fwd: layer %d reaches cross-attention" % li)
-        if side is not None:
-            side.wait_or_join("ctx")    # the context rows of kv come from the side stream (its tail may still run)
-        ops.attention_heads(t["qc"], kv, t["ca"], H, dh, T, S, 0, 2 * li, 2 * li + 1, lse=t["lse_c"], drop=t["d_ca"])
-        t["f"] = torch.empty(B, T, layer.linear1.out_features, device=x.device, dtype=torch.float32)
-        t["m2"], t["r2"] = ops.rowchain_fwd(
-            t["ca"], pk[("d", li, "co")], _p(layer.multihead_attn.out_proj.bias), t["x1"], _p(layer.norm2.weight),
-            _p(layer.norm2.bias), layer.norm2.eps, t["x2"], drop1=t["d2"], o_out=t["o2"], save_stats=True,
-            w2p=pk[("d", li, "l1")], b2=_p(layer.linear1.bias), y2=t["f"], relu=True, drop2=t["d_ff"])
-        layers = dec.transformer_decoder.layers
-        nxt = layers[li + 1] if li + 1 < len(layers) else None
-        x3 = torch.empty_like(x)
-        qkv_n = None if nxt is None else torch.empty(B, 3, H, T, ops.DHP, device=x.device, dtype=torch.float32)
-        t["m3"], t["r3"] = ops.rowchain_fwd(
-            t["f"], pk[("d", li, "l2")], _p(layer.linear2.bias), t["x2"], _p(layer.norm3.weight), _p(layer.norm3.bias),
-            layer.norm3.eps, x3, drop1=t["d3"], o_out=t["o3"], save_stats=True,
-            w2p=None if nxt is None else pk[("d", li + 1, "si")],
-            b2=None if nxt is None else _p(nxt.self_attn.in_proj_bias), y2=qkv_n,
-            heads=None if nxt is None else (3, H, T, 0, T))
-        tape_list.append(t)
-        return x3, qkv_n
-    ops.stamp("fwd: layer %d reaches cross-attention" % li)
-    if side is not None:
-        side.wait_or_join("ctx")    # the context rows of kv come from the side stream (its tail may still run)
-    ops.attention_heads(t["qc"], kv, t["ca"], H, dh, T, S, 0, 2 * li, 2 * li + 1, lse=t["lse_c"], drop=t["d_ca"])
-    t["o2"] = ops.linear(t["ca"], _p(layer.multihead_attn.out_proj.weight), _p(layer.multihead_attn.out_proj.bias))
-    t["x2"], t["m2"], t["r2"] = ops.add_layernorm(t["o2"], t["x1"], _p(layer.norm2.weight), _p(layer.norm2.bias),
-                                                  layer.norm2.eps, save_stats=True, drop=t["d2"])
-    t["f"] = ops.linear(t["x2"], _p(layer.linear1.weight), _p(layer.linear1.bias), relu=True, drop=t["d_ff"])
-    t["o3"] = ops.linear(t["f"], _p(layer.linear2.weight), _p(layer.linear2.bias))
-    x, t["m3"], t["r3"] = ops.add_layernorm(t["o3"], t["x2"], _p(layer.norm3.weight), _p(layer.norm3.bias),
-                                            layer.norm3.eps, save_stats=True, drop=t["d3"])
-    tape_list.append(t)
-    return x, None
-
-
 def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gmap, seed=0, epoch=None,
                       fresh_pack=False, overlap=False, feats=None, conv1=None, side_tail=None, derived=None, pre_side=None):
     """Teacher-forced forward on already length-sorted inputs; returns (scores, tape).  Dropout is
@@ -245,17 +91,10 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
     first = lambda k: k[0] != "d" or (k[1] == 0 and k[2] in ("so", "cq", "si"))     # context encoders + layer 0's self block
     split_on = ops.gemm_split_mode() >= 1 and not ops.is_deterministic()
 
-    def encode_context_inputs():
-        ee_ = ops.entity_encode(dec.variant, entities, _p(dec.entity_encoder.type_embedding.weight), d,
-                                facts=facts if dec.has_facts else None,
-                                word_emb=_p(dec.word_embedding.weight) if dec.variant == "news" else None)
-        fe_ = ops.fact_encode(facts, ee_, _p(dec.predicate_embedding.weight)) if dec.has_facts else None
-        return ee_, fe_
-
     lazy = pre_side is not None and side is not None and feats is not None and derived is not None
     if pre_side is not None and not lazy:
         pre_side()
-    ee, fe = (None, None) if lazy else encode_context_inputs()
+    ee, fe = (None, None) if lazy else dec._encode_entities(entities, facts)
     if derived is not None:
         wkv, bkv, pk = derived.wkv, derived.bkv, derived.pk
         m["pkb"] = derived.pkb
@@ -311,7 +150,7 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
                 ops.presplit_weights([(_p(dec.fc_vocab.weight), m["vocab_ps"]),
                                       (_p(dec.fc_vocab.weight).t(), m["vocab_t_ps"])])
             else:
-                m["vocab_ps"] = dec._vocab_presplit()
+                m["vocab_ps"] = dec._vocab_presplit(B * L)
 
     head = {}
 
@@ -320,13 +159,13 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
         if lazy:
             ops.stamp("side: deferred optimizer update starts")
             pre_side()
-            ee, fe = head["ee"], head["fe"] = encode_context_inputs()
+            ee, fe = head["ee"], head["fe"] = dec._encode_entities(entities, facts)
             side.signal("head")
         ops.stamp("side: context chain starts")
         # the stack's last add & norm writes the entity rows of the memory buffer directly; beside Encoder.conv1 and the
         # image K/V projection the chain runs in its 8-wave form, which finds room on the CUs the bulk GEMMs occupy
-        ctx_e = _context_encoder_fwd(dec, dec.transformer_encoder_entities, ee, tape.enc_layers["entities"], ds, pk=pk,
-                                     tag="e", out=mem[:, P:P + K], slim=overlap)
+        ctx_e = dec._context_stack(dec.transformer_encoder_entities, ee, pk, "e", out=mem[:, P:P + K], slim=overlap, ds=ds,
+                                   tape=tape.enc_layers["entities"])
         ops.project_heads(ctx_e, wkv, bkv, nseg, H, S, out=kv, s0=P, grp=K)
         if side is not None:
             side.signal("ctx")      # the first cross-attention waits for this point, not for the packing / zeroing below
@@ -339,8 +178,8 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
             side_tail()
 
     def fact_chain():
-        ctx_f = _context_encoder_fwd(dec, dec.transformer_encoder_facts, fe, tape.enc_layers["facts"], ds, pk=pk,
-                                     tag="f", out=mem[:, P + K:], slim=overlap)
+        ctx_f = dec._context_stack(dec.transformer_encoder_facts, fe, pk, "f", out=mem[:, P + K:], slim=overlap, ds=ds,
+                                   tape=tape.enc_layers["facts"])
         ops.project_heads(ctx_f, wkv, bkv, nseg, H, S, out=kv, s0=P + K, grp=Fn)
 
     pe = dec.pos_encoder.pe.view(-1, d)
@@ -381,11 +220,14 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
     m["d_pos"] = ds.site(dec.pos_encoder.dropout.p)
     x = ops.caption_embed(captions, caption_masks, _p(dec.word_embedding.weight), ee, fe, pe, V,
                           dec.word_map["<pad>"], math.sqrt(d), drop=m["d_pos"])
-    t0 = _decoder_self_block(dec, 0, dec.transformer_decoder.layers[0], x, ds, pk, None)
     qkv = None
     for li, layer in enumerate(dec.transformer_decoder.layers):
-        x, qkv = _decoder_layer_fwd(dec, li, layer, x, kv, S, tape.dec_layers, ds, side=side if li == 0 else None,
-                                    pk=pk, qkv=qkv, t=t0 if li == 0 else None)
+        t = dec._decoder_self_block(li, layer, x, pk, qkv=qkv, ds=ds, save=True)
+        ops.stamp("fwd: layer %d reaches cross-attention" % li)
+        if side is not None and li == 0:
+            side.wait_or_join("ctx")    # the context rows of kv come from the side stream (its tail may still run)
+        x, qkv = dec._decoder_cross_block(li, layer, t, kv, S, pk, save=True)
+        tape.dec_layers.append(t)
     if side is not None:
         side.join()
     ops.stamp("fwd: decoder layers done")
@@ -402,11 +244,7 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
     # weight-gradient GEMMs read the score gradients with 16-byte loads only from aligned rows (645 -> ~470 us)
     ld = (Vx + 3) // 4 * 4
     scores = torch.empty(B, L, ld, device=x.device, dtype=torch.float32)[:, :, :Vx]
-    ops.gemm_raw(hv if dec.has_facts else x, _p(dec.fc_vocab.weight), scores, B * L, V, d, d, 1, d, 1, ld,
-                 bias=_p(dec.fc_vocab.bias), b_ps=m.get("vocab_ps"))
-    ops.pointer_scores(x, ee, _p(dec.fc_entity.weight), _p(dec.fc_entity.bias), scores, V)
-    if dec.has_facts:
-        ops.pointer_scores(x, fe, _p(dec.fc_fact.weight), _p(dec.fc_fact.bias), scores, V + K, ind=eib)
+    dec._score_head(x, ee, fe, eib, hv, scores, m.get("vocab_ps"))
     m.update(ee=ee, fe=fe, mem=mem, kv=kv, h=x, hv=hv, eib=eib, gate=gate, captions=captions, masks=caption_masks,
              entities=entities, facts=facts, P=P, K=K, Fn=Fn, S=S, wkv=wkv)
     return scores, tape

@@ -196,7 +196,8 @@ def test_backward_chain_matches_reference(M, ffn, pre, p):
 @pytest.mark.parametrize("d,H,FF,NL,variant", [(300, 10, 512, 3, "geo"), (256, 8, 384, 2, "geo"), (300, 10, 512, 2, "knowledge")])
 def test_model_scores_and_gradients_with_and_without_chains(d, H, FF, NL, variant):
     """The row chains (forward and backward) against the separate GEMM / add & norm / LayerNorm-backward kernels they
-    replace, through the whole drop-in module (autograd bridge, dropout off): scores and every parameter gradient."""
+    replace, through the whole drop-in module (autograd bridge, dropout off): scores and every parameter gradient; and
+    through the eval-mode forward: scores."""
     import ick_amd
     import ick_amd.synth as synth
     from torch.nn.utils.rnn import pack_padded_sequence
@@ -229,9 +230,14 @@ def test_model_scores_and_gradients_with_and_without_chains(d, H, FF, NL, varian
         tp = pack_padded_sequence(caps[:, 1:], dl, batch_first=True).data
         loss = torch.nn.functional.cross_entropy(sp, tp, ignore_index=wm["<pad>"])
         loss.backward()
-        results.append((scores.detach(), loss.item(), {k: p.grad.clone() for k, p in dec.named_parameters() if p.grad is not None}))
-    (s1, l1, g1), (s0, l0, g0) = results
+        grads = {k: p.grad.clone() for k, p in dec.named_parameters() if p.grad is not None}
+        dec.eval()
+        with torch.no_grad():
+            eval_scores = dec(*args)[0]
+        results.append((scores.detach(), eval_scores, loss.item(), grads))
+    (s1, e1, l1, g1), (s0, e0, l0, g0) = results
     assert (s1 - s0).abs().max().item() < 2e-4
+    assert (e1 - e0).abs().max().item() < 2e-4
     assert abs(l1 - l0) < 2e-5
     assert g1.keys() == g0.keys()
     for k in g1:
