@@ -8,6 +8,7 @@ Import as `ick_amd` (see /ick_amd.py).  Sub-modules:
   decoder    DecoderTransformer / Encoder engine shared by the three variants
   training   TrainStep: the fused cross-entropy training step
   scst       SelfCriticalStep: self-critical sequence training on sampled captions (also `ick_amd.SelfCriticalStep`)
+  cider      CiderD: CIDEr-D on token ids, on the device (also `ick_amd.CiderD`)
   geo_aware/models.py, knowledge_aware/models.py, news_knowledge_aware/models.py
              drop-in replacements for the reference's per-variant `models` module
 """
@@ -26,4 +27,7 @@ def __getattr__(name):
     if name == "SelfCriticalStep":
         from .scst import SelfCriticalStep
         return SelfCriticalStep
+    if name == "CiderD":
+        from .cider import CiderD
+        return CiderD
     raise AttributeError("module 'ick_amd' has no attribute %r" % name)

@@ -179,6 +179,8 @@ SIGNATURES = {
     "ick_packed_ce": [vp, i64, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "ick_packed_ce_weighted": [vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "ick_samples_to_captions": [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "ick_cider_d": [vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, f32, f32, i32, i32, i32, vp, i32, i32, vp, i32,
+                    vp, vp, vp],
     "ick_decode_supported": [i32, i32, i32, i32, i32],
     "ick_decode_layers": [C.POINTER(DecodeCtx), i32, vp],
     "ick_decode_layers_part": [C.POINTER(DecodeCtx), i32, i32, vp],

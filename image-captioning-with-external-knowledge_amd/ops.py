@@ -694,6 +694,46 @@ def samples_to_captions(tokens, V, K, has_facts, start, end, pad, out=None):
     return caps, masks, lengths
 
 
+CIDER_MODES = {None: 0, "greedy": 1, "mean": 2}
+
+
+def cider_d(tokens, refs, keys, counts, log_ref_len, sigma, start, end, pad, ignore=(), image_index=None,
+            num_samples=0, baseline=None):
+    """CIDEr-D of candidate rows tokens (N, T) against refs (B, M, Lr) (ick_cider_d; the metric: cider.py).  keys (U, 4)
+    int32 (the uint32 df-table keys), counts (U,) int32, all int64 / int32 device tensors.  Returns (rewards (N,) f32,
+    advantages (B * num_samples,) f32 or None).
+    baseline=None: general mode, row i against image image_index[i] ((N,) int32 on the device).
+    baseline="greedy" / "mean": the SCST layout (rows b * n + j, then with "greedy" the B greedy rows)."""
+    if baseline not in CIDER_MODES:
+        raise L.IckError('baseline must be None, "greedy" or "mean"')
+    for t, name, dt in ((tokens, "tokens", torch.int64), (refs, "refs", torch.int64), (keys, "keys", torch.int32),
+                        (counts, "counts", torch.int32)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise L.IckError("cider_d: %s must be a contiguous %s device tensor" % (name, dt))
+    if tokens.dim() != 2 or refs.dim() != 3 or keys.dim() != 2 or keys.shape[1] != 4 or counts.shape != keys.shape[:1]:
+        raise L.IckError("cider_d needs tokens (N, T), refs (B, M, Lr), keys (U, 4) and counts (U,)")
+    ignore = [int(i) for i in ignore]
+    if len(ignore) > 16:
+        raise L.IckError("cider_d takes at most 16 ignore ids")
+    N, T = tokens.shape
+    B, M, Lr = refs.shape
+    dev = tokens.device
+    mode = CIDER_MODES[baseline]
+    idx = None
+    if mode == 0:
+        if image_index is None or image_index.shape != (N,):
+            raise L.IckError("cider_d: general mode needs an (N,) image_index")
+        idx = image_index.to(device=dev, dtype=torch.int32).contiguous()
+    rewards = torch.empty(N, device=dev, dtype=torch.float32)
+    adv = torch.empty(B * num_samples, device=dev, dtype=torch.float32) if mode else None
+    ign = (C.c_int32 * 16)(*ignore)
+    L.check(L.load().ick_cider_d(_p(tokens), N, T, _p(refs), B, M, Lr, _p(keys), _p(counts), keys.shape[0],
+                                 float(log_ref_len), float(sigma), start, end, pad, ign, len(ignore), mode, _p(idx),
+                                 int(num_samples), _p(rewards), _p(adv), _stream()),
+            "ick_cider_d")
+    return rewards, adv
+
+
 # ------------------------------------------------------------------------------------------------
 # Backward / training-step wrappers
 # ------------------------------------------------------------------------------------------------

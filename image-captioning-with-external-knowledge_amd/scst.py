@@ -10,6 +10,10 @@ The sample and greedy decode graphs belong to the step (not to the decoder's own
 step drops): each opens with one launch that re-derives every weight copy the decode reads from the live parameters
 (DecoderTransformer._refresh_decode_copies), so the graphs stay valid across updates and are captured once per shape.
 
+Device reward: with a cider.CiderD as reward_fn, step(..., refs=) scores every caption on the device in one launch
+(ick_cider_d, SCST layout) that writes the rewards and the advantages the training step takes as caption weights --
+nothing is copied to the host.
+
 Dropout: sampling and the greedy decode never apply it; the teacher-forced pass uses the decoder's own mode, as TrainStep
 does.  In train() mode the gradient is therefore taken at the dropout-perturbed model, not at the model that drew the
 samples (the standard recipe).
@@ -20,6 +24,7 @@ import struct
 import torch
 
 from . import ops
+from .cider import CiderD
 from .decoder import _GraphedCall
 from .lib import IckError
 
@@ -28,7 +33,7 @@ SCSTOutput = collections.namedtuple("SCSTOutput", "loss samples rewards advantag
 
 class SelfCriticalStep:
     """step = SelfCriticalStep(train_step, reward_fn, num_samples=5, baseline="greedy" | "mean", max_len=20, ...)
-    out = step(encoder_out, entities, facts=None)
+    out = step(encoder_out, entities, facts=None, refs=None)
 
     reward_fn(tokens, image_index) -> N floats: tokens (N, max_len) CPU LongTensor (<pad> after <end>), image_index (N,)
     CPU LongTensor.  It is called once per step over the B * n samples (row b * n + j = sample j of image b) followed,
@@ -37,6 +42,9 @@ class SelfCriticalStep:
     Returns SCSTOutput: loss (device scalar, the weighted token-mean loss), samples (B * n, max_len) and rewards (B * n,),
     advantages (B * n,), greedy (B, max_len) and greedy_rewards (B,) (None with baseline="mean"), and the sampler seed
     of this step (predict_sample(..., seed=sample_seed) reproduces the samples from the same parameters).
+    reward_fn may instead be a cider.CiderD: each call then needs refs, the batch's reference captions (B, M, Lr) or
+    (B, L) int64, and the rewards and advantages come from one device launch.  SCSTOutput then holds DEVICE tensors
+    (samples, rewards, advantages, greedy, greedy_rewards) and the step never synchronises with the host.
     Advantages: "greedy" a_bj = r_bj - r_greedy_b; "mean" the leave-one-out mean a_bj = r_bj - (sum_k r_bk - r_bj)/(n-1).
     encoder_out: (B, d, P) encoder output, or the (B, 2048, 14, 14) feature map with an encoder attached to the decoder or
     given to the TrainStep (Encoder.conv1 then runs once per step at B rows)."""
@@ -107,8 +115,13 @@ class SelfCriticalStep:
             idx = self._index[(B, dev)] = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(self.n)
         return idx
 
-    def __call__(self, encoder_out, entities, facts=None):
+    def __call__(self, encoder_out, entities, facts=None, refs=None):
         ts, dec, n, T = self.ts, self.dec, self.n, self.max_len
+        on_device = isinstance(self.reward_fn, CiderD)
+        if on_device and refs is None:
+            raise IckError("a CiderD reward needs refs= (the batch's reference captions)")
+        if refs is not None and not on_device:
+            raise IckError("refs= belongs to a CiderD reward; a host reward_fn takes the tokens only")
         ts.flush()                  # the decode reads the parameters: apply a pending lazy update first
         encoder_out, entities, facts = dec._prepare_inputs(encoder_out, entities, facts)
         entities = entities.contiguous()
@@ -145,6 +158,14 @@ class SelfCriticalStep:
             greedy = self._graphed("greedy", shape, lambda t, e, f: dec._predict_device(t, e, f, T),
                                    [enc_tok, entities, facts], B)
         self._mark("greedy")
+        if on_device:
+            # 3-4. rewards and advantages on the device: one launch over the sample rows and the greedy rows
+            rows = torch.cat([tokens, greedy]) if greedy is not None else tokens
+            rewards, adv = self.reward_fn.scst(rows, refs, n, self.baseline)
+            self._mark("reward")
+            return self._train(tokens, entities, facts, encoder_out, adv, adv, rows[:R], rewards[:R],
+                               rows[R:] if greedy is not None else None,
+                               rewards[R:] if greedy is not None else None, seed)
         # 3. rewards on the host, one call
         host = torch.cat([tokens, greedy]) if greedy is not None else tokens
         host = host.cpu()
@@ -163,6 +184,18 @@ class SelfCriticalStep:
             adv = r - (r.sum(dim=1, keepdim=True) - r) / (n - 1)
         adv = adv.reshape(-1).to(torch.float32)
         self._mark("reward")
+        return self._train(tokens, entities, facts, encoder_out, adv.to(dev), adv, host[:R],
+                           rewards[:R].to(torch.float32),
+                           host[R:] if greedy is not None else None,
+                           g_r.to(torch.float32) if g_r is not None else None, seed)
+
+    def _train(self, tokens, entities, facts, encoder_out, weights, adv, samples, rewards, greedy, greedy_rewards,
+               seed):
+        """Steps 4-5; weights: the advantages on the device (the caption weights), adv: as SCSTOutput reports them."""
+        ts, dec, n = self.ts, self.dec, self.n
+        R = tokens.shape[0]
+        B = R // n
+        dev = tokens.device
         # 4. samples -> teacher-forced training rows, on the device
         wm = dec.word_map
         caps, masks, lengths = ops.samples_to_captions(tokens, dec.vocab_size, entities.shape[1], dec.has_facts,
@@ -171,9 +204,8 @@ class SelfCriticalStep:
         # 5. one weighted training step; the image rows exist once per image (image_index)
         ents_r = entities.repeat_interleave(n, dim=0)
         facts_r = facts.repeat_interleave(n, dim=0) if facts is not None else None
-        loss = ts(caps, encoder_out, masks, lengths.view(R, 1), ents_r, facts_r, caption_weights=adv.to(dev),
+        loss = ts(caps, encoder_out, masks, lengths.view(R, 1), ents_r, facts_r, caption_weights=weights,
                   image_index=self._image_index(B, dev))
         self._mark("train")
         self.step_count += 1
-        return SCSTOutput(loss, host[:R], rewards[:R].to(torch.float32), adv, host[R:] if greedy is not None else None,
-                          g_r.to(torch.float32) if g_r is not None else None, seed)
+        return SCSTOutput(loss, samples, rewards, adv, greedy, greedy_rewards, seed)

@@ -8,7 +8,13 @@ Differences from the reference, all deliberate: images are precomputed 14x14x204
 (datasets.CaptionDataset); `fused=True` (default) replaces Adam + clip_gradient + loss.backward() by
 training.TrainStep (same update, one flat bucket, one all-reduce per step under torchrun); `fused=False` keeps the
 reference's exact statement sequence (CrossEntropyLoss on pack_padded_sequence, loss.backward() through the HIP
-autograd bridge, utils.clip_gradient, torch Adam).  Checkpoints use the reference's layout (utils.save_checkpoint)."""
+autograd bridge, utils.clip_gradient, torch Adam).  Checkpoints use the reference's layout (utils.save_checkpoint).
+
+SCST fine-tuning (`scst=True`, fused single-process runs only; usually from an XE checkpoint via `checkpoint`): every
+TRAIN batch runs one scst.SelfCriticalStep with a CIDEr-D reward on the device (cider.CiderD, df from the TRAIN split's
+captions), the batch's own captions as the references (one per image in this dataset format), in place of the
+cross-entropy step.  It uses the plain fused loop, not the prefetch pipeline; validation (the cross-entropy loss) and
+checkpointing are unchanged."""
 import json
 import os
 import time
@@ -21,7 +27,9 @@ from torch.nn.utils.rnn import pack_padded_sequence
 
 from . import dp, load_models, ops
 from . import utils as ut
+from .cider import CiderD
 from .datasets import CaptionDataset
+from .scst import SelfCriticalStep
 from .training import TrainStep
 
 
@@ -59,6 +67,9 @@ class Config:
     deterministic: object = None                       # True / False: fixed-order reductions on / off; None: what
                                                        # ICK_DETERMINISTIC says at the time main() runs, else the
                                                        # library's current mode
+    scst: bool = False                                 # self-critical fine-tuning with a device CIDEr-D reward
+    scst_samples: int = 5                              # sampled captions per image
+    scst_baseline: str = "greedy"                      # "greedy" | "mean" (leave-one-out)
 
 
 def _batch_to_device(batch, device, has_facts):
@@ -294,6 +305,31 @@ def _train_fused_pipelined(loader, encoder, step, epoch, cfg, device, has_facts)
     return avg
 
 
+def _train_scst(loader, encoder, sc, epoch, cfg, device, has_facts):
+    """One SCST epoch: the plain fused loop (batches moved synchronously, no prefetch pipeline); each batch's captions
+    are its references.  The host waits only when a line is printed (mean sample and greedy CIDEr-D of that batch,
+    also kept in STATS["scst_rewards"]).  Returns the mean weighted loss."""
+    loss_sum = torch.zeros(1, device=device)
+    n, t_epoch = 0, time.time()
+    for i, batch in enumerate(loader):
+        imgs, caps, caplens, capmasks, ent, facts = _batch_to_device(batch, device, has_facts)
+        with torch.no_grad():
+            enc = encoder(imgs)
+        out = sc(enc, ent, facts, refs=caps)
+        loss_sum += out.loss
+        n = i + 1
+        if i % cfg.print_freq == 0:
+            r_s = out.rewards.mean().item()
+            r_g = out.greedy_rewards.mean().item() if out.greedy_rewards is not None else float("nan")
+            STATS.setdefault("scst_rewards", []).append((epoch, i, r_s, r_g))
+            print("Epoch: [%d][%d/%d]\tSCST loss %.4f\tCIDEr-D sample %.4f greedy %.4f" %
+                  (epoch, i, len(loader), out.loss.item(), r_s, r_g))
+        if cfg.max_batches and i + 1 >= cfg.max_batches:
+            break
+    STATS["last_epoch_steps_per_s"] = n / max(time.time() - t_epoch, 1e-9)
+    return loss_sum.item() / max(n, 1)
+
+
 def validate(loader, encoder, decoder, criterion, cfg, device):
     """Token-weighted mean loss over the validation split (geo-aware/train.py:317-386).  Under torchrun every rank
     scores its own shard and the (sum, count) pair is all-reduced, so all ranks return the same number and take the
@@ -372,6 +408,9 @@ def main(cfg=None):
                          "gradient all-reduce; the encoder's gradients are not part of its bucket)")
     fused = cfg.fused and not cfg.fine_tune_encoder     # fine-tuning the encoder takes the reference's statement
                                                         # sequence: loss.backward() through the HIP autograd bridge
+    if cfg.scst and (not fused or world > 1 or cfg.scst_baseline not in ("greedy", "mean")):
+        raise ValueError('scst=True needs a fused single-process run (fused=True, fine_tune_encoder=False, no torchrun) '
+                         'and scst_baseline "greedy" or "mean"')
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
     torch.cuda.set_device(device)
     models = load_models(cfg.variant)
@@ -413,11 +452,12 @@ def main(cfg=None):
         det = cfg.deterministic
         if det is None and os.environ.get("ICK_DETERMINISTIC") is not None:
             det = os.environ["ICK_DETERMINISTIC"] not in ("", "0")      # the script's switch, read when main() runs
+        pipelined = cfg.prefetch and not cfg.scst
         step = TrainStep(decoder, lr=cfg.decoder_lr, grad_clip=cfg.grad_clip, seed=cfg.seed * 1000 + rank,
-                         encoder=encoder if cfg.prefetch else None, deterministic=det,
+                         encoder=encoder if pipelined else None, deterministic=det,
                          # the pipelined loop lets step i's optimizer update run at the head of step i + 1's graph beside
                          # Encoder.conv1; _train_fused_pipelined() flushes the last one of an epoch
-                         lazy_update=bool(cfg.prefetch))
+                         lazy_update=bool(pipelined))
         if decoder_optimizer is not None:
             # resume: Adam moments, step count (bias correction + dropout stream position) and the decayed lr come
             # back from the pickled optimizer (ours or one written by the reference, geo-aware/utils.py:32-46)
@@ -430,6 +470,13 @@ def main(cfg=None):
         decoder_optimizer = torch.optim.Adam([p for p in decoder.parameters() if p.requires_grad], lr=cfg.decoder_lr)
     criterion = nn.CrossEntropyLoss(ignore_index=word_map["<pad>"]).to(device)
     loaders, samplers, shuffle_gen = make_loaders(cfg, rank, world, fused)
+    sc = None
+    if cfg.scst:
+        captions = torch.as_tensor(np.asarray(loaders["TRAIN"].dataset.captions), dtype=torch.long)
+        cider = CiderD(captions, word_map, device=device)
+        # sampled rows one shorter than the dataset's captions: the training rows ([<start>] + samples) keep its width
+        sc = SelfCriticalStep(step, cider, num_samples=cfg.scst_samples, baseline=cfg.scst_baseline,
+                              max_len=captions.shape[1] - 1, seed=cfg.seed)
     history = []
     for epoch in range(start_epoch, cfg.epochs):
         if epochs_since_improvement == cfg.max_epochs_since_improvement:
@@ -446,8 +493,11 @@ def main(cfg=None):
         shuffle_gen.manual_seed(cfg.seed * 100003 + epoch)
         if samplers["TRAIN"] is not None:
             samplers["TRAIN"].set_epoch(epoch)
-        tr = train(loaders["TRAIN"], encoder, decoder, criterion, decoder_optimizer, step, epoch, cfg, device,
-                   encoder_optimizer)
+        if sc is not None:
+            tr = _train_scst(loaders["TRAIN"], encoder, sc, epoch, cfg, device, decoder.has_facts)
+        else:
+            tr = train(loaders["TRAIN"], encoder, decoder, criterion, decoder_optimizer, step, epoch, cfg, device,
+                       encoder_optimizer)
         last_loss = validate(loaders["VAL"], encoder, decoder, criterion, cfg, device)   # identical on every rank
         is_best = last_loss < best_loss
         best_loss = min(last_loss, best_loss)

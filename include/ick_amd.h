@@ -449,6 +449,36 @@ int ick_samples_to_captions(const int64_t* tokens, int32_t R, int32_t T, int32_t
                             int32_t start_token, int32_t end_token, int32_t pad_token, int64_t* captions, int64_t* masks,
                             int64_t* lengths, void* stream);
 
+/* CIDEr-D on token ids, the reward of self-critical training (cider.py: CiderD; csrc/cider.hip).  The metric is
+ * coco-caption's CIDEr-D applied to token ids:
+ *   words of a row (candidate, reference, corpus alike): the tokens before the first end_token, without start_token,
+ *     pad_token and the `ignore` ids (removal closes the gap: "a <pad> b" has the bigram "a b"); pointer ids (>= V)
+ *     stay ids; a row without end_token uses all its tokens;
+ *   n-grams n = 1..4 with their counts tf(g);
+ *   df(g): the number of corpus images whose references, together, contain g; log_ref_len = log(corpus images);
+ *   x_n(g) = tf(g) * (log_ref_len - log(max(1, df(g)))), norm ||x_n||_2;
+ *   length: the row's BIGRAM count (coco-caption accumulates its length at n-index 1 -- kept as is);
+ *   with one reference: s_n = sum over g in the candidate of min(x_n^c(g), x_n^r(g)) * x_n^r(g) / (|x_n^c| |x_n^r|),
+ *     0 if either norm is 0, times exp(-(len_c - len_r)^2 / (2 sigma^2));
+ *   score: the mean of s_n over n = 1..4, averaged over the image's M references, x 10 (range [0, 10]).
+ * It equals coco-caption's CIDEr-D on the space-joined id strings, not on detokenised text.
+ *
+ * cand (N, T) int64 candidate rows; refs (B, M, Lr) int64, every one of the M rows of an image counts as a reference.
+ * df table: df_keys (U, 4) uint32 n-grams (unused slots 0xFFFFFFFF), sorted lexicographically as unsigned, unique,
+ * 16-byte aligned; df_count (U,) int32.  ignore: a HOST array of n_ignore <= 16 ids (copied into the launch).
+ * Ids must lie in [0, 2^31 - 1) (others are read as their low 32 bits).
+ * mode 0 (general): row i is scored against image image_index[i] (int32, (N,)); an index outside [0, B) gives NaN.
+ * mode 1 / 2 (SCST layout): rows b * n + j (j < n = num_samples) are the samples of image b; mode 1 ("greedy") adds the
+ *   greedy rows B * n + b (N = B * (n + 1)), mode 2 ("mean", n >= 2) has none (N = B * n).  Writes also
+ *   advantages (B * n,) f32: mode 1 r_bj - r_greedy_b, mode 2 the leave-one-out mean r_bj - (sum_k r_bk - r_bj)/(n-1).
+ * rewards (N,) f32.  Limits: T, Lr <= 64, M <= 16, rows per image (n or n + 1) <= 64, U >= 1.  fp32 with fixed-order
+ * sums, no atomics: bit-reproducible. */
+int ick_cider_d(const int64_t* cand, int32_t N, int32_t T, const int64_t* refs, int32_t B, int32_t M, int32_t Lr,
+                const uint32_t* df_keys, const int32_t* df_count, int32_t U, float log_ref_len, float sigma,
+                int32_t start_token, int32_t end_token, int32_t pad_token, const int32_t* ignore, int32_t n_ignore,
+                int32_t mode, const int32_t* image_index, int32_t num_samples, float* rewards, float* advantages,
+                void* stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Training step (row a14): backward kernels behind loss.backward() of geo-aware/train.py:282-292,
