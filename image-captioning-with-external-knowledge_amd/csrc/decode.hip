@@ -148,6 +148,7 @@ template <int G, int NWAVES>
 struct RowGather {
     static constexpr int WPR = NWAVES / G;                                  // waves per row (G = 3, 5: some waves idle)
     static constexpr int NS = (12 + WPR - 1) / WPR < 6 ? (12 + WPR - 1) / WPR : 6;   // source rows per wave and sweep
+    static constexpr int PSUM = G * WPR * kD4Max;                           // float4 of the psum slices in LDS
     float4 a[NS], b[NS];
     float4 gm0, gm1, bt0, bt1;
 
@@ -259,6 +260,11 @@ struct RowGather {
         }
     }
 };
+
+// float4 of the LDS buffer a block kernel shares between RowGather's slice sums and ColDot's partial sums (with G = 1
+// the eight slices of kD4Max float4 outgrow ColDot's G * kNT)
+template <int G>
+constexpr int part_f4() { return G * kNT > RowGather<G, kNW>::PSUM ? G * kNT : RowGather<G, kNW>::PSUM; }
 
 // Dot products of up to 4 * kNW * NPASS weight rows (k contiguous) with the G LDS vectors xs[g]: 16 lanes per weight
 // row, four weight rows per wave and pass; the weights stay in registers for all G rows.  load() only issues the weight
@@ -654,7 +660,7 @@ __global__ __launch_bounds__(kNT) void dec_self_kernel(SelfArgs a) {
     __shared__ uint64_t selkeys[FSEL ? G * kNW * 2 : 2];
     __shared__ __attribute__((aligned(16))) float qkv[G][128];     // q | k | v of this head (3 x dh <= 96), zero tail
     __shared__ __attribute__((aligned(16))) float o[G][kOPad];
-    __shared__ __attribute__((aligned(16))) float4 part[G * kNT];
+    __shared__ __attribute__((aligned(16))) float4 part[part_f4<G>()];
     int h, grp;
     xcd_unit(h, grp, gridDim.y);
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
@@ -772,7 +778,7 @@ __global__ __launch_bounds__(kNT) void dec_cross_kernel(CrossArgs a) {
     __shared__ __attribute__((aligned(16))) float xs[G][kDMax];
     __shared__ __attribute__((aligned(16))) float qs[G][32];
     __shared__ __attribute__((aligned(16))) float o[G][kOPad];
-    __shared__ __attribute__((aligned(16))) float4 part[G * kNT];
+    __shared__ __attribute__((aligned(16))) float4 part[part_f4<G>()];
     __shared__ __attribute__((aligned(16))) float4 pacc[G][kNW][8];
     __shared__ float pm[G][kNW], pl[G][kNW];
     int h, grp;
@@ -883,7 +889,7 @@ __global__ __launch_bounds__(kNT) void dec_ffn_kernel(FfnArgs a) {
     static_assert(G <= kNW, "one wave per row");
     __shared__ __attribute__((aligned(16))) float xs[G][kDMax];
     __shared__ __attribute__((aligned(16))) float f[G][96];
-    __shared__ __attribute__((aligned(16))) float4 part[G * kNT];
+    __shared__ __attribute__((aligned(16))) float4 part[part_f4<G>()];
     int ch, grp;
     xcd_unit(ch, grp, gridDim.y);
     const int tid = threadIdx.x, nch = gridDim.x;
@@ -1369,7 +1375,7 @@ __global__ __launch_bounds__(256) void dec_select_kernel(SelectArgs a) {
         for (int q = 0; q < 3; ++q) ph[q] = hs[max(i - 1 - q, 0)];
     }
     Top2 s{-INFINITY, -INFINITY, kNone, kNone};
-    constexpr int NC = 4;                      // 1024 candidate tiles (16 384 words) per sweep
+    constexpr int NC = 4;                      // 1024 candidate tiles (49 152 words) per sweep
     for (int t0 = 0; t0 < a.ntiles; t0 += 256 * NC) {
         float4 cd[NC];
 #pragma unroll
@@ -1701,21 +1707,40 @@ static RowSrc make_src(const ick_decode_ctx* c, const float* res, const float* p
 // a workgroup share that stream, and the grid should not exceed one workgroup per CU.  ICK_DEC_G="self,cross,ffn"
 // overrides the choice (tuning).
 // ---------------------------------------------------------------------------------------------------------
-struct GroupPlan { int g_self, g_cross, g_ffn; bool cross_shared; };
+struct GroupPlan {
+    int g_self, g_cross, g_ffn;
+    bool cross_shared;
+    bool fsel;          // rows_per_sample == 1: a context with sel_state runs dec_self_kernel<g_self, true> at step >= 1
+    bool head_merged;   // one dec_headvocab_kernel launch instead of dec_head_kernel + dec_vocab_kernel
+    bool gather_loop;   // some LN-on-load source (RowGather) has more rows than one sweep of its kernel holds
+};
 static int pick_group(int units_per_row_group, int R, const int* cand, int ncand) {
     int g = cand[ncand - 1];
     for (int i = 0; i < ncand; ++i)
         if (units_per_row_group * ceil_div(R, cand[i]) <= kNumCU) { g = cand[i]; break; }
     return g;
 }
-static GroupPlan plan_groups(const ick_decode_ctx* c) {
+// source rows one sweep of RowGather<G, kNW> holds (more take the loop in slice_sums)
+template <int G> constexpr int sweep_rows() { return RowGather<G, kNW>::WPR * RowGather<G, kNW>::NS; }
+static int sweep_rows_of(int g) {
+    switch (g) {
+    case 1: return sweep_rows<1>();
+    case 2: return sweep_rows<2>();
+    case 3: return sweep_rows<3>();
+    case 4: return sweep_rows<4>();
+    case 5: return sweep_rows<5>();
+    default: return sweep_rows<8>();
+    }
+}
+// the launches of a step are a function of these five sizes only: ick_decode_plan reports this to the tests
+static GroupPlan plan_groups(int R, int rps, int H, int FF) {
     static const int pow2[] = {1, 2, 4, 8};
     GroupPlan p;
-    const int R = c->R, rps = c->rows_per_sample;
-    p.g_self = pick_group(c->H, R, pow2, 4);
-    p.g_ffn = pick_group(ceil_div(c->FF, 64), R, pow2, 4);
+    const int nch = ceil_div(FF, 64);
+    p.g_self = pick_group(H, R, pow2, 4);
+    p.g_ffn = pick_group(nch, R, pow2, 4);
     p.cross_shared = false;
-    p.g_cross = pick_group(c->H, R, pow2, 4);
+    p.g_cross = pick_group(H, R, pow2, 4);
     if (rps > 1) {
         // hypotheses of one caption read the same K / V: the largest group that divides the beam
         static const int shared[] = {8, 5, 4, 3, 2};
@@ -1723,6 +1748,13 @@ static GroupPlan plan_groups(const ick_decode_ctx* c) {
         for (int g : shared)
             if (rps % g == 0) { p.g_cross = g; p.cross_shared = true; break; }
     }
+    p.fsel = rps == 1;
+    // one launch for both when the rows fit one 32-row block and the final LayerNorm's sources fit the merged kernel's
+    // registers (greedy decoding at cfg5)
+    p.head_merged = R <= 32 && nch + 2 <= kHvSrc;
+    // sources: self (layers >= 1) and the head sum the FFN chunks, cross and FFN the heads
+    p.gather_loop = nch + 2 > sweep_rows_of(p.g_self) || H + 2 > sweep_rows_of(p.g_cross) ||
+                    H + 2 > sweep_rows_of(p.g_ffn) || nch + 2 > RowGather<1, 4>::WPR * RowGather<1, 4>::NS;
     return p;
 }
 static void launch_self(int g, bool fsel, dim3 grid, hipStream_t s, const SelfArgs& a) {
@@ -1780,6 +1812,16 @@ extern "C" int ick_decode_beam_supported(int32_t Vx, int32_t beam) {
     return (int64_t)beam * beam * ceil_div(Vx, kBeamChunk) <= 256 * kBeamCandPerThread;   // candidates the selection holds
 }
 
+extern "C" int ick_decode_plan(int32_t R, int32_t rows_per_sample, int32_t d, int32_t H, int32_t FF, int32_t* out) {
+    ICK_CHECK_ARG(out && R > 0 && R <= 65535 && rows_per_sample > 0 && R % rows_per_sample == 0);
+    ICK_CHECK_ARG(d > 0 && d % 4 == 0 && d <= kDMax && H > 0 && H <= kPartsMax && d % H == 0 && FF > 0 &&
+                  FF % 4 == 0 && FF <= 64 * kPartsMax);
+    const GroupPlan p = plan_groups(R, rows_per_sample, H, FF);
+    out[0] = p.g_self; out[1] = p.fsel; out[2] = p.g_cross; out[3] = p.cross_shared; out[4] = p.g_ffn;
+    out[5] = p.head_merged; out[6] = p.gather_loop;
+    return 0;
+}
+
 // which: bit 0 self, 1 cross, 2 ffn, 3 head, 4 vocabulary (all set in the product path; the diagnostic build times subsets)
 static int decode_layers_impl(const ick_decode_ctx* c, int32_t pos, void* stream, unsigned which, int part = 0) {
     ICK_CHECK_ARG(c && c->R > 0 && c->layers > 0 && c->layers <= ICK_MAX_LAYERS && pos >= 0 && pos < c->max_len);
@@ -1791,7 +1833,7 @@ static int decode_layers_impl(const ick_decode_ctx* c, int32_t pos, void* stream
     const int d = c->d, H = c->H, dh = d / H, R = c->R;
     const int nch = ceil_div(c->FF, 64);
     const float scale = 1.f / sqrtf((float)dh);
-    const GroupPlan plan = plan_groups(c);
+    const GroupPlan plan = plan_groups(R, c->rows_per_sample, H, c->FF);
     RowSrc src = make_src(c, c->x0, nullptr, 0, nullptr, nullptr, nullptr, c->xa);
     for (int l = 0; l < c->layers; ++l) {
         const ick_decode_layer& w = c->layer[l];
@@ -1849,9 +1891,7 @@ static int decode_layers_impl(const ick_decode_ctx* c, int32_t pos, void* stream
     va.hv = c->hv; va.wv = c->wv; va.bv = c->bv; va.scores = c->scores; va.ld = c->scores_ld;
     va.cand = reinterpret_cast<float4*>(c->cand); va.R = R; va.d = d; va.V = c->V; va.ntiles = ceil_div(c->V, kVocabTile);
     va.n_done = c->n_done; va.n_total = R;
-    // one launch for both when the rows fit one 32-row block and the final LayerNorm's sources fit the merged kernel's
-    // registers (greedy decoding at cfg5)
-    if ((which & 24u) == 24u && R <= 32 && src.nparts + 2 <= kHvSrc) {
+    if ((which & 24u) == 24u && plan.head_merged) {
         hipLaunchKernelGGL(dec_headvocab_kernel, dim3(va.ntiles + R), dim3(kNT), 0, s, ha, va);
         ICK_LAUNCH_RET();
     }

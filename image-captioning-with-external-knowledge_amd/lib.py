@@ -182,6 +182,7 @@ SIGNATURES = {
     "ick_cider_d": [vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, f32, f32, i32, i32, i32, vp, i32, i32, vp, i32,
                     vp, vp, vp],
     "ick_decode_supported": [i32, i32, i32, i32, i32],
+    "ick_decode_plan": [i32, i32, i32, i32, i32, C.POINTER(i32)],
     "ick_decode_layers": [C.POINTER(DecodeCtx), i32, vp],
     "ick_decode_layers_part": [C.POINTER(DecodeCtx), i32, i32, vp],
     "ick_decode_init": [C.POINTER(DecodeCtx), i32, i32, vp],

@@ -596,6 +596,16 @@ def decode_supported(d, H, FF, S, max_len):
     return bool(L.load().ick_decode_supported(d, H, FF, S, max_len))
 
 
+DECODE_PLAN_KEYS = ("g_self", "fsel", "g_cross", "cross_shared", "g_ffn", "head_merged", "gather_loop")
+
+
+def decode_plan(R, rows_per_sample, d, H, FF):
+    """The kernels ick_decode_layers launches for these sizes (ick_decode_plan; host only, no GPU needed)."""
+    out = (C.c_int32 * len(DECODE_PLAN_KEYS))()
+    L.check(L.load().ick_decode_plan(R, rows_per_sample, d, H, FF, out), "ick_decode_plan")
+    return dict(zip(DECODE_PLAN_KEYS, (int(v) for v in out)))
+
+
 def decode_beam_supported(Vx, beam):
     return bool(L.load().ick_decode_beam_supported(Vx, beam))
 

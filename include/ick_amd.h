@@ -373,6 +373,13 @@ typedef struct {
 /* 1 when the fused path handles these sizes (d % 4 == 0, 64 <= d <= 320, head width <= 32, S <= 1024,
  * max_len <= 128); callers fall back to the per-op launches otherwise. */
 int ick_decode_supported(int32_t d, int32_t H, int32_t FF, int32_t S, int32_t max_len);
+/* The launch plan of ick_decode_layers for R rows (rows_per_sample per caption) of a d / H / FF model, host only:
+ * out[0] rows per workgroup of dec_self_kernel, out[1] 1 when a context with sel_state fuses the greedy selection
+ * into it (rows_per_sample == 1), out[2] rows per workgroup of dec_cross_kernel, out[3] 1 when those rows share a
+ * caption's K / V, out[4] rows per workgroup of dec_ffn_kernel, out[5] 1 for the merged score head + vocabulary
+ * launch, out[6] 1 when some LayerNorm-on-load source has more rows than one sweep of its kernel.  ick_decode_layers
+ * launches by the same function. */
+int ick_decode_plan(int32_t R, int32_t rows_per_sample, int32_t d, int32_t H, int32_t FF, int32_t* out);
 /* Decoder stack + score head for position `pos`: reads x0, leaves ptr / cand (/ scores / hfin). */
 int ick_decode_layers(const ick_decode_ctx* ctx, int32_t pos, void* stream);
 /* The same in two parts (part 1: the first self-attention block -- with sel_state the selection of the previous step --,
