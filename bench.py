@@ -1,7 +1,7 @@
 """bench.py -- decode-steps/s of the caption-decoder hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--mode train|forward|greedy|beam] [--config cfg2] [--no-modes]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--mode train|forward|greedy|beam] [--config cfg2]
+                    [--dump-outputs DIR] [--full [--no-modes] [--no-profile] [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (`python bench.py --gpus N` with N > 1 and no WORLD_SIZE starts that torch.distributed.run line itself, as a child
 process, and relays rank 0's JSON line; `ranks_seen` in the line is what the probe all-reduce returned.)
@@ -28,7 +28,11 @@ The train outputs differ in their last bits from run to run (the backward pass's
 atomics, amplified by Adam) unless ICK_DETERMINISTIC=1 (bit-reproducible, slower).
 When the arrays exceed 64 MB in all, every array above 2M elements is replaced by <name>_sample.npy: the elements at
 2M fixed indices (torch.randperm with seed 0, sorted).
-Rank 0 prints ONE JSON line with the whole-job rate plus
+Rank 0 prints ONE JSON line with the whole-job rate.  A plain run does nothing else: set-up, warm-up, the timed block,
+the dump, the line (its roofline holds only the pass fraction, a closed form over ms_per_step).  --full adds what takes
+runs of its own, as below; --no-profile, --no-modes and --no-cpu-baseline leave single ones of them out again:
+  ms_per_step_with_input_copy  (forward / greedy / beam) one more block of K steps whose inputs are not yet in the
+                graph's own buffers
   roofline      by_kernel: every kernel class of the step (launches per step, mean duration from HIP events on
                 the launch stream in an eager single-stream pass, algorithmic FLOP or bytes, fraction of the fp32
                 MFMA / HBM peak); the headline kernel/achieved/frac describe the class with the LARGEST share of
@@ -82,11 +86,14 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", default="train", choices=["train", "forward", "greedy", "beam"])
     ap.add_argument("--config", default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the input-copy block, the per-kernel pass, the other modes and the CPU baseline "
+                         "(default: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the host baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-profile", action="store_true", help="skip the eager per-kernel pass (roofline.by_kernel)")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the eager per-kernel pass (roofline.by_kernel)")
     ap.add_argument("--profile-steps", type=int, default=3)
-    ap.add_argument("--no-modes", action="store_true", help="headline only: skip the forward / greedy / beam / cfg4 legs")
+    ap.add_argument("--no-modes", action="store_true", help="--full without the forward / greedy / beam / cfg4 legs")
     ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="repeat the K-step block until this much timed work (default: one block of exactly K steps)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -337,9 +344,10 @@ def dump_outputs(dirname, arrays):
         np.save(os.path.join(dirname, k + ".npy"), v.numpy())
 
 
-def run_workload(wl, steps, warmup, min_seconds, world, profile_steps, max_repeats=400, dump_dir=None):
+def run_workload(wl, steps, warmup, min_seconds, world, profile_steps, max_repeats=400, dump_dir=None, input_copy=False):
     """-> dict(ms_per_step, value, repeats, timed_region_s, graph, by_kernel).  dump_dir: rank 0 writes the outputs of
-    the last timed step there (dump_outputs) before anything else runs on the device."""
+    the last timed step there (dump_outputs) before anything else runs on the device.  input_copy: one more block with
+    the inputs outside the graph's buffers (forward / greedy / beam; --full)."""
     import torch.distributed as dist
     import ick_amd.profiling as prof
 
@@ -385,7 +393,7 @@ def run_workload(wl, steps, warmup, min_seconds, world, profile_steps, max_repea
     # it: eval.py / train.py do).  A caller that hands over OTHER device tensors pays a device-to-device copy of the
     # inputs in front of every replay (103 MB of features at B = 64): that number too, one block, not the headline.
     dt_copy = None
-    if wl.mode != "train":
+    if input_copy and wl.mode != "train":
         step_copy = wl.make_step(adopt_buffers=False)
         step_copy()
         dt_copy = block(step_copy)
@@ -487,8 +495,9 @@ def main():
 
     cfgname = args.config or ("cfg5" if args.mode in ("greedy", "beam") else "cfg2")
     wl = Workload(args.mode, cfgname, rank)
-    res = run_workload(wl, args.steps, args.warmup, args.min_seconds, world, 0 if args.no_profile else args.profile_steps,
-                       dump_dir=args.dump_outputs)
+    res = run_workload(wl, args.steps, args.warmup, args.min_seconds, world,
+                       args.profile_steps if args.full and not args.no_profile else 0, dump_dir=args.dump_outputs,
+                       input_copy=args.full)
     cfg, seed = wl.cfg, wl.seed
     B, L = cfg["B"], cfg["L"]
 
@@ -594,7 +603,7 @@ def main():
     # other down (measured: greedy 9.3 ms instead of 2.4 ms per decode behind a train workload -- the streams and
     # graphs of the earlier workloads stay with the HIP runtime), and a child's number is the number a user of that
     # mode alone would see.
-    if world == 1 and not args.no_modes:
+    if world == 1 and args.full and not args.no_modes:
         import subprocess
         modes = {}
         del wl
@@ -615,8 +624,8 @@ def main():
             # the CPU port beside the forward and greedy numbers as well (north_star: "in the same run"): bounded legs of
             # ~3 s each inside those children; the headline's own leg runs at the end of this process
             cpu_leg = name in ("forward_cfg2", "greedy_cfg5") and not args.no_cpu_baseline
-            cmd = [sys.executable, os.path.abspath(__file__), "--mode", mode, "--config", cname, "--steps", str(steps),
-                   "--warmup", "3", "--min-seconds", "0.5", "--no-modes", "--profile-steps",
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--mode", mode, "--config", cname,
+                   "--steps", str(steps), "--warmup", "3", "--min-seconds", "0.5", "--no-modes", "--profile-steps",
                    "0" if args.no_profile else "2"] + (["--no-profile"] if args.no_profile else []) + \
                   (["--cpu-seconds", "3"] if cpu_leg else ["--no-cpu-baseline"])
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
@@ -660,7 +669,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, seed, args.cpu_seconds,
                                                {"train": "train", "greedy": "greedy", "beam": "greedy"}.get(args.mode, "forward"))
         print(json.dumps(out), flush=True)

@@ -75,3 +75,82 @@ def test_dump_outputs_writes_float_arrays_within_the_budget(monkeypatch, tmp_pat
     assert sorted(os.listdir(str(tmp_path / "b"))) == ["loss.npy", "params_sample.npy"]
     b, c = (np.load(str(tmp_path / d / "params_sample.npy")) for d in ("b", "c"))
     assert b.shape == (100,) and np.array_equal(b, c) and np.isin(b, big.numpy()).all()
+
+
+def _run_main(monkeypatch, capsys, argv):
+    """bench.main() with the device work stubbed out: -> (JSON line, what the GPU / host legs were asked to do)."""
+    sys.path.insert(0, ROOT)
+    import torch
+    import bench
+    calls = {"children": [], "cpu_baseline": 0}
+
+    class FakeWorkload:
+        def __init__(self, mode, cfgname, rank):
+            import ick_amd.synth as synth
+            self.mode, self.cfgname, self.rank = mode, cfgname, rank
+            self.cfg, self.seed, self.train_step = dict(synth.CONFIGS[cfgname]), 100 + rank, None
+
+        def describe(self):
+            return self.cfgname
+
+    def fake_run_workload(wl, steps, warmup, min_seconds, world, profile_steps, max_repeats=400, dump_dir=None,
+                          input_copy=False):
+        calls["run_workload"] = {"steps": steps, "warmup": warmup, "profile_steps": profile_steps,
+                                 "input_copy": input_copy, "dump_dir": dump_dir}
+        return {"ms_per_step": 2.0, "value": 640000.0, "repeats": 1, "timed_region_s": 2e-3 * steps,
+                "block_s_min_median_max": [2e-3 * steps] * 3, "graph": True, "by_kernel": [],
+                "ms_per_step_with_input_copy": 2.5 if input_copy else None}
+
+    def fake_subprocess_run(cmd, **kw):
+        calls["children"].append(cmd)
+        child = {"config": {"workload": "w", "graph": True}, "repeats": 1, "ms_per_step": 1.0, "value": 1.0,
+                 "unit": "decode-steps/s", "roofline": {}}
+        return subprocess.CompletedProcess(cmd, 0, stdout=json.dumps(child) + "\n", stderr="")
+
+    def fake_cpu_baseline(*a, **kw):
+        calls["cpu_baseline"] += 1
+        return {"value": 1.0, "unit": "decode-steps/s", "cores": 1, "kind": "port", "sample": "", "threads": 1,
+                "one_thread": {"value": 1.0, "cores": 1, "sample": ""}}
+
+    monkeypatch.setattr(bench, "Workload", FakeWorkload)
+    monkeypatch.setattr(bench, "run_workload", fake_run_workload)
+    monkeypatch.setattr(bench, "cpu_baseline", fake_cpu_baseline)
+    monkeypatch.setattr(bench, "_gemm_mode", lambda: 1)
+    monkeypatch.setattr(subprocess, "run", fake_subprocess_run)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda *a: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    monkeypatch.setattr(torch.cuda, "empty_cache", lambda *a: None)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), calls
+
+
+def test_plain_run_times_the_headline_and_nothing_else(monkeypatch, capsys):
+    """`bench.py --gpus 1 --steps K --warmup W`: warm-up, the timed block, the line -- no per-kernel pass, no input-copy
+    block, no child workloads, no host baseline."""
+    d, calls = _run_main(monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert calls["run_workload"] == {"steps": 7, "warmup": 2, "profile_steps": 0, "input_copy": False, "dump_dir": None}
+    assert calls["children"] == [] and calls["cpu_baseline"] == 0
+    assert "modes" not in d and "cpu_baseline" not in d and "by_kernel" not in d["roofline"]
+    assert d["metric"] == "decode_steps_per_sec" and d["unit"] == "decode-steps/s" and d["higher_is_better"] is True
+    assert d["value"] == 640000.0 and d["ms_per_step"] == 2.0 and d["steps"] == 7 and d["warmup"] == 2
+    assert d["dtype"] == "f32 (3xbf16 split products, fp32 accumulate)"
+    assert d["roofline"]["pass_frac_executed"] > 0
+
+
+def test_full_run_adds_the_other_legs(monkeypatch, capsys):
+    """--full: the per-kernel pass, the input-copy block, the other workloads (each a child run with --full) and the host
+    baseline, as a run without --full did before; --no-modes / --no-cpu-baseline / --no-profile drop single legs."""
+    d, calls = _run_main(monkeypatch, capsys, ["--full", "--steps", "7", "--warmup", "2"])
+    assert calls["run_workload"]["profile_steps"] == 3 and calls["run_workload"]["input_copy"] is True
+    assert calls["cpu_baseline"] == 1 and "cpu_baseline" in d
+    assert sorted(d["modes"]) == ["beam5_cfg5", "forward_cfg2", "forward_cfg2_exact_fp32", "greedy_cfg5",
+                                  "train_cfg2_exact_fp32", "train_cfg4"]
+    assert len(calls["children"]) == 6 and all("--full" in c and "--no-modes" in c for c in calls["children"])
+    d, calls = _run_main(monkeypatch, capsys, ["--full", "--no-modes", "--no-cpu-baseline", "--no-profile"])
+    assert calls["run_workload"]["profile_steps"] == 0 and calls["run_workload"]["input_copy"] is True
+    assert calls["children"] == [] and calls["cpu_baseline"] == 0 and "modes" not in d and "cpu_baseline" not in d

@@ -403,7 +403,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     """`python bench.py --gpus 2` exactly as the driver types it, WITHOUT torchrun: bench.py starts torch.distributed.run
     itself as a child process (two ranks on the one GPU of this box, collectives over gloo instead of RCCL): rendezvous,
     per-rank shards, the bucket all-reduce inside the timed loop, the single JSON line relayed from rank 0 with the number
-    of ranks the probe all-reduce saw and the host baseline."""
+    of ranks the probe all-reduce saw and the host baseline (--full)."""
     import json
     import os
     import subprocess
@@ -412,7 +412,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(ICK_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-           "--cpu-seconds", "2", "--min-seconds", "0.2"]
+           "--full", "--cpu-seconds", "2", "--min-seconds", "0.2"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
