@@ -30,6 +30,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 // Diagnostic build (-DICK_DECODE_STAMPS, tools/debug/decode_stamps.py): workgroup (0, 0) of every decode kernel
 // records the shader clock at its phase boundaries.  Compiled out of the product library.
@@ -416,9 +417,12 @@ struct AttnState {      // running softmax state of one query row in one wave
 
 // pnew >= 0: position pnew is not in memory yet -- its key / value (kn, vn: this lane's float4 c) come from registers.
 // The chunk's registers are masked in place (pad columns, rows past the range).
-template <int NPC, int NQ>
+// STORE: the raw scores of query row n also go to sdst[n * sstride + p] (LDS); lane (p8, c < NPC) stores position
+// p0 + 8 c + p8, so one instruction writes the chunk's 56 scores contiguously.
+template <int NPC, int NQ, bool STORE = false>
 __device__ __forceinline__ void attend_chunk(KVRegs<NPC>& kv, const float4 (&q4)[NQ], int p0, int len, int dh,
-                                             int pnew, const float4& kn, const float4& vn, AttnState (&st)[NQ]) {
+                                             int pnew, const float4& kn, const float4& vn, AttnState (&st)[NQ],
+                                             float* sdst = nullptr, int sstride = 0) {
     const int lane = threadIdx.x & 63, p8 = lane >> 3, c = lane & 7;
     float4 (&kk)[NPC] = kv.k;
     float4 (&vv)[NPC] = kv.v;
@@ -438,6 +442,13 @@ __device__ __forceinline__ void attend_chunk(KVRegs<NPC>& kv, const float4 (&q4)
             const float s = sum8(dot4(q4[n], kk[q]));
             sc[q] = p0 + 8 * q + p8 < len ? s : -INFINITY;
             mc = fmaxf(mc, sc[q]);
+        }
+        if constexpr (STORE) {
+            float v = sc[0];
+#pragma unroll
+            for (int q = 1; q < NPC; ++q) v = c == q ? sc[q] : v;
+            const int p = p0 + 8 * c + p8;
+            if (c < NPC && p < len) sdst[n * sstride + p] = v;
         }
         mc = wave_max(mc);
         const float mnew = fmaxf(st[n].m, mc);
@@ -761,15 +772,29 @@ struct CrossArgs {
     float scale;
     const int32_t* n_done; int n_total;
 };
+// the ATTN variants' arguments (a type of their own: the kernel arguments of the others stay as they were)
+struct CrossAttnArgs : CrossArgs {
+    float* attn; int64_t attn_rs;             // (R, ., H, S) weights of this step and layer, row stride
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // cross-attention block, one workgroup per (head, group of G rows).  SHARED: the G rows are hypotheses of one caption
 // (beam search) -- its K and V are read once for all of them, each of the eight waves taking an eighth of the S memory
 // rows; otherwise the waves are dealt out as (row, part of S).  Every wave keeps its part's keys and values in
 // registers; the parts of a row meet in LDS as (maximum, sum, weighted values) records.
+// ATTN: the attention weights are written too.  A wave keeps its part's raw scores in LDS while it attends (the final
+// maximum M and sum L exist only after the parts have met); after the merge the workgroup writes exp(s - M) / L.
 // ---------------------------------------------------------------------------------------------------------
-template <int G, bool SHARED>
-__global__ __launch_bounds__(kNT) void dec_cross_kernel(CrossArgs a) {
+// ATTN: the raw scores of the G rows of a workgroup, (G, kSMax) in LDS (only the ATTN variants reference it, so the
+// others' LDS layout and code stay as they were)
+template <int G>
+__device__ __forceinline__ float* cross_scores() {
+    __shared__ float ss[G][kSMax];
+    return &ss[0][0];
+}
+
+template <int G, bool SHARED, bool ATTN>
+__global__ __launch_bounds__(kNT) void dec_cross_kernel(std::conditional_t<ATTN, CrossAttnArgs, CrossArgs> a) {
     constexpr int PARTS = SHARED ? kNW : kNW / G;       // waves per row
     constexpr int NQ = SHARED ? G : 1;                  // query rows per wave
     constexpr int NPC = 7;                              // 56 memory rows per chunk and wave
@@ -836,7 +861,11 @@ __global__ __launch_bounds__(kNT) void dec_cross_kernel(CrossArgs a) {
         const float4 none = f4zero();
         for (int p0 = 0; p0 < len; p0 += 8 * NPC) {
             if (p0 > 0) kv.template load<true>(Kb, Vb, p0, len, kv_off, kv_off);
-            attend_chunk<NPC, NQ>(kv, q4, p0, len, dh, -1, none, none, st);
+            if constexpr (ATTN)
+                attend_chunk<NPC, NQ, true>(kv, q4, p0, len, dh, -1, none, none, st,
+                                            cross_scores<G>() + (SHARED ? 0 : g_mine) * kSMax + lo, kSMax);
+            else
+                attend_chunk<NPC, NQ>(kv, q4, p0, len, dh, -1, none, none, st);
         }
 #pragma unroll
         for (int n = 0; n < NQ; ++n) {
@@ -865,11 +894,25 @@ __global__ __launch_bounds__(kNT) void dec_cross_kernel(CrossArgs a) {
         }
         const float inv = 1.f / L;
         reinterpret_cast<float4*>(&o[g][0])[cc] = make_float4(t.x * inv, t.y * inv, t.z * inv, t.w * inv);
+        if constexpr (ATTN) {
+            if (cc == 0) { pm[g][0] = M; pl[g][0] = inv; }      // tid < G * 8 is one wave: its reads are issued above
+        }
     }
     __syncthreads();
     ICK_STAMP(1, 14);
     od.template run<G>(&o[0][0], kOPad, d4, part, a.w.part + (r0 * a.H + h) * d, (int64_t)a.H * d, (int)min((int64_t)G, R - r0));
     ICK_STAMP(1, 15);
+    if constexpr (ATTN) {
+        // the rows' weights, exp(s - M) / L, in one coalesced pass of the whole workgroup (shared groups divide the rows
+        // of a caption, so only unshared groups can run past the last row)
+        const int gn = (int)min((int64_t)G, R - r0);
+        const float* ss = cross_scores<G>();
+        float* dst = a.attn + r0 * a.attn_rs + (int64_t)h * S;
+        for (int g = 0; g < gn; ++g) {
+            const float M = pm[g][0], inv = pl[g][0];
+            for (int p = tid; p < S; p += kNT) dst[g * a.attn_rs + p] = __expf(ss[g * kSMax + p] - M) * inv;
+        }
+    }
 }
 
 struct FfnArgs {
@@ -1782,23 +1825,28 @@ static void launch_ffn(int g, dim3 grid, hipStream_t s, const FfnArgs& a) {
     default: hipLaunchKernelGGL(dec_ffn_kernel<8>, grid, dim3(kNT), 0, s, a); break;
     }
 }
-static void launch_cross(int g, bool shared, dim3 grid, hipStream_t s, const CrossArgs& a) {
+template <bool ATTN, typename Args>
+static void launch_cross_t(int g, bool shared, dim3 grid, hipStream_t s, const Args& a) {
     if (!shared) {
         switch (g) {
-        case 1: hipLaunchKernelGGL((dec_cross_kernel<1, false>), grid, dim3(kNT), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((dec_cross_kernel<2, false>), grid, dim3(kNT), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((dec_cross_kernel<4, false>), grid, dim3(kNT), 0, s, a); break;
-        default: hipLaunchKernelGGL((dec_cross_kernel<8, false>), grid, dim3(kNT), 0, s, a); break;
+        case 1: hipLaunchKernelGGL((dec_cross_kernel<1, false, ATTN>), grid, dim3(kNT), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((dec_cross_kernel<2, false, ATTN>), grid, dim3(kNT), 0, s, a); break;
+        case 4: hipLaunchKernelGGL((dec_cross_kernel<4, false, ATTN>), grid, dim3(kNT), 0, s, a); break;
+        default: hipLaunchKernelGGL((dec_cross_kernel<8, false, ATTN>), grid, dim3(kNT), 0, s, a); break;
         }
         return;
     }
     switch (g) {
-    case 2: hipLaunchKernelGGL((dec_cross_kernel<2, true>), grid, dim3(kNT), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((dec_cross_kernel<3, true>), grid, dim3(kNT), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((dec_cross_kernel<4, true>), grid, dim3(kNT), 0, s, a); break;
-    case 5: hipLaunchKernelGGL((dec_cross_kernel<5, true>), grid, dim3(kNT), 0, s, a); break;
-    default: hipLaunchKernelGGL((dec_cross_kernel<8, true>), grid, dim3(kNT), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((dec_cross_kernel<2, true, ATTN>), grid, dim3(kNT), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((dec_cross_kernel<3, true, ATTN>), grid, dim3(kNT), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((dec_cross_kernel<4, true, ATTN>), grid, dim3(kNT), 0, s, a); break;
+    case 5: hipLaunchKernelGGL((dec_cross_kernel<5, true, ATTN>), grid, dim3(kNT), 0, s, a); break;
+    default: hipLaunchKernelGGL((dec_cross_kernel<8, true, ATTN>), grid, dim3(kNT), 0, s, a); break;
     }
+}
+static void launch_cross(int g, bool shared, dim3 grid, hipStream_t s, const CrossAttnArgs& a) {
+    if (a.attn == nullptr) launch_cross_t<false>(g, shared, grid, s, static_cast<const CrossArgs&>(a));
+    else launch_cross_t<true>(g, shared, grid, s, a);
 }
 
 extern "C" int ick_decode_supported(int32_t d, int32_t H, int32_t FF, int32_t S, int32_t max_len) {
@@ -1823,7 +1871,9 @@ extern "C" int ick_decode_plan(int32_t R, int32_t rows_per_sample, int32_t d, in
 }
 
 // which: bit 0 self, 1 cross, 2 ffn, 3 head, 4 vocabulary (all set in the product path; the diagnostic build times subsets)
-static int decode_layers_impl(const ick_decode_ctx* c, int32_t pos, void* stream, unsigned which, int part = 0) {
+// attn: optional (max_len, R, layers, H, S) cross-attention weights (ick_decode_layers_attn)
+static int decode_layers_impl(const ick_decode_ctx* c, int32_t pos, void* stream, unsigned which, int part = 0,
+                              float* attn = nullptr) {
     ICK_CHECK_ARG(c && c->R > 0 && c->layers > 0 && c->layers <= ICK_MAX_LAYERS && pos >= 0 && pos < c->max_len);
     ICK_CHECK_ARG(ick_decode_supported(c->d, c->H, c->FF, c->S, c->max_len));
     ICK_CHECK_ARG(c->rows_per_sample > 0 && c->R % c->rows_per_sample == 0 && c->R <= 65535);
@@ -1864,13 +1914,15 @@ static int decode_layers_impl(const ick_decode_ctx* c, int32_t pos, void* stream
         if ((which & 1u) && !(part == 2 && first_self))
             launch_self(plan.g_self, fsel, dim3(H, ceil_div(R, plan.g_self)), s, sa);
         if (part == 1) { ICK_LAUNCH_RET(); }
-        CrossArgs ca;
+        CrossAttnArgs ca;
         ca.w.in_w = w.ca_in_w; ca.w.in_b = w.ca_in_b; ca.w.out_wt = w.ca_out_wt;
         ca.w.src = make_src(c, c->xa, c->p1, H, w.sa_out_b, w.n1_g, w.n1_b, c->xb);
         ca.w.part = c->p2;
         ca.Kmem = w.cross_k; ca.Vmem = w.cross_v; ca.kv_bs = c->kv_bs;
         ca.R = R; ca.rows_per_sample = c->rows_per_sample; ca.d = d; ca.H = H; ca.dh = dh; ca.S = c->S; ca.scale = scale;
         ca.n_done = c->n_done; ca.n_total = R;
+        ca.attn = attn == nullptr ? nullptr : attn + ((int64_t)pos * R * c->layers + l) * H * c->S;
+        ca.attn_rs = (int64_t)c->layers * H * c->S;
         if (which & 2u) launch_cross(plan.g_cross, plan.cross_shared, dim3(H, ceil_div(R, plan.g_cross)), s, ca);
         FfnArgs fa;
         fa.w1 = w.w1; fa.b1 = w.b1; fa.w2t = w.w2t;
@@ -1907,6 +1959,11 @@ extern "C" int ick_decode_layers(const ick_decode_ctx* c, int32_t pos, void* str
 extern "C" int ick_decode_layers_part(const ick_decode_ctx* c, int32_t pos, int32_t part, void* stream) {
     ICK_CHECK_ARG(part >= 0 && part <= 2);
     return decode_layers_impl(c, pos, stream, 31u, part);
+}
+
+extern "C" int ick_decode_layers_attn(const ick_decode_ctx* c, float* attn, int32_t pos, int32_t part, void* stream) {
+    ICK_CHECK_ARG(part >= 0 && part <= 2);
+    return decode_layers_impl(c, pos, stream, 31u, part, attn);
 }
 
 // every per-call buffer of a greedy decode in one launch (they were eight fills, an embedding and a copy)

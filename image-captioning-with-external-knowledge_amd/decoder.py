@@ -97,6 +97,39 @@ class DropSites:
 
 _NO_DROPOUT = DropSites(0, False)
 
+# return_attention: the largest weight buffer a decode call may allocate, (max_len, rows, layers, H, S) fp32
+ATTENTION_MAX_BYTES = 1 << 30
+
+
+def _attention_check(what, max_len, rows, layers, H, S):
+    nbytes = 4 * max_len * rows * layers * H * S
+    if nbytes > ATTENTION_MAX_BYTES:
+        raise IckError("%s(return_attention=True) would need a %.0f MB weight buffer (max_len %d x rows %d x layers %d x "
+                       "heads %d x S %d fp32); the limit is ATTENTION_MAX_BYTES = %d MB"
+                       % (what, nbytes / 2 ** 20, max_len, rows, layers, H, S, ATTENTION_MAX_BYTES >> 20))
+
+
+def _zero_after_end(attn, tokens, end_token):
+    """Zero, in place, the steps of every row after its first <end> in tokens (rows, max_len); attn (max_len, rows, ...).
+    The <end> step itself keeps the weights that chose it."""
+    is_end = (tokens == end_token).to(torch.int32)
+    live = (torch.cumsum(is_end, dim=1) - is_end) == 0            # no <end> before this step
+    attn.mul_(live.t().to(attn.dtype).reshape(live.shape[1], live.shape[0], *([1] * (attn.dim() - 2))))
+    return attn
+
+
+def split_attention(attn, P, K, F=0):
+    """Views of a cross-attention weight tensor (..., S) along its memory axis S = P + K + F, in the decode K/V order
+    [image ; entities ; facts]: {"image": (..., P), or (..., h, w) when P = h * w is a perfect square (the encoder's
+    h x w grid, row-major), "entities": (..., K), "facts": (..., F)}."""
+    if attn.shape[-1] != P + K + F:
+        raise IckError("split_attention: the last axis has %d rows, P + K + F = %d" % (attn.shape[-1], P + K + F))
+    img = attn[..., :P]
+    side = math.isqrt(P)
+    if side * side == P:
+        img = img.unflatten(-1, (side, side))
+    return {"image": img, "entities": attn[..., P:P + K], "facts": attn[..., P + K:]}
+
 
 def _wb(linear):
     return linear.weight.detach(), linear.bias.detach()
@@ -1113,8 +1146,9 @@ class DecoderTransformer(nn.Module):
         ops.decode_init(c, self.word_map["<start>"], n_done_init)
         return c, t
 
-    def _predict_fused(self, enc_tok, entities, facts, max_pred_len):
-        """predict() on the fused decode kernels (csrc/decode.hip): 12 launches per token (13 with facts)."""
+    def _predict_fused(self, enc_tok, entities, facts, max_pred_len, attention=False):
+        """predict() on the fused decode kernels (csrc/decode.hip): 12 launches per token (13 with facts).  attention:
+        also return the cross-attention weights (max_len, B, layers, H, S), zero after each row's <end>."""
         B = enc_tok.shape[0]
         d, V, K = self.emb_dim, self.vocab_size, entities.shape[1]
         ee, fe, kv, _, side = self._encode_context(enc_tok, entities, facts, None)
@@ -1124,6 +1158,7 @@ class DecoderTransformer(nn.Module):
         # last step needs the selection kernel of its own: 11 launches per token (12 with facts)
         fuse = self.fuse_select
         c, t = self._decode_ctx(kv, ee, fe, 1, max_pred_len, S, fuse_select=fuse)
+        attn = torch.zeros(max_pred_len, B, c.layers, c.H, S, device=kv.device) if attention else None
 
         def indicators():
             ops.context_indicators(t["cap_buf"], facts, K, V, self._pred_wt(), self.fc_predicate.bias.detach(),
@@ -1134,19 +1169,29 @@ class DecoderTransformer(nn.Module):
                 ops.decode_layers_part(c, i, 1)           # selection of step i - 1 + first self-attention block
                 if self.has_facts:
                     indicators()
-                ops.decode_layers_part(c, i, 2)
+                if attention:
+                    ops.decode_layers_attn(c, attn, i, 2)
+                else:
+                    ops.decode_layers_part(c, i, 2)
             else:
                 if self.has_facts:
                     indicators()
-                ops.decode_layers(c, i)
+                if attention:
+                    ops.decode_layers_attn(c, attn, i)
+                else:
+                    ops.decode_layers(c, i)
             if not fuse or i == max_pred_len - 1:
                 ops.decode_select_greedy(c, i)
+        if attention:
+            return t["output"], _zero_after_end(attn, t["output"], self.word_map["<end>"])
         return t["output"]
 
-    def _predict_beam_device(self, enc_tok, entities, facts, max_pred_len, beam):
+    def _predict_beam_device(self, enc_tok, entities, facts, max_pred_len, beam, attention=False):
         """Beam search on the fused decode kernels: R = B * beam rows share their caption's cross K/V; the
         self-attention cache is never reordered -- an ancestry table says which cache row holds position p of a
-        hypothesis.  Returns (best sequence (B, max_len), its log-probability (B), all sequences, all scores)."""
+        hypothesis.  Returns (best sequence (B, max_len), its log-probability (B), all sequences, all scores); with
+        attention also the cross-attention weights of the best (max_len, B, layers, H, S) and of every final hypothesis
+        (max_len, B, beam, layers, H, S)."""
         from . import lib as L
         B = enc_tok.shape[0]
         d, V, K = self.emb_dim, self.vocab_size, entities.shape[1]
@@ -1172,6 +1217,7 @@ class DecoderTransformer(nn.Module):
         Vx = V + K + (fe.shape[1] if fe is not None else 0)
         rec = torch.empty(R, (Vx + 1023) // 1024, 18, device=dev, dtype=torch.float32)
         bs.rec = rec.data_ptr()
+        attn = torch.zeros(max_pred_len, R, c.layers, c.H, S, device=dev) if attention else None
         for i in range(max_pred_len):
             cur, nxt = i & 1, (i + 1) & 1
             c.anc = anc[cur].data_ptr()
@@ -1179,25 +1225,40 @@ class DecoderTransformer(nn.Module):
                 ops.context_indicators(cap[cur], facts_r, K, V, self._pred_wt(), self.fc_predicate.bias.detach(), mode=1,
                                        eib=t["eib"], gate=t["gate"])
                 bs.cap_in, bs.cap_out = cap[cur].data_ptr(), cap[nxt].data_ptr()
-            ops.decode_layers(c, i)
+            if attention:
+                ops.decode_layers_attn(c, attn, i)
+            else:
+                ops.decode_layers(c, i)
             bs.seq_in, bs.seq_out = seq[cur].data_ptr(), seq[nxt].data_ptr()
             bs.anc_in, bs.anc_out = anc[cur].data_ptr(), anc[nxt].data_ptr()
             ops.decode_select_beam(c, bs, i)
         final = seq[max_pred_len & 1].view(B, beam, max_pred_len)
         best = cum.argmax(dim=1)                          # ties: the lower hypothesis
         out = final[torch.arange(B, device=dev), best]
-        return out, cum.gather(1, best.view(B, 1)).view(B), final, cum
+        if not attention:
+            return out, cum.gather(1, best.view(B, 1)).view(B), final, cum
+        # rows are never reordered: position p of a final hypothesis was computed by row anc[hyp, p] (global row index)
+        anc_fin = anc[max_pred_len & 1].t().long()                                        # (max_len, R)
+        steps = torch.arange(max_pred_len, device=dev).view(-1, 1)
+        hyp = _zero_after_end(attn[steps, anc_fin], final.view(R, max_pred_len), self.word_map["<end>"])
+        hyp = hyp.view(max_pred_len, B, beam, *hyp.shape[2:])
+        return out, cum.gather(1, best.view(B, 1)).view(B), final, cum, hyp[:, torch.arange(B, device=dev), best], hyp
 
     @torch.no_grad()
-    def predict_beam(self, encoder_out, max_pred_len, entities, facts=None, beam_size=5, return_all=False):
+    def predict_beam(self, encoder_out, max_pred_len, entities, facts=None, beam_size=5, return_all=False,
+                     return_attention=False):
         """Beam-search decode (north_star cfg5: beam 5, batch 32).  The reference decodes greedily only
         (geo-aware/eval.py:61,83), so beam > 1 has no reference output to pin against ("parity-unpinned"); the tests
         check it against a CPU beam search written to the same rules.  beam_size == 1 IS predict(): the pinned greedy path with
         its n-gram clean-up.  Hypotheses are scored by their summed log-probability (log_softmax over the V+K+F
         scores); an ended hypothesis keeps competing with its final score; the best of the beam is returned as
-        LongTensor (max_pred_len, B), <pad> after <end>."""
+        LongTensor (max_pred_len, B), <pad> after <end>.  return_all adds (best log-probability (B), every final
+        hypothesis (B, beam, max_len), their log-probabilities (B, beam)).  return_attention appends the cross-attention
+        weights of the best hypothesis, float32 (max_pred_len, B, layers, H, S) (see predict()), and with return_all
+        those of every final hypothesis, (max_pred_len, B, beam, layers, H, S)."""
         if beam_size == 1:
-            return DecoderTransformer.predict(self, encoder_out, max_pred_len, entities, facts)
+            return DecoderTransformer.predict(self, encoder_out, max_pred_len, entities, facts,
+                                              return_attention=return_attention)
         encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
         entities = entities.contiguous()
         enc_tok, P = self._image_input(encoder_out)
@@ -1209,21 +1270,31 @@ class DecoderTransformer(nn.Module):
                 or not ops.decode_beam_supported(Vx, beam_size):
             raise IckError("predict_beam needs 1 <= beam_size <= 8, beam_size^2 * ceil((V+K+F)/1024) <= 4096 and sizes "
                            "the fused decode kernels support")
+        if return_attention:
+            _attention_check("predict_beam", max_pred_len, enc_tok.shape[0] * beam_size,
+                             len(self.transformer_decoder.layers), self.num_heads, S_all)
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, beam_size) + self._enc_key(enc_tok)
-            res = self._graphed("beam", key, lambda t, e, f: self._predict_beam_device(t, e, f, max_pred_len, beam_size),
+            res = self._graphed("beam_attn" if return_attention else "beam", key,
+                                lambda t, e, f: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
+                                                                          return_attention),
                                 [enc_tok, entities, facts])
         else:
-            res = self._predict_beam_device(enc_tok, entities, facts, max_pred_len, beam_size)
+            res = self._predict_beam_device(enc_tok, entities, facts, max_pred_len, beam_size, return_attention)
         out = res[0].t().contiguous()
-        return (out, res[1], res[2], res[3]) if return_all else out
+        if not return_attention:
+            return (out, res[1], res[2], res[3]) if return_all else out
+        if return_all:
+            return out, res[1], res[2], res[3], res[4].clone(), res[5].clone()
+        return out, res[4].clone()
 
-    def _predict_sample_device(self, enc_tok, entities, facts, knobs, max_pred_len, n):
+    def _predict_sample_device(self, enc_tok, entities, facts, knobs, max_pred_len, n, attention=False):
         """Sampled decode on the fused decode kernels: R = B * n rows, the n samples of a caption share its cross K/V
         and keep their own self-attention caches.  knobs: int64 (3) device tensor [seed, temperature | top_p << 32
         (two fp32 words), top_k] -- read by the selection kernel, so a replay sees whatever was copied into it.
-        Returns (tokens (R, max_len), log-probabilities (R, max_len))."""
+        Returns (tokens (R, max_len), log-probabilities (R, max_len)[, cross-attention weights (max_len, R, layers, H,
+        S)])."""
         from . import lib as L
         dev = enc_tok.device
         V, K = self.vocab_size, entities.shape[1]
@@ -1235,17 +1306,23 @@ class DecoderTransformer(nn.Module):
         st = L.SampleState()
         base = knobs.data_ptr()
         st.seed, st.temp_top_p, st.top_k, st.log_prob = base, base + 8, base + 16, log_prob.data_ptr()
+        attn = torch.zeros(max_pred_len, c.R, c.layers, c.H, c.S, device=dev) if attention else None
         for i in range(max_pred_len):
             if self.has_facts:
                 ops.context_indicators(t["cap_buf"], facts_r, K, V, self._pred_wt(), self.fc_predicate.bias.detach(),
                                        mode=1, eib=t["eib"], gate=t["gate"])
-            ops.decode_layers(c, i)
+            if attention:
+                ops.decode_layers_attn(c, attn, i)
+            else:
+                ops.decode_layers(c, i)
             ops.decode_select_sample(c, st, i)
+        if attention:
+            return t["output"], log_prob, _zero_after_end(attn, t["output"], self.word_map["<end>"])
         return t["output"], log_prob
 
     @torch.no_grad()
     def predict_sample(self, encoder_out, max_pred_len, entities, facts=None, num_samples=1, temperature=1.0, top_k=0,
-                       top_p=1.0, seed=None, return_log_probs=False):
+                       top_p=1.0, seed=None, return_log_probs=False, return_attention=False):
         """Stochastic decode: `num_samples` captions per image drawn from the model's distribution, with temperature,
         top-k and nucleus (top-p) truncation.  Per row and step over the V+K+F raw scores s: z = s / temperature;
         top-k keeps s >= the k-th largest s (ties at the boundary all kept); top-p then keeps the tokens whose
@@ -1259,7 +1336,9 @@ class DecoderTransformer(nn.Module):
         after <end>; with return_log_probs also a float tensor of the same shape: the model's log-probability
         (log_softmax of the raw scores, T = 1, untruncated) of every generated token, 0 after <end>.  seed=None draws a
         63-bit seed from torch's default CPU generator; an integer seed makes the call bit-reproducible.  The knobs
-        and the seed are inputs of the captured decode graph: changing them replays it without a new capture."""
+        and the seed are inputs of the captured decode graph: changing them replays it without a new capture.
+        return_attention appends the cross-attention weights, float32 (max_pred_len, B * num_samples, layers, H, S) (see
+        predict()); the tokens and log-probabilities are the same bits as without it."""
         if not (isinstance(num_samples, int) and num_samples >= 1):
             raise IckError("predict_sample needs num_samples >= 1")
         if not (math.isfinite(temperature) and temperature > 0):
@@ -1280,6 +1359,9 @@ class DecoderTransformer(nn.Module):
                 or not ops.decode_sample_supported(Vx, num_samples):
             raise IckError("predict_sample needs B * num_samples <= 65535, V+K+F <= 65536 and sizes the fused decode "
                            "kernels support")
+        if return_attention:
+            _attention_check("predict_sample", max_pred_len, B * num_samples, len(self.transformer_decoder.layers),
+                             self.num_heads, S_all)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (), dtype=torch.int64))
         seed = int(seed) & (2 ** 64 - 1)
@@ -1289,15 +1371,19 @@ class DecoderTransformer(nn.Module):
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, num_samples) + self._enc_key(enc_tok)
-            tok, lp = self._graphed("sample", key,
-                                    lambda t, e, f, k: self._predict_sample_device(t, e, f, k, max_pred_len, num_samples),
-                                    [enc_tok, entities, facts, knobs])
+            res = self._graphed("sample_attn" if return_attention else "sample", key,
+                                lambda t, e, f, k: self._predict_sample_device(t, e, f, k, max_pred_len, num_samples,
+                                                                               return_attention),
+                                [enc_tok, entities, facts, knobs])
         else:
-            tok, lp = self._predict_sample_device(enc_tok, entities, facts, knobs, max_pred_len, num_samples)
-        out = tok.t().contiguous()
-        return (out, lp.t().contiguous()) if return_log_probs else out
+            res = self._predict_sample_device(enc_tok, entities, facts, knobs, max_pred_len, num_samples, return_attention)
+        out = res[0].t().contiguous()
+        ret = (out, res[1].t().contiguous()) if return_log_probs else (out,)
+        if return_attention:
+            ret += (res[2].clone(),)
+        return ret if len(ret) > 1 else out
 
-    def _predict_device(self, enc_tok, entities, facts, max_pred_len):
+    def _predict_device(self, enc_tok, entities, facts, max_pred_len, attention=False):
         """Whole greedy decode on the device: every step's token choice, clean-up and stop flag are computed
         by kernels (no host round trip), so the loop can be captured as one hipGraph."""
         dev = enc_tok.device
@@ -1307,7 +1393,9 @@ class DecoderTransformer(nn.Module):
         S_all = P + K + (facts.shape[1] if facts is not None else 0)
         FF = self.transformer_decoder.layers[0].linear1.out_features
         if self.fused_decode and ops.decode_supported(d, self.num_heads, FF, S_all, max_pred_len):
-            return self._predict_fused(enc_tok, entities, facts, max_pred_len)
+            return self._predict_fused(enc_tok, entities, facts, max_pred_len, attention)
+        if attention:
+            raise IckError("return_attention needs the fused decode kernels")
         ee, fe, kv, _, side = self._encode_context(enc_tok, entities, facts, None)
         side.join()
         S = kv.shape[3]
@@ -1342,18 +1430,36 @@ class DecoderTransformer(nn.Module):
         return output
 
     @torch.no_grad()
-    def predict(self, encoder_out, max_pred_len, entities, facts=None):
+    def predict(self, encoder_out, max_pred_len, entities, facts=None, return_attention=False):
         """Greedy decode with the reference's semantics per caption (argmax, <end> stop, repeated
         n-gram clean-up, pointer masks), KV-cached: step i only projects position i.  Works for any
-        batch size (B independent captions); returns LongTensor (max_pred_len, B), <pad> after <end>."""
+        batch size (B independent captions); returns LongTensor (max_pred_len, B), <pad> after <end>.
+
+        return_attention=True also returns the decoder's cross-attention weights, float32 on the device,
+        (max_pred_len, B, layers, H, S): softmax(q . k / sqrt(dh)) of the query at step i (the one that produced output
+        token i) over the S = P + K + F memory rows [image ; entities ; facts] (split_attention() cuts that axis).  Steps
+        after a row's <end> are zero (the <end> step keeps the weights that chose it).  Needs the fused decode kernels
+        and a buffer of at most ATTENTION_MAX_BYTES; the tokens are the same bits as without it."""
         encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
         entities = entities.contiguous()
-        enc_tok = self._image_input(encoder_out)[0].contiguous()
+        enc_tok, P = self._image_input(encoder_out)
+        enc_tok = enc_tok.contiguous()
+        if return_attention:
+            FF = self.transformer_decoder.layers[0].linear1.out_features
+            S_all = P + entities.shape[1] + (facts.shape[1] if facts is not None else 0)
+            if not self.fused_decode or not ops.decode_supported(self.emb_dim, self.num_heads, FF, S_all, max_pred_len):
+                raise IckError("predict(return_attention=True) needs fused_decode and sizes the fused decode kernels "
+                               "support")
+            _attention_check("predict", max_pred_len, enc_tok.shape[0], len(self.transformer_decoder.layers),
+                             self.num_heads, S_all)
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len) + self._enc_key(enc_tok)
-            output = self._graphed("greedy", key, lambda t, e, f: self._predict_device(t, e, f, max_pred_len),
-                                   [enc_tok, entities, facts])
+            res = self._graphed("greedy_attn" if return_attention else "greedy", key,
+                                lambda t, e, f: self._predict_device(t, e, f, max_pred_len, return_attention),
+                                [enc_tok, entities, facts])
         else:
-            output = self._predict_device(enc_tok, entities, facts, max_pred_len)
-        return output.t().contiguous()
+            res = self._predict_device(enc_tok, entities, facts, max_pred_len, return_attention)
+        if return_attention:
+            return res[0].t().contiguous(), res[1].clone()
+        return res.t().contiguous()

@@ -5,6 +5,7 @@ generated_captions.csv.  The domain metrics that follow in the reference (Jensen
 are CPU text statistics outside this path."""
 import os
 
+import numpy as np
 import pandas as pd
 import torch
 
@@ -38,10 +39,13 @@ def detokenize(seq, word_map, rev_word_map, entity_names, fact_names=None):
 
 @torch.no_grad()
 def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="generated_captions.csv", device="cuda",
-             sample=None):
+             sample=None, attention_out=None):
     """sample=None: greedy decode (predict), one CSV row per image.  sample = a dict of predict_sample keyword arguments
     (num_samples, temperature, top_k, top_p, seed): sampled decode, one CSV row per (image, sample) with the columns
-    image (running index over the loader), sample, generated_caption; an explicit seed is advanced by one per batch."""
+    image (running index over the loader), sample, generated_caption; an explicit seed is advanced by one per batch.
+    attention_out: a path for one .npz of the decoder's cross-attention (return_attention of predict / predict_sample):
+    "attention" float16 (N, max_len, S), the last decoder layer's weights averaged over its heads, one row per CSV row;
+    "tokens" int64 (N, max_len); "P", "K", "F": how the S memory rows split into image, entity and fact rows."""
     decoder.eval()
     encoder.eval()
     rev = {v: k for k, v in word_map.items()}
@@ -51,6 +55,8 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
     # beside the context encoders (decoder.attach_encoder); raw images go through the encoder's trunk first
     decoder.attach_encoder(encoder)
     img_buf = None
+    attn_rows, attn_split = [], None
+    want_attn = attention_out is not None
     for bi, batch in enumerate(loader):                       # any batch size: captions decode independently
         ent, names = batch[4], batch[5]
         has_facts = len(batch) > 6
@@ -64,13 +70,25 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
         else:
             image = batch[0].to(device)
         enc_in = image if feature_map else encoder(image)
+        attn = None
         if sample is None:
-            seq = decoder.predict(enc_in, max_caption_len, ent, *extra)                     # (max_len, B)
+            seq = decoder.predict(enc_in, max_caption_len, ent, *extra, return_attention=want_attn)  # (max_len, B)
         else:
             kw = dict(sample)
             if kw.get("seed") is not None:       # a batch's caption b would otherwise reuse the noise of every other batch's b
                 kw["seed"] = int(kw["seed"]) + bi
-            seq = decoder.predict_sample(enc_in, max_caption_len, ent, *extra, **kw)   # (max_len, B * n)
+            kw.pop("return_log_probs", None)
+            seq = decoder.predict_sample(enc_in, max_caption_len, ent, *extra, return_attention=want_attn, **kw)
+        if want_attn:
+            seq, attn = seq
+            # (max_len, rows, layers, H, S) -> last layer, mean over heads -> (rows, max_len, S)
+            attn_rows.append(attn[:, :, -1].mean(dim=2).transpose(0, 1).to(torch.float16).cpu())
+            K, F = ent.shape[1], (batch[6].shape[1] if has_facts else 0)
+            split = (attn.shape[-1] - K - F, K, F)
+            if attn_split is not None and attn_split != split:
+                raise ValueError("evaluate(attention_out=...): batches with different memory sizes %s / %s"
+                                 % (attn_split, split))
+            attn_split = split
         bufs = decoder.input_buffers() if feature_map else None
         img_buf = bufs[0] if bufs is not None and bufs[0] is not None and bufs[0].dim() == 4 else None
         for b in range(seq.shape[1]):
@@ -79,6 +97,10 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
             k = b // n
             captions.append(detokenize(ids, word_map, rev, names[k], batch[7][k] if has_facts else None))
             rows.append((len(rows) // n, b % n))
+    if want_attn:
+        P, K, F = attn_split if attn_split is not None else (0, 0, 0)
+        np.savez(attention_out, attention=torch.cat(attn_rows).numpy() if attn_rows else np.zeros((0, max_caption_len, 0),
+                 np.float16), tokens=np.asarray(sequences, dtype=np.int64).reshape(-1, max_caption_len), P=P, K=K, F=F)
     if out_csv:
         if sample is None:
             pd.DataFrame({"generated_caption": captions}).to_csv(out_csv, index=False)

@@ -18,5 +18,5 @@ class DecoderTransformer(_Engine):
     def forward(self, captions, encoder_out, caption_masks, caption_lengths, entities):
         return super().forward(captions, encoder_out, caption_masks, caption_lengths, entities)
 
-    def predict(self, encoder_out, max_pred_len, entities):
-        return super().predict(encoder_out, max_pred_len, entities)
+    def predict(self, encoder_out, max_pred_len, entities, return_attention=False):
+        return super().predict(encoder_out, max_pred_len, entities, return_attention=return_attention)

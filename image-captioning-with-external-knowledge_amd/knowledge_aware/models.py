@@ -15,5 +15,5 @@ class DecoderTransformer(_Engine):
     def forward(self, captions, encoder_out, caption_masks, caption_lengths, entities, facts):
         return super().forward(captions, encoder_out, caption_masks, caption_lengths, entities, facts)
 
-    def predict(self, encoder_out, max_pred_len, entities, facts):
-        return super().predict(encoder_out, max_pred_len, entities, facts)
+    def predict(self, encoder_out, max_pred_len, entities, facts, return_attention=False):
+        return super().predict(encoder_out, max_pred_len, entities, facts, return_attention=return_attention)

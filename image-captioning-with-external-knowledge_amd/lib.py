@@ -185,6 +185,7 @@ SIGNATURES = {
     "ick_decode_plan": [i32, i32, i32, i32, i32, C.POINTER(i32)],
     "ick_decode_layers": [C.POINTER(DecodeCtx), i32, vp],
     "ick_decode_layers_part": [C.POINTER(DecodeCtx), i32, i32, vp],
+    "ick_decode_layers_attn": [C.POINTER(DecodeCtx), vp, i32, i32, vp],
     "ick_decode_init": [C.POINTER(DecodeCtx), i32, i32, vp],
     "ick_decode_select_greedy": [C.POINTER(DecodeCtx), i32, vp],
     "ick_decode_select_beam": [C.POINTER(DecodeCtx), C.POINTER(BeamState), i32, vp],

@@ -625,6 +625,20 @@ def decode_layers_part(ctx, pos, part):
     L.check(L.load().ick_decode_layers_part(C.byref(ctx), pos, part, _stream()), "ick_decode_layers_part")
 
 
+def decode_layers_attn(ctx, attn, pos, part=0):
+    """decode_layers_part that also writes step `pos`'s cross-attention weights into attn: a float32 device tensor
+    (max_len, R, layers, H, S) (ick_decode_layers_attn; attn=None: exactly decode_layers_part)."""
+    if attn is not None:
+        want = (ctx.max_len, ctx.R, ctx.layers, ctx.H, ctx.S)
+        if not (attn.is_cuda and attn.dtype == torch.float32 and attn.is_contiguous() and tuple(attn.shape) == want):
+            raise L.IckError("decode_layers_attn needs a contiguous float32 device tensor of shape %s (got %s %s on %s)"
+                             % (want, tuple(attn.shape), attn.dtype, attn.device))
+    if part not in (0, 1, 2):
+        raise L.IckError("decode_layers_attn: part must be 0, 1 or 2")
+    L.check(L.load().ick_decode_layers_attn(C.byref(ctx), None if attn is None else attn.data_ptr(), pos, part,
+                                            _stream()), "ick_decode_layers_attn")
+
+
 def decode_init(ctx, start_token, n_done_init=0):
     L.check(L.load().ick_decode_init(C.byref(ctx), start_token, n_done_init, _stream()), "ick_decode_init")
 

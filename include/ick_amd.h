@@ -386,6 +386,14 @@ int ick_decode_layers(const ick_decode_ctx* ctx, int32_t pos, void* stream);
  * part 2: everything behind it; part 0 = ick_decode_layers): the knowledge variants run ick_context_indicators on the
  * caption buffer between the two. */
 int ick_decode_layers_part(const ick_decode_ctx* ctx, int32_t pos, int32_t part, void* stream);
+/* ick_decode_layers_part that also writes the cross-attention weights of step `pos`: softmax(q . k / sqrt(dh)) over
+ * the S memory rows [P image ; K entity ; F fact] (the order of the cross K/V buffer), for every row, layer and head,
+ * with the query of position pos (the one that produces output token pos).  attn: caller-owned fp32
+ * (max_len, R, layers, H, S); this call fills attn[pos] (parts 0 and 2; part 1 launches no cross-attention).  Nothing
+ * is written when every row has ended before the step (*n_done >= R), and rows that ended earlier are still written:
+ * the caller zeroes the buffer before the decode and masks the steps after each row's <end> afterwards.
+ * attn == NULL: exactly ick_decode_layers_part. */
+int ick_decode_layers_attn(const ick_decode_ctx* ctx, float* attn, int32_t pos, int32_t part, void* stream);
 /* One launch that initialises every per-call buffer of a decode: output = <pad>, history / flags / windows = 0,
  * caption buffer = <start>, *n_done = n_done_init, x0 = embedding of <start> at position 0. */
 int ick_decode_init(const ick_decode_ctx* ctx, int32_t start_token, int32_t n_done_init, void* stream);
