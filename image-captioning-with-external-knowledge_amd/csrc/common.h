@@ -170,6 +170,52 @@ __device__ __forceinline__ uint32_t epoch_seed(uint32_t seed, const uint32_t* ep
     return seed + *epoch;                   // (the host pass only parses device code)
 #endif
 }
+// Decoding rules of beam search and sampling (ick_decode_rules).  The four rule words
+// {no_repeat_ngram_size, min_len, length penalty on, 0} are device memory written by the host before a (replayed)
+// decode; the first three are read through the scalar cache like epoch_seed()'s counter.  words == nullptr: every
+// rule off.
+constexpr int kRuleHistMax = 128;        // caption positions a ban looks back over (the fused decode's max_len)
+__device__ __forceinline__ uint4 rule_words(const int32_t* words) {
+    if (words == nullptr) return make_uint4(0u, 0u, 0u, 0u);    // uniform
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t w01;
+    uint32_t w2;
+    asm volatile("s_load_dwordx2 %0, %2, 0x0\n\ts_load_dword %1, %2, 0x8\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(w01), "=&s"(w2) : "s"(words) : "memory");
+    return make_uint4((uint32_t)w01, (uint32_t)(w01 >> 32), w2, 0u);
+#else
+    return make_uint4((uint32_t)words[0], (uint32_t)words[1], (uint32_t)words[2], (uint32_t)words[3]);
+#endif
+}
+
+// The banned columns of one row at step t, as a bit mask in LDS over the columns [c0, c0 + 32 * nwords):
+//   no-repeat n-gram (n > 0): y_p for n-1 <= p <= t-1 with y_{p-n+1..p-1} == y_{t-n+1..t-1} (n = 1: every earlier token)
+//   min length:              <end> while t < m
+// hist: the row's tokens y_0 .. y_{t-1} (global, t <= kRuleHistMax); hs: LDS scratch of kRuleHistMax ints.  Every
+// thread of the workgroup calls it (it synchronises); on return the mask is complete and visible to all of them.
+template <typename Tok>
+__device__ __forceinline__ void mark_bans(const Tok* hist, int t, int n, int m, int end_token, uint32_t* bits, int c0,
+                                          int nwords, int* hs) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int w = tid; w < nwords; w += nt) bits[w] = 0u;
+    if (n > 0)
+        for (int p = tid; p < t; p += nt) hs[p] = (int)hist[p];
+    __syncthreads();
+    if (n > 0) {
+        for (int p = n - 1 + tid; p < t; p += nt) {
+            bool match = true;
+            for (int j = 1; j < n; ++j) match = match && hs[p - j] == hs[t - j];
+            const int c = hs[p] - c0;
+            if (match && c >= 0 && c < 32 * nwords) atomicOr(&bits[c >> 5], 1u << (c & 31));
+        }
+    }
+    if (tid == 0 && t < m) {
+        const int c = end_token - c0;
+        if (c >= 0 && c < 32 * nwords) atomicOr(&bits[c >> 5], 1u << (c & 31));
+    }
+    __syncthreads();
+}
+
 struct DropArg {
     float p;
     uint32_t seed, site;

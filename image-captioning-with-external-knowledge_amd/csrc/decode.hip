@@ -1513,6 +1513,9 @@ struct BeamArgs {
     int R, k, d, V, K, F, step, max_len, has_facts, end_token, pad_token, start_token;
     float emb_scale;
     int n_total;
+    // decoding rules (the RULES variant): rule words (length penalty: words[2] != 0), lp[0..max_len], and the tokens
+    // of every hypothesis, <end> included
+    const int32_t* words; const float* lp; int32_t* len;
 };
 
 // Block-wide arg-best of (value, code) pairs: larger value wins, ties go to the smaller code.  Result in every thread.
@@ -1550,15 +1553,23 @@ struct BeamPartArgs {
     float* rec;                         // (R, nchunk, kBeamRec)
     int R, k, V, np, nchunk;
     const int32_t* n_done; int n_total;
+    // decoding rules (nullptr: off): the row's tokens so far seq (R, max_len), the rule words
+    const int64_t* seq; const int32_t* words;
+    int step, max_len, end_token;
 };
+template <bool RULES>      // RULES: the decoding-rules variant (ick_decode_select_beam_rules)
 __global__ __launch_bounds__(256) void dec_beam_partial_kernel(BeamPartArgs a) {
     if (*a.n_done >= a.n_total) return;
     __shared__ float shv[4];
     __shared__ int shc[4];
     __shared__ float red[8];
+    __shared__ uint32_t ban[kBeamChunk / 32];
+    __shared__ int hs[kRuleHistMax];
     const int tid = threadIdx.x, ch = blockIdx.x;
     const int64_t r = blockIdx.y;
     if (a.fin[r] || a.cum[r] == -INFINITY) return;         // ended / unused hypothesis: nothing to expand (uniform)
+    const uint4 rw = RULES ? rule_words(a.words) : make_uint4(0u, 0u, 0u, 0u);
+    const int nrep = (int)rw.x, mlen = (int)rw.y;
     const int Vx = a.V + a.np;
     const float* row = a.scores + r * a.ld;
     const float* pr = a.ptr + r * a.np;
@@ -1579,6 +1590,14 @@ __global__ __launch_bounds__(256) void dec_beam_partial_kernel(BeamPartArgs a) {
     e = block_sum<4>(e, red);
     float* rec = a.rec + (r * a.nchunk + ch) * kBeamRec;
     if (tid == 0) { rec[0] = m; rec[1] = e; }
+    if (RULES && (nrep > 0 || a.step < mlen)) {             // uniform: the banned columns leave the pool (not the sums)
+        mark_bans(a.seq + r * a.max_len, a.step, nrep, mlen, a.end_token, ban, ch * kBeamChunk, kBeamChunk / 32, hs);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c = tid + 256 * q;
+            if ((ban[c >> 5] >> (c & 31)) & 1u) { x[q] = -INFINITY; idx[q] = kNone; }
+        }
+    }
     for (int round = 0; round < a.k; ++round) {
         float bv = -INFINITY; int bc = kNone;
 #pragma unroll
@@ -1595,6 +1614,7 @@ __global__ __launch_bounds__(256) void dec_beam_partial_kernel(BeamPartArgs a) {
     }
 }
 
+template <bool RULES>
 __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     // No exit on *n_done here: other workgroups of this very launch add to it, and the hypothesis tables are
     // ping-pong buffers -- a step that skipped its carry-copy would leave the previous step's rows (in another
@@ -1604,11 +1624,19 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     __shared__ int shc[4];
     __shared__ float cum_s[kBeamMax], lse_s[kBeamMax];
     __shared__ int fin_s[kBeamMax], parent_s[kBeamMax], tok_s[kBeamMax], nfin_s[kBeamMax];
+    __shared__ int len_s[kBeamMax];
+    __shared__ float lpf_s[kBeamMax];
     const int tid = threadIdx.x, k = a.k;
     const int64_t r0 = (int64_t)blockIdx.x * k;
     const int np = a.K + a.F, Vx = a.V + np;
     const int nchunk = (Vx + kBeamChunk - 1) / kBeamChunk;
-    if (tid < k) { cum_s[tid] = a.cum[r0 + tid]; fin_s[tid] = a.fin[r0 + tid]; }
+    // length penalty (uniform): candidates are ranked by cum / lp[L], L = step + 1 for a live expansion and the length
+    // it ended at for an ended hypothesis; cum itself stays the raw summed log-probability
+    const bool lp_on = RULES && rule_words(a.words).z != 0u;
+    if (tid < k) {
+        cum_s[tid] = a.cum[r0 + tid]; fin_s[tid] = a.fin[r0 + tid];
+        if (lp_on) { len_s[tid] = a.len[r0 + tid]; lpf_s[tid] = a.lp[len_s[tid]]; }
+    }
     __syncthreads();
     bool live_any = false;
     for (int j = 0; j < k; ++j) live_any = live_any || !(fin_s[j] || cum_s[j] == -INFINITY);
@@ -1641,6 +1669,7 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     __syncthreads();
     // candidates: k per (live row, chunk), one per ended row; every thread keeps up to NC of them
     constexpr int NC = kBeamCandPerThread;
+    const float lp_live = lp_on ? a.lp[a.step + 1] : 1.f;
     float cv[NC]; int cc[NC];
     const int per_row = nchunk * k, total = k * per_row;
 #pragma unroll
@@ -1651,11 +1680,16 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
             const int j = id / per_row, rem = id - j * per_row, c = rem / k, slot = rem - c * k;
             if (cum_s[j] != -INFINITY) {
                 if (fin_s[j]) {
-                    if (rem == 0) { cv[q] = cum_s[j]; cc[q] = j * Vx; }        // an ended hypothesis competes as it is
+                    if (rem == 0) {                                      // an ended hypothesis competes as it is
+                        cv[q] = lp_on ? cum_s[j] / lpf_s[j] : cum_s[j]; cc[q] = j * Vx;
+                    }
                 } else {
                     const float* rc = a.rec + ((r0 + j) * nchunk + c) * kBeamRec;
                     const int idx = __float_as_int(rc[3 + 2 * slot]);
-                    if (idx != kNone) { cv[q] = cum_s[j] - lse_s[j] + rc[2 + 2 * slot]; cc[q] = j * Vx + idx; }
+                    if (idx != kNone) {
+                        const float v = cum_s[j] - lse_s[j] + rc[2 + 2 * slot];
+                        cv[q] = lp_on ? v / lp_live : v; cc[q] = j * Vx + idx;
+                    }
                 }
             }
         }
@@ -1674,15 +1708,27 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
             if (cc[q] == bc) { cv[q] = -INFINITY; cc[q] = kNone; }
         if (tid == 0) {
             float v = bv; const int c = bc;
-            int parent = 0, tok = a.pad_token, nf = 1;
+            int parent = 0, tok = a.pad_token, nf = 1, len = 0;
             if (c != kNone) {
                 parent = c / Vx;
                 if (fin_s[parent]) { nf = 1; tok = a.pad_token; }
                 else { tok = c - parent * Vx; nf = tok == a.end_token; }
+                if (lp_on) {       // v is the key: the raw log-probability again, by the expression that made the key
+                    if (fin_s[parent]) {
+                        v = cum_s[parent]; len = len_s[parent];
+                    } else {
+                        const float* rc = a.rec + ((r0 + parent) * nchunk + tok / kBeamChunk) * kBeamRec;
+                        int slot = 0;
+                        while (slot + 1 < k && __float_as_int(rc[3 + 2 * slot]) != tok) ++slot;
+                        v = cum_s[parent] - lse_s[parent] + rc[2 + 2 * slot];
+                        len = a.step + 1;
+                    }
+                }
             } else {
                 v = -INFINITY;                                      // fewer candidates than beams: a dead slot
             }
             parent_s[round] = parent; tok_s[round] = tok; nfin_s[round] = nf;
+            if (lp_on) a.len[r0 + round] = len;
             a.cum[r0 + round] = v;
             a.fin[r0 + round] = nf;
             const bool live = c != kNone && !nf;
@@ -2022,7 +2068,8 @@ extern "C" int ick_decode_select_greedy(const ick_decode_ctx* c, int32_t pos, vo
     ICK_LAUNCH_RET();
 }
 
-extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_state* bs, int32_t pos, void* stream) {
+static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, const ick_decode_rules* rules,
+                            int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && bs && c->R > 0 && pos >= 0 && pos < c->max_len);
     ICK_CHECK_ARG(c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax && c->R % c->rows_per_sample == 0);
     ICK_CHECK_ARG(c->scores && c->scores_ld >= c->V && c->ptr && c->n_done && c->next_token && c->next_mask &&
@@ -2036,7 +2083,10 @@ extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_st
     pa.scores = c->scores; pa.ld = c->scores_ld; pa.ptr = c->ptr; pa.cum = bs->cum; pa.fin = bs->fin; pa.rec = bs->rec;
     pa.R = c->R; pa.k = c->rows_per_sample; pa.V = c->V; pa.np = c->K + c->F; pa.nchunk = nchunk;
     pa.n_done = c->n_done; pa.n_total = c->R;
-    hipLaunchKernelGGL(dec_beam_partial_kernel, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, pa);
+    pa.seq = bs->seq_in; pa.words = rules ? rules->words : nullptr;
+    pa.step = pos; pa.max_len = c->max_len; pa.end_token = c->end_token;
+    void (*part)(BeamPartArgs) = rules ? dec_beam_partial_kernel<true> : dec_beam_partial_kernel<false>;
+    hipLaunchKernelGGL(part, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, pa);
     BeamArgs a;
     a.rec = bs->rec; a.cum = bs->cum; a.fin = bs->fin;
     a.seq_in = bs->seq_in; a.seq_out = bs->seq_out; a.anc_in = bs->anc_in; a.anc_out = bs->anc_out;
@@ -2046,6 +2096,19 @@ extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_st
     a.R = c->R; a.k = c->rows_per_sample; a.d = c->d; a.V = c->V; a.K = c->K; a.F = c->F; a.step = pos;
     a.max_len = c->max_len; a.has_facts = c->F > 0; a.end_token = c->end_token; a.pad_token = c->pad_token;
     a.start_token = bs->start_token; a.emb_scale = c->emb_scale; a.n_total = c->R;
-    hipLaunchKernelGGL(dec_select_beam_kernel, dim3(c->R / c->rows_per_sample), dim3(256), 0, (hipStream_t)stream, a);
+    a.words = rules ? rules->words : nullptr; a.lp = rules ? rules->lp : nullptr; a.len = rules ? rules->len : nullptr;
+    void (*sel)(BeamArgs) = rules ? dec_select_beam_kernel<true> : dec_select_beam_kernel<false>;
+    hipLaunchKernelGGL(sel, dim3(c->R / c->rows_per_sample), dim3(256), 0, (hipStream_t)stream, a);
     ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_state* bs, int32_t pos, void* stream) {
+    return select_beam_impl(c, bs, nullptr, pos, stream);
+}
+
+extern "C" int ick_decode_select_beam_rules(const ick_decode_ctx* c, const ick_beam_state* bs,
+                                            const ick_decode_rules* rules, int32_t pos, void* stream) {
+    ICK_CHECK_ARG(c && rules && rules->words && rules->lp && rules->len && ((uintptr_t)rules->words & 15) == 0);
+    ICK_CHECK_ARG(c->max_len <= kRuleHistMax && c->end_token >= 0 && c->end_token < c->V);
+    return select_beam_impl(c, bs, rules, pos, stream);
 }

@@ -13,6 +13,9 @@
 //                   one draw in 2^24 whose fp32 sum rounds up to 1.0 from becoming g = +inf.
 // The noise of a column is a pure function of (seed, b, j, step, c): a caption's samples do not depend on the batch.
 // log_prob receives the model's log_softmax(s)[token] (T = 1, no truncation).  No repeated n-gram clean-up.
+// Decoding rules (ick_decode_select_sample_rules): columns banned by the no-repeat n-gram / min-length
+// rules are absent before top-k and top-p (not counted in k, no mass; the top-p weights are taken relative to the
+// allowed maximum) and from the draw; m, the sum of exp and log_prob still cover every column.
 //
 // Determinism: every thread owns the same columns on every launch (lane t of group g: columns 4 (g*1024 + t) + 0..3),
 // float reductions run per lane in column order, then over the wave (DPP / readlane, fixed pattern), then over the 16
@@ -51,6 +54,7 @@ struct SampleArgs {
     int R, rows_per_sample, d, V, K, F, step, max_len, has_facts, end_token, pad_token;
     float emb_scale;
     int n_total;
+    const int32_t* words;                  // optional rule words (no-repeat n-gram size, min length)
 };
 
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
@@ -103,7 +107,8 @@ __device__ __forceinline__ void scan_desc(const T* hist, T need, T above, int* d
 
 // NG = groups of 4 columns a lane holds in registers: 4 (Vx <= 16 384, cfg5) keeps them in VGPRs; 16 (cfg4's 50 071)
 // exceeds the 128 registers a lane of a 1024-thread workgroup has and spills part of the row to scratch.
-template <int NG>
+// RULES: the decoding-rules variant (ick_decode_select_sample_rules); the rule-free one compiles without the ban pass.
+template <int NG, bool RULES>
 __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int64_t r = blockIdx.x;
@@ -137,6 +142,15 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
     __shared__ float bv_sh[kSNW], bs_sh[kSNW];
     __shared__ int bc_sh[kSNW];
     __shared__ int64_t tok_sh[2];
+    __shared__ uint32_t ban[NG * kSNT * 4 / 32];
+    __shared__ int hs[kRuleHistMax];
+    __shared__ int all_sh;
+
+    const uint4 rw = RULES ? rule_words(a.words) : make_uint4(0u, 0u, 0u, 0u);
+    const int nrep = (int)rw.x, mlen = (int)rw.y;
+    // decoding rules (uniform): banned columns are absent from top-k, top-p and the draw -- not from the log-softmax
+    const bool ban_any = RULES && !fin && (nrep > 0 || i < mlen);
+    if (ban_any) mark_bans(a.output + r * a.max_len, i, nrep, mlen, a.end_token, ban, 0, NG * kSNT * 4 / 32, hs);
 
     if (!fin) {
         const float T = __uint_as_float((uint32_t)tp), top_p = __uint_as_float((uint32_t)(tp >> 32));
@@ -152,6 +166,15 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
             for (int q = 0; q < 4; ++q) {
                 const int c = (g * kSNT + tid) * 4 + q;
                 s[g * 4 + q] = g >= ng ? -INFINITY : (c < a.V ? srow[c] : (c < Vx ? prow[c - a.V] : -INFINITY));
+            }
+        }
+        // banned[g * 4 + q]: column (g * 1024 + tid) * 4 + q is banned (the 4 columns of a group share a mask word)
+        uint64_t banned = 0;
+        if (ban_any) {
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                const int c = (g * kSNT + tid) * 4;
+                if (g < ng) banned |= (uint64_t)((ban[c >> 5] >> (c & 31)) & 15u) << (4 * g);
             }
         }
         // pass 1: maximum, then sum(exp(s - m)) for the log-probability (T = 1, untruncated)
@@ -174,6 +197,21 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
         }
         se = wave_sum(se);
         if (lane == 0) red[1][wid] = se;
+        // the maximum over the allowed columns: the top-p weights are exp(z - its z)
+        float mk = m;
+        if (ban_any) {
+            mk = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < NG * 4; ++e)
+                if (!((banned >> e) & 1u)) mk = fmaxf(mk, s[e]);
+            mk = wave_max(mk);
+            __syncthreads();                           // every wave has read red[0]
+            if (lane == 0) red[0][wid] = mk;
+            __syncthreads();
+            mk = red[0][0];
+#pragma unroll
+            for (int w = 1; w < kSNW; ++w) mk = fmaxf(mk, red[0][w]);
+        }
         // top-k threshold: the key of the k-th largest s (radix select on counts); 0 keeps everything
         uint32_t thk = 0;
         if (top_k > 0 && top_k < Vx) {
@@ -188,25 +226,32 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const uint32_t key = okey(s[g * 4 + q]);
-                        if ((g * kSNT + tid) * 4 + q < Vx && (key & pmask) == prefix)
+                        if ((g * kSNT + tid) * 4 + q < Vx && !((banned >> (g * 4 + q)) & 1u) && (key & pmask) == prefix)
                             atomicAdd(&hist_n[(key >> shift) & 255u], 1u);
                     }
                 }
                 __syncthreads();
                 if (wid == 0) {
+                    if (pass == 0 && ban_any) {     // k >= the allowed columns: every allowed column is kept
+                        uint32_t t4 = hist_n[4 * lane] + hist_n[4 * lane + 1] + hist_n[4 * lane + 2] + hist_n[4 * lane + 3];
+#pragma unroll
+                        for (int off = 32; off >= 1; off >>= 1) t4 += __shfl_xor(t4, off, 64);
+                        if (lane == 0) all_sh = t4 <= need;
+                    }
                     uint32_t above_out = 0;
                     int dig = -1;
                     scan_desc<uint32_t>(hist_n, need, 0u, &dig, &above_out, lane);
                     if (dig >= 0) { dig_sh = dig; need_sh = need - above_out; }
                 }
                 __syncthreads();
+                if (pass == 0 && ban_any && all_sh) { prefix = 0; break; }     // uniform
                 prefix |= (uint32_t)dig_sh << shift;
                 pmask |= 255u << shift;
                 need = need_sh;
             }
             thk = prefix;
         }
-        const float zmax = m / T;
+        const float zmax = mk / T;
         // top-p threshold: the key of the first z (descending) where the running fixed-point mass of the top-k kept
         // set reaches p * W; 0 keeps everything
         uint32_t thp = 0;
@@ -226,7 +271,8 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
                         const float sv = s[g * 4 + q];
                         const float z = sv / T;
                         const uint32_t key = okey(z);
-                        if ((g * kSNT + tid) * 4 + q < Vx && okey(sv) >= thk && (key & pmask) == prefix) {
+                        if ((g * kSNT + tid) * 4 + q < Vx && !((banned >> (g * 4 + q)) & 1u) && okey(sv) >= thk &&
+                            (key & pmask) == prefix) {
                             const unsigned long long wf = __float2ull_rn(expf(z - zmax) * 0x1p32f);
                             if (wf) atomicAdd(&hist_m[(key >> shift) & 255u], wf);
                         }
@@ -268,7 +314,8 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float sv = s[g * 4 + q];
-                kept[q] = (int)(quad * 4 + q) < Vx && okey(sv) >= thk && okey(sv / T) >= thp;
+                kept[q] = (int)(quad * 4 + q) < Vx && !((banned >> (g * 4 + q)) & 1u) && okey(sv) >= thk &&
+                          okey(sv / T) >= thp;
                 anyk |= kept[q];
             }
             if (!anyk) continue;
@@ -349,7 +396,8 @@ extern "C" int ick_decode_sample_supported(int32_t Vx, int32_t rows_per_sample) 
     return Vx >= 1 && Vx <= kSVxMax && rows_per_sample >= 1 && rows_per_sample <= 65535 ? 1 : 0;
 }
 
-extern "C" int ick_decode_select_sample(const ick_decode_ctx* c, const ick_sample_state* s, int32_t pos, void* stream) {
+static int select_sample_impl(const ick_decode_ctx* c, const ick_sample_state* s, const ick_decode_rules* rules,
+                              int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && s && c->R > 0 && c->R <= 65535 && pos >= 0 && pos < c->max_len);
     ICK_CHECK_ARG(c->rows_per_sample >= 1 && c->R % c->rows_per_sample == 0);
     ICK_CHECK_ARG(c->V > 0 && c->K > 0 && c->F >= 0 && c->end_token >= 0 && c->end_token < c->V);
@@ -368,9 +416,20 @@ extern "C" int ick_decode_select_sample(const ick_decode_ctx* c, const ick_sampl
     a.R = c->R; a.rows_per_sample = c->rows_per_sample; a.d = c->d; a.V = c->V; a.K = c->K; a.F = c->F; a.step = pos;
     a.max_len = c->max_len; a.has_facts = c->F > 0; a.end_token = c->end_token; a.pad_token = c->pad_token;
     a.emb_scale = c->emb_scale; a.n_total = c->R;
-    if (c->V + c->K + c->F <= 4 * 4 * kSNT)
-        hipLaunchKernelGGL(dec_sample_kernel<4>, dim3(c->R), dim3(kSNT), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(dec_sample_kernel<kSGMax>, dim3(c->R), dim3(kSNT), 0, (hipStream_t)stream, a);
+    a.words = rules ? rules->words : nullptr;
+    const bool small = c->V + c->K + c->F <= 4 * 4 * kSNT;
+    void (*kern)(SampleArgs) = rules == nullptr ? (small ? dec_sample_kernel<4, false> : dec_sample_kernel<kSGMax, false>)
+                                                : (small ? dec_sample_kernel<4, true> : dec_sample_kernel<kSGMax, true>);
+    hipLaunchKernelGGL(kern, dim3(c->R), dim3(kSNT), 0, (hipStream_t)stream, a);
     ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_decode_select_sample(const ick_decode_ctx* c, const ick_sample_state* s, int32_t pos, void* stream) {
+    return select_sample_impl(c, s, nullptr, pos, stream);
+}
+
+extern "C" int ick_decode_select_sample_rules(const ick_decode_ctx* c, const ick_sample_state* s,
+                                              const ick_decode_rules* rules, int32_t pos, void* stream) {
+    ICK_CHECK_ARG(c && rules && rules->words && ((uintptr_t)rules->words & 15) == 0 && c->max_len <= kRuleHistMax);
+    return select_sample_impl(c, s, rules, pos, stream);
 }

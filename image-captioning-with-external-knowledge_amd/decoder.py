@@ -131,6 +131,51 @@ def split_attention(attn, P, K, F=0):
     return {"image": img, "entities": attn[..., P:P + K], "facts": attn[..., P + K:]}
 
 
+RULES_MAX_NGRAM = 8
+
+
+def length_penalty_table(alpha, max_len):
+    """GNMT length penalty lp[L] = ((5 + L) / 6) ** alpha for L = 0 .. max_len, computed in float64 and rounded to
+    fp32 (lp[0] = 1 is never a real length: it keeps an unused beam slot's key at -inf)."""
+    lp = [((5.0 + L) / 6.0) ** float(alpha) for L in range(max_len + 1)]
+    lp[0] = 1.0
+    return torch.tensor(lp, dtype=torch.float64).to(torch.float32)
+
+
+def check_rules(what, max_len, Vx, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0):
+    """Validate the decoding rules of predict_beam / predict_sample (IckError); True when any rule is on."""
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or \
+            not math.isfinite(length_penalty) or length_penalty < 0:
+        raise IckError("%s needs a finite length_penalty >= 0 (0 = off)" % what)
+    if isinstance(no_repeat_ngram_size, bool) or not isinstance(no_repeat_ngram_size, int) or \
+            not 0 <= no_repeat_ngram_size <= RULES_MAX_NGRAM:
+        raise IckError("%s needs an integer no_repeat_ngram_size in 0..%d (0 = off)" % (what, RULES_MAX_NGRAM))
+    if isinstance(min_len, bool) or not isinstance(min_len, int) or not 0 <= min_len <= max_len:
+        raise IckError("%s needs an integer min_len in 0..max_pred_len (0 = off)" % what)
+    on = length_penalty != 0 or no_repeat_ngram_size != 0 or min_len != 0
+    if on and Vx <= max_len:
+        raise IckError("%s: decoding rules need V+K+F (%d) > max_pred_len (%d), so that some token stays allowed"
+                       % (what, Vx, max_len))
+    return on
+
+
+def rules_tensor(max_len, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0, device="cuda"):
+    """The device input of the rules (lib.DecodeRules): int32 (4 + max_len + 1) = the rule words
+    {no_repeat_ngram_size, min_len, length penalty on, 0} followed by the fp32 bits of length_penalty_table()."""
+    words = torch.tensor([no_repeat_ngram_size, min_len, int(length_penalty != 0), 0], dtype=torch.int32)
+    lp = length_penalty_table(length_penalty, max_len).view(torch.int32)
+    return torch.cat([words, lp]).to(device)
+
+
+def _rules_struct(rules, lens=None):
+    """lib.DecodeRules over a rules_tensor() (and a beam's (R) int32 length buffer)."""
+    from . import lib as L
+    r = L.DecodeRules()
+    r.words, r.lp = rules.data_ptr(), rules.data_ptr() + 16
+    r.len = None if lens is None else lens.data_ptr()
+    return r
+
+
 def _wb(linear):
     return linear.weight.detach(), linear.bias.detach()
 
@@ -1186,12 +1231,13 @@ class DecoderTransformer(nn.Module):
             return t["output"], _zero_after_end(attn, t["output"], self.word_map["<end>"])
         return t["output"]
 
-    def _predict_beam_device(self, enc_tok, entities, facts, max_pred_len, beam, attention=False):
+    def _predict_beam_device(self, enc_tok, entities, facts, max_pred_len, beam, attention=False, rules=None):
         """Beam search on the fused decode kernels: R = B * beam rows share their caption's cross K/V; the
         self-attention cache is never reordered -- an ancestry table says which cache row holds position p of a
         hypothesis.  Returns (best sequence (B, max_len), its log-probability (B), all sequences, all scores); with
         attention also the cross-attention weights of the best (max_len, B, layers, H, S) and of every final hypothesis
-        (max_len, B, beam, layers, H, S)."""
+        (max_len, B, beam, layers, H, S).  rules: a rules_tensor() (device input read at run time) or None; with it the
+        best hypothesis is the argmax of cum / lp[length]."""
         from . import lib as L
         B = enc_tok.shape[0]
         d, V, K = self.emb_dim, self.vocab_size, entities.shape[1]
@@ -1218,6 +1264,9 @@ class DecoderTransformer(nn.Module):
         rec = torch.empty(R, (Vx + 1023) // 1024, 18, device=dev, dtype=torch.float32)
         bs.rec = rec.data_ptr()
         attn = torch.zeros(max_pred_len, R, c.layers, c.H, S, device=dev) if attention else None
+        if rules is not None:
+            lens = torch.zeros(R, dtype=torch.int32, device=dev)
+            rs = _rules_struct(rules, lens)
         for i in range(max_pred_len):
             cur, nxt = i & 1, (i + 1) & 1
             c.anc = anc[cur].data_ptr()
@@ -1231,9 +1280,16 @@ class DecoderTransformer(nn.Module):
                 ops.decode_layers(c, i)
             bs.seq_in, bs.seq_out = seq[cur].data_ptr(), seq[nxt].data_ptr()
             bs.anc_in, bs.anc_out = anc[cur].data_ptr(), anc[nxt].data_ptr()
-            ops.decode_select_beam(c, bs, i)
+            if rules is None:
+                ops.decode_select_beam(c, bs, i)
+            else:
+                ops.decode_select_beam_rules(c, bs, rs, i)
         final = seq[max_pred_len & 1].view(B, beam, max_pred_len)
-        best = cum.argmax(dim=1)                          # ties: the lower hypothesis
+        if rules is None:
+            best = cum.argmax(dim=1)                      # ties: the lower hypothesis
+        else:                                             # the kernel's ranking key; ties: the lower hypothesis
+            lp = rules[4:].view(torch.float32)
+            best = (cum / lp[lens.view(B, beam).long()]).argmax(dim=1)
         out = final[torch.arange(B, device=dev), best]
         if not attention:
             return out, cum.gather(1, best.view(B, 1)).view(B), final, cum
@@ -1246,7 +1302,7 @@ class DecoderTransformer(nn.Module):
 
     @torch.no_grad()
     def predict_beam(self, encoder_out, max_pred_len, entities, facts=None, beam_size=5, return_all=False,
-                     return_attention=False):
+                     return_attention=False, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0):
         """Beam-search decode (north_star cfg5: beam 5, batch 32).  The reference decodes greedily only
         (geo-aware/eval.py:61,83), so beam > 1 has no reference output to pin against ("parity-unpinned"); the tests
         check it against a CPU beam search written to the same rules.  beam_size == 1 IS predict(): the pinned greedy path with
@@ -1255,8 +1311,19 @@ class DecoderTransformer(nn.Module):
         LongTensor (max_pred_len, B), <pad> after <end>.  return_all adds (best log-probability (B), every final
         hypothesis (B, beam, max_len), their log-probabilities (B, beam)).  return_attention appends the cross-attention
         weights of the best hypothesis, float32 (max_pred_len, B, layers, H, S) (see predict()), and with return_all
-        those of every final hypothesis, (max_pred_len, B, beam, layers, H, S)."""
-        if beam_size == 1:
+        those of every final hypothesis, (max_pred_len, B, beam, layers, H, S).
+
+        Decoding rules (0 = off, the default, which gives the bits of a call without them):
+        length_penalty = alpha >= 0 ranks hypotheses by log-probability / ((5 + L) / 6) ** alpha, L = generated tokens
+        including <end> (max_pred_len for one that never ended); no_repeat_ngram_size = n in 0..8 bans every token that
+        would repeat an n-gram of the hypothesis; min_len = m bans <end> before step m.  Bans remove candidates only:
+        the returned log-probabilities stay the model's untruncated ones.  The rules are a device input of the
+        captured decode graph (a new value replays it); beam_size == 1 with a rule on runs the beam kernels with one
+        hypothesis (predict()'s clean-up is not applied)."""
+        P_ = entities.shape[1] + (facts.shape[1] if facts is not None else 0)
+        rules_on = check_rules("predict_beam", max_pred_len, self.vocab_size + P_, length_penalty,
+                               no_repeat_ngram_size, min_len)
+        if beam_size == 1 and not rules_on:
             return DecoderTransformer.predict(self, encoder_out, max_pred_len, entities, facts,
                                               return_attention=return_attention)
         encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
@@ -1266,22 +1333,30 @@ class DecoderTransformer(nn.Module):
         FF = self.transformer_decoder.layers[0].linear1.out_features
         S_all = P + entities.shape[1] + (facts.shape[1] if facts is not None else 0)
         Vx = self.vocab_size + S_all - P
-        if not (1 < beam_size <= 8) or not ops.decode_supported(self.emb_dim, self.num_heads, FF, S_all, max_pred_len) \
+        if not (1 <= beam_size <= 8) or not ops.decode_supported(self.emb_dim, self.num_heads, FF, S_all, max_pred_len) \
                 or not ops.decode_beam_supported(Vx, beam_size):
             raise IckError("predict_beam needs 1 <= beam_size <= 8, beam_size^2 * ceil((V+K+F)/1024) <= 4096 and sizes "
                            "the fused decode kernels support")
         if return_attention:
             _attention_check("predict_beam", max_pred_len, enc_tok.shape[0] * beam_size,
                              len(self.transformer_decoder.layers), self.num_heads, S_all)
+        rules = rules_tensor(max_pred_len, length_penalty, no_repeat_ngram_size, min_len, enc_tok.device) \
+            if rules_on else None
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, beam_size) + self._enc_key(enc_tok)
-            res = self._graphed("beam_attn" if return_attention else "beam", key,
-                                lambda t, e, f: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
-                                                                          return_attention),
-                                [enc_tok, entities, facts])
+            if rules_on:
+                res = self._graphed("beam_rules_attn" if return_attention else "beam_rules", key,
+                                    lambda t, e, f, r: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
+                                                                                 return_attention, r),
+                                    [enc_tok, entities, facts, rules])
+            else:
+                res = self._graphed("beam_attn" if return_attention else "beam", key,
+                                    lambda t, e, f: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
+                                                                              return_attention),
+                                    [enc_tok, entities, facts])
         else:
-            res = self._predict_beam_device(enc_tok, entities, facts, max_pred_len, beam_size, return_attention)
+            res = self._predict_beam_device(enc_tok, entities, facts, max_pred_len, beam_size, return_attention, rules)
         out = res[0].t().contiguous()
         if not return_attention:
             return (out, res[1], res[2], res[3]) if return_all else out
@@ -1289,11 +1364,11 @@ class DecoderTransformer(nn.Module):
             return out, res[1], res[2], res[3], res[4].clone(), res[5].clone()
         return out, res[4].clone()
 
-    def _predict_sample_device(self, enc_tok, entities, facts, knobs, max_pred_len, n, attention=False):
+    def _predict_sample_device(self, enc_tok, entities, facts, knobs, max_pred_len, n, attention=False, rules=None):
         """Sampled decode on the fused decode kernels: R = B * n rows, the n samples of a caption share its cross K/V
         and keep their own self-attention caches.  knobs: int64 (3) device tensor [seed, temperature | top_p << 32
         (two fp32 words), top_k] -- read by the selection kernel, so a replay sees whatever was copied into it.
-        Returns (tokens (R, max_len), log-probabilities (R, max_len)[, cross-attention weights (max_len, R, layers, H,
+        rules: a rules_tensor() (read the same way) or None.  Returns (tokens (R, max_len), log-probabilities (R, max_len)[, cross-attention weights (max_len, R, layers, H,
         S)])."""
         from . import lib as L
         dev = enc_tok.device
@@ -1307,6 +1382,7 @@ class DecoderTransformer(nn.Module):
         base = knobs.data_ptr()
         st.seed, st.temp_top_p, st.top_k, st.log_prob = base, base + 8, base + 16, log_prob.data_ptr()
         attn = torch.zeros(max_pred_len, c.R, c.layers, c.H, c.S, device=dev) if attention else None
+        rs = None if rules is None else _rules_struct(rules)
         for i in range(max_pred_len):
             if self.has_facts:
                 ops.context_indicators(t["cap_buf"], facts_r, K, V, self._pred_wt(), self.fc_predicate.bias.detach(),
@@ -1315,14 +1391,18 @@ class DecoderTransformer(nn.Module):
                 ops.decode_layers_attn(c, attn, i)
             else:
                 ops.decode_layers(c, i)
-            ops.decode_select_sample(c, st, i)
+            if rs is None:
+                ops.decode_select_sample(c, st, i)
+            else:
+                ops.decode_select_sample_rules(c, st, rs, i)
         if attention:
             return t["output"], log_prob, _zero_after_end(attn, t["output"], self.word_map["<end>"])
         return t["output"], log_prob
 
     @torch.no_grad()
     def predict_sample(self, encoder_out, max_pred_len, entities, facts=None, num_samples=1, temperature=1.0, top_k=0,
-                       top_p=1.0, seed=None, return_log_probs=False, return_attention=False):
+                       top_p=1.0, seed=None, return_log_probs=False, return_attention=False, no_repeat_ngram_size=0,
+                       min_len=0):
         """Stochastic decode: `num_samples` captions per image drawn from the model's distribution, with temperature,
         top-k and nucleus (top-p) truncation.  Per row and step over the V+K+F raw scores s: z = s / temperature;
         top-k keeps s >= the k-th largest s (ties at the boundary all kept); top-p then keeps the tokens whose
@@ -1338,7 +1418,14 @@ class DecoderTransformer(nn.Module):
         63-bit seed from torch's default CPU generator; an integer seed makes the call bit-reproducible.  The knobs
         and the seed are inputs of the captured decode graph: changing them replays it without a new capture.
         return_attention appends the cross-attention weights, float32 (max_pred_len, B * num_samples, layers, H, S) (see
-        predict()); the tokens and log-probabilities are the same bits as without it."""
+        predict()); the tokens and log-probabilities are the same bits as without it.
+
+        Decoding rules (as predict_beam; 0 = off, the default): no_repeat_ngram_size = n in 0..8 bans every token that
+        would repeat an n-gram of the row, min_len = m bans <end> before step m.  A banned token is absent before top-k
+        and top-p (not counted in k, no mass); its Gumbel noise is unchanged, so a step where no ban fires draws the
+        same token as without rules.  return_log_probs stays the untruncated log-probability."""
+        P_ = entities.shape[1] + (facts.shape[1] if facts is not None else 0)
+        rules_on = check_rules("predict_sample", max_pred_len, self.vocab_size + P_, 0.0, no_repeat_ngram_size, min_len)
         if not (isinstance(num_samples, int) and num_samples >= 1):
             raise IckError("predict_sample needs num_samples >= 1")
         if not (math.isfinite(temperature) and temperature > 0):
@@ -1368,15 +1455,23 @@ class DecoderTransformer(nn.Module):
         seed = seed - 2 ** 64 if seed >= 2 ** 63 else seed          # the same 64 bits as an int64
         tp = struct.unpack("<q", struct.pack("<ff", temperature, top_p))[0]
         knobs = torch.tensor([seed, tp, min(top_k, 2 ** 31 - 1)], dtype=torch.int64).to(enc_tok.device)
+        rules = rules_tensor(max_pred_len, 0.0, no_repeat_ngram_size, min_len, enc_tok.device) if rules_on else None
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, num_samples) + self._enc_key(enc_tok)
-            res = self._graphed("sample_attn" if return_attention else "sample", key,
-                                lambda t, e, f, k: self._predict_sample_device(t, e, f, k, max_pred_len, num_samples,
-                                                                               return_attention),
-                                [enc_tok, entities, facts, knobs])
+            if rules_on:
+                res = self._graphed("sample_rules_attn" if return_attention else "sample_rules", key,
+                                    lambda t, e, f, k, r: self._predict_sample_device(t, e, f, k, max_pred_len,
+                                                                                      num_samples, return_attention, r),
+                                    [enc_tok, entities, facts, knobs, rules])
+            else:
+                res = self._graphed("sample_attn" if return_attention else "sample", key,
+                                    lambda t, e, f, k: self._predict_sample_device(t, e, f, k, max_pred_len,
+                                                                                   num_samples, return_attention),
+                                    [enc_tok, entities, facts, knobs])
         else:
-            res = self._predict_sample_device(enc_tok, entities, facts, knobs, max_pred_len, num_samples, return_attention)
+            res = self._predict_sample_device(enc_tok, entities, facts, knobs, max_pred_len, num_samples, return_attention,
+                                              rules)
         out = res[0].t().contiguous()
         ret = (out, res[1].t().contiguous()) if return_log_probs else (out,)
         if return_attention:

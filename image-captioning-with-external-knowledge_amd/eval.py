@@ -39,13 +39,19 @@ def detokenize(seq, word_map, rev_word_map, entity_names, fact_names=None):
 
 @torch.no_grad()
 def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="generated_captions.csv", device="cuda",
-             sample=None, attention_out=None):
+             sample=None, attention_out=None, beam=None):
     """sample=None: greedy decode (predict), one CSV row per image.  sample = a dict of predict_sample keyword arguments
-    (num_samples, temperature, top_k, top_p, seed): sampled decode, one CSV row per (image, sample) with the columns
-    image (running index over the loader), sample, generated_caption; an explicit seed is advanced by one per batch.
+    (num_samples, temperature, top_k, top_p, seed, and the decoding rules no_repeat_ngram_size, min_len): sampled
+    decode, one CSV row per (image, sample) with the columns image (running index over the loader), sample,
+    generated_caption; an explicit seed is advanced by one per batch.  beam = a dict of predict_beam keyword arguments
+    (beam_size, length_penalty, no_repeat_ngram_size, min_len): beam-search decode, one CSV row per image (the best
+    hypothesis); beam and sample together are a ValueError.
     attention_out: a path for one .npz of the decoder's cross-attention (return_attention of predict / predict_sample):
     "attention" float16 (N, max_len, S), the last decoder layer's weights averaged over its heads, one row per CSV row;
-    "tokens" int64 (N, max_len); "P", "K", "F": how the S memory rows split into image, entity and fact rows."""
+    "tokens" int64 (N, max_len); "P", "K", "F": how the S memory rows split into image, entity and fact rows.  With
+    beam, the weights are those of the best hypothesis."""
+    if beam is not None and sample is not None:
+        raise ValueError("evaluate: beam and sample are two different decoders; pass one of them")
     decoder.eval()
     encoder.eval()
     rev = {v: k for k, v in word_map.items()}
@@ -71,7 +77,11 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
             image = batch[0].to(device)
         enc_in = image if feature_map else encoder(image)
         attn = None
-        if sample is None:
+        if beam is not None:
+            kw = dict(beam)
+            kw.pop("return_all", None)
+            seq = decoder.predict_beam(enc_in, max_caption_len, ent, *extra, return_attention=want_attn, **kw)
+        elif sample is None:
             seq = decoder.predict(enc_in, max_caption_len, ent, *extra, return_attention=want_attn)  # (max_len, B)
         else:
             kw = dict(sample)

@@ -145,6 +145,10 @@ class SampleState(C.Structure):     # ick_sample_state: the knobs of the sampled
     _fields_ = [(n, vp) for n in ("seed", "temp_top_p", "top_k", "log_prob")]
 
 
+class DecodeRules(C.Structure):     # ick_decode_rules: rule words, length-penalty table, beam lengths (device memory)
+    _fields_ = [(n, vp) for n in ("words", "lp", "len")]
+
+
 # name -> argtypes; every entry returns int (0 ok, <0 ICK_E*, >0 hipError_t)
 SIGNATURES = {
     "ick_version": [],
@@ -192,6 +196,8 @@ SIGNATURES = {
     "ick_decode_beam_supported": [i32, i32],
     "ick_decode_select_sample": [C.POINTER(DecodeCtx), C.POINTER(SampleState), i32, vp],
     "ick_decode_sample_supported": [i32, i32],
+    "ick_decode_select_beam_rules": [C.POINTER(DecodeCtx), C.POINTER(BeamState), C.POINTER(DecodeRules), i32, vp],
+    "ick_decode_select_sample_rules": [C.POINTER(DecodeCtx), C.POINTER(SampleState), C.POINTER(DecodeRules), i32, vp],
     "ick_attention_bwd": [C.POINTER(AttnBwdArgs), vp],
     "ick_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, f32, u32, u32, vp, vp, vp],
     "ick_layernorm_bwd_rows_per_block": [],

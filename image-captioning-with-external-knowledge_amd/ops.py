@@ -651,6 +651,18 @@ def decode_select_beam(ctx, beam_state, pos):
     L.check(L.load().ick_decode_select_beam(C.byref(ctx), C.byref(beam_state), pos, _stream()), "ick_decode_select_beam")
 
 
+def decode_select_beam_rules(ctx, beam_state, rules, pos):
+    """ick_decode_select_beam under decoding rules (lib.DecodeRules): n-gram / min-length bans, length penalty."""
+    L.check(L.load().ick_decode_select_beam_rules(C.byref(ctx), C.byref(beam_state), C.byref(rules), pos, _stream()),
+            "ick_decode_select_beam_rules")
+
+
+def decode_select_sample_rules(ctx, sample_state, rules, pos):
+    """ick_decode_select_sample under decoding rules (lib.DecodeRules): n-gram / min-length bans."""
+    L.check(L.load().ick_decode_select_sample_rules(C.byref(ctx), C.byref(sample_state), C.byref(rules), pos,
+                                                    _stream()), "ick_decode_select_sample_rules")
+
+
 def decode_select_sample(ctx, sample_state, pos):
     """Sampled token of step `pos` for every live row (ick_decode_select_sample); sample_state: lib.SampleState."""
     L.check(L.load().ick_decode_select_sample(C.byref(ctx), C.byref(sample_state), pos, _stream()),

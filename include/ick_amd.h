@@ -439,6 +439,27 @@ int ick_decode_select_sample(const ick_decode_ctx* ctx, const ick_sample_state* 
  * caption (<= 65535); host-only, callers check it BEFORE capturing a decode graph. */
 int ick_decode_sample_supported(int32_t Vx, int32_t rows_per_sample);
 
+/* Decoding rules of beam search and sampling.  At step t a row has generated y_0 .. y_{t-1}:
+ *   no-repeat n-gram (n = words[0], 0..8, 0 = off): every y_p, n-1 <= p <= t-1, with y_{p-n+1..p-1} == y_{t-n+1..t-1}
+ *     is banned (n = 1: every earlier token);
+ *   min length (m = words[1], 0 = off): <end> is banned while t < m;
+ *   length penalty (beam only, on when words[2] != 0): candidates are ranked by the fp32 key cum / lp[L], L = t + 1 for
+ *     a live expansion, the length it ended at (<end> counted) for an ended hypothesis; len carries L with the parents.
+ * A ban only removes candidates: the log-softmax normaliser still runs over all V+K+F scores, so cum and log_prob stay
+ * the model's untruncated log-probabilities; in sampling banned columns are absent before top-k / top-p.  words, lp and
+ * len are device memory read by the kernels at run time, so a captured decode graph replays with new rules; with every
+ * word 0 the results are the bits of the entry points without rules.  Needs max_len <= 128; the caller keeps
+ * V+K+F > max_len so that some column is always allowed. */
+typedef struct {
+    const int32_t* words;         /* (4) {no_repeat_ngram_size, min_len, length penalty on, 0}, 16-byte aligned */
+    const float* lp;              /* (max_len + 1) lp[L] = ((5 + L) / 6)^alpha, fp32 (beam only) */
+    int32_t* len;                 /* (R) beam only: hypothesis lengths, zeroed by the caller before step 0 */
+} ick_decode_rules;
+int ick_decode_select_beam_rules(const ick_decode_ctx* ctx, const ick_beam_state* beam, const ick_decode_rules* rules,
+                                 int32_t pos, void* stream);
+int ick_decode_select_sample_rules(const ick_decode_ctx* ctx, const ick_sample_state* s, const ick_decode_rules* rules,
+                                   int32_t pos, void* stream);
+
 /* fused token-mean cross entropy over the packed rows of train.py
  * (pack_padded_sequence + CrossEntropyLoss(ignore_index=<pad>), geo-aware/train.py:275-281):
  * rows (b,t) with t < decode_len[b] and target != pad contribute.  Writes loss_sum[0] (sum of
