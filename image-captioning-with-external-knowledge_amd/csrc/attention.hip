@@ -161,22 +161,23 @@ __global__ __launch_bounds__(256) void attn_kernel(ick_attn_args p, int TQ, int 
     }
 }
 
+constexpr size_t kAttnBudget = 150 * 1024 / sizeof(float);     // LDS floats of one workgroup
+
+// queries per workgroup of the general forward kernel: all of them when they fit next to V in LDS, else chunks
+inline int attn_fwd_chunk(int T, int S, int DHP) {
+    const int VLD = DHP + 4, SLD = S | 1;
+    const size_t fixed = (size_t)S * VLD;
+    int TQ = T;
+    while (TQ > 1 && fixed + (size_t)TQ * (DHP + SLD + 1) > kAttnBudget) TQ = (TQ + 1) / 2;
+    return TQ;
+}
+inline size_t attn_fwd_floats(int TQ, int S, int DHP) { return (size_t)S * (DHP + 4) + (size_t)TQ * (DHP + (S | 1) + 1); }
+
 template <int DHP>
-int launch_attn(const ick_attn_args& a, hipStream_t s) {
-    constexpr int VLD = DHP + 4;
+int launch_attn(const ick_attn_args& a, int TQ, hipStream_t s) {
     const int SLD = a.S | 1;
-    // queries per workgroup: all of them when they fit next to V in LDS, else chunks
-    const size_t fixed = (size_t)a.S * VLD;
-    int TQ = a.T;
-    const size_t budget = 150 * 1024 / sizeof(float);
-    while (TQ > 1 && fixed + (size_t)TQ * (DHP + SLD + 1) > budget) TQ = (TQ + 1) / 2;
-    const size_t fl = fixed + (size_t)TQ * (DHP + SLD + 1);
-    if (fl > budget) return ICK_EINVAL;
-    const size_t smem = fl * sizeof(float);
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool vec = a.q_ts == DHP && a.k_ss == DHP && a.v_ss == DHP && al16(a.Q) && al16(a.K) && al16(a.V) &&
-                     a.q_bs % 4 == 0 && a.q_hs % 4 == 0 && a.k_bs % 4 == 0 && a.k_hs % 4 == 0 && a.v_bs % 4 == 0 &&
-                     a.v_hs % 4 == 0;
+    const size_t smem = attn_fwd_floats(TQ, a.S, DHP) * sizeof(float);
+    const bool vec = attn_head_major(a, DHP);
     static LdsAttrOnce attr_set[2];
     const void* kern = vec ? (const void*)attn_kernel<DHP, true> : (const void*)attn_kernel<DHP, false>;
     if (int e = attr_set[vec].ensure(kern, 160 * 1024)) return e;
@@ -240,11 +241,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(ick_attn_bwd_args p, int 
         x.z = 4 * g + 2 < dh ? x.z : 0.f; x.w = 4 * g + 3 < dh ? x.w : 0.f;
         *reinterpret_cast<float4*>(Ks + s * VLD + 4 * g) = x;
     }
-    if (tid < nt) {
+    for (int t = tid; t < nt; t += 256) {      // a chunk may hold more queries than the workgroup has threads
         float dsum = 0.f;
-        for (int j = 0; j < dh; ++j) dsum = fmaf(gb[(int64_t)tid * p.o_ts + j], ob[(int64_t)tid * p.o_ts + j], dsum);
-        Dl[tid] = dsum;
-        Ls[tid] = p.lse[((int64_t)b * p.H + h) * p.T + t0 + tid];
+        for (int j = 0; j < dh; ++j) dsum = fmaf(gb[(int64_t)t * p.o_ts + j], ob[(int64_t)t * p.o_ts + j], dsum);
+        Dl[t] = dsum;
+        Ls[t] = p.lse[((int64_t)b * p.H + h) * p.T + t0 + t];
     }
     __syncthreads();
 
@@ -343,30 +344,58 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(ick_attn_bwd_args p, int 
 
 // queries per workgroup of the general backward kernel (all of them when they fit in LDS, else chunks whose
 // dK / dV contributions are combined with float atomics)
+inline size_t attn_bwd_floats(int TQ, int S, int DHP) {
+    return (size_t)S * (DHP + 4) + (size_t)256 * DHP + 4 + (size_t)TQ * (2 * DHP + (S | 1) + 2);
+}
 inline int attn_bwd_chunk(int T, int S, int DHP) {
-    const int VLD = DHP + 4, SLD = S | 1;
-    const size_t fixed = (size_t)S * VLD, budget = 150 * 1024 / sizeof(float), stage = (size_t)256 * DHP + 4;
     int TQ = T;
-    while (TQ > 1 && fixed + stage + (size_t)TQ * (2 * DHP + SLD + 2) > budget) TQ = (TQ + 1) / 2;
+    while (TQ > 1 && attn_bwd_floats(TQ, S, DHP) > kAttnBudget) TQ = (TQ + 1) / 2;
     return TQ;
 }
-inline bool attn_bwd_single_chunk(int T, int S, int DHP) { return attn_bwd_chunk(T, S, DHP) >= T; }
 
 template <int DHP>
-int launch_attn_bwd(const ick_attn_bwd_args& a, hipStream_t s) {
-    constexpr int VLD = DHP + 4;
+int launch_attn_bwd(const ick_attn_bwd_args& a, int TQ, hipStream_t s) {
     const int SLD = a.S | 1;
-    const size_t fixed = (size_t)a.S * VLD;
-    const size_t budget = 150 * 1024 / sizeof(float);
-    const size_t stage = (size_t)256 * DHP + 4;
-    const int TQ = attn_bwd_chunk(a.T, a.S, DHP);
-    const size_t fl = fixed + stage + (size_t)TQ * (2 * DHP + SLD + 2);
-    if (fl > budget) return ICK_EINVAL;
+    const size_t fl = attn_bwd_floats(TQ, a.S, DHP);
     auto kern = attn_bwd_kernel<DHP>;
     static LdsAttrOnce attr_set;
     if (int e = attr_set.ensure((const void*)kern, 160 * 1024)) return e;
     hipLaunchKernelGGL(kern, dim3(a.H, a.B, ceil_div(a.T, TQ)), dim3(256), fl * sizeof(float), s, a, TQ, SLD);
     ICK_LAUNCH_RET();
+}
+
+// The launch plan of ick_attention (dir 0) / ick_attention_bwd (dir 1): both entry points launch by it, and
+// ick_attention_plan reports it.  hm: Q / K / V in the head-major padded layout (attn_head_major).
+struct AttnPlan {
+    int mfma, nqt, maxt, dhp, tq, chunks, overwrites;
+};
+
+inline bool attn_no_mfma() {
+    static const bool v = getenv("ICK_ATTN_NO_MFMA") != nullptr;   // experiment hook: force the general kernels
+    return v;
+}
+
+int attn_plan(int dir, int T, int S, int dh, bool hm, AttnPlan& pl) {
+    pl = AttnPlan{0, 0, 0, 0, 0, 0, 1};
+    if (!(dir == 0 || dir == 1) || T <= 0 || S <= 0 || dh <= 0 || dh > 64) return ICK_EINVAL;
+    const int DHP = dh <= 32 ? 32 : 64;
+    if (dir == 1 && !hm) return ICK_EINVAL;       // the backward reads the head-major padded operands only
+    if (DHP == 32 && hm && !attn_no_mfma() && attn_mfma_shape_ok(T, S, dh)) {
+        // one workgroup per (sample, head) holds every query: it writes all of dQ / dK / dV
+        pl.mfma = 1; pl.nqt = attn_mfma_nqt(T); pl.maxt = attn_mfma_maxt(S); pl.tq = T; pl.chunks = 1;
+        return 0;
+    }
+    pl.dhp = DHP;
+    if (dir == 0) {
+        pl.tq = attn_fwd_chunk(T, S, DHP);
+        if (attn_fwd_floats(pl.tq, S, DHP) > kAttnBudget) return ICK_EINVAL;
+    } else {
+        pl.tq = attn_bwd_chunk(T, S, DHP);
+        if (attn_bwd_floats(pl.tq, S, DHP) > kAttnBudget) return ICK_EINVAL;
+    }
+    pl.chunks = ceil_div(T, pl.tq);
+    pl.overwrites = dir == 0 || pl.chunks == 1;   // query chunks of the backward meet in dK / dV with float atomics
+    return 0;
 }
 
 }  // namespace
@@ -380,13 +409,11 @@ extern "C" int ick_attention(const ick_attn_args* in, void* stream) {
     ICK_CHECK_ARG(a.B > 0 && a.H > 0 && a.T > 0 && a.S > 0 && a.dh > 0 && a.dh <= 64);
     ICK_CHECK_ARG(a.B <= 65535);
     hipStream_t s = (hipStream_t)stream;
-    static const bool no_mfma = getenv("ICK_ATTN_NO_MFMA") != nullptr;   // experiment hook: force the general kernels
-    if (!no_mfma) {
-        const int rc = launch_attn_mfma(a, s);
-        if (rc != kAttnMfmaUnsupported) return rc;
-    }
-    if (a.dh <= 32) return launch_attn<32>(a, s);
-    return launch_attn<64>(a, s);
+    AttnPlan pl;
+    if (int e = attn_plan(0, a.T, a.S, a.dh, attn_head_major(a, a.dh <= 32 ? 32 : 64), pl)) return e;
+    if (pl.mfma) return launch_attn_mfma(a, s);
+    if (pl.dhp == 32) return launch_attn<32>(a, pl.tq, s);
+    return launch_attn<64>(a, pl.tq, s);
 }
 
 
@@ -396,24 +423,29 @@ extern "C" int ick_attention_bwd(const ick_attn_bwd_args* in, void* stream) {
     const ick_attn_bwd_args& a = *in;
     ICK_CHECK_ARG(a.Q && a.K && a.V && a.O && a.dO && a.lse && a.dQ && a.dK && a.dV);
     ICK_CHECK_ARG(a.B > 0 && a.B <= 65535 && a.H > 0 && a.T > 0 && a.S > 0 && a.dh > 0 && a.dh <= 64);
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const int DHP = a.dh <= 32 ? 32 : 64;
     // head-major padded operands only (what the training forward produces)
-    ICK_CHECK_ARG(a.q_ts == DHP && a.k_ss == DHP && a.v_ss == DHP && al16(a.Q) && al16(a.K) && al16(a.V));
-    ICK_CHECK_ARG(a.q_bs % 4 == 0 && a.q_hs % 4 == 0 && a.k_bs % 4 == 0 && a.k_hs % 4 == 0 && a.v_bs % 4 == 0 &&
-                  a.v_hs % 4 == 0);
+    const int DHP = a.dh <= 32 ? 32 : 64;
+    ICK_CHECK_ARG(attn_head_major(a, DHP));
     hipStream_t s = (hipStream_t)stream;
-    static const bool no_mfma = getenv("ICK_ATTN_NO_MFMA") != nullptr;
-    if (DHP == 32 && !no_mfma) {
-        const int rc = launch_attn_bwd_mfma(a, s);
-        if (rc != kAttnMfmaUnsupported) return rc;
-    }
-    if (DHP == 32) return launch_attn_bwd<32>(a, s);
-    return launch_attn_bwd<64>(a, s);
+    AttnPlan pl;
+    if (int e = attn_plan(1, a.T, a.S, a.dh, true, pl)) return e;
+    if (pl.mfma) return launch_attn_bwd_mfma(a, s);
+    if (pl.dhp == 32) return launch_attn_bwd<32>(a, pl.tq, s);
+    return launch_attn_bwd<64>(a, pl.tq, s);
 }
 
 extern "C" int ick_attention_bwd_overwrites(int32_t T, int32_t S, int32_t dh) {
     using namespace ick;
-    if (dh <= 32 && attn_mfma_shape_ok(T, S, dh) && getenv("ICK_ATTN_NO_MFMA") == nullptr) return 1;
-    return attn_bwd_single_chunk(T, S, dh <= 32 ? 32 : 64) ? 1 : 0;
+    AttnPlan pl;
+    return attn_plan(1, T, S, dh, true, pl) == 0 && pl.overwrites ? 1 : 0;
+}
+
+extern "C" int ick_attention_plan(int32_t dir, int32_t T, int32_t S, int32_t dh, int32_t head_major, int32_t* out) {
+    using namespace ick;
+    if (!out) return ICK_EINVAL;
+    AttnPlan pl;
+    const int e = attn_plan(dir, T, S, dh, head_major != 0, pl);
+    const int v[7] = {pl.mfma, pl.nqt, pl.maxt, pl.dhp, pl.tq, pl.chunks, pl.overwrites};
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
+    return e;
 }

@@ -504,8 +504,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(ick_attn_bwd_args p,
     ICK_ASTAMP(SK, 6);
 }
 
-inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 template <int NQT, int MAXT>
 int launch_fwd(const ick_attn_args& a, int SP, hipStream_t s) {
     const size_t fl = std::max<size_t>((size_t)DHP * SP, 4 * NQT * 2 * 256) + (size_t)NQT * 16 * QLD + 10 * NQT * 16;
@@ -545,16 +543,18 @@ bool attn_mfma_shape_ok(int T, int S, int dh) {
     return std::max(tr * sp + 2 * nq * QLD + 2 * DHP * (nq + 4) + 2 * nq + 4 * 16 * QLD, nq * sp + 64) * sizeof(float) <= 150 * 1024;
 }
 
+int attn_mfma_nqt(int T) { return (T + 15) / 16; }
+
+// key tiles per wave (compile time: register arrays): 1 for S <= 64 (self-attention), 4 up to 256 (geo: 216),
+// 5 up to 320 (knowledge: 267), 8 up to 512
+int attn_mfma_maxt(int S) { return S <= 64 ? 1 : (S <= 256 ? 4 : (S <= 320 ? 5 : 8)); }
+
 int launch_attn_mfma(const ick_attn_args& a, hipStream_t s) {
     if (!attn_mfma_shape_ok(a.T, a.S, a.dh)) return kAttnMfmaUnsupported;
-    if (!(a.q_ts == DHP && a.k_ss == DHP && a.v_ss == DHP && aligned16(a.Q) && aligned16(a.K) && aligned16(a.V) &&
-          a.q_bs % 4 == 0 && a.q_hs % 4 == 0 && a.k_bs % 4 == 0 && a.k_hs % 4 == 0 && a.v_bs % 4 == 0 && a.v_hs % 4 == 0))
-        return kAttnMfmaUnsupported;
+    if (!attn_head_major(a, DHP)) return kAttnMfmaUnsupported;
     const int SP = ((a.S + 15) / 16) * 16 + 4;
-    const int nqt = (a.T + 15) / 16;
-    // key tiles per wave (compile time: register arrays): 1 for S <= 64 (self-attention), 4 up to 256 (geo: 216),
-    // 5 up to 320 (knowledge: 267), 8 up to 512
-    const int mt = a.S <= 64 ? 1 : (a.S <= 256 ? 4 : (a.S <= 320 ? 5 : 8));
+    const int nqt = attn_mfma_nqt(a.T);
+    const int mt = attn_mfma_maxt(a.S);
 #define ICK_FWD(N)                                                                                   \
     case N: return mt == 1 ? launch_fwd<N, 1>(a, SP, s) : (mt == 4 ? launch_fwd<N, 4>(a, SP, s) :   \
                    (mt == 5 ? launch_fwd<N, 5>(a, SP, s) : launch_fwd<N, 8>(a, SP, s)))
@@ -568,11 +568,11 @@ int launch_attn_mfma(const ick_attn_args& a, hipStream_t s) {
 int launch_attn_bwd_mfma(const ick_attn_bwd_args& a, hipStream_t s) {
     if (!attn_mfma_shape_ok(a.T, a.S, a.dh)) return kAttnMfmaUnsupported;
     const int SP = ((a.S + 15) / 16) * 16 + 4;
-    const int mt = a.S <= 64 ? 1 : (a.S <= 256 ? 4 : (a.S <= 320 ? 5 : 8));
+    const int mt = attn_mfma_maxt(a.S);
 #define ICK_BWD(N)                                                                                   \
     case N: return mt == 1 ? launch_bwd<N, 1>(a, SP, s) : (mt == 4 ? launch_bwd<N, 4>(a, SP, s) :   \
                    (mt == 5 ? launch_bwd<N, 5>(a, SP, s) : launch_bwd<N, 8>(a, SP, s)))
-    switch ((a.T + 15) / 16) {
+    switch (attn_mfma_nqt(a.T)) {
         ICK_BWD(1); ICK_BWD(2); ICK_BWD(3); ICK_BWD(4);
     }
 #undef ICK_BWD

@@ -490,11 +490,12 @@ def attention_heads(q, kv, O, H, dh, T, S, q_seg=0, k_seg=0, v_seg=1, causal=Fal
     """Attention over head-major buffers: q (B, nq, H, Tq_alloc, DHP), kv (B, nkv, H, S_alloc, DHP);
     the first T query rows starting at q_t0 attend to the first S key rows."""
     B = q.shape[0]
-    Tq, Sa = q.shape[3], kv.shape[3]
+    Tq, Sa, hp = q.shape[3], kv.shape[3], q.shape[4]
+    assert kv.shape[4] == hp
     attention_raw(q, kv, kv, O, B, H, T, S, dh,
-                  q.stride(0), Tq * DHP, DHP, kv.stride(0), Sa * DHP, DHP, kv.stride(0), Sa * DHP, DHP,
+                  q.stride(0), Tq * hp, hp, kv.stride(0), Sa * hp, hp, kv.stride(0), Sa * hp, hp,
                   O.stride(0), O.stride(1), causal=causal, q_pos0=q_pos0, kv_len=kv_len, lse=lse, drop=drop,
-                  q_off=q_seg * H * Tq * DHP + q_t0 * DHP, k_off=k_seg * H * Sa * DHP, v_off=v_seg * H * Sa * DHP)
+                  q_off=q_seg * H * Tq * hp + q_t0 * hp, k_off=k_seg * H * Sa * hp, v_off=v_seg * H * Sa * hp)
     return O
 
 
@@ -781,29 +782,45 @@ def attention_bwd_buffer(shape, T, S, dh, device):
     return torch.zeros(shape, device=device, dtype=torch.float32)
 
 
+ATTN_PLAN_KEYS = ("mfma", "nqt", "maxt", "dhp", "tq", "chunks", "overwrites")
+
+
+def attention_plan(direction, T, S, dh, head_major=True):
+    """The kernels ick_attention (direction "fwd") / ick_attention_bwd ("bwd") launch for a (T, S, dh) problem
+    (ick_attention_plan; host only, no GPU needed).  None when the entry point rejects the shape."""
+    out = (C.c_int32 * len(ATTN_PLAN_KEYS))()
+    rc = L.load_raw().ick_attention_plan({"fwd": 0, "bwd": 1}[direction], T, S, dh, int(head_major), out)
+    if rc == -1:
+        return None
+    L.check(rc, "ick_attention_plan")
+    return dict(zip(ATTN_PLAN_KEYS, (int(v) for v in out)))
+
+
 def attention_heads_bwd(q, kv, O, dO, lse, dQ, dK, dV, H, dh, T, S, q_seg=0, k_seg=0, v_seg=1, causal=False,
-                        drop=None):
+                        drop=None, q_pos0=0):
     """Backward of attention_heads.  q (B,nq,H,Tq,DHP), kv (B,nkv,H,Sa,DHP); O/dO (B,T,d) row-major;
     dQ (B,T,*) / dK, dV (B,S,*) row-major views (last-dim stride 1; their column offset selects the
-    segment), written as [h*dh + j]."""
+    segment), written as [h*dh + j].  The head-major buffers' row stride is DHP (dh <= 32) or 2 DHP."""
     B = q.shape[0]
     Tq, Sa = q.shape[3], kv.shape[3]
+    hp = q.shape[4]
+    assert kv.shape[4] == hp
     a = L.AttnBwdArgs()
-    a.Q = q.data_ptr() + 4 * (q_seg * H * Tq * DHP)
-    a.K = kv.data_ptr() + 4 * (k_seg * H * Sa * DHP)
-    a.V = kv.data_ptr() + 4 * (v_seg * H * Sa * DHP)
+    a.Q = q.data_ptr() + 4 * (q_seg * H * Tq * hp)
+    a.K = kv.data_ptr() + 4 * (k_seg * H * Sa * hp)
+    a.V = kv.data_ptr() + 4 * (v_seg * H * Sa * hp)
     a.O, a.dO, a.lse = _p(O), _p(dO), _p(lse)
     a.dQ, a.dK, a.dV = _p(dQ), _p(dK), _p(dV)
     a.B, a.H, a.T, a.S, a.dh = B, H, T, S, dh
-    a.q_bs, a.q_hs, a.q_ts = q.stride(0), Tq * DHP, DHP
-    a.k_bs, a.k_hs, a.k_ss = kv.stride(0), Sa * DHP, DHP
-    a.v_bs, a.v_hs, a.v_ss = kv.stride(0), Sa * DHP, DHP
+    a.q_bs, a.q_hs, a.q_ts = q.stride(0), Tq * hp, hp
+    a.k_bs, a.k_hs, a.k_ss = kv.stride(0), Sa * hp, hp
+    a.v_bs, a.v_hs, a.v_ss = kv.stride(0), Sa * hp, hp
     a.o_bs, a.o_ts = O.stride(0), O.stride(1)
     a.dq_bs, a.dq_ts = dQ.stride(0), dQ.stride(1)
     a.dk_bs, a.dk_ss = dK.stride(0), dK.stride(1)
     a.dv_bs, a.dv_ss = dV.stride(0), dV.stride(1)
     a.scale = 1.0 / math.sqrt(dh)
-    a.causal, a.q_pos0 = int(causal), 0
+    a.causal, a.q_pos0 = int(causal), q_pos0
     _drop(a, drop)
     L.check(L.load().ick_attention_bwd(C.byref(a), _stream()), "ick_attention_bwd")
 

@@ -165,13 +165,13 @@ typedef struct {
     float* o; int64_t o_rs;
     float* x; int64_t x_rs; int32_t x_grp; int64_t x_gs;
     float* mean; float* rstd;
-    const float* w2p; const float* b2; int32_t N2; int32_t flags;   /* flags: ICK_GEMM_RELU, ICK_CHAIN_SLIM */
+    const float* w2p; const float* b2; int32_t N2; int32_t flags;   /* flags: ICK_GEMM_RELU, ICK_CHAIN_SLIM, ICK_CHAIN_PROJ */
     float drop2_p; uint32_t drop2_site;
     float* y2; int64_t y2_rs; int32_t y2_grp; int64_t y2_gs;
     int32_t hs_dh, hs_dhp, hs_H, hs_S, hs_s0;
 } ick_rowchain_args;
-#define ICK_CHAIN_SLIM 256   /* 8-wave workgroups: for chains that run beside bulk GEMMs on another stream (they find
-                                room on a busy CU where the 16-wave form waits for the bulk kernel to drain) */
+#define ICK_CHAIN_SLIM 256   /* ick_rowchain_fwd: 8-wave workgroups, for chains that run beside bulk GEMMs on another stream
+                                (they find room on a busy CU where the 16-wave form waits for the bulk kernel to drain) */
 #define ICK_CHAIN_PROJ 512   /* ick_rowchain_fwd: projection only, y2 = act(A W2^T + b2) with A (M, d); w1p / norm arguments unused */
 int ick_rowchain_supported(int32_t K1, int32_t d, int32_t N2);
 int ick_rowchain_fwd(const ick_rowchain_args* args, void* stream);
@@ -209,7 +209,7 @@ typedef struct {
     float* do2; float* part2;
     const float* w3p; float* out3;
     float* dz_out;
-    int32_t flags;                     /* ICK_CHAIN_SLIM: the 8-wave form (same bits), for launches beside another stream's kernels */
+    int32_t flags;                     /* unused (0): the backward chain has one form, ICK_CHAIN_SLIM is ignored */
 } ick_rowchain_bwd_args;
 int ick_rowchain_bwd_supported(int32_t K0, int32_t d, int32_t N1);
 int ick_rowchain_bwd(const ick_rowchain_bwd_args* args, void* stream);
@@ -540,6 +540,15 @@ int ick_attention_bwd(const ick_attn_bwd_args* args, void* stream);
 /* 1 when ick_attention_bwd writes every element of dQ / dK / dV for this shape (no pre-zeroing needed), 0 when it
  * accumulates query chunks with float atomics into buffers the caller must have zeroed. */
 int ick_attention_bwd_overwrites(int32_t T, int32_t S, int32_t dh);
+/* The launch plan of ick_attention (dir 0) / ick_attention_bwd (dir 1) for a (T, S, dh) problem, host only (nothing is
+ * launched; both entry points choose their kernels by the same function, ICK_ATTN_NO_MFMA included).  head_major: Q / K /
+ * V in the head-major padded layout (row stride 32 floats for dh <= 32, else 64; rows 16-byte aligned), which the
+ * backward requires.  out[0] 1 for the matrix-core kernels (attention_mfma.hip), 0 for the general ones (attention.hip);
+ * out[1] NQT (query tiles of 16) and out[2] MAXT (key tiles per wave) of the matrix-core instantiation, else 0; out[3] DHP
+ * of the general instantiation (32 or 64), else 0; out[4] queries per workgroup; out[5] query chunks (workgroups per
+ * (sample, head)); out[6] 1 when every element of the outputs is overwritten, 0 when the backward's chunks accumulate
+ * dK / dV with float atomics (ick_attention_bwd_overwrites).  Returns ICK_EINVAL for what the entry point rejects. */
+int ick_attention_plan(int32_t dir, int32_t T, int32_t S, int32_t dh, int32_t head_major, int32_t* out);
 
 /* dz = dLN/d(x+res).  Parameter gradients: with `partials` == NULL, dgamma += ..., dbeta += ... (float atomics);
  * otherwise workgroup i writes its partial [dgamma | dbeta] sums to partials[i*2d .. i*2d+2d) for

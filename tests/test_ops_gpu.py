@@ -216,15 +216,18 @@ def test_attention(ops, B, T, S, causal):
     (3, 20, 20, True, 0, False),       # decoder self-attention
     (2, 7, 6, False, 0, True),         # one partial tile each way, ragged keys
     (2, 40, 300, False, 0, True),      # three query tiles, five key tiles per wave (MAXT = 8 instantiation)
-    (2, 64, 512, True, 448, False),    # the largest shape of the matrix-core path, causal with an offset
+    (2, 64, 512, True, 448, False),    # past the matrix-core LDS limit at T = 64: the general kernel, causal offset
+    (2, 64, 416, True, 352, False),    # the largest matrix-core shape at T = 64, causal with an offset
     (2, 33, 257, False, 0, True),      # just past the tile boundaries
     (2, 2, 1, False, 0, False),        # smallest
 ])
 def test_attention_matrix_core_path(ops, B, T, S, causal, q_pos0, use_len):
-    """Head-major padded operands with T >= 2 take the MFMA kernels (attention_mfma.hip): outputs and the
-    log-sum-exp against float64 math, with NaN in the pad columns and in the rows beyond kv_len."""
+    """Head-major padded operands with T >= 2 take the MFMA kernels (attention_mfma.hip) where attn_mfma_shape_ok allows,
+    the general kernels beyond: outputs and the log-sum-exp against float64 math, with NaN in the pad columns and in
+    the rows beyond kv_len."""
     H, d = 10, 300
     dh = d // H
+    assert ops.attention_plan("fwd", T, S, dh)["mfma"] == (S <= (416 if T == 64 else 512))
     x, mem = rnd(B, T, d, seed=11), rnd(B, S, d, seed=12)
     q = torch.full((B, 1, H, T, ops.DHP), float("nan"), device="cuda")
     kv = torch.full((B, 2, H, S, ops.DHP), float("nan"), device="cuda")
