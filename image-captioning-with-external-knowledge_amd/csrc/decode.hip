@@ -1516,7 +1516,22 @@ struct BeamArgs {
     // decoding rules (the RULES variant): rule words (length penalty: words[2] != 0), lp[0..max_len], and the tokens
     // of every hypothesis, <end> included
     const int32_t* words; const float* lp; int32_t* len;
+    // diverse beam search (the DIVERSE variant): `groups` groups of k / groups hypotheses, and the penalty lambda (one
+    // fp32 in device memory)
+    int groups; const float* penalty;
 };
+
+// The diversity penalty lambda of ick_decode_diversity, read through the scalar cache like rule_words(): a device input
+// the host writes before a (replayed) decode.
+__device__ __forceinline__ float diversity_penalty(const float* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
+    return __uint_as_float(v);
+#else
+    return *p;                              // (the host pass only parses device code)
+#endif
+}
 
 // Block-wide arg-best of (value, code) pairs: larger value wins, ties go to the smaller code.  Result in every thread.
 __device__ __forceinline__ void block_best(float& v, int& c, float* shv, int* shc) {
@@ -1614,7 +1629,8 @@ __global__ __launch_bounds__(256) void dec_beam_partial_kernel(BeamPartArgs a) {
     }
 }
 
-template <bool RULES>
+// DIVERSE: diverse beam search (ick_decode_select_beam_diverse)
+template <bool RULES, bool DIVERSE>
 __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     // No exit on *n_done here: other workgroups of this very launch add to it, and the hypothesis tables are
     // ping-pong buffers -- a step that skipped its carry-copy would leave the previous step's rows (in another
@@ -1694,6 +1710,7 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
             }
         }
     }
+    if constexpr (!DIVERSE) {
     for (int round = 0; round < k; ++round) {
         float bv = -INFINITY; int bc = kNone;
 #pragma unroll
@@ -1734,6 +1751,71 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
             const bool live = c != kNone && !nf;
             a.next_token[r0 + round] = live ? tok : 0;
             a.next_mask[r0 + round] = !live ? 0 : ((a.has_facts && tok >= a.V + a.K) ? 2 : (tok >= a.V ? 1 : 0));
+        }
+    }
+    } else {
+        // Diverse beam search: the groups choose in order.  Group g ranks the candidates of its own rows g*kg ..
+        // (g+1)*kg - 1 by key - lambda * n, n = the number of hypotheses of groups 0 .. g-1 expanded with the
+        // candidate's column at this step (an ended hypothesis competes with its key as it is), and its kg rounds fill
+        // slots g*kg + round: k rounds in all, as without groups.  The winner's bookkeeping is the loop's above (kept
+        // apart so that the instantiations without groups keep their instructions), with the raw log-probability
+        // always re-derived, since the key is penalised.
+        __shared__ int xtok_s[kBeamMax];                    // column expanded into slot j at this step, or -1
+        const int kg = k / a.groups;
+        const float lam = diversity_penalty(a.penalty);
+        for (int g = 0; g < a.groups; ++g) {
+            const int lo = g * kg * Vx, hi = lo + kg * Vx;
+            float gv[NC]; int gc[NC];
+#pragma unroll
+            for (int q = 0; q < NC; ++q) {
+                gv[q] = -INFINITY; gc[q] = kNone;
+                if (cc[q] >= lo && cc[q] < hi) {            // (kNone is above every code)
+                    const int j = cc[q] / Vx, col = cc[q] - j * Vx;
+                    int n = 0;
+                    if (!fin_s[j])
+                        for (int i = 0; i < g * kg; ++i) n += xtok_s[i] == col;
+                    gv[q] = cv[q] - lam * (float)n; gc[q] = cc[q];
+                }
+            }
+            for (int round = 0; round < kg; ++round) {
+                float bv = -INFINITY; int bc = kNone;
+#pragma unroll
+                for (int q = 0; q < NC; ++q) {
+                    const bool take = gv[q] > bv || (gv[q] == bv && gc[q] < bc);
+                    bv = take ? gv[q] : bv;
+                    bc = take ? gc[q] : bc;
+                }
+                block_best(bv, bc, shv, shc);
+#pragma unroll
+                for (int q = 0; q < NC; ++q)
+                    if (gc[q] == bc) { gv[q] = -INFINITY; gc[q] = kNone; }
+                if (tid != 0) continue;
+                const int h = g * kg + round, c = bc;
+                float v = -INFINITY;                                // fewer candidates than beams: a dead slot
+                int parent = 0, tok = a.pad_token, nf = 1, len = 0;
+                if (c != kNone) {
+                    parent = c / Vx;
+                    if (fin_s[parent]) {
+                        v = cum_s[parent]; len = lp_on ? len_s[parent] : 0;
+                    } else {
+                        tok = c - parent * Vx; nf = tok == a.end_token;
+                        const float* rc = a.rec + ((r0 + parent) * nchunk + tok / kBeamChunk) * kBeamRec;
+                        int slot = 0;
+                        while (slot + 1 < k && __float_as_int(rc[3 + 2 * slot]) != tok) ++slot;
+                        v = cum_s[parent] - lse_s[parent] + rc[2 + 2 * slot];
+                        len = a.step + 1;
+                    }
+                }
+                parent_s[h] = parent; tok_s[h] = tok; nfin_s[h] = nf;
+                xtok_s[h] = c != kNone && !fin_s[parent] ? tok : -1;
+                if (lp_on) a.len[r0 + h] = len;
+                a.cum[r0 + h] = v;
+                a.fin[r0 + h] = nf;
+                const bool live = c != kNone && !nf;
+                a.next_token[r0 + h] = live ? tok : 0;
+                a.next_mask[r0 + h] = !live ? 0 : ((a.has_facts && tok >= a.V + a.K) ? 2 : (tok >= a.V ? 1 : 0));
+            }
+            __syncthreads();                                // xtok_s of this group before the next group reads it
         }
     }
     __syncthreads();
@@ -2069,7 +2151,7 @@ extern "C" int ick_decode_select_greedy(const ick_decode_ctx* c, int32_t pos, vo
 }
 
 static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, const ick_decode_rules* rules,
-                            int32_t pos, void* stream) {
+                            const ick_decode_diversity* div, int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && bs && c->R > 0 && pos >= 0 && pos < c->max_len);
     ICK_CHECK_ARG(c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax && c->R % c->rows_per_sample == 0);
     ICK_CHECK_ARG(c->scores && c->scores_ld >= c->V && c->ptr && c->n_done && c->next_token && c->next_mask &&
@@ -2097,18 +2179,32 @@ static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, c
     a.max_len = c->max_len; a.has_facts = c->F > 0; a.end_token = c->end_token; a.pad_token = c->pad_token;
     a.start_token = bs->start_token; a.emb_scale = c->emb_scale; a.n_total = c->R;
     a.words = rules ? rules->words : nullptr; a.lp = rules ? rules->lp : nullptr; a.len = rules ? rules->len : nullptr;
-    void (*sel)(BeamArgs) = rules ? dec_select_beam_kernel<true> : dec_select_beam_kernel<false>;
+    a.groups = div ? div->groups : 1; a.penalty = div ? div->penalty : nullptr;
+    void (*sel)(BeamArgs) = div ? (rules ? dec_select_beam_kernel<true, true> : dec_select_beam_kernel<false, true>)
+                                : (rules ? dec_select_beam_kernel<true, false> : dec_select_beam_kernel<false, false>);
     hipLaunchKernelGGL(sel, dim3(c->R / c->rows_per_sample), dim3(256), 0, (hipStream_t)stream, a);
     ICK_LAUNCH_RET();
 }
 
 extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_state* bs, int32_t pos, void* stream) {
-    return select_beam_impl(c, bs, nullptr, pos, stream);
+    return select_beam_impl(c, bs, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_rules(const ick_decode_ctx* c, const ick_beam_state* bs,
                                             const ick_decode_rules* rules, int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && rules && rules->words && rules->lp && rules->len && ((uintptr_t)rules->words & 15) == 0);
     ICK_CHECK_ARG(c->max_len <= kRuleHistMax && c->end_token >= 0 && c->end_token < c->V);
-    return select_beam_impl(c, bs, rules, pos, stream);
+    return select_beam_impl(c, bs, rules, nullptr, pos, stream);
+}
+
+extern "C" int ick_decode_select_beam_diverse(const ick_decode_ctx* c, const ick_beam_state* bs,
+                                              const ick_decode_rules* rules, const ick_decode_diversity* div,
+                                              int32_t pos, void* stream) {
+    ICK_CHECK_ARG(c && div && div->penalty && div->groups >= 1 && c->rows_per_sample >= 1 &&
+                  c->rows_per_sample % div->groups == 0);
+    if (rules != nullptr) {
+        ICK_CHECK_ARG(rules->words && rules->lp && rules->len && ((uintptr_t)rules->words & 15) == 0);
+        ICK_CHECK_ARG(c->max_len <= kRuleHistMax && c->end_token >= 0 && c->end_token < c->V);
+    }
+    return select_beam_impl(c, bs, rules, div, pos, stream);
 }

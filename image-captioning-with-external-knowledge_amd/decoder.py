@@ -159,6 +159,18 @@ def check_rules(what, max_len, Vx, length_penalty=0.0, no_repeat_ngram_size=0, m
     return on
 
 
+def check_diversity(what, beam_size, num_beam_groups=1, diversity_penalty=0.0):
+    """Validate the diverse beam search arguments of predict_beam (IckError); True when there is more than one group."""
+    if isinstance(num_beam_groups, bool) or not isinstance(num_beam_groups, int) or num_beam_groups < 1 or \
+            (num_beam_groups > 1 and (num_beam_groups > beam_size or beam_size % num_beam_groups != 0)):
+        raise IckError("%s needs an integer num_beam_groups in 1..beam_size that divides beam_size (%d)"
+                       % (what, beam_size))
+    if isinstance(diversity_penalty, bool) or not isinstance(diversity_penalty, (int, float)) or \
+            not math.isfinite(diversity_penalty) or diversity_penalty < 0:
+        raise IckError("%s needs a finite diversity_penalty >= 0" % what)
+    return num_beam_groups > 1
+
+
 def rules_tensor(max_len, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0, device="cuda"):
     """The device input of the rules (lib.DecodeRules): int32 (4 + max_len + 1) = the rule words
     {no_repeat_ngram_size, min_len, length penalty on, 0} followed by the fp32 bits of length_penalty_table()."""
@@ -1231,13 +1243,17 @@ class DecoderTransformer(nn.Module):
             return t["output"], _zero_after_end(attn, t["output"], self.word_map["<end>"])
         return t["output"]
 
-    def _predict_beam_device(self, enc_tok, entities, facts, max_pred_len, beam, attention=False, rules=None):
+    def _predict_beam_device(self, enc_tok, entities, facts, max_pred_len, beam, attention=False, rules=None, groups=1,
+                             penalty=None):
         """Beam search on the fused decode kernels: R = B * beam rows share their caption's cross K/V; the
         self-attention cache is never reordered -- an ancestry table says which cache row holds position p of a
         hypothesis.  Returns (best sequence (B, max_len), its log-probability (B), all sequences, all scores); with
         attention also the cross-attention weights of the best (max_len, B, layers, H, S) and of every final hypothesis
         (max_len, B, beam, layers, H, S).  rules: a rules_tensor() (device input read at run time) or None; with it the
-        best hypothesis is the argmax of cum / lp[length]."""
+        best hypothesis is the argmax of cum / lp[length].  groups > 1: diverse beam search with the
+        penalty lambda read from the (1) fp32 device tensor `penalty`; every group starts from the <start> hypothesis,
+        and the best hypothesis of each group (by the unpenalised key) follows: (its sequence (B * G, max_len), its
+        log-probability (B * G)), and with attention its weights (max_len, B * G, layers, H, S)."""
         from . import lib as L
         B = enc_tok.shape[0]
         d, V, K = self.emb_dim, self.vocab_size, entities.shape[1]
@@ -1248,10 +1264,11 @@ class DecoderTransformer(nn.Module):
         R = B * beam
         anc = [torch.zeros(R, max_pred_len, dtype=torch.int32, device=dev) for _ in range(2)]
         c, t = self._decode_ctx(kv, ee, fe, beam, max_pred_len, S, anc=anc[0], want_scores=True,
-                                n_done_init=B * (beam - 1))             # the unused slots count as ended
+                                n_done_init=B * (beam - groups))        # the unused slots count as ended
         seq = [torch.full((R, max_pred_len), self.word_map["<pad>"], dtype=torch.long, device=dev) for _ in range(2)]
         cum = torch.full((B, beam), float("-inf"), device=dev)
-        cum[:, 0] = 0.0                                   # one live hypothesis per caption at the start
+        kg = beam // groups
+        cum[:, ::kg] = 0.0                                # one live hypothesis per caption (per group) at the start
         fin = torch.zeros(R, dtype=torch.int32, device=dev)
         facts_r = cap = None
         if self.has_facts:
@@ -1264,9 +1281,13 @@ class DecoderTransformer(nn.Module):
         rec = torch.empty(R, (Vx + 1023) // 1024, 18, device=dev, dtype=torch.float32)
         bs.rec = rec.data_ptr()
         attn = torch.zeros(max_pred_len, R, c.layers, c.H, S, device=dev) if attention else None
+        rs = None
         if rules is not None:
             lens = torch.zeros(R, dtype=torch.int32, device=dev)
             rs = _rules_struct(rules, lens)
+        if groups > 1:
+            dv = L.DecodeDiversity()
+            dv.groups, dv.penalty = groups, penalty.data_ptr()
         for i in range(max_pred_len):
             cur, nxt = i & 1, (i + 1) & 1
             c.anc = anc[cur].data_ptr()
@@ -1280,29 +1301,42 @@ class DecoderTransformer(nn.Module):
                 ops.decode_layers(c, i)
             bs.seq_in, bs.seq_out = seq[cur].data_ptr(), seq[nxt].data_ptr()
             bs.anc_in, bs.anc_out = anc[cur].data_ptr(), anc[nxt].data_ptr()
-            if rules is None:
+            if groups > 1:
+                ops.decode_select_beam_diverse(c, bs, rs, dv, i)
+            elif rules is None:
                 ops.decode_select_beam(c, bs, i)
             else:
                 ops.decode_select_beam_rules(c, bs, rs, i)
         final = seq[max_pred_len & 1].view(B, beam, max_pred_len)
         if rules is None:
+            key = cum
             best = cum.argmax(dim=1)                      # ties: the lower hypothesis
         else:                                             # the kernel's ranking key; ties: the lower hypothesis
             lp = rules[4:].view(torch.float32)
-            best = (cum / lp[lens.view(B, beam).long()]).argmax(dim=1)
+            key = cum / lp[lens.view(B, beam).long()]
+            best = key.argmax(dim=1)
         out = final[torch.arange(B, device=dev), best]
+        group_res = ()
+        if groups > 1:                                    # the best of each group by the same key (no penalty)
+            gbest = key.view(B, groups, kg).argmax(dim=2) + torch.arange(0, beam, kg, device=dev)      # (B, G)
+            bidx = torch.arange(B, device=dev).view(B, 1)
+            group_res = (final[bidx, gbest].reshape(B * groups, max_pred_len), cum.gather(1, gbest).reshape(B * groups))
         if not attention:
-            return out, cum.gather(1, best.view(B, 1)).view(B), final, cum
+            return (out, cum.gather(1, best.view(B, 1)).view(B), final, cum) + group_res
         # rows are never reordered: position p of a final hypothesis was computed by row anc[hyp, p] (global row index)
         anc_fin = anc[max_pred_len & 1].t().long()                                        # (max_len, R)
         steps = torch.arange(max_pred_len, device=dev).view(-1, 1)
         hyp = _zero_after_end(attn[steps, anc_fin], final.view(R, max_pred_len), self.word_map["<end>"])
         hyp = hyp.view(max_pred_len, B, beam, *hyp.shape[2:])
-        return out, cum.gather(1, best.view(B, 1)).view(B), final, cum, hyp[:, torch.arange(B, device=dev), best], hyp
+        if groups > 1:
+            group_res += (hyp[:, bidx, gbest].reshape(max_pred_len, B * groups, *hyp.shape[3:]),)
+        return (out, cum.gather(1, best.view(B, 1)).view(B), final, cum, hyp[:, torch.arange(B, device=dev), best],
+                hyp) + group_res
 
     @torch.no_grad()
     def predict_beam(self, encoder_out, max_pred_len, entities, facts=None, beam_size=5, return_all=False,
-                     return_attention=False, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0):
+                     return_attention=False, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0, num_beam_groups=1,
+                     diversity_penalty=0.0, return_groups=False):
         """Beam-search decode (north_star cfg5: beam 5, batch 32).  The reference decodes greedily only
         (geo-aware/eval.py:61,83), so beam > 1 has no reference output to pin against ("parity-unpinned"); the tests
         check it against a CPU beam search written to the same rules.  beam_size == 1 IS predict(): the pinned greedy path with
@@ -1319,10 +1353,23 @@ class DecoderTransformer(nn.Module):
         would repeat an n-gram of the hypothesis; min_len = m bans <end> before step m.  Bans remove candidates only:
         the returned log-probabilities stay the model's untruncated ones.  The rules are a device input of the
         captured decode graph (a new value replays it); beam_size == 1 with a rule on runs the beam kernels with one
-        hypothesis (predict()'s clean-up is not applied)."""
+        hypothesis (predict()'s clean-up is not applied).
+
+        Diverse beam search (Vijayakumar et al., AAAI 2018): num_beam_groups = G splits the beam into G
+        groups of beam_size / G hypotheses (G divides beam_size; group g holds hypotheses g*k_g .. (g+1)*k_g - 1), each
+        starting from <start>.  At every step the groups choose in order, and group g ranks a candidate token w by its
+        key (with the rules above) minus diversity_penalty * (the number of hypotheses of groups 0 .. g-1 expanded with
+        w at this step).  The penalty only ranks: every returned log-probability stays the model's.  diversity_penalty
+        is a device input of the captured graph (a new value replays it); G = 1, the default, is the call without
+        groups, bit for bit.  The best hypothesis is the best of all groups by the unpenalised key, and return_all
+        lists every hypothesis group-major.  return_groups=True returns the best hypothesis of each group instead of
+        the best of the caption: (max_pred_len, B * G), column b * G + g for group g of caption b; with return_all
+        their log-probabilities (B * G) come second (the (B, beam, ...) values follow unchanged), and with
+        return_attention their weights are (max_pred_len, B * G, layers, H, S)."""
         P_ = entities.shape[1] + (facts.shape[1] if facts is not None else 0)
         rules_on = check_rules("predict_beam", max_pred_len, self.vocab_size + P_, length_penalty,
                                no_repeat_ngram_size, min_len)
+        diverse = check_diversity("predict_beam", beam_size, num_beam_groups, diversity_penalty)
         if beam_size == 1 and not rules_on:
             return DecoderTransformer.predict(self, encoder_out, max_pred_len, entities, facts,
                                               return_attention=return_attention)
@@ -1342,10 +1389,18 @@ class DecoderTransformer(nn.Module):
                              len(self.transformer_decoder.layers), self.num_heads, S_all)
         rules = rules_tensor(max_pred_len, length_penalty, no_repeat_ngram_size, min_len, enc_tok.device) \
             if rules_on else None
+        G = num_beam_groups
+        penalty = torch.tensor([diversity_penalty], dtype=torch.float32).to(enc_tok.device) if diverse else None
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, beam_size) + self._enc_key(enc_tok)
-            if rules_on:
+            if diverse:
+                kind = ("beam_div_rules" if rules_on else "beam_div") + ("_attn" if return_attention else "")
+                res = self._graphed(kind, key + (G,),
+                                    lambda t, e, f, r, lam: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
+                                                                                      return_attention, r, G, lam),
+                                    [enc_tok, entities, facts, rules, penalty])
+            elif rules_on:
                 res = self._graphed("beam_rules_attn" if return_attention else "beam_rules", key,
                                     lambda t, e, f, r: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
                                                                                  return_attention, r),
@@ -1356,7 +1411,11 @@ class DecoderTransformer(nn.Module):
                                                                               return_attention),
                                     [enc_tok, entities, facts])
         else:
-            res = self._predict_beam_device(enc_tok, entities, facts, max_pred_len, beam_size, return_attention, rules)
+            res = self._predict_beam_device(enc_tok, entities, facts, max_pred_len, beam_size, return_attention, rules,
+                                            G, penalty)
+        if return_groups and diverse:       # the best of each group in place of the best of the caption
+            n = 6 if return_attention else 4
+            res = (res[n], res[n + 1], res[2], res[3]) + ((res[n + 2], res[5]) if return_attention else ())
         out = res[0].t().contiguous()
         if not return_attention:
             return (out, res[1], res[2], res[3]) if return_all else out

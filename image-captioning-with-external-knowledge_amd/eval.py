@@ -44,12 +44,14 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
     (num_samples, temperature, top_k, top_p, seed, and the decoding rules no_repeat_ngram_size, min_len): sampled
     decode, one CSV row per (image, sample) with the columns image (running index over the loader), sample,
     generated_caption; an explicit seed is advanced by one per batch.  beam = a dict of predict_beam keyword arguments
-    (beam_size, length_penalty, no_repeat_ngram_size, min_len): beam-search decode, one CSV row per image (the best
-    hypothesis); beam and sample together are a ValueError.
+    (beam_size, length_penalty, no_repeat_ngram_size, min_len, num_beam_groups, diversity_penalty, return_groups):
+    beam-search decode, one CSV row per image (the best hypothesis); with return_groups (diverse beam search), one CSV
+    row per (image, group) with the columns image, group, generated_caption, the best hypothesis of each group; beam
+    and sample together are a ValueError.
     attention_out: a path for one .npz of the decoder's cross-attention (return_attention of predict / predict_sample):
     "attention" float16 (N, max_len, S), the last decoder layer's weights averaged over its heads, one row per CSV row;
     "tokens" int64 (N, max_len); "P", "K", "F": how the S memory rows split into image, entity and fact rows.  With
-    beam, the weights are those of the best hypothesis."""
+    beam, the weights are those of the best hypothesis (of each group with return_groups)."""
     if beam is not None and sample is not None:
         raise ValueError("evaluate: beam and sample are two different decoders; pass one of them")
     decoder.eval()
@@ -57,6 +59,9 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
     rev = {v: k for k, v in word_map.items()}
     captions, sequences, rows = [], [], []
     n = int(sample.get("num_samples", 1)) if sample is not None else 1
+    groups = beam is not None and bool(beam.get("return_groups", False))
+    if groups:
+        n = int(beam.get("num_beam_groups", 1))         # predict_beam's column b*G + g: image b, group g
     # precomputed feature maps go to predict() as they are: Encoder.conv1 then runs inside the captured decode graph
     # beside the context encoders (decoder.attach_encoder); raw images go through the encoder's trunk first
     decoder.attach_encoder(encoder)
@@ -112,7 +117,10 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
         np.savez(attention_out, attention=torch.cat(attn_rows).numpy() if attn_rows else np.zeros((0, max_caption_len, 0),
                  np.float16), tokens=np.asarray(sequences, dtype=np.int64).reshape(-1, max_caption_len), P=P, K=K, F=F)
     if out_csv:
-        if sample is None:
+        if groups:
+            pd.DataFrame({"image": [r[0] for r in rows], "group": [r[1] for r in rows],
+                          "generated_caption": captions}).to_csv(out_csv, index=False)
+        elif sample is None:
             pd.DataFrame({"generated_caption": captions}).to_csv(out_csv, index=False)
         else:
             pd.DataFrame({"image": [r[0] for r in rows], "sample": [r[1] for r in rows],

@@ -149,6 +149,10 @@ class DecodeRules(C.Structure):     # ick_decode_rules: rule words, length-penal
     _fields_ = [(n, vp) for n in ("words", "lp", "len")]
 
 
+class DecodeDiversity(C.Structure):     # ick_decode_diversity: beam groups, the penalty lambda (one fp32, device memory)
+    _fields_ = [("groups", i32), ("penalty", vp)]
+
+
 # name -> argtypes; every entry returns int (0 ok, <0 ICK_E*, >0 hipError_t)
 SIGNATURES = {
     "ick_version": [],
@@ -198,6 +202,8 @@ SIGNATURES = {
     "ick_decode_sample_supported": [i32, i32],
     "ick_decode_select_beam_rules": [C.POINTER(DecodeCtx), C.POINTER(BeamState), C.POINTER(DecodeRules), i32, vp],
     "ick_decode_select_sample_rules": [C.POINTER(DecodeCtx), C.POINTER(SampleState), C.POINTER(DecodeRules), i32, vp],
+    "ick_decode_select_beam_diverse": [C.POINTER(DecodeCtx), C.POINTER(BeamState), C.POINTER(DecodeRules),
+                                       C.POINTER(DecodeDiversity), i32, vp],
     "ick_attention_bwd": [C.POINTER(AttnBwdArgs), vp],
     "ick_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, f32, u32, u32, vp, vp, vp],
     "ick_layernorm_bwd_rows_per_block": [],

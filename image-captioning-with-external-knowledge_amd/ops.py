@@ -658,6 +658,14 @@ def decode_select_beam_rules(ctx, beam_state, rules, pos):
             "ick_decode_select_beam_rules")
 
 
+def decode_select_beam_diverse(ctx, beam_state, rules, diversity, pos):
+    """ick_decode_select_beam_diverse: diverse beam search (lib.DecodeDiversity: groups, penalty), under decoding rules
+    (lib.DecodeRules) or none (rules=None)."""
+    L.check(L.load().ick_decode_select_beam_diverse(C.byref(ctx), C.byref(beam_state),
+                                                    None if rules is None else C.byref(rules), C.byref(diversity),
+                                                    pos, _stream()), "ick_decode_select_beam_diverse")
+
+
 def decode_select_sample_rules(ctx, sample_state, rules, pos):
     """ick_decode_select_sample under decoding rules (lib.DecodeRules): n-gram / min-length bans."""
     L.check(L.load().ick_decode_select_sample_rules(C.byref(ctx), C.byref(sample_state), C.byref(rules), pos,

@@ -460,6 +460,24 @@ int ick_decode_select_beam_rules(const ick_decode_ctx* ctx, const ick_beam_state
 int ick_decode_select_sample_rules(const ick_decode_ctx* ctx, const ick_sample_state* s, const ick_decode_rules* rules,
                                    int32_t pos, void* stream);
 
+/* Diverse beam search (Vijayakumar et al., AAAI 2018): the beam of a caption is split into `groups`
+ * groups of k_g = beam / groups hypotheses, rows g*k_g .. (g+1)*k_g - 1 of the caption forming group g.  At each step
+ * the groups choose in order g = 0 .. groups-1; group g ranks the candidates of its own rows by
+ *   key - lambda * c(w),  c(w) = number of hypotheses of groups 0 .. g-1 that were expanded with column w at this step
+ * (key: the ranking key of ick_decode_select_beam, or of ick_decode_select_beam_rules with rules; an ended hypothesis
+ * competes with its key as it is, and carried or dead slots count for no column), and its k_g best (ties: lower
+ * hypothesis, lower token) fill slots g*k_g + round.  The penalty only ranks: cum stays the raw summed log-probability.
+ * The caller starts every group from the <start> hypothesis (cum = 0 at rows g*k_g, -inf elsewhere).  penalty is one
+ * fp32 in device memory, read at run time, so a captured decode graph replays with a new lambda.  groups must divide
+ * ctx->rows_per_sample; rules == NULL: no decoding rules. */
+typedef struct {
+    int32_t groups;               /* G >= 1, divides the beam */
+    const float* penalty;         /* (1) lambda >= 0, fp32, device memory */
+} ick_decode_diversity;
+int ick_decode_select_beam_diverse(const ick_decode_ctx* ctx, const ick_beam_state* beam,
+                                   const ick_decode_rules* rules /* NULL: no rules */,
+                                   const ick_decode_diversity* div, int32_t pos, void* stream);
+
 /* fused token-mean cross entropy over the packed rows of train.py
  * (pack_padded_sequence + CrossEntropyLoss(ignore_index=<pad>), geo-aware/train.py:275-281):
  * rows (b,t) with t < decode_len[b] and target != pad contribute.  Writes loss_sum[0] (sum of
