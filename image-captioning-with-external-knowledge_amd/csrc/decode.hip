@@ -1519,7 +1519,12 @@ struct BeamArgs {
     // diverse beam search (the DIVERSE variant): `groups` groups of k / groups hypotheses, and the penalty lambda (one
     // fp32 in device memory)
     int groups; const float* penalty;
+    // constrained beam search (the FORCED variant): the forced columns (B, kForceMax), -1 = empty slot, the met-slot
+    // mask of every hypothesis (R), and the step's score rows (the unmet forced columns are read from them)
+    const int32_t* force; int32_t* met;
+    const float* scores; int64_t ld; const float* ptr;
 };
+constexpr int kForceMax = 8;            // forced-column slots per caption (ick_decode_constraints)
 
 // The diversity penalty lambda of ick_decode_diversity, read through the scalar cache like rule_words(): a device input
 // the host writes before a (replayed) decode.
@@ -1555,6 +1560,34 @@ __device__ __forceinline__ void block_best(float& v, int& c, float* shv, int* sh
     }
 }
 
+// block_best() with a leading integer rank: the larger rank wins, then the larger value, then the smaller code.
+__device__ __forceinline__ bool ranked_before(int p, float v, int c, int op, float ov, int oc) {
+    return op > p || (op == p && (ov > v || (ov == v && oc < c)));
+}
+__device__ __forceinline__ void block_best_ranked(int& p, float& v, int& c, int* shp, float* shv, int* shc) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int op = __shfl_xor(p, off, 64);
+        const float ov = __shfl_xor(v, off, 64);
+        const int oc = __shfl_xor(c, off, 64);
+        const bool take = ranked_before(p, v, c, op, ov, oc);
+        p = take ? op : p;
+        v = take ? ov : v;
+        c = take ? oc : c;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { shp[threadIdx.x >> 6] = p; shv[threadIdx.x >> 6] = v; shc[threadIdx.x >> 6] = c; }
+    __syncthreads();
+    p = shp[0]; v = shv[0]; c = shc[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        const bool take = ranked_before(p, v, c, shp[w], shv[w], shc[w]);
+        p = take ? shp[w] : p;
+        v = take ? shv[w] : v;
+        c = take ? shc[w] : c;
+    }
+}
+
 constexpr int kBeamChunk = 1024;      // scores per stage-1 workgroup
 constexpr int kBeamCandPerThread = 16; // stage 2 holds beam^2 x chunks candidates in the registers of 256 threads
 constexpr int kBeamRec = 2 + 2 * kBeamMax;   // floats per (row, chunk) record: max, sum of exp, kBeamMax x (value, index)
@@ -1572,8 +1605,17 @@ struct BeamPartArgs {
     const int64_t* seq; const int32_t* words;
     int step, max_len, end_token;
 };
-template <bool RULES>      // RULES: the decoding-rules variant (ick_decode_select_beam_rules)
-__global__ __launch_bounds__(256) void dec_beam_partial_kernel(BeamPartArgs a) {
+// Constrained beam search (the FORCED variant) appends the forced columns (R / k, kForceMax) and the met-slot masks (R).
+// They extend the struct for that variant alone: the hidden launch arguments the other instantiations read follow the
+// explicit ones, and would move with them.
+struct BeamPartForcedArgs : BeamPartArgs {
+    const int32_t* force; const int32_t* met;
+};
+// RULES: the decoding-rules variant (ick_decode_select_beam_rules); FORCED: constrained beam search
+// (ick_decode_select_beam_forced)
+template <bool RULES, bool FORCED = false>
+__global__ __launch_bounds__(256)
+void dec_beam_partial_kernel(std::conditional_t<FORCED, BeamPartForcedArgs, BeamPartArgs> a) {
     if (*a.n_done >= a.n_total) return;
     __shared__ float shv[4];
     __shared__ int shc[4];
@@ -1613,6 +1655,25 @@ __global__ __launch_bounds__(256) void dec_beam_partial_kernel(BeamPartArgs a) {
             if ((ban[c >> 5] >> (c & 31)) & 1u) { x[q] = -INFINITY; idx[q] = kNone; }
         }
     }
+    if constexpr (FORCED) {
+        // The row's unmet forced columns, and <end> while one is unmet, leave the pool as bans do (not the sums):
+        // stage 2 ranks the former as candidates of their own, in a higher bank.  Every column left has the row's bank.
+        const int32_t* fr = a.force + (r / a.k) * kForceMax;
+        const int met = a.met[r];
+        bool unmet_any = false;
+#pragma unroll
+        for (int s = 0; s < kForceMax; ++s) {
+            const int w = fr[s];
+            const bool unmet = w >= 0 && !((met >> s) & 1);
+            unmet_any = unmet_any || unmet;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (unmet && idx[q] == w) { x[q] = -INFINITY; idx[q] = kNone; }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (unmet_any && idx[q] == a.end_token) { x[q] = -INFINITY; idx[q] = kNone; }
+    }
     for (int round = 0; round < a.k; ++round) {
         float bv = -INFINITY; int bc = kNone;
 #pragma unroll
@@ -1629,8 +1690,9 @@ __global__ __launch_bounds__(256) void dec_beam_partial_kernel(BeamPartArgs a) {
     }
 }
 
-// DIVERSE: diverse beam search (ick_decode_select_beam_diverse)
-template <bool RULES, bool DIVERSE>
+// DIVERSE: diverse beam search (ick_decode_select_beam_diverse); FORCED: constrained beam search
+// (ick_decode_select_beam_forced)
+template <bool RULES, bool DIVERSE = false, bool FORCED = false>
 __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     // No exit on *n_done here: other workgroups of this very launch add to it, and the hypothesis tables are
     // ping-pong buffers -- a step that skipped its carry-copy would leave the previous step's rows (in another
@@ -1642,6 +1704,8 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     __shared__ int fin_s[kBeamMax], parent_s[kBeamMax], tok_s[kBeamMax], nfin_s[kBeamMax];
     __shared__ int len_s[kBeamMax];
     __shared__ float lpf_s[kBeamMax];
+    __shared__ int met_s[FORCED ? kBeamMax : 1], force_s[FORCED ? kForceMax : 1], nmet_s[FORCED ? kBeamMax : 1];
+    __shared__ int shp[FORCED ? 4 : 1];
     const int tid = threadIdx.x, k = a.k;
     const int64_t r0 = (int64_t)blockIdx.x * k;
     const int np = a.K + a.F, Vx = a.V + np;
@@ -1652,6 +1716,10 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     if (tid < k) {
         cum_s[tid] = a.cum[r0 + tid]; fin_s[tid] = a.fin[r0 + tid];
         if (lp_on) { len_s[tid] = a.len[r0 + tid]; lpf_s[tid] = a.lp[len_s[tid]]; }
+    }
+    if constexpr (FORCED) {
+        if (tid < k) met_s[tid] = a.met[r0 + tid];
+        if (tid >= 64 && tid < 64 + kForceMax) force_s[tid - 64] = a.force[blockIdx.x * kForceMax + tid - 64];
     }
     __syncthreads();
     bool live_any = false;
@@ -1710,6 +1778,83 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
             }
         }
     }
+    if constexpr (FORCED) {
+        // Constrained beam search (dynamic beam allocation): every candidate carries its bank, the number of met slots
+        // of the hypothesis it would make.  A pool candidate has its row's bank (stage 1 took the unmet forced columns
+        // and a closed <end> out of the pool); thread j * kForceMax + s adds row j's unmet forced column of slot s,
+        // scored from the row like the pool's.  The k rounds visit the banks from the highest down and round again,
+        // skipping empty ones: the rank below puts the non-empty bank whose turn it is first, so one ranked arg-best
+        // per round takes that bank's best candidate.
+        constexpr int NF = NC + 1;
+        float fv[NF]; int fc[NF], fb[NF];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            fv[q] = cv[q]; fc[q] = cc[q];
+            fb[q] = cc[q] == kNone ? -32 : __popc(met_s[cc[q] / Vx]);
+        }
+        fv[NC] = -INFINITY; fc[NC] = kNone; fb[NC] = -32;
+        if (tid < k * kForceMax) {
+            const int j = tid / kForceMax, s = tid - j * kForceMax, w = force_s[s];
+            bool cand = w >= 0 && !((met_s[j] >> s) & 1) && !fin_s[j] && cum_s[j] != -INFINITY;
+            int add = 0;
+#pragma unroll
+            for (int s2 = 0; s2 < kForceMax; ++s2) {
+                const bool same = force_s[s2] == w;
+                cand = cand && !(same && s2 < s);               // slots holding one id: one candidate, the first slot's
+                add |= same ? 1 << s2 : 0;
+            }
+            if (cand) {
+                const float x = w < a.V ? a.scores[(r0 + j) * a.ld + w] : a.ptr[(r0 + j) * np + (w - a.V)];
+                const float v = cum_s[j] - lse_s[j] + x;
+                fv[NC] = lp_on ? v / lp_live : v; fc[NC] = j * Vx + w;
+                fb[NC] = __popc(met_s[j] | add);
+            }
+        }
+        int turn = kForceMax + 1;                               // the bank visited last
+        for (int round = 0; round < k; ++round) {
+            int bp = -64; float bv = -INFINITY; int bc = kNone;
+#pragma unroll
+            for (int q = 0; q < NF; ++q) {
+                const int p = fb[q] < turn ? fb[q] + 16 : fb[q];
+                const bool take = ranked_before(bp, bv, bc, p, fv[q], fc[q]);
+                bp = take ? p : bp;
+                bv = take ? fv[q] : bv;
+                bc = take ? fc[q] : bc;
+            }
+            block_best_ranked(bp, bv, bc, shp, shv, shc);
+#pragma unroll
+            for (int q = 0; q < NF; ++q)
+                if (fc[q] == bc) { fv[q] = -INFINITY; fc[q] = kNone; fb[q] = -32; }
+            if (bc != kNone) turn = bp >= 16 ? bp - 16 : bp;
+            if (tid != 0) continue;
+            const int c = bc;
+            float v = -INFINITY;                                    // fewer candidates than beams: a dead slot
+            int parent = 0, tok = a.pad_token, nf = 1, len = 0, met = 0;
+            if (c != kNone) {
+                parent = c / Vx;
+                met = met_s[parent];
+                if (fin_s[parent]) {
+                    v = cum_s[parent]; len = lp_on ? len_s[parent] : 0;
+                } else {
+                    tok = c - parent * Vx; nf = tok == a.end_token;
+                    const float x = tok < a.V ? a.scores[(r0 + parent) * a.ld + tok]
+                                              : a.ptr[(r0 + parent) * np + (tok - a.V)];
+                    v = cum_s[parent] - lse_s[parent] + x;          // the expression that made the key
+                    len = a.step + 1;
+                    for (int s = 0; s < kForceMax; ++s) met |= force_s[s] == tok ? 1 << s : 0;
+                }
+            }
+            parent_s[round] = parent; tok_s[round] = tok; nfin_s[round] = nf; nmet_s[round] = met;
+            if (lp_on) a.len[r0 + round] = len;
+            a.cum[r0 + round] = v;
+            a.fin[r0 + round] = nf;
+            const bool live = c != kNone && !nf;
+            a.next_token[r0 + round] = live ? tok : 0;
+            a.next_mask[r0 + round] = !live ? 0 : ((a.has_facts && tok >= a.V + a.K) ? 2 : (tok >= a.V ? 1 : 0));
+        }
+        __syncthreads();
+        if (tid < k) a.met[r0 + tid] = nmet_s[tid];
+    } else
     if constexpr (!DIVERSE) {
     for (int round = 0; round < k; ++round) {
         float bv = -INFINITY; int bc = kNone;
@@ -2151,7 +2296,8 @@ extern "C" int ick_decode_select_greedy(const ick_decode_ctx* c, int32_t pos, vo
 }
 
 static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, const ick_decode_rules* rules,
-                            const ick_decode_diversity* div, int32_t pos, void* stream) {
+                            const ick_decode_diversity* div, const ick_decode_constraints* fc, int32_t pos,
+                            void* stream) {
     ICK_CHECK_ARG(c && bs && c->R > 0 && pos >= 0 && pos < c->max_len);
     ICK_CHECK_ARG(c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax && c->R % c->rows_per_sample == 0);
     ICK_CHECK_ARG(c->scores && c->scores_ld >= c->V && c->ptr && c->n_done && c->next_token && c->next_mask &&
@@ -2161,14 +2307,20 @@ static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, c
     ICK_CHECK_ARG(bs->rec != nullptr);
     const int Vx = c->V + c->K + c->F, nchunk = ceil_div(Vx, kBeamChunk);
     ICK_CHECK_ARG(ick_decode_beam_supported(Vx, c->rows_per_sample));
-    BeamPartArgs pa;
+    BeamPartForcedArgs pa;
     pa.scores = c->scores; pa.ld = c->scores_ld; pa.ptr = c->ptr; pa.cum = bs->cum; pa.fin = bs->fin; pa.rec = bs->rec;
     pa.R = c->R; pa.k = c->rows_per_sample; pa.V = c->V; pa.np = c->K + c->F; pa.nchunk = nchunk;
     pa.n_done = c->n_done; pa.n_total = c->R;
     pa.seq = bs->seq_in; pa.words = rules ? rules->words : nullptr;
     pa.step = pos; pa.max_len = c->max_len; pa.end_token = c->end_token;
-    void (*part)(BeamPartArgs) = rules ? dec_beam_partial_kernel<true> : dec_beam_partial_kernel<false>;
-    hipLaunchKernelGGL(part, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, pa);
+    if (fc != nullptr) {
+        pa.force = fc->force; pa.met = fc->met;
+        void (*part)(BeamPartForcedArgs) = rules ? dec_beam_partial_kernel<true, true> : dec_beam_partial_kernel<false, true>;
+        hipLaunchKernelGGL(part, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, pa);
+    } else {
+        void (*part)(BeamPartArgs) = rules ? dec_beam_partial_kernel<true> : dec_beam_partial_kernel<false>;
+        hipLaunchKernelGGL(part, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, (const BeamPartArgs&)pa);
+    }
     BeamArgs a;
     a.rec = bs->rec; a.cum = bs->cum; a.fin = bs->fin;
     a.seq_in = bs->seq_in; a.seq_out = bs->seq_out; a.anc_in = bs->anc_in; a.anc_out = bs->anc_out;
@@ -2180,21 +2332,25 @@ static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, c
     a.start_token = bs->start_token; a.emb_scale = c->emb_scale; a.n_total = c->R;
     a.words = rules ? rules->words : nullptr; a.lp = rules ? rules->lp : nullptr; a.len = rules ? rules->len : nullptr;
     a.groups = div ? div->groups : 1; a.penalty = div ? div->penalty : nullptr;
-    void (*sel)(BeamArgs) = div ? (rules ? dec_select_beam_kernel<true, true> : dec_select_beam_kernel<false, true>)
+    a.force = fc ? fc->force : nullptr; a.met = fc ? fc->met : nullptr;
+    a.scores = c->scores; a.ld = c->scores_ld; a.ptr = c->ptr;
+    void (*sel)(BeamArgs) = fc ? (rules ? dec_select_beam_kernel<true, false, true>
+                                        : dec_select_beam_kernel<false, false, true>) :
+                            div ? (rules ? dec_select_beam_kernel<true, true> : dec_select_beam_kernel<false, true>)
                                 : (rules ? dec_select_beam_kernel<true, false> : dec_select_beam_kernel<false, false>);
     hipLaunchKernelGGL(sel, dim3(c->R / c->rows_per_sample), dim3(256), 0, (hipStream_t)stream, a);
     ICK_LAUNCH_RET();
 }
 
 extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_state* bs, int32_t pos, void* stream) {
-    return select_beam_impl(c, bs, nullptr, nullptr, pos, stream);
+    return select_beam_impl(c, bs, nullptr, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_rules(const ick_decode_ctx* c, const ick_beam_state* bs,
                                             const ick_decode_rules* rules, int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && rules && rules->words && rules->lp && rules->len && ((uintptr_t)rules->words & 15) == 0);
     ICK_CHECK_ARG(c->max_len <= kRuleHistMax && c->end_token >= 0 && c->end_token < c->V);
-    return select_beam_impl(c, bs, rules, nullptr, pos, stream);
+    return select_beam_impl(c, bs, rules, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_diverse(const ick_decode_ctx* c, const ick_beam_state* bs,
@@ -2206,5 +2362,16 @@ extern "C" int ick_decode_select_beam_diverse(const ick_decode_ctx* c, const ick
         ICK_CHECK_ARG(rules->words && rules->lp && rules->len && ((uintptr_t)rules->words & 15) == 0);
         ICK_CHECK_ARG(c->max_len <= kRuleHistMax && c->end_token >= 0 && c->end_token < c->V);
     }
-    return select_beam_impl(c, bs, rules, div, pos, stream);
+    return select_beam_impl(c, bs, rules, div, nullptr, pos, stream);
+}
+
+extern "C" int ick_decode_select_beam_forced(const ick_decode_ctx* c, const ick_beam_state* bs,
+                                             const ick_decode_rules* rules, const ick_decode_constraints* fc,
+                                             int32_t pos, void* stream) {
+    ICK_CHECK_ARG(c && fc && fc->force && fc->met && c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax);
+    if (rules != nullptr) {
+        ICK_CHECK_ARG(rules->words && rules->lp && rules->len && ((uintptr_t)rules->words & 15) == 0);
+        ICK_CHECK_ARG(c->max_len <= kRuleHistMax && c->end_token >= 0 && c->end_token < c->V);
+    }
+    return select_beam_impl(c, bs, rules, nullptr, fc, pos, stream);
 }

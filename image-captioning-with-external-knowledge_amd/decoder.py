@@ -171,6 +171,38 @@ def check_diversity(what, beam_size, num_beam_groups=1, diversity_penalty=0.0):
     return num_beam_groups > 1
 
 
+FORCE_MAX = 8
+
+
+def check_force(what, B, Vx, special, force_tokens=None, num_beam_groups=1):
+    """Validate predict_beam's force_tokens (IckError): None, or an integer tensor / nested list (B, C), C in 1..8, of
+    column ids in [0, Vx) with -1 for an empty slot; `special` holds the ids that cannot be forced (<start>, <end>,
+    <pad>).  Returns None, or the int32 CPU tensor (B, 8) padded with -1 that becomes the device input."""
+    if force_tokens is None:
+        return None
+    if isinstance(num_beam_groups, int) and num_beam_groups > 1:
+        raise IckError("%s: force_tokens does not compose with num_beam_groups > 1" % what)
+    ft = force_tokens
+    if not torch.is_tensor(ft):
+        try:
+            ft = torch.tensor(ft)
+        except (TypeError, ValueError, RuntimeError):
+            raise IckError("%s needs force_tokens as an integer tensor or nested list (B, 1..%d)" % (what, FORCE_MAX))
+    if ft.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or ft.dim() != 2 or \
+            ft.shape[0] != B or not 1 <= ft.shape[1] <= FORCE_MAX:
+        raise IckError("%s needs force_tokens as an integer tensor or nested list (B = %d, 1..%d)"
+                       % (what, B, FORCE_MAX))
+    ft = ft.detach().to("cpu", torch.int64)                  # one small read-back per call
+    if bool((ft < -1).any()) or bool((ft >= Vx).any()):
+        raise IckError("%s: force_tokens holds column ids in [0, V+K+F = %d) or -1 for an empty slot" % (what, Vx))
+    for tok in special:
+        if bool((ft == tok).any()):
+            raise IckError("%s: <start>, <end> and <pad> cannot be forced" % what)
+    out = torch.full((B, FORCE_MAX), -1, dtype=torch.int32)
+    out[:, :ft.shape[1]] = ft.to(torch.int32)
+    return out
+
+
 def rules_tensor(max_len, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0, device="cuda"):
     """The device input of the rules (lib.DecodeRules): int32 (4 + max_len + 1) = the rule words
     {no_repeat_ngram_size, min_len, length penalty on, 0} followed by the fp32 bits of length_penalty_table()."""
@@ -1244,7 +1276,7 @@ class DecoderTransformer(nn.Module):
         return t["output"]
 
     def _predict_beam_device(self, enc_tok, entities, facts, max_pred_len, beam, attention=False, rules=None, groups=1,
-                             penalty=None):
+                             penalty=None, force=None):
         """Beam search on the fused decode kernels: R = B * beam rows share their caption's cross K/V; the
         self-attention cache is never reordered -- an ancestry table says which cache row holds position p of a
         hypothesis.  Returns (best sequence (B, max_len), its log-probability (B), all sequences, all scores); with
@@ -1253,7 +1285,9 @@ class DecoderTransformer(nn.Module):
         best hypothesis is the argmax of cum / lp[length].  groups > 1: diverse beam search with the
         penalty lambda read from the (1) fp32 device tensor `penalty`; every group starts from the <start> hypothesis,
         and the best hypothesis of each group (by the unpenalised key) follows: (its sequence (B * G, max_len), its
-        log-probability (B * G)), and with attention its weights (max_len, B * G, layers, H, S)."""
+        log-probability (B * G)), and with attention its weights (max_len, B * G, layers, H, S).  force: the (B, 8) int32
+        device tensor of check_force() (read at run time) or None; with it the search is the constrained one of
+        DESIGN.md §3.2g and the best hypothesis is the best by (met slots, key)."""
         from . import lib as L
         B = enc_tok.shape[0]
         d, V, K = self.emb_dim, self.vocab_size, entities.shape[1]
@@ -1288,6 +1322,10 @@ class DecoderTransformer(nn.Module):
         if groups > 1:
             dv = L.DecodeDiversity()
             dv.groups, dv.penalty = groups, penalty.data_ptr()
+        if force is not None:
+            met = torch.zeros(R, dtype=torch.int32, device=dev)
+            fc = L.DecodeConstraints()
+            fc.force, fc.met = force.data_ptr(), met.data_ptr()
         for i in range(max_pred_len):
             cur, nxt = i & 1, (i + 1) & 1
             c.anc = anc[cur].data_ptr()
@@ -1301,7 +1339,9 @@ class DecoderTransformer(nn.Module):
                 ops.decode_layers(c, i)
             bs.seq_in, bs.seq_out = seq[cur].data_ptr(), seq[nxt].data_ptr()
             bs.anc_in, bs.anc_out = anc[cur].data_ptr(), anc[nxt].data_ptr()
-            if groups > 1:
+            if force is not None:
+                ops.decode_select_beam_forced(c, bs, rs, fc, i)
+            elif groups > 1:
                 ops.decode_select_beam_diverse(c, bs, rs, dv, i)
             elif rules is None:
                 ops.decode_select_beam(c, bs, i)
@@ -1315,6 +1355,10 @@ class DecoderTransformer(nn.Module):
             lp = rules[4:].view(torch.float32)
             key = cum / lp[lens.view(B, beam).long()]
             best = key.argmax(dim=1)
+        if force is not None:                             # bank first: the key ranks among the most-met hypotheses
+            bank = ((met.view(B, beam, 1) >> torch.arange(FORCE_MAX, device=dev, dtype=torch.int32)) & 1).sum(dim=2)
+            top = bank == bank.max(dim=1, keepdim=True).values
+            best = torch.where(top, key, torch.full_like(key, float("-inf"))).argmax(dim=1)
         out = final[torch.arange(B, device=dev), best]
         group_res = ()
         if groups > 1:                                    # the best of each group by the same key (no penalty)
@@ -1336,7 +1380,7 @@ class DecoderTransformer(nn.Module):
     @torch.no_grad()
     def predict_beam(self, encoder_out, max_pred_len, entities, facts=None, beam_size=5, return_all=False,
                      return_attention=False, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0, num_beam_groups=1,
-                     diversity_penalty=0.0, return_groups=False):
+                     diversity_penalty=0.0, return_groups=False, force_tokens=None):
         """Beam-search decode (north_star cfg5: beam 5, batch 32).  The reference decodes greedily only
         (geo-aware/eval.py:61,83), so beam > 1 has no reference output to pin against ("parity-unpinned"); the tests
         check it against a CPU beam search written to the same rules.  beam_size == 1 IS predict(): the pinned greedy path with
@@ -1365,12 +1409,24 @@ class DecoderTransformer(nn.Module):
         lists every hypothesis group-major.  return_groups=True returns the best hypothesis of each group instead of
         the best of the caption: (max_pred_len, B * G), column b * G + g for group g of caption b; with return_all
         their log-probabilities (B * G) come second (the (B, beam, ...) values follow unchanged), and with
-        return_attention their weights are (max_pred_len, B * G, layers, H, S)."""
+        return_attention their weights are (max_pred_len, B * G, layers, H, S).
+
+        Constrained beam search (dynamic beam allocation, Post & Vilar, NAACL 2018): force_tokens is
+        an integer tensor or nested list (B, C), C in 1..8, of columns every caption must contain: a word id, V + k for
+        entity slot k, V + K + j for fact j, or -1 for an empty slot (<start>, <end> and <pad> cannot be forced).  A
+        hypothesis cannot end before it has emitted all its caption's columns, and at every step the beam is shared
+        out between the hypotheses by how many they have emitted, so that the furthest always keeps a slot; the
+        returned caption contains every forced column whenever max_pred_len >= their number.  The ids are a device
+        input of the captured graph (new ids, or another C, replay it); scores stay the model's log-probabilities, the
+        rules compose, and return shapes do not change.  A caption whose slots are all empty gets the plain search, bit
+        for bit; None, the default, is the call without the argument.  Not with num_beam_groups > 1."""
         P_ = entities.shape[1] + (facts.shape[1] if facts is not None else 0)
         rules_on = check_rules("predict_beam", max_pred_len, self.vocab_size + P_, length_penalty,
                                no_repeat_ngram_size, min_len)
         diverse = check_diversity("predict_beam", beam_size, num_beam_groups, diversity_penalty)
-        if beam_size == 1 and not rules_on:
+        force = check_force("predict_beam", encoder_out.shape[0], self.vocab_size + P_,
+                            [self.word_map[w] for w in ("<start>", "<end>", "<pad>")], force_tokens, num_beam_groups)
+        if beam_size == 1 and not rules_on and force is None:
             return DecoderTransformer.predict(self, encoder_out, max_pred_len, entities, facts,
                                               return_attention=return_attention)
         encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
@@ -1394,7 +1450,14 @@ class DecoderTransformer(nn.Module):
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, beam_size) + self._enc_key(enc_tok)
-            if diverse:
+            if force is not None:
+                force = force.to(enc_tok.device)
+                kind = ("beam_force_rules" if rules_on else "beam_force") + ("_attn" if return_attention else "")
+                res = self._graphed(kind, key,
+                                    lambda t, e, f, r, ft: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
+                                                                                     return_attention, r, force=ft),
+                                    [enc_tok, entities, facts, rules, force])
+            elif diverse:
                 kind = ("beam_div_rules" if rules_on else "beam_div") + ("_attn" if return_attention else "")
                 res = self._graphed(kind, key + (G,),
                                     lambda t, e, f, r, lam: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
@@ -1412,7 +1475,7 @@ class DecoderTransformer(nn.Module):
                                     [enc_tok, entities, facts])
         else:
             res = self._predict_beam_device(enc_tok, entities, facts, max_pred_len, beam_size, return_attention, rules,
-                                            G, penalty)
+                                            G, penalty, None if force is None else force.to(enc_tok.device))
         if return_groups and diverse:       # the best of each group in place of the best of the caption
             n = 6 if return_attention else 4
             res = (res[n], res[n + 1], res[2], res[3]) + ((res[n + 2], res[5]) if return_attention else ())

@@ -46,7 +46,9 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
     generated_caption; an explicit seed is advanced by one per batch.  beam = a dict of predict_beam keyword arguments
     (beam_size, length_penalty, no_repeat_ngram_size, min_len, num_beam_groups, diversity_penalty, return_groups):
     beam-search decode, one CSV row per image (the best hypothesis); with return_groups (diverse beam search), one CSV
-    row per (image, group) with the columns image, group, generated_caption, the best hypothesis of each group; beam
+    row per (image, group) with the columns image, group, generated_caption, the best hypothesis of each group;
+    force_tokens (constrained beam search) is a callable fn(batch_index, batch) -> the (B, C) forced column ids of
+    that batch, since one tensor cannot fit every batch; beam
     and sample together are a ValueError.
     attention_out: a path for one .npz of the decoder's cross-attention (return_attention of predict / predict_sample):
     "attention" float16 (N, max_len, S), the last decoder layer's weights averaged over its heads, one row per CSV row;
@@ -85,6 +87,8 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
         if beam is not None:
             kw = dict(beam)
             kw.pop("return_all", None)
+            if kw.get("force_tokens") is not None:           # a callable: the forced columns of this batch
+                kw["force_tokens"] = kw["force_tokens"](bi, batch)
             seq = decoder.predict_beam(enc_in, max_caption_len, ent, *extra, return_attention=want_attn, **kw)
         elif sample is None:
             seq = decoder.predict(enc_in, max_caption_len, ent, *extra, return_attention=want_attn)  # (max_len, B)

@@ -153,6 +153,10 @@ class DecodeDiversity(C.Structure):     # ick_decode_diversity: beam groups, the
     _fields_ = [("groups", i32), ("penalty", vp)]
 
 
+class DecodeConstraints(C.Structure):   # ick_decode_constraints: forced columns (B, 8) int32, met-slot masks (R) int32
+    _fields_ = [("force", vp), ("met", vp)]
+
+
 # name -> argtypes; every entry returns int (0 ok, <0 ICK_E*, >0 hipError_t)
 SIGNATURES = {
     "ick_version": [],
@@ -204,6 +208,8 @@ SIGNATURES = {
     "ick_decode_select_sample_rules": [C.POINTER(DecodeCtx), C.POINTER(SampleState), C.POINTER(DecodeRules), i32, vp],
     "ick_decode_select_beam_diverse": [C.POINTER(DecodeCtx), C.POINTER(BeamState), C.POINTER(DecodeRules),
                                        C.POINTER(DecodeDiversity), i32, vp],
+    "ick_decode_select_beam_forced": [C.POINTER(DecodeCtx), C.POINTER(BeamState), C.POINTER(DecodeRules),
+                                      C.POINTER(DecodeConstraints), i32, vp],
     "ick_attention_bwd": [C.POINTER(AttnBwdArgs), vp],
     "ick_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, f32, u32, u32, vp, vp, vp],
     "ick_layernorm_bwd_rows_per_block": [],

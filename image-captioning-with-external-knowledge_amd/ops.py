@@ -666,6 +666,14 @@ def decode_select_beam_diverse(ctx, beam_state, rules, diversity, pos):
                                                     pos, _stream()), "ick_decode_select_beam_diverse")
 
 
+def decode_select_beam_forced(ctx, beam_state, rules, constraints, pos):
+    """ick_decode_select_beam_forced: constrained beam search (lib.DecodeConstraints: force, met), under decoding rules
+    (lib.DecodeRules) or none (rules=None)."""
+    L.check(L.load().ick_decode_select_beam_forced(C.byref(ctx), C.byref(beam_state),
+                                                   None if rules is None else C.byref(rules), C.byref(constraints),
+                                                   pos, _stream()), "ick_decode_select_beam_forced")
+
+
 def decode_select_sample_rules(ctx, sample_state, rules, pos):
     """ick_decode_select_sample under decoding rules (lib.DecodeRules): n-gram / min-length bans."""
     L.check(L.load().ick_decode_select_sample_rules(C.byref(ctx), C.byref(sample_state), C.byref(rules), pos,

@@ -478,6 +478,25 @@ int ick_decode_select_beam_diverse(const ick_decode_ctx* ctx, const ick_beam_sta
                                    const ick_decode_rules* rules /* NULL: no rules */,
                                    const ick_decode_diversity* div, int32_t pos, void* stream);
 
+/* Constrained beam search (dynamic beam allocation, Post & Vilar, NAACL 2018, for single-column constraints; DESIGN.md
+ * §3.2g): up to 8 forced columns per caption, ids in [0, V+K+F) (entity k: V + k, fact j: V + K + j), -1 = empty slot.
+ * Every hypothesis carries the mask `met` of the slots whose column it has emitted (slots holding one id are met
+ * together); its bank is the number of met slots.  <end> is closed to a hypothesis with an unmet slot.  At each step
+ * every candidate (an ended hypothesis as it is, or a live hypothesis and a column the rules do not ban) has the bank
+ * of the hypothesis it would make and the ranking key of ick_decode_select_beam(_rules); the k new hypotheses are taken
+ * by visiting the banks n_req, n_req - 1, .., 0 (n_req = the caption's non-empty slots) and round again, each visit
+ * taking that bank's best remaining candidate (ties: lower hypothesis, lower column) and skipping empty banks; slot i
+ * receives the i-th candidate taken.  cum stays the raw summed log-probability.  With every slot empty this is
+ * ick_decode_select_beam(_rules) bit for bit.  force is read at run time, so a captured decode graph replays with new
+ * ids; the caller zeroes met before step 0 and picks the final best by (bank, key).  rules == NULL: no rules. */
+typedef struct {
+    const int32_t* force;         /* (R / rows_per_sample, 8) forced columns, -1 = empty, device memory */
+    int32_t* met;                 /* (R) bit s: slot s met; zeroed by the caller before step 0 */
+} ick_decode_constraints;
+int ick_decode_select_beam_forced(const ick_decode_ctx* ctx, const ick_beam_state* beam,
+                                  const ick_decode_rules* rules /* NULL: no rules */,
+                                  const ick_decode_constraints* constraints, int32_t pos, void* stream);
+
 /* fused token-mean cross entropy over the packed rows of train.py
  * (pack_padded_sequence + CrossEntropyLoss(ignore_index=<pad>), geo-aware/train.py:275-281):
  * rows (b,t) with t < decode_len[b] and target != pad contribute.  Writes loss_sum[0] (sum of
