@@ -298,14 +298,26 @@ __global__ __launch_bounds__(256) void fact_encode_bwd_det_kernel(const float* _
 //   dh[b,t,:]   += sum_k ds*ind * ctx[b,k,:] * w        (one workgroup per (b,t))
 //   dctx[b,k,:] += sum_t ds*ind * h[b,t,:] * w          (one workgroup per (b,k))
 //   dw          += sum ds*ind * h * ctx ;  dbias += sum ds
+// Packed form (ick_pointer_scores_bwd_packed; rowmap / rowstart of ick_head_rowmap): ds holds the packed rows of the
+// valid positions only -- sample b's are rows rowstart[b] .. rowstart[b + 1] - 1 in position order -- while h, ind, dh keep
+// their logical rows.  The dh kernel's workgroup m takes packed row m (logical row rowmap[m]) and exits past the row count
+// rowstart[B]; the dctx kernel reads a zero gradient for the positions beyond a sample's rows.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pointer_bwd_dh_kernel(const float* __restrict__ ds, int64_t ds_ld, int col0,
                                                              const float* __restrict__ ctx, const float* __restrict__ w,
                                                              const float* __restrict__ ind, float* __restrict__ dh,
-                                                             int T, int Kc, int d) {
+                                                             int T, int Kc, int d, const int32_t* __restrict__ rowmap,
+                                                             const int32_t* __restrict__ count) {
     chain_priority();
-    const int b = blockIdx.y, t = blockIdx.x;
-    const float* dsr = ds + ((int64_t)b * T + t) * ds_ld + col0;
+    int b = blockIdx.y, t = blockIdx.x;
+    int64_t dsrow = (int64_t)b * T + t;
+    if (rowmap != nullptr) {     // uniform
+        if (dsrow >= device_bound((int)gridDim.y * T, count)) return;
+        const int lr = rowmap[dsrow];
+        b = lr / T;
+        t = lr - b * T;
+    }
+    const float* dsr = ds + dsrow * ds_ld + col0;
     for (int c = threadIdx.x; c < d; c += 256) {
         float acc = 0.f;
         const float* cc = ctx + (int64_t)b * Kc * d + c;
@@ -340,7 +352,8 @@ __global__ __launch_bounds__(256) void pointer_bwd_dctx_kernel(const float* __re
                                                                const float* __restrict__ h, const float* __restrict__ ctx,
                                                                const float* __restrict__ w, const float* __restrict__ ind,
                                                                float* __restrict__ dctx, float* __restrict__ dw,
-                                                               float* __restrict__ dbias, int B, int T, int Kc, int d) {
+                                                               float* __restrict__ dbias, int B, int T, int Kc, int d,
+                                                               const int32_t* __restrict__ rowstart) {
     chain_priority();
     extern __shared__ float gs[];   // T * Kc gradients (indicator applied), 4 floats of scratch, 4 x 64 partial d w
     float* red = gs + T * Kc;
@@ -348,9 +361,12 @@ __global__ __launch_bounds__(256) void pointer_bwd_dctx_kernel(const float* __re
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int b = SEQ ? 0 : blockIdx.x; b < (SEQ ? B : (int)blockIdx.x + 1); ++b) {
     float bsum = 0.f;
+    // packed score gradients: the sample's nrow rows start at row0; the positions beyond them contribute exact zeros
+    const int64_t row0 = rowstart ? rowstart[b] : (int64_t)b * T;
+    const int nrow = rowstart ? min(T, rowstart[b + 1] - rowstart[b]) : T;
     for (int idx = threadIdx.x; idx < T * Kc; idx += 256) {
         const int t = idx / Kc, k = idx - t * Kc;
-        float g = ds[((int64_t)b * T + t) * ds_ld + col0 + k];
+        float g = t < nrow ? ds[(row0 + t) * ds_ld + col0 + k] : 0.f;
         bsum += g;
         if (ind) g *= ind[((int64_t)b * T + t) * Kc + k];
         gs[idx] = g;
@@ -663,17 +679,27 @@ extern "C" int ick_caption_embed_bwd(const float* dx, const int64_t* captions, c
 extern "C" int ick_pointer_scores_bwd(const float* ds, int64_t ds_ld, int32_t col0, const float* h, const float* ctx,
                                       const float* w, const float* ind, float* dh, float* dctx, float* dw,
                                       float* dbias, int32_t B, int32_t T, int32_t Kc, int32_t d, void* stream) {
+    return ick_pointer_scores_bwd_packed(ds, ds_ld, col0, h, ctx, w, ind, dh, dctx, dw, dbias, B, T, Kc, d, nullptr, nullptr,
+                                         stream);
+}
+
+extern "C" int ick_pointer_scores_bwd_packed(const float* ds, int64_t ds_ld, int32_t col0, const float* h, const float* ctx,
+                                             const float* w, const float* ind, float* dh, float* dctx, float* dw,
+                                             float* dbias, int32_t B, int32_t T, int32_t Kc, int32_t d,
+                                             const int32_t* rowmap, const int32_t* rowstart, void* stream) {
     ICK_CHECK_ARG(ds && h && ctx && w && dh && dctx && dw && dbias && B > 0 && B <= 65535 && T > 0 && Kc > 0 && d > 0);
+    ICK_CHECK_ARG((rowmap == nullptr) == (rowstart == nullptr) && (int64_t)B * T <= INT32_MAX);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pointer_bwd_dh_kernel, dim3(T, B), dim3(256), 0, s, ds, ds_ld, col0, ctx, w, ind, dh, T, Kc, d);
+    hipLaunchKernelGGL(pointer_bwd_dh_kernel, dim3(T, B), dim3(256), 0, s, ds, ds_ld, col0, ctx, w, ind, dh, T, Kc, d, rowmap,
+                       rowstart ? rowstart + B : nullptr);
     const size_t smem = ((size_t)T * Kc + 4 + 256) * sizeof(float);
     ICK_CHECK_ARG(smem <= 64 * 1024);
     if (deterministic())
         hipLaunchKernelGGL(pointer_bwd_dctx_kernel<true>, dim3(1, ceil_div(d, 64)), dim3(256), smem, s, ds, ds_ld, col0, h,
-                           ctx, w, ind, dctx, dw, dbias, B, T, Kc, d);
+                           ctx, w, ind, dctx, dw, dbias, B, T, Kc, d, rowstart);
     else
         hipLaunchKernelGGL(pointer_bwd_dctx_kernel<false>, dim3(B, ceil_div(d, 64)), dim3(256), smem, s, ds, ds_ld, col0, h,
-                           ctx, w, ind, dctx, dw, dbias, B, T, Kc, d);
+                           ctx, w, ind, dctx, dw, dbias, B, T, Kc, d, rowstart);
     ICK_LAUNCH_RET();
 }
 

@@ -170,6 +170,19 @@ __device__ __forceinline__ uint32_t epoch_seed(uint32_t seed, const uint32_t* ep
     return seed + *epoch;                   // (the host pass only parses device code)
 #endif
 }
+// An extent that is only known on the device (ick_gemm_args.m_bound / k_bound, the row count of the packed score head):
+// min(host extent, *dev), read once per workgroup through the scalar cache like epoch_seed()'s counter -- it was written
+// by an earlier kernel (ick_head_rowmap) and a dispatch starts with a clean scalar cache.  dev == nullptr: the host extent.
+__device__ __forceinline__ int device_bound(int host, const int32_t* dev) {
+    if (dev == nullptr) return host;        // uniform
+#if defined(__HIP_DEVICE_COMPILE__)
+    int v;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(dev) : "memory");
+    return min(host, max(v, 0));
+#else
+    return host;                            // (the host pass only parses device code)
+#endif
+}
 // Decoding rules of beam search and sampling (ick_decode_rules).  The four rule words
 // {no_repeat_ngram_size, min_len, length penalty on, 0} are device memory written by the host before a (replayed)
 // decode; the first three are read through the scalar cache like epoch_seed()'s counter.  words == nullptr: every

@@ -277,10 +277,10 @@ __device__ __forceinline__ bool split_major(int& bid, int& zid, int nt, int nspl
     return true;
 }
 
-// One output tile: workgroup `bid` of the tiles_m x tiles_n grid of problem p, K slice `zid`.
+// One output tile: workgroup `bid` of the tiles_m x tiles_n grid of problem p, K slice `zid` of `nsplit`.
 template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, int BKT, bool SPL = false, int LSTG = 2>
 __device__ __forceinline__ void gemm_tile(const ick_gemm_args& p, int tiles_m, int tiles_n, int kchunk, int bid,
-                                          int zid, float* smem, bool xcd_remap = true) {
+                                          int zid, int nsplit, float* smem, bool xcd_remap = true) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     constexpr int BK = BKT;
     using SA = Stager<BM, AKM, VEC, BKT, WM * WN * 64, SPL>;
@@ -308,13 +308,18 @@ __device__ __forceinline__ void gemm_tile(const ick_gemm_args& p, int tiles_m, i
     if (tiles_m <= tiles_n) { tm = bid % tiles_m; tn = bid / tiles_m; }
     else { tn = bid % tiles_n; tm = bid / tiles_n; }
     const int m0 = tm * BM, n0 = tn * BN;
+    // Device-side extents (m_bound / k_bound; uniform): the grid was sized for p.M rows and p.K, the rows and the reduction
+    // length that exist are read here.  The K slices partition [0, K'); a tile at or past a bound exits before any load.
+    const int Mr = device_bound(p.M, p.m_bound), Kr = device_bound(p.K, p.k_bound);
+    if (p.k_bound != nullptr) kchunk = ((Kr + nsplit - 1) / nsplit + 31) / 32 * 32;
     const int kbeg = zid * kchunk;
-    const int kend = min(p.K, kbeg + kchunk);
+    if (m0 >= Mr || kbeg >= Kr) return;
+    const int kend = min(Kr, kbeg + kchunk);
 
     const RowMap amap{p.a_grp, p.a_gs, p.a_gmap, p.a_rs};
     const RowMap bmap{0, 0, nullptr, p.b_rs};
     SA sa; SB sb;
-    sa.init(p.A, amap, p.a_ks, m0, p.M, p.a_extent);
+    sa.init(p.A, amap, p.a_ks, m0, Mr, p.a_extent);
     const bool only = (p.flags & ICK_GEMM_COLSUM_ONLY) != 0;   // uniform: column sums of A, no product
     sb.init(only ? p.A : p.B, bmap, p.b_ks, n0, p.N, p.b_extent);
 
@@ -447,10 +452,10 @@ __device__ __forceinline__ void gemm_tile(const ick_gemm_args& p, int tiles_m, i
             }
         }
     }
-    if (colsum && threadIdx.x < BM && m0 + (int)threadIdx.x < p.M) atomicAdd(p.colsum_a + m0 + threadIdx.x, csum);
+    if (colsum && threadIdx.x < BM && m0 + (int)threadIdx.x < Mr) atomicAdd(p.colsum_a + m0 + threadIdx.x, csum);
     if (only) return;
 
-    gemm_epilogue<TM, TN>(p, acc, m0, n0, wm, wn, fi, fq, zid);
+    gemm_epilogue<TM, TN>(p, Mr, acc, m0, n0, wm, wn, fi, fq, zid);
     ICK_GSTAMP(3);
 }
 
@@ -461,7 +466,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(ick_gemm_args p, int
     const int nt = tiles_m * tiles_n;
     int bid = blockIdx.x, zid = blockIdx.z;
     const bool by_split = split_major(bid, zid, nt, gridDim.z);
-    gemm_tile<WM, WN, TM, TN, AKM, BKM, VEC, BKT, SPL, LSTG>(p, tiles_m, tiles_n, kchunk, bid, zid, smem, !by_split);
+    gemm_tile<WM, WN, TM, TN, AKM, BKM, VEC, BKT, SPL, LSTG>(p, tiles_m, tiles_n, kchunk, bid, zid, (int)gridDim.z, smem,
+                                                             !by_split);
 }
 
 // Several independent problems of the same kernel configuration in one launch (the weight-gradient GEMMs of a
@@ -486,7 +492,7 @@ __global__ __launch_bounds__(256) void gemm_group_kernel(GroupArgs ga) {
     int zid = local / nt, bid = local - zid * nt;
     const bool by_split = split_major(bid, zid, nt, ga.split[gi]);
     gemm_tile<WM, WN, TM, TN, AKM, BKM, VEC, BKT, SPL>(ga.g[gi], ga.tiles_m[gi], ga.tiles_n[gi], ga.kchunk[gi], bid, zid,
-                                                       smem, !by_split);
+                                                       ga.split[gi], smem, !by_split);
 }
 
 // Host-side plan of one problem: validated arguments + kernel configuration.
@@ -614,6 +620,8 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
     } else {
         a.hs_dh = 0;
     }
+    // device-side extents: dropout and the gate are keyed by the row number, the column sums by M (see include/ick_amd.h)
+    if (a.m_bound) ICK_CHECK_ARG(!(a.drop_p > 0.f) && a.gate == nullptr && a.colsum_a == nullptr);
     if (a.a_grp <= 0) { a.a_grp = 0; a.a_gmap = nullptr; }
     if (a.c_grp <= 0) { a.c_grp = 0; a.c_gmap = nullptr; }
     // 16-byte vector staging is legal when every float4 the stager forms is aligned and in bounds.

@@ -95,9 +95,10 @@ __device__ __forceinline__ int kc_swz(int row) { return (-(row >> 2)) & 3; }
 // Epilogue of one workgroup tile whose waves hold TM x TN accumulator blocks of 16 x 16 (C/D map of the 16x16 MFMA:
 // col = lane & 15, row = (lane >> 4) * 4 + reg): alpha, bias, ReLU, dropout, gate, accumulate / atomic, grouped or
 // head-split rows.  wm / wn: the wave's block coordinates inside the tile; zid: K slice (bias only on slice 0).
+// M: the rows that exist (p.M, or the device-side bound below it: device_bound(p.M, p.m_bound), at least one).
 template <int TM, int TN>
-__device__ __forceinline__ void gemm_epilogue(const ick_gemm_args& p, f32x4 (&acc)[TM][TN], int m0, int n0, int wm, int wn,
-                                              int fi, int fq, int zid) {
+__device__ __forceinline__ void gemm_epilogue(const ick_gemm_args& p, int M, f32x4 (&acc)[TM][TN], int m0, int n0, int wm,
+                                              int wn, int fi, int fq, int zid) {
     // Epilogue.  C/D map of the 16x16 MFMA: col = lane & 15, row = (lane >> 4) * 4 + reg.
     const bool hs = p.hs_dh > 0;
     const RowMap cmap{p.c_grp, p.c_gs, p.c_gmap, hs ? (int64_t)p.hs_dhp : p.c_rs};
@@ -125,13 +126,13 @@ __device__ __forceinline__ void gemm_epilogue(const ick_gemm_args& p, f32x4 (&ac
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 rowid[a][r] = m0 + (wm * TM + a) * 16 + fq * 4 + r;
-                rws[a * 4 + r] = min(rowid[a][r], p.M - 1);
+                rws[a * 4 + r] = min(rowid[a][r], M - 1);
             }
         map_rows<TM * 4>(cmap, rws, mo);
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) coff[a][r] = rowid[a][r] < p.M ? mo[a * 4 + r] + row_bias : -1;
+            for (int r = 0; r < 4; ++r) coff[a][r] = rowid[a][r] < M ? mo[a * 4 + r] + row_bias : -1;
     }
     // Values first, memory second: vmcnt counts loads and stores in one queue, so a load between two stores (the gate,
     // the old value of an accumulating epilogue) makes every row wait for the previous row's stores to be acknowledged

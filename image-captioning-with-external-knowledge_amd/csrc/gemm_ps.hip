@@ -75,6 +75,9 @@ __global__ __launch_bounds__(256) void presplit_kernel(PsBatch b) {
     const int nb = local % blocks_n, s = local / blocks_n;
     const int t = threadIdx.x;
     const float* src = it.src;
+    // columns that exist (device-side bound; uniform): slices past them are left alone, the last one is zero-padded
+    const int Kr = device_bound(it.K, it.k_bound);
+    if (32 * s >= Kr) return;
     // 32 contiguous source bytes per thread: two 16-byte loads where the view allows (the activation planes of the backward
     // pass -- memory^T, h^T -- are made inside the step: a dword per lane moves a quarter of what a dwordx4 does)
     const bool al16 = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(256) void presplit_kernel(PsBatch b) {
         const int r = t >> 2, kk = (t & 3) * 8;
         const int n = nb * 64 + r;
         const int k0 = 32 * s + kk;
-        if (al16 && (it.src_rs & 3) == 0 && n < it.N && k0 + 7 < it.K) {
+        if (al16 && (it.src_rs & 3) == 0 && n < it.N && k0 + 7 < Kr) {
             const float4* q = reinterpret_cast<const float4*>(src + (int64_t)n * it.src_rs + k0);
             const float4 a = q[0], b = q[1];
             tile[r][kk + 0] = a.x; tile[r][kk + 1] = a.y; tile[r][kk + 2] = a.z; tile[r][kk + 3] = a.w;
@@ -91,15 +94,17 @@ __global__ __launch_bounds__(256) void presplit_kernel(PsBatch b) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int k = k0 + j;
-                tile[r][kk + j] = (n < it.N && k < it.K) ? src[(int64_t)n * it.src_rs + k] : 0.f;
+                tile[r][kk + j] = (n < it.N && k < Kr) ? src[(int64_t)n * it.src_rs + k] : 0.f;
             }
         }
     } else {                              // rows contiguous (a transposed view): 8 consecutive rows at one k per thread
         const int kk = t >> 3, r0 = (t & 7) * 8;
         const int k = 32 * s + kk;
         const int n0 = nb * 64 + r0;
-        if (al16 && it.src_rs == 1 && (it.src_cs & 3) == 0 && n0 + 7 < it.N && k < it.K) {
-            const float4* q = reinterpret_cast<const float4*>(src + n0 + (int64_t)k * it.src_cs);
+        // k_map: column k of the matrix is source column k_map[k] (activation rows gathered through a row list)
+        const int ks = (it.k_map != nullptr && k < Kr) ? it.k_map[k] : k;
+        if (al16 && it.src_rs == 1 && (it.src_cs & 3) == 0 && n0 + 7 < it.N && k < Kr) {
+            const float4* q = reinterpret_cast<const float4*>(src + n0 + (int64_t)ks * it.src_cs);
             const float4 a = q[0], b = q[1];
             tile[r0 + 0][kk] = a.x; tile[r0 + 1][kk] = a.y; tile[r0 + 2][kk] = a.z; tile[r0 + 3][kk] = a.w;
             tile[r0 + 4][kk] = b.x; tile[r0 + 5][kk] = b.y; tile[r0 + 6][kk] = b.z; tile[r0 + 7][kk] = b.w;
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(256) void presplit_kernel(PsBatch b) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int n = n0 + j;
-                tile[n - nb * 64][kk] = (n < it.N && k < it.K) ? src[(int64_t)n * it.src_rs + (int64_t)k * it.src_cs] : 0.f;
+                tile[n - nb * 64][kk] = (n < it.N && k < Kr) ? src[(int64_t)n * it.src_rs + (int64_t)ks * it.src_cs] : 0.f;
             }
         }
     }
@@ -268,8 +273,13 @@ __attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>:
     if (tiles_m <= tiles_n) { tm = bid % tiles_m; tn = bid / tiles_m; }
     else { tn = bid % tiles_n; tm = bid / tiles_n; }
     const int m0 = tm * BM, n0 = tn * BN;
+    // Device-side extents (m_bound / k_bound; uniform), as in csrc/gemm.hip: the K slices partition [0, K'), a tile at or
+    // past a bound exits before any load.  (The pre-split copy of B is zero from K' to the end of its last slice.)
+    const int Mr = device_bound(p.M, p.m_bound), Kr = device_bound(p.K, p.k_bound);
+    if (p.k_bound != nullptr) kchunk = ((Kr + (int)gridDim.z - 1) / (int)gridDim.z + 31) / 32 * 32;
     const int kbeg = zid * kchunk;
-    const int kend = min(p.K, kbeg + kchunk);
+    if (m0 >= Mr || kbeg >= Kr) return;
+    const int kend = min(Kr, kbeg + kchunk);
     const int nk = (kend - kbeg + 31) >> 5;
     const int s0 = kbeg >> 5;
 
@@ -290,20 +300,20 @@ __attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>:
             row = m0 + 4 * c;
             akl[j] = kl;
             extra = 0;
-            const int one[1] = {min(row, p.M - 1)};
+            const int one[1] = {min(row, Mr - 1)};
             int64_t mo[1];
             map_rows<1>(amap, one, mo);
-            avoff[j] = row < p.M ? (uint32_t)(mo[0] * 4) + (uint32_t)((int64_t)kl * p.a_ks * 4) : kOobOffset;
+            avoff[j] = row < Mr ? (uint32_t)(mo[0] * 4) + (uint32_t)((int64_t)kl * p.a_ks * 4) : kOobOffset;
         } else {
             const int rt = g * 8 + (lane >> 3), cpos = lane & 7;
             const int c = cpos ^ ((rt >> 1) & 7);
             row = m0 + rt;
             akl[j] = 4 * c;
             extra = 4 * c;
-            const int one[1] = {min(row, p.M - 1)};
+            const int one[1] = {min(row, Mr - 1)};
             int64_t mo[1];
             map_rows<1>(amap, one, mo);
-            avoff[j] = row < p.M ? (uint32_t)((mo[0] + extra) * 4) : kOobOffset;
+            avoff[j] = row < Mr ? (uint32_t)((mo[0] + extra) * 4) : kOobOffset;
         }
     }
     // ---- B: one per-lane offset; plane / 16-row block / slice are scalar
@@ -444,7 +454,7 @@ __attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>:
     const unsigned long long t_loop_end = t_end;
 #endif
     ICK_WAIT_VMCNT(0);       // the zero fills of the last iterations write LDS too: none may outlive the workgroup
-    gemm_epilogue<TM, TN>(p, acc, m0, n0, wm, wn, fi, fq, zid);
+    gemm_epilogue<TM, TN>(p, Mr, acc, m0, n0, wm, wn, fi, fq, zid);
 #ifdef ICK_PS_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stores of the epilogue have been acknowledged
     ICK_PSTAMP(t_end);
@@ -547,6 +557,7 @@ extern "C" int ick_presplit_weights(const ick_presplit_item* items, int32_t coun
             const ick_presplit_item& it = items[i0 + i];
             ICK_CHECK_ARG(it.src && it.dst && it.N > 0 && it.K > 0);
             ICK_CHECK_ARG(it.src_cs == 1 || it.src_rs == 1);
+            ICK_CHECK_ARG(it.k_map == nullptr || (it.src_rs == 1 && it.src_cs != 1));
             ICK_CHECK_ARG((reinterpret_cast<uintptr_t>(it.dst) & 15) == 0);
             b.it[i] = it;
             b.first[i] = total;

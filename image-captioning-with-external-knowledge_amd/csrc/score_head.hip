@@ -15,16 +15,29 @@ constexpr int kMaxPerLane = 16;
 
 // one workgroup per (b, t) row of h; each wave walks context rows k = wave, wave+4, ... in batches of KB rows
 // whose loads are all issued before the first reduction (one memory round trip per batch, not per row)
+// rowmap / count (ick_pointer_scores_packed): workgroup m of the (T, B) grid takes the logical row rowmap[m] of h / ind and
+// writes PACKED row m of out; workgroups m >= *count exit at once.
 template <int NJ>
 __global__ __launch_bounds__(256) void pointer_scores_kernel(const float* __restrict__ h, const float* __restrict__ ctx,
                                                              const float* __restrict__ w, const float* __restrict__ bias,
                                                              const float* __restrict__ ind, float* __restrict__ out,
                                                              int T, int Kc, int d, int64_t out_ld, int col0,
-                                                             const int32_t* __restrict__ out_gmap) {
+                                                             const int32_t* __restrict__ out_gmap,
+                                                             const int32_t* __restrict__ rowmap,
+                                                             const int32_t* __restrict__ count) {
     chain_priority();
     constexpr int KB = 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.y, t = blockIdx.x;
+    int b = blockIdx.y, t = blockIdx.x;
+    int64_t orow_id = -1;
+    if (rowmap != nullptr) {     // uniform
+        const int m = b * T + t;
+        if (m >= device_bound((int)gridDim.y * T, count)) return;
+        const int lr = rowmap[m];
+        b = lr / T;
+        t = lr - b * T;
+        orow_id = m;
+    }
     const float* hr = h + ((int64_t)b * T + t) * d;
     float hv[NJ], wv[NJ];
 #pragma unroll
@@ -33,8 +46,8 @@ __global__ __launch_bounds__(256) void pointer_scores_kernel(const float* __rest
         hv[j] = c < d ? hr[c] : 0.f;
         wv[j] = c < d ? w[c] : 0.f;
     }
-    const int ob = out_gmap ? out_gmap[b] : b;
-    float* orow = out + ((int64_t)ob * T + t) * out_ld + col0;
+    if (orow_id < 0) orow_id = (int64_t)(out_gmap ? out_gmap[b] : b) * T + t;
+    float* orow = out + orow_id * out_ld + col0;
     const float bs = bias[0];
     for (int k0 = wave; k0 < Kc; k0 += 4 * KB) {
         float cv[KB][NJ];
@@ -193,19 +206,30 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restr
 // Packed cross entropy: one workgroup per (b, t) score row.  kWeighted (ick_packed_ce_weighted): the gradient of row
 // (b, t) is scaled by weight[b]; row_loss keeps the UNWEIGHTED loss (>= 0, so the -1 marker still tells the rows apart)
 // and the reduction applies the weight.  With kWeighted = false the weight is the constant 1 and folds away.
-template <bool kWeighted>
+// kPacked (ick_packed_ce_packed): scores / row_loss / dscores hold the PACKED rows of the valid positions; workgroup m takes
+// packed row m, which belongs to position rowmap[m] = b * L + t (valid by construction: t < min(length - 1, L - 1)); dl is
+// the device row count, and workgroups at or past it exit without writing anything.
+template <bool kWeighted, bool kPacked = false>
 __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __restrict__ scores, int64_t ld,
                                                              const int64_t* __restrict__ caps,
                                                              const int32_t* __restrict__ dl, int L, int Vx, int pad,
                                                              float* __restrict__ row_loss, float* __restrict__ dscores,
-                                                             const float* __restrict__ weight) {
+                                                             const float* __restrict__ weight,
+                                                             const int32_t* __restrict__ rowmap) {
     __shared__ float red[4];
-    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    int t = blockIdx.x, b = blockIdx.y;
+    const int tid = threadIdx.x;
     const int64_t row = (int64_t)b * L + t;
+    if constexpr (kPacked) {
+        if (row >= device_bound((int)gridDim.y * L, dl)) return;      // uniform
+        const int lr = rowmap[row];
+        b = lr / L;
+        t = lr - b * L;
+    }
     const float* r = scores + row * ld;
     float* dr = dscores ? dscores + row * ld : nullptr;
     int64_t target = -1;
-    bool use = t < L - 1 && t < dl[b];
+    bool use = t < L - 1 && (kPacked || t < dl[b]);
     if (use) {
         target = caps[(int64_t)b * L + t + 1];
         use = target != pad && target >= 0 && target < Vx;
@@ -361,21 +385,91 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
 
 // Fixed-order reduction of the per-row losses (deterministic, unlike float atomics); kWeighted: row i belongs to caption
 // i / L and its loss enters the sum times that caption's weight (the count stays the number of rows).
+// rowmap / nrows (the packed form): the first *nrows of the n rows exist, row i belongs to caption rowmap[i] / L.
 template <bool kWeighted>
 __global__ __launch_bounds__(256) void packed_ce_reduce_kernel(const float* __restrict__ row_loss, int n, int L,
                                                                const float* __restrict__ weight,
-                                                               float* __restrict__ loss_sum, float* __restrict__ count) {
+                                                               float* __restrict__ loss_sum, float* __restrict__ count,
+                                                               const int32_t* __restrict__ rowmap,
+                                                               const int32_t* __restrict__ nrows) {
     __shared__ float red[4];
     float s = 0.f, c = 0.f;
+    n = device_bound(n, nrows);
     for (int i = threadIdx.x; i < n; i += 256) {
         const float v = row_loss[i];
-        if (v > -0.5f) { s += kWeighted ? weight[i / L] * v : v; c += 1.f; }
+        if (v > -0.5f) { s += kWeighted ? weight[(rowmap ? rowmap[i] : i) / L] * v : v; c += 1.f; }
     }
     s = block_sum<4>(s, red);
     c = block_sum<4>(c, red);
     if (threadIdx.x == 0) { loss_sum[0] = s; count[0] = c; }
 }
 
+// The packed row list of the training step's score head (ick_head_rowmap): one workgroup scans the B lengths.
+__global__ __launch_bounds__(256) void head_rowmap_kernel(const int64_t* __restrict__ lengths, int B, int L,
+                                                          int32_t* __restrict__ decode_len, int32_t* __restrict__ rowstart,
+                                                          int32_t* __restrict__ rowmap) {
+    __shared__ int part[256];
+    __shared__ int total;
+    const int tid = threadIdx.x;
+    const int per = (B + 255) / 256;             // consecutive samples per thread
+    const int b0 = min(B, tid * per), b1 = min(B, b0 + per);
+    auto valid = [&](int64_t len) { return (int)min((int64_t)(L - 1), max((int64_t)0, len - 1)); };
+    int sum = 0;
+    for (int b = b0; b < b1; ++b) {
+        const int64_t len = lengths[b];
+        decode_len[b] = (int32_t)(len - 1);
+        sum += valid(len);
+    }
+    part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {                              // exclusive scan of the 256 partial sums
+        int run = 0;
+        for (int i = 0; i < 256; ++i) { const int v = part[i]; part[i] = run; run += v; }
+        total = run;
+        rowstart[B] = run;
+    }
+    __syncthreads();
+    int run = part[tid];
+    for (int b = b0; b < b1; ++b) {
+        const int n = valid(lengths[b]);
+        rowstart[b] = run;
+        for (int t = 0; t < n; ++t) rowmap[run + t] = b * L + t;
+        run += n;
+    }
+    for (int m = total + tid; m < B * L; m += 256) rowmap[m] = 0;      // never used: a defined value all the same
+}
+
+// dst[m, :] = src[rowmap[m], :], one wave per packed row m < *count
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ src, int64_t src_rs,
+                                                          const int32_t* __restrict__ rowmap,
+                                                          const int32_t* __restrict__ count, float* __restrict__ dst,
+                                                          int64_t dst_rs, int max_rows, int d) {
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (m >= device_bound(max_rows, count)) return;
+    const float* s = src + (int64_t)rowmap[m] * src_rs;
+    float* o = dst + (int64_t)m * dst_rs;
+    for (int c = lane; c < d; c += 64) o[c] = s[c];
+}
+
+}  // namespace
+}  // namespace ick
+
+namespace ick {
+namespace {
+int launch_pointer_scores(const float* h, const float* ctx, const float* w, const float* bias, const float* ind, float* out,
+                          int B, int T, int Kc, int d, int64_t out_ld, int col0, const int32_t* out_gmap,
+                          const int32_t* rowmap, const int32_t* count, hipStream_t s) {
+    if (d <= 320)
+        hipLaunchKernelGGL(pointer_scores_kernel<5>, dim3(T, B), dim3(256), 0, s, h, ctx, w, bias, ind, out, T, Kc, d,
+                           out_ld, col0, out_gmap, rowmap, count);
+    else if (d <= 512)
+        hipLaunchKernelGGL(pointer_scores_kernel<8>, dim3(T, B), dim3(256), 0, s, h, ctx, w, bias, ind, out, T, Kc, d,
+                           out_ld, col0, out_gmap, rowmap, count);
+    else
+        hipLaunchKernelGGL(pointer_scores_kernel<kMaxPerLane>, dim3(T, B), dim3(256), 0, s, h, ctx, w, bias, ind, out, T,
+                           Kc, d, out_ld, col0, out_gmap, rowmap, count);
+    ICK_LAUNCH_RET();
+}
 }  // namespace
 }  // namespace ick
 
@@ -385,16 +479,36 @@ extern "C" int ick_pointer_scores(const float* h, const float* ctx, const float*
     using namespace ick;
     ICK_CHECK_ARG(h && ctx && w && bias && out && B > 0 && T > 0 && Kc > 0 && d > 0 && d <= 64 * kMaxPerLane);
     ICK_CHECK_ARG(B <= 65535 && col0 >= 0 && out_ld >= col0 + Kc);
-    hipStream_t s = (hipStream_t)stream;
-    if (d <= 320)
-        hipLaunchKernelGGL(pointer_scores_kernel<5>, dim3(T, B), dim3(256), 0, s, h, ctx, w, bias, ind, out, T, Kc, d,
-                           out_ld, col0, out_gmap);
-    else if (d <= 512)
-        hipLaunchKernelGGL(pointer_scores_kernel<8>, dim3(T, B), dim3(256), 0, s, h, ctx, w, bias, ind, out, T, Kc, d,
-                           out_ld, col0, out_gmap);
-    else
-        hipLaunchKernelGGL(pointer_scores_kernel<kMaxPerLane>, dim3(T, B), dim3(256), 0, s, h, ctx, w, bias, ind, out, T,
-                           Kc, d, out_ld, col0, out_gmap);
+    return ick::launch_pointer_scores(h, ctx, w, bias, ind, out, B, T, Kc, d, out_ld, col0, out_gmap, nullptr, nullptr,
+                                      (hipStream_t)stream);
+}
+
+extern "C" int ick_pointer_scores_packed(const float* h, const float* ctx, const float* w, const float* bias,
+                                         const float* ind, float* out, int32_t B, int32_t T, int32_t Kc, int32_t d,
+                                         int64_t out_ld, int32_t col0, const int32_t* rowmap, const int32_t* count,
+                                         void* stream) {
+    using namespace ick;
+    ICK_CHECK_ARG(h && ctx && w && bias && out && B > 0 && T > 0 && Kc > 0 && d > 0 && d <= 64 * kMaxPerLane);
+    ICK_CHECK_ARG(B <= 65535 && col0 >= 0 && out_ld >= col0 + Kc && rowmap && count && (int64_t)B * T <= INT32_MAX);
+    return launch_pointer_scores(h, ctx, w, bias, ind, out, B, T, Kc, d, out_ld, col0, nullptr, rowmap, count,
+                                 (hipStream_t)stream);
+}
+
+extern "C" int ick_head_rowmap(const int64_t* lengths, int32_t B, int32_t L, int32_t* decode_len, int32_t* rowstart,
+                               int32_t* rowmap, void* stream) {
+    using namespace ick;
+    ICK_CHECK_ARG(lengths && decode_len && rowstart && rowmap && B > 0 && L > 0 && (int64_t)B * L <= INT32_MAX);
+    hipLaunchKernelGGL(head_rowmap_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, lengths, B, L, decode_len, rowstart,
+                       rowmap);
+    ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_gather_rows(const float* src, int64_t src_rs, const int32_t* rowmap, const int32_t* count, float* dst,
+                               int64_t dst_rs, int32_t max_rows, int32_t d, void* stream) {
+    using namespace ick;
+    ICK_CHECK_ARG(src && rowmap && count && dst && max_rows > 0 && d > 0 && src_rs >= d && dst_rs >= d);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div(max_rows, 4)), dim3(256), 0, (hipStream_t)stream, src, src_rs,
+                       rowmap, count, dst, dst_rs, max_rows, d);
     ICK_LAUNCH_RET();
 }
 
@@ -439,9 +553,31 @@ extern "C" int ick_packed_ce(const float* scores, int64_t ld, const int64_t* cap
     ICK_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Vx > 0 && ld >= Vx);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(packed_ce_rows_kernel<false>, dim3(L, B), dim3(256), 0, s, scores, ld, captions_sorted, decode_len,
-                       L, Vx, pad_token, row_loss, dscores, nullptr);
+                       L, Vx, pad_token, row_loss, dscores, nullptr, nullptr);
     hipLaunchKernelGGL(packed_ce_reduce_kernel<false>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, nullptr, loss_sum,
-                       count);
+                       count, nullptr, nullptr);
+    ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_packed_ce_packed(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                                    const int32_t* count, const float* weights, int32_t B, int32_t L, int32_t Vx,
+                                    int32_t pad_token, float* row_loss, float* loss_sum, float* count_out, float* dscores,
+                                    void* stream) {
+    using namespace ick;
+    ICK_CHECK_ARG(scores && captions && rowmap && count && row_loss && loss_sum && count_out);
+    ICK_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Vx > 0 && ld >= Vx && (int64_t)B * L <= INT32_MAX);
+    hipStream_t s = (hipStream_t)stream;
+    if (weights != nullptr) {
+        hipLaunchKernelGGL((packed_ce_rows_kernel<true, true>), dim3(L, B), dim3(256), 0, s, scores, ld, captions, count, L,
+                           Vx, pad_token, row_loss, dscores, weights, rowmap);
+        hipLaunchKernelGGL(packed_ce_reduce_kernel<true>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, weights, loss_sum,
+                           count_out, rowmap, count);
+    } else {
+        hipLaunchKernelGGL((packed_ce_rows_kernel<false, true>), dim3(L, B), dim3(256), 0, s, scores, ld, captions, count, L,
+                           Vx, pad_token, row_loss, dscores, nullptr, rowmap);
+        hipLaunchKernelGGL(packed_ce_reduce_kernel<false>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, nullptr, loss_sum,
+                           count_out, rowmap, count);
+    }
     ICK_LAUNCH_RET();
 }
 
@@ -454,8 +590,8 @@ extern "C" int ick_packed_ce_weighted(const float* scores, int64_t ld, const int
     ICK_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Vx > 0 && ld >= Vx && (int64_t)B * L <= INT32_MAX);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(packed_ce_rows_kernel<true>, dim3(L, B), dim3(256), 0, s, scores, ld, captions_sorted, decode_len,
-                       L, Vx, pad_token, row_loss, dscores, weights);
+                       L, Vx, pad_token, row_loss, dscores, weights, nullptr);
     hipLaunchKernelGGL(packed_ce_reduce_kernel<true>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, weights, loss_sum,
-                       count);
+                       count, nullptr, nullptr);
     ICK_LAUNCH_RET();
 }

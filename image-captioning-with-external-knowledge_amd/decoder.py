@@ -893,17 +893,19 @@ class DecoderTransformer(nn.Module):
             heads=None if nxt is None else (3, H, T, 0, T))
         return x3, qkv_n
 
-    def _score_head(self, h, ee, fe, eib, hv, out, vocab_ps=None):
+    def _score_head(self, h, ee, fe, eib, hv, out, vocab_ps=None, pack=None):
         """get_scores into `out`, a (B, T, V+K[+F]) view with any row stride: the vocabulary logits of hv (facts
         variants: h times the predicate gate; None: h) through fc_vocab (vocab_ps: its pre-split copy) and the pointer
-        scores of h."""
+        scores of h.  pack (ops.HeadRows; the fused training step): only the valid rows are computed -- gathered through
+        pack.rowmap, written to the first pack.count rows of `out` (row m of the B * T, not position (b, t))."""
         B, T, d = h.shape
         V, K = self.vocab_size, ee.shape[1]
+        gather = {} if pack is None else dict(a_grp=1, a_gs=d, a_gmap=pack.rowmap, m_bound=pack.count)
         ops.gemm_raw(h if hv is None else hv, self.fc_vocab.weight.detach(), out, B * T, V, d, d, 1, d, 1, out.stride(1),
-                     bias=self.fc_vocab.bias.detach(), b_ps=vocab_ps)
-        ops.pointer_scores(h, ee, *_wb(self.fc_entity), out, V)
+                     bias=self.fc_vocab.bias.detach(), b_ps=vocab_ps, **gather)
+        ops.pointer_scores(h, ee, *_wb(self.fc_entity), out, V, pack=pack)
         if self.has_facts:
-            ops.pointer_scores(h, fe, *_wb(self.fc_fact), out, V + K, ind=eib)
+            ops.pointer_scores(h, fe, *_wb(self.fc_fact), out, V + K, ind=eib, pack=pack)
 
     # ------------------------------------------------------------------ public score-head methods
     @torch.no_grad()

@@ -35,6 +35,7 @@ class GemmArgs(C.Structure):
         ("a_extent", i64), ("b_extent", i64), ("colsum_a", vp),
         ("gate", vp), ("gate_rs", i64), ("gate_scale", f32),
         ("b_ps", vp),
+        ("m_bound", vp), ("k_bound", vp),
     ]
 
 
@@ -82,7 +83,8 @@ class GemmPlanInfo(C.Structure):
 
 
 class PresplitItem(C.Structure):
-    _fields_ = [("src", vp), ("dst", vp), ("N", i32), ("K", i32), ("src_rs", i64), ("src_cs", i64)]
+    _fields_ = [("src", vp), ("dst", vp), ("N", i32), ("K", i32), ("src_rs", i64), ("src_cs", i64),
+                ("k_map", vp), ("k_bound", vp)]
 
 
 class AdamItem(C.Structure):      # ick_adam_item: a 2-D block of the bucket + the images of it the optimizer keeps current
@@ -230,6 +232,11 @@ SIGNATURES = {
     "ick_timestamp": [vp, vp],
     "ick_copy_batch": [vp, vp, vp, i32, vp],
     "ick_scale_by_ratio": [vp, i64, vp, vp, vp],
+    "ick_head_rowmap": [vp, i32, i32, vp, vp, vp, vp],
+    "ick_pointer_scores_packed": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i32, vp, vp, vp],
+    "ick_packed_ce_packed": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+    "ick_pointer_scores_bwd_packed": [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],
+    "ick_gather_rows": [vp, i64, vp, vp, vp, i64, i32, i32, vp],
 }
 
 _lib = None

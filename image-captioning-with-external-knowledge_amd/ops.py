@@ -51,11 +51,13 @@ def _dargs(drop):
 
 def gemm_args(A, B, Cout, M, N, K, a_rs, a_ks, b_rs, b_ks, c_rs, bias=None, a_grp=0, a_gs=0, a_gmap=None,
               c_grp=0, c_gs=0, c_gmap=None, relu=False, accumulate=False, atomic=False, split_k=1, alpha=1.0,
-              drop=None, colsum_a=None, gate=None, gate_scale=1.0, b_ps=None):
+              drop=None, colsum_a=None, gate=None, gate_scale=1.0, b_ps=None, m_bound=None, k_bound=None):
     """ick_gemm_args for C[m,n] = act(alpha * sum_k A(m,k) B(n,k) + bias[n]) with explicit element strides; A/B/Cout
     are tensors (only their data pointers are used -- the caller guarantees the strides stay in bounds).
     colsum_a (k-major A only): colsum_a[m] += sum_k A(m,k).  b_ps: the pre-split copy of the (N, K) matrix B
-    (presplit_weights): large problems then run on the LDS-DMA kernel of csrc/gemm_ps.hip."""
+    (presplit_weights): large problems then run on the LDS-DMA kernel of csrc/gemm_ps.hip.
+    m_bound / k_bound: one-element int32 device tensors that bound the rows / the reduction length below M / K (the
+    packed score head's row count; include/ick_amd.h)."""
     for t in (A, B, Cout):
         if t.dtype != torch.float32:
             raise L.IckError("ick_gemm operands must be float32, got %s" % t.dtype)
@@ -75,6 +77,10 @@ def gemm_args(A, B, Cout, M, N, K, a_rs, a_ks, b_rs, b_ks, c_rs, bias=None, a_gr
     if b_ps is not None:
         assert b_ps.numel() * b_ps.element_size() == presplit_bytes(N, K), "b_ps is not the pre-split copy of an (N, K) matrix"
         a.b_ps = _p(b_ps)
+    for name, t in (("m_bound", m_bound), ("k_bound", k_bound)):
+        if t is not None:
+            assert t.dtype == torch.int32 and t.numel() == 1 and t.is_cuda, "%s is a one-element int32 device tensor" % name
+            setattr(a, name, _p(t))
     _drop(a, drop)
     return a
 
@@ -88,16 +94,21 @@ def presplit_bytes(N, K):
     return int(n.value)
 
 
-def presplit_weights(pairs):
+def presplit_weights(pairs, k_map=None, k_bound=None):
     """[(w (N, K) 2-D view with one unit stride -- a weight or its transposed view, dst uint8 buffer of
     presplit_bytes(N, K))]: the exact three-way bf16 split of every matrix in the image ick_gemm's b_ps wants
-    (include/ick_amd.h, ick_presplit_weights); up to 16 matrices per launch."""
+    (include/ick_amd.h, ick_presplit_weights); up to 16 matrices per launch.
+    k_map / k_bound (int32 device tensors, transposed views only): column k of every matrix is read from source column
+    k_map[k], and only the columns below k_bound[0] exist (the activation rows of the packed score head)."""
     items = (L.PresplitItem * len(pairs))()
     for it, (src, dst) in zip(items, pairs):
         assert src.dim() == 2 and src.dtype == torch.float32 and (src.stride(1) == 1 or src.stride(0) == 1)
         assert dst.numel() * dst.element_size() == presplit_bytes(src.shape[0], src.shape[1])
         it.src, it.dst, it.N, it.K = _p(src), _p(dst), src.shape[0], src.shape[1]
         it.src_rs, it.src_cs = src.stride(0), src.stride(1)
+        if k_map is not None:
+            assert k_map.dtype == torch.int32 and k_map.numel() >= src.shape[1] and src.stride(0) == 1
+        it.k_map, it.k_bound = _p(k_map), _p(k_bound)
     L.check(L.load().ick_presplit_weights(items, len(pairs), _stream()), "ick_presplit_weights")
 
 
@@ -122,9 +133,10 @@ def presplit_cached(holder, name, w2d, key):
     return ent[1]
 
 
-def colsum_problem(a2d, out, split_k=1):
+def colsum_problem(a2d, out, split_k=1, k_bound=None):
     """ick_gemm_args of a pure column sum out[n] += sum_m a2d[m, n] (ICK_GEMM_COLSUM_ONLY): no kernel of its own,
-    it rides in a grouped launch (gemm_grouped) with the weight-gradient GEMMs.  split_k: row slices (float atomics)."""
+    it rides in a grouped launch (gemm_grouped) with the weight-gradient GEMMs.  split_k: row slices (float atomics).
+    k_bound: one-element int32 device tensor, only the rows below it are summed."""
     rows, cols = a2d.shape
     a = L.GemmArgs()
     a.A, a.colsum_a = _p(a2d), _p(out)
@@ -132,6 +144,7 @@ def colsum_problem(a2d, out, split_k=1):
     a.a_rs, a.a_ks = 1, a2d.stride(0)
     a.flags, a.split_k, a.alpha = L.GEMM_COLSUM_ONLY | (L.GEMM_ATOMIC if split_k > 1 else 0), split_k, 1.0
     a.a_extent = _extent(a2d)
+    a.k_bound = _p(k_bound)
     return a
 
 
@@ -555,9 +568,16 @@ def context_indicators(captions, facts, K, V, fc_pred_wt=None, fc_pred_b=None, m
     return eib, gate
 
 
-def pointer_scores(h, ctx, w, bias, out, col0, ind=None, out_gmap=None):
+def pointer_scores(h, ctx, w, bias, out, col0, ind=None, out_gmap=None, pack=None):
+    """pack (HeadRows): the scores of the valid rows only, into the packed rows of `out` (ick_pointer_scores_packed)."""
     B, T, d = h.shape
     Kc = ctx.shape[1]
+    if pack is not None:
+        assert out_gmap is None
+        L.check(L.load().ick_pointer_scores_packed(_p(h), _p(ctx), _p(w), _p(bias), _p(ind), _p(out), B, T, Kc, d,
+                                                   out.stride(-2), col0, _p(pack.rowmap), _p(pack.count), _stream()),
+                "ick_pointer_scores_packed")
+        return out
     L.check(L.load().ick_pointer_scores(_p(h), _p(ctx), _p(w), _p(bias), _p(ind), _p(out), B, T, Kc, d,
                                         out.stride(-2), col0, _p(out_gmap), _stream()), "ick_pointer_scores")
     return out
@@ -684,6 +704,57 @@ def decode_select_sample(ctx, sample_state, pos):
     """Sampled token of step `pos` for every live row (ick_decode_select_sample); sample_state: lib.SampleState."""
     L.check(L.load().ick_decode_select_sample(C.byref(ctx), C.byref(sample_state), pos, _stream()),
             "ick_decode_select_sample")
+
+
+class HeadRows:
+    """The packed row list of a training step's score head (ick_head_rowmap), all int32 on the device:
+    decode_len (B,), rowstart (B + 1,) with count = rowstart[B:] the number of valid rows M', rowmap (B * L,): packed row
+    -> logical row b * L + t."""
+
+    def __init__(self, lengths, B, Lc):
+        dev = lengths.device
+        lengths = lengths.reshape(-1)
+        if lengths.dtype != torch.int64 or not lengths.is_contiguous():
+            lengths = lengths.to(torch.int64).contiguous()
+        assert lengths.numel() == B
+        self.B, self.L = B, Lc
+        self.decode_len = torch.empty(B, device=dev, dtype=torch.int32)
+        self.rowstart = torch.empty(B + 1, device=dev, dtype=torch.int32)
+        self.rowmap = torch.empty(B * Lc, device=dev, dtype=torch.int32)
+        self.count = self.rowstart[B:]
+        L.check(L.load().ick_head_rowmap(_p(lengths), B, Lc, _p(self.decode_len), _p(self.rowstart), _p(self.rowmap),
+                                         _stream()), "ick_head_rowmap")
+
+
+def gather_rows(x2, pack):
+    """Packed copy of the valid rows of x2 (B * L, d): out[m] = x2[rowmap[m]] for m < M' (the rest is not written)."""
+    rows, d = x2.shape
+    assert x2.stride(1) == 1 and rows == pack.rowmap.numel()
+    out = torch.empty(rows, d, device=x2.device, dtype=torch.float32)
+    L.check(L.load().ick_gather_rows(_p(x2), x2.stride(0), _p(pack.rowmap), _p(pack.count), _p(out), d, rows, d,
+                                     _stream()), "ick_gather_rows")
+    return out
+
+
+def packed_ce_rows(scores, captions, pack, pad_token, weights=None, want_grad=False, out_sum=None, out_count=None):
+    """packed_ce / packed_ce_weighted over PACKED score rows (scores (B, L, Vx): the first M' rows of its B * L hold the
+    valid positions in pack.rowmap's order): -> (loss_sum, count, dscores packed alike; rows from M' on are not written)."""
+    B, Lc, Vx = scores.shape
+    dev = scores.device
+    if weights is not None and (weights.shape != (B,) or weights.dtype != torch.float32 or not weights.is_cuda or
+                                not weights.is_contiguous()):
+        raise L.IckError("packed_ce_rows needs contiguous (B,) float32 weights on the device")
+    row_loss = torch.empty(B * Lc, device=dev, dtype=torch.float32)
+    loss_sum = out_sum if out_sum is not None else torch.empty(1, device=dev, dtype=torch.float32)
+    count = out_count if out_count is not None else torch.empty(1, device=dev, dtype=torch.float32)
+    dscores = None
+    assert scores.stride(0) == Lc * scores.stride(1) and scores.stride(2) == 1
+    if want_grad:
+        dscores = torch.empty(B, Lc, scores.stride(1), device=dev, dtype=torch.float32)[:, :, :Vx]
+    L.check(L.load().ick_packed_ce_packed(_p(scores), scores.stride(1), _p(captions), _p(pack.rowmap), _p(pack.count),
+                                          _p(weights), B, Lc, Vx, pad_token, _p(row_loss), _p(loss_sum), _p(count),
+                                          _p(dscores), _stream()), "ick_packed_ce_packed")
+    return loss_sum, count, dscores
 
 
 def packed_ce(scores, captions_sorted, decode_len, pad_token, want_grad=False, out_sum=None, out_count=None):
@@ -1065,15 +1136,22 @@ SIDE = None   # set by training.TrainStep / backward_from_tape for the duration 
 
 
 def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, group_now=False, gate=None,
-               gate_scale=1.0, wt_ps=None, xt_ps=None):
+               gate_scale=1.0, wt_ps=None, xt_ps=None, pack=None):
     """Backward of y = x @ w.T + b for row-major 2-D views dy (M,N), x (M,K), w (N,K):
     dw += dy.T @ x (split-K over M, float atomics), db += colsum(dy), dx = dy @ w.
     With a SideStream installed the two parameter gradients run beside the data gradient.
     wt_ps: the pre-split copy of w.t() (presplit_weights) -- the data gradient's B operand.
     xt_ps: the pre-split copy of x.t() -- the weight gradient's B operand: dw then runs on csrc/gemm_ps.hip's kernel (the
-    vocabulary: 10 000 x 300 outputs over 1 280 rows) and db becomes a column-sum problem of the same group."""
+    vocabulary: 10 000 x 300 outputs over 1 280 rows) and db becomes a column-sum problem of the same group.
+    pack (HeadRows; the packed score head): dy holds the M' = pack.count valid rows packed at its top, x and dx keep their
+    logical rows.  The reductions of dw / db run over M' rows (xt_ps must have been gathered through pack.rowmap; without
+    it a packed copy of x is made here), dx is computed for M' rows and scattered through pack.rowmap into a dx that the
+    caller zeroed (accumulate_dx): the rows of padded positions stay exactly zero."""
     M, N = dy.shape
     K = x.shape[1]
+    kb = pack.count if pack is not None else None
+    xk = x
+    assert pack is None or (need_dx and dx is not None and accumulate_dx and gate is None)
 
     # dw += dy.T @ x with db += colsum(dy) riding on the first tile column of the same kernel
     wg = None
@@ -1083,12 +1161,14 @@ def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, gro
         tiles = ((N + 127) // 128) * ((K + 127) // 128)
         split = max(1, min(8, 480 // tiles, M // 512))
         wg = gemm_args(dy, x, dw, N, K, M, 1, dy.stride(0), 1, x.stride(0), dw.stride(0), atomic=True,
-                       split_k=split, b_ps=xt_ps)
+                       split_k=split, b_ps=xt_ps, k_bound=kb)
         if db is not None:
-            extra.append(colsum_problem(dy, db, split_k=max(1, min(16, M // 256))))
+            extra.append(colsum_problem(dy, db, split_k=max(1, min(16, M // 256)), k_bound=kb))
     elif dw is not None:
-        wg = gemm_args(dy, x, dw, N, K, M, 1, dy.stride(0), 1, x.stride(0), dw.stride(0), atomic=True,
-                       split_k=wgrad_split(M, N, K, grouped=SIDE is not None), colsum_a=db)
+        # (the kernels of csrc/gemm.hip cannot gather their k-major B operand: they read a packed copy of x)
+        xk = gather_rows(x, pack) if pack is not None else x
+        wg = gemm_args(dy, xk, dw, N, K, M, 1, dy.stride(0), 1, xk.stride(0), dw.stride(0), atomic=True,
+                       split_k=wgrad_split(M, N, K, grouped=SIDE is not None), colsum_a=db, k_bound=kb)
 
     def param_grads():
         if wg is not None and extra:
@@ -1097,7 +1177,10 @@ def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, gro
             _log_plan(wg)
             L.check(L.load().ick_gemm(C.byref(wg), _stream()), "ick_gemm(wgrad)")
         elif db is not None:
-            colsum(dy, db)
+            if pack is not None:
+                gemm_grouped([colsum_problem(dy, db, k_bound=kb)])
+            else:
+                colsum(dy, db)
 
     # With a SideStream the weight gradients of a whole layer are queued and go out as one grouped launch at the
     # layer's end (SideStream.flush_group): each alone is a ~15 us latency-bound kernel, and every fork point of
@@ -1106,7 +1189,7 @@ def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, gro
     overlap = SIDE is not None and (dw is not None or db is not None)
     if overlap:
         if wg is not None:
-            SIDE.add_problem(wg, dy, x, xt_ps)
+            SIDE.add_problem(wg, dy, x, xk, xt_ps)
             for e in extra:
                 SIDE.add_problem(e, dy)
             if group_now:      # a large problem of its own (the vocabulary): runs beside its data gradient
@@ -1114,6 +1197,8 @@ def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, gro
         else:
             SIDE.submit(param_grads, dy, x)
     if need_dx:
+        # packed rows: M' of them, row m lands in row pack.rowmap[m] of dx
+        scatter = {} if pack is None else dict(m_bound=kb, c_grp=1, c_gs=dx.stride(0), c_gmap=pack.rowmap)
         # a long reduction (the vocabulary: N = 10k..50k) over few output tiles is split over workgroups
         split = max(1, min(16, N // 1024)) if (M * K) <= 1280 * 512 else 1
         if is_deterministic():
@@ -1132,13 +1217,13 @@ def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, gro
             elif not accumulate_dx:
                 dx.zero_()
             gemm_raw(dy, w, dx, M, K, N, dy.stride(0), 1, 1, w.stride(0), dx.stride(0), atomic=True, split_k=split,
-                     b_ps=wt_ps)
+                     b_ps=wt_ps, **scatter)
         else:
             if dx is None:
                 dx = torch.empty(M, K, device=dy.device, dtype=torch.float32)
             # gate: the consumer wants ReLU'(act) * dx (FFN inner activation): applied in the epilogue
             gemm_raw(dy, w, dx, M, K, N, dy.stride(0), 1, 1, w.stride(0), dx.stride(0), accumulate=accumulate_dx,
-                     gate=gate, gate_scale=gate_scale)
+                     gate=gate, gate_scale=gate_scale, **scatter)
             gate = None
     if not overlap:
         param_grads()
@@ -1155,9 +1240,15 @@ def caption_embed_bwd(dx, captions, masks, dword, dee, dfe, V, pad_token, scale,
                                            V, d, pad_token, scale, *_dargs(drop), _stream()), "ick_caption_embed_bwd")
 
 
-def pointer_scores_bwd(dscores, col0, h, ctx, w, ind, dh, dctx, dw, dbias):
+def pointer_scores_bwd(dscores, col0, h, ctx, w, ind, dh, dctx, dw, dbias, pack=None):
+    """pack (HeadRows): dscores holds the packed rows of the valid positions (ick_pointer_scores_bwd_packed)."""
     B, T, d = h.shape
     Kc = ctx.shape[1]
+    if pack is not None:
+        L.check(L.load().ick_pointer_scores_bwd_packed(_p(dscores), dscores.stride(-2), col0, _p(h), _p(ctx), _p(w), _p(ind),
+                                                       _p(dh), _p(dctx), _p(dw), _p(dbias), B, T, Kc, d, _p(pack.rowmap),
+                                                       _p(pack.rowstart), _stream()), "ick_pointer_scores_bwd_packed")
+        return
     L.check(L.load().ick_pointer_scores_bwd(_p(dscores), dscores.stride(-2), col0, _p(h), _p(ctx), _p(w), _p(ind),
                                             _p(dh), _p(dctx), _p(dw), _p(dbias), B, T, Kc, d, _stream()),
             "ick_pointer_scores_bwd")

@@ -117,6 +117,12 @@ def classify(name, args):
     if name == "ick_packed_ce_weighted":
         B, Lc, Vx = args[5], args[6], args[7]
         return "weighted packed cross entropy (+ gradient)", 4.0 * B * Lc * Vx * (2 if args[12] else 1), "byte"
+    if name == "ick_packed_ce_packed":
+        # the packed score head: the row count lives on the device, so the launch is priced at all B * L rows -- the achieved
+        # rate of this class then overstates what the kernel moves
+        B, Lc, Vx = args[6], args[7], args[8]
+        return (("weighted " if args[5] else "") + "packed cross entropy (+ gradient)",
+                4.0 * B * Lc * Vx * (2 if args[13] else 1), "byte")
     if name == "ick_adam_clamp":
         return "clamp + Adam", 4.0 * args[4] * 7, "byte"
     if name == "ick_adam_clamp_derive":

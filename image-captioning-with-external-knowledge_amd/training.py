@@ -46,7 +46,8 @@ def _p(x):
 # forward with saved activations
 # ----------------------------------------------------------------------------------------------
 def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gmap, seed=0, epoch=None,
-                      fresh_pack=False, overlap=False, feats=None, conv1=None, side_tail=None, derived=None, pre_side=None):
+                      fresh_pack=False, overlap=False, feats=None, conv1=None, side_tail=None, derived=None, pre_side=None,
+                      head_rows=None):
     """Teacher-forced forward on already length-sorted inputs; returns (scores, tape).  Dropout is
     active iff the module is in train() mode (masks derive from `seed` + the device counter `epoch`).
     fresh_pack: rebuild the packed cross-K/V / transposed predicate weights from the live parameters
@@ -64,7 +65,9 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
     pre_side (needs overlap, feats and derived): work of the caller that must run BEFORE anything here reads a parameter
     -- TrainStep's deferred optimizer update of the previous step.  It opens the side stream, beside Encoder.conv1 on the
     main stream (frozen weights, input features: the one large kernel of the step that reads no trainable parameter);
-    the entity / fact encoders follow it there and the main stream waits for that point behind conv1."""
+    the entity / fact encoders follow it there and the main stream waits for that point behind conv1.
+    head_rows: callable -> ops.HeadRows or None, asked when the score head is reached (TrainStep makes the row list in its
+    side tail): the head then runs over the packed list of valid rows only and `scores` holds packed rows."""
     tape = Tape()
     m = tape.misc
     ds = DropSites(seed, dec.training, epoch)
@@ -245,7 +248,8 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
     # weight-gradient GEMMs read the score gradients with 16-byte loads only from aligned rows (645 -> ~470 us)
     ld = (Vx + 3) // 4 * 4
     scores = torch.empty(B, L, ld, device=x.device, dtype=torch.float32)[:, :, :Vx]
-    dec._score_head(x, ee, fe, eib, hv, scores, m.get("vocab_ps"))
+    m["pack"] = head_rows() if head_rows is not None else None
+    dec._score_head(x, ee, fe, eib, hv, scores, m.get("vocab_ps"), pack=m["pack"])
     m.update(ee=ee, fe=fe, mem=mem, kv=kv, h=x, hv=hv, eib=eib, gate=gate, captions=captions, masks=caption_masks,
              entities=entities, facts=facts, P=P, K=K, Fn=Fn, S=S, wkv=wkv)
     return scores, tape
@@ -264,7 +268,7 @@ def _g(grads, param):
 
 
 def _lin_bwd(grads, dy2, x2, lin_w, lin_b, w_rows=None, need_dx=True, dx=None, acc=False, group_now=False,
-             gate=None, gate_scale=1.0, wt_ps=None, xt_ps=None):
+             gate=None, gate_scale=1.0, wt_ps=None, xt_ps=None, pack=None):
     """Backward of a Linear whose weight is `lin_w` (optionally the row slice w_rows of it)."""
     gw, gb = _g(grads, lin_w), _g(grads, lin_b)
     w = _p(lin_w)
@@ -273,7 +277,7 @@ def _lin_bwd(grads, dy2, x2, lin_w, lin_b, w_rows=None, need_dx=True, dx=None, a
         gw = gw[w_rows] if gw is not None else None
         gb = gb[w_rows] if gb is not None else None
     return ops.linear_bwd(dy2, x2, w, gw, gb, need_dx=need_dx, dx=dx, accumulate_dx=acc, group_now=group_now,
-                          gate=gate, gate_scale=gate_scale, wt_ps=wt_ps, xt_ps=xt_ps)
+                          gate=gate, gate_scale=gate_scale, wt_ps=wt_ps, xt_ps=xt_ps, pack=pack)
 
 
 def _prezeroed(dec, captions, entities, facts):
@@ -537,17 +541,22 @@ def _memory_t_presplit(m, B, S, d):
     return buf
 
 
-def _rows_t_presplit(x2):
+def _rows_t_presplit(x2, pack=None):
     """Pre-split copy of x2^T (x2: (rows, d) activations): the B operand of a weight gradient dW = dy^T @ x2 on
     csrc/gemm_ps.hip's kernel -- the vocabulary's (10 000 x 300 outputs over the 1 280 caption rows), made on the side
-    stream in front of that gradient; None in the exact / deterministic modes and for few rows."""
+    stream in front of that gradient; None in the exact / deterministic modes and for few rows.
+    pack (ops.HeadRows): the rows are gathered through pack.rowmap -- column m of the copy is the m-th valid row -- and
+    only the pack.count valid ones are split (zeros up to the end of the last 32-row slice)."""
     rows, d = x2.shape
     if ops.gemm_split_mode() < 1 or ops.is_deterministic() or rows < 1024:
         return None
     buf = ops.presplit_buffer(d, rows, x2.device)
 
     def make():
-        ops.presplit_weights([(x2.t(), buf)])
+        if pack is None:
+            ops.presplit_weights([(x2.t(), buf)])
+        else:
+            ops.presplit_weights([(x2.t(), buf)], k_map=pack.rowmap, k_bound=pack.count)
 
     if ops.SIDE is not None:
         ops.SIDE.submit(make, x2, buf)
@@ -645,8 +654,15 @@ def _backward_phases(dec, tape, dscores, grads, want_image_grad=False):
     hv = m["hv"] if dec.has_facts else h
     # the vocabulary weight gradient is a large problem of its own: it starts beside its data gradient
     dhv0 = pre.get("dhv")
-    hv_t_ps = _rows_t_presplit(hv.view(M, d)) if _g(grads, dec.fc_vocab.weight) is not None else None
-    if dhv0 is not None and dhv0.shape == (M, d) and not ops.is_deterministic():
+    pack = m.get("pack")        # packed score head: dscores holds the valid rows only, packed at its top
+    hv_t_ps = _rows_t_presplit(hv.view(M, d), pack) if _g(grads, dec.fc_vocab.weight) is not None else None
+    if pack is not None:
+        # M' rows of data gradient, scattered into the zeroed logical buffer: the padded positions stay exactly zero
+        if dhv0 is None or dhv0.shape != (M, d):
+            dhv0 = torch.zeros(M, d, device=dev, dtype=torch.float32)
+        dhv = _lin_bwd(grads, dsc2[:, :V], hv.view(M, d), dec.fc_vocab.weight, dec.fc_vocab.bias, dx=dhv0, acc=True,
+                       group_now=True, wt_ps=m.get("vocab_t_ps"), xt_ps=hv_t_ps, pack=pack).view(B, L, d)
+    elif dhv0 is not None and dhv0.shape == (M, d) and not ops.is_deterministic():
         # split-K partial sums add into the buffer the forward pass's side stream zeroed
         dhv = _lin_bwd(grads, dsc2[:, :V], hv.view(M, d), dec.fc_vocab.weight, dec.fc_vocab.bias, dx=dhv0, acc=True,
                        group_now=True, wt_ps=m.get("vocab_t_ps"), xt_ps=hv_t_ps).view(B, L, d)
@@ -666,10 +682,10 @@ def _backward_phases(dec, tape, dscores, grads, want_image_grad=False):
         return _g(grads, param)
 
     ops.pointer_scores_bwd(dscores, V, h, ee, _p(dec.fc_entity.weight), None, dh, dee, gbuf(dec.fc_entity.weight),
-                           gbuf(dec.fc_entity.bias))
+                           gbuf(dec.fc_entity.bias), pack=pack)
     if dec.has_facts:
         ops.pointer_scores_bwd(dscores, V + K, h, fe, _p(dec.fc_fact.weight), m["eib"], dh, dfe,
-                               gbuf(dec.fc_fact.weight), gbuf(dec.fc_fact.bias))
+                               gbuf(dec.fc_fact.weight), gbuf(dec.fc_fact.bias), pack=pack)
     # ---- decoder stack
     layers = list(dec.transformer_decoder.layers)
     nseg = 2 * len(layers)
@@ -800,6 +816,9 @@ class TrainStep:
         # same order of optimizer steps; needs the captured two-stream step with the feature-map input (encoder=) and the
         # optimizer-maintained weight images, else the update stays where it was.
         self.lazy = bool(lazy_update)
+        # the score head over the packed list of valid caption rows; ICK_NO_PACKED_HEAD=1 restores the
+        # head over all B * L positions (A/B runs)
+        self.packed_head = os.environ.get("ICK_NO_PACKED_HEAD", "0") in ("", "0")
         self._pending = False
         self._gb = None
         # deterministic (default: ICK_DETERMINISTIC=1 in the environment): the library's fixed-order reductions, no
@@ -891,35 +910,50 @@ class TrainStep:
             return dict(enc_tok=None, feats=enc_in, conv1=(c1.weight.detach(), c1.bias.detach(), self.enc.conv1_presplit()))
         return dict(enc_tok=enc_in)
 
-    def _loss(self, scores, captions, decode_len, weights):
+    def _loss(self, scores, captions, decode_len, weights, pack=None):
         """Packed cross entropy into the tail of the gradient bucket (it was zeroed by the side tail; nothing else touches
-        those two floats); with per-caption weights (SelfCriticalStep's advantages) the weighted form."""
+        those two floats); with per-caption weights (SelfCriticalStep's advantages) the weighted form.  pack: the scores
+        are the packed rows of the valid positions, and so are the score gradients."""
         tail = dict(want_grad=True, out_sum=self.flat_g[self.n:self.n + 1], out_count=self.flat_g[self.n + 1:])
         pad = self.dec.word_map["<pad>"]
+        if pack is not None:
+            return ops.packed_ce_rows(scores, captions, pack, pad, weights=weights, **tail)
         if weights is None:
             return ops.packed_ce(scores, captions, decode_len, pad, **tail)
         return ops.packed_ce_weighted(scores, captions, decode_len, weights, pad, **tail)
+
+    def _side_tail(self, box, captions, entities, facts, lengths):
+        """Work of a step that nothing in the forward pass waits for (forward_with_tape runs it on the side stream behind
+        the context chain): zeroing the gradient bucket and the backward pass's accumulation targets, and the decode
+        lengths -- with the packed score head (the default; ICK_NO_PACKED_HEAD=1: every position runs through the head,
+        as before) one row-map launch that also lists the valid rows."""
+        def tail():
+            self.flat_g.zero_()
+            if self.packed_head:
+                box["pack"] = ops.HeadRows(lengths, captions.shape[0], captions.shape[1])
+                box["decode_len"] = box["pack"].decode_len
+            else:
+                box["decode_len"] = (lengths.reshape(-1) - 1).to(torch.int32)
+            box["prezero"] = _prezeroed(self.dec, captions, entities, facts)
+
+        return tail
 
     def _part_a(self, captions, caption_masks, entities, facts, enc_in, gmap, lengths, weights=None):
         dec = self.dec
         ops.stamp("A: start")
         box = {}
-
-        def tail():      # nothing in the forward pass waits for these: they run on the side stream behind the context chain
-            self.flat_g.zero_()
-            box["decode_len"] = (lengths.reshape(-1) - 1).to(torch.int32)
-            box["prezero"] = _prezeroed(dec, captions, entities, facts)
+        tail = self._side_tail(box, captions, entities, facts, lengths)
 
         scores, tape = forward_with_tape(dec, captions, caption_masks, entities, facts, gmap=gmap,
                                          seed=self.seed * 2654435761 & 0xFFFFFFFF, epoch=self.counter, fresh_pack=True,
                                          overlap=self._overlap("ICK_NO_FWD_OVERLAP"),
                                          side_tail=tail, derived=self.derived,
                                          pre_side=self._deferred_update if self._lazy_active(enc_in) else None,
-                                         **self._enc_kwargs(enc_in))
+                                         head_rows=lambda: box.get("pack"), **self._enc_kwargs(enc_in))
         decode_len = box["decode_len"]
         tape.misc["prezero"] = box.get("prezero")
         ops.stamp("fwd: scores done")
-        _, _, dscores = self._loss(scores, captions, decode_len, weights)
+        _, _, dscores = self._loss(scores, captions, decode_len, weights, box.get("pack"))
         ops.stamp("CE done")
         backward_from_tape(dec, tape, dscores, self.grads, overlap=self._overlap("ICK_NO_BWD_OVERLAP"))
         ops.stamp("A: end (after join)")
@@ -966,19 +1000,16 @@ class TrainStep:
     def _part_a1(self, captions, caption_masks, entities, facts, enc_in, gmap, lengths, weights=None):
         dec = self.dec
         box = {}
-
-        def tail():
-            self.flat_g.zero_()
-            box["decode_len"] = (lengths.reshape(-1) - 1).to(torch.int32)
-            box["prezero"] = _prezeroed(dec, captions, entities, facts)
+        tail = self._side_tail(box, captions, entities, facts, lengths)
 
         scores, tape = forward_with_tape(dec, captions, caption_masks, entities, facts, gmap=gmap,
                                          seed=self.seed * 2654435761 & 0xFFFFFFFF, epoch=self.counter, fresh_pack=True,
                                          overlap=self._overlap("ICK_NO_FWD_OVERLAP"),
-                                         side_tail=tail, derived=self.derived, **self._enc_kwargs(enc_in))
+                                         side_tail=tail, derived=self.derived, head_rows=lambda: box.get("pack"),
+                                         **self._enc_kwargs(enc_in))
         decode_len = box["decode_len"]
         tape.misc["prezero"] = box.get("prezero")
-        self._ce = self._loss(scores, captions, decode_len, weights)
+        self._ce = self._loss(scores, captions, decode_len, weights, box.get("pack"))
         self._bp = BackwardPass(dec, tape, self._ce[2], self.grads,
                                 overlap=self._overlap("ICK_NO_BWD_OVERLAP"))
         self._bp.early(join=True)

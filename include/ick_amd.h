@@ -84,6 +84,15 @@ typedef struct {
                                      operands by LDS-DMA and splits only the A fragments (csrc/gemm_ps.hip); B itself must
                                      still be valid (the other kernels read it).  The caller refreshes the copy whenever B
                                      changes (training: once per step, in the packing launches) */
+    const int32_t* m_bound;       /* optional DEVICE scalar: only rows m < min(M, *m_bound) of the problem exist.  The grid
+                                     stays sized for M; tiles at or past the bound exit before any load, the partial tile
+                                     masks its rows, nothing beyond the bound is written.  Not with dropout / gate (both are
+                                     keyed by the row number) or colsum_a. */
+    const int32_t* k_bound;       /* optional DEVICE scalar: the reduction runs over k < K' = min(K, *k_bound); the K slices
+                                     of a split-K problem partition [0, K') (slices past it exit), colsum_a sums K' rows.
+                                     K' = 0: C and colsum_a stay untouched.  Both bounds are read once per workgroup through
+                                     the scalar cache (training: the number of valid caption rows of a captured step, whose
+                                     lengths are a device input -- the packed score head) */
 } ick_gemm_args;
 
 #define ICK_GEMM_RELU 1
@@ -121,6 +130,10 @@ typedef struct {
     const float* src; void* dst;
     int32_t N, K;
     int64_t src_rs, src_cs;
+    const int32_t* k_map;     /* optional (src_rs == 1 only), device array: column k of the matrix is read from source column
+                                 k_map[k] -- the transposed view of activation rows gathered through a row list */
+    const int32_t* k_bound;   /* optional device scalar: columns k >= K' = min(K, *k_bound) do not exist: the 32-column slices
+                                 below K' are written (zeros from K' up to the slice's end), the slices past it are left alone */
 } ick_presplit_item;
 int ick_presplit_bytes(int32_t N, int32_t K, int64_t* bytes);
 int ick_presplit_weights(const ick_presplit_item* items, int32_t count, void* stream);
@@ -678,6 +691,43 @@ int ick_copy_batch(const void* const* src, void* const* dst, const long long* by
 int ick_timestamp(unsigned long long* out, void* stream);
 /* x *= num[0] / den[0] with device-resident scalars (token-mean normalisation without a host sync). */
 int ick_scale_by_ratio(float* x, int64_t n, const float* num, const float* den, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Packed score head of the fused training step: the loss of geo-aware/train.py:275-281 only reads the
+ * positions t < caption_length[b] - 1, and the decoder's causal self-attention (geo-aware/models.py:315-361, no
+ * key-padding mask) lets no valid position read a padded one -- so the head (vocabulary projection, pointer scores, cross
+ * entropy and their backward) runs over the packed list of valid rows only.  The list's length is known on the device
+ * alone; every launch keeps a grid sized for B * L rows and its surplus workgroups exit at once.
+ *
+ * ick_head_rowmap (one workgroup): n_b = clamp(lengths[b] - 1, 0, L - 1);
+ *   decode_len[b] = lengths[b] - 1 (int32, as the unpacked loss takes it), rowstart[b] = sum_{b' < b} n_b' (B + 1 entries:
+ *   rowstart[B] = M', the number of valid rows -- the `count` of the entry points below), rowmap[m] = b * L + t for packed
+ *   row m = rowstart[b] + t, t < n_b (sample-major, t ascending); entries m >= M' are set to 0 and never used. */
+int ick_head_rowmap(const int64_t* lengths, int32_t B, int32_t L, int32_t* decode_len, int32_t* rowstart,
+                    int32_t* rowmap, void* stream);
+/* ick_pointer_scores over the packed rows: h / ind are indexed by the logical row rowmap[m], the scores go to columns
+ * [col0, col0 + Kc) of PACKED row m of out (row stride out_ld), m < *count. */
+int ick_pointer_scores_packed(const float* h, const float* ctx, const float* w, const float* bias, const float* ind,
+                              float* out, int32_t B, int32_t T, int32_t Kc, int32_t d, int64_t out_ld, int32_t col0,
+                              const int32_t* rowmap, const int32_t* count, void* stream);
+/* ick_packed_ce[_weighted] (weights may be NULL) over packed score rows: row m < *count belongs to position
+ * (b, t) = (rowmap[m] / L, rowmap[m] % L), its target is captions[b, t + 1] and its weight weights[b]; row_loss and
+ * dscores are packed like the scores; rows >= *count are neither read nor written (nothing is zero-filled).
+ * *count == 0: loss_sum = count_out = 0. */
+int ick_packed_ce_packed(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                         const int32_t* count, const float* weights, int32_t B, int32_t L, int32_t Vx, int32_t pad_token,
+                         float* row_loss, float* loss_sum, float* count_out, float* dscores, void* stream);
+/* ick_pointer_scores_bwd reading PACKED score-gradient rows (sample b's rows are rowstart[b] .. rowstart[b + 1] - 1, in
+ * position order); h, ind and dh keep their logical (B, T) rows; dh rows of padded positions are not touched. */
+int ick_pointer_scores_bwd_packed(const float* ds, int64_t ds_ld, int32_t col0, const float* h, const float* ctx,
+                                  const float* w, const float* ind, float* dh, float* dctx, float* dw, float* dbias,
+                                  int32_t B, int32_t T, int32_t Kc, int32_t d, const int32_t* rowmap,
+                                  const int32_t* rowstart, void* stream);
+/* dst[m, :] = src[rowmap[m], :] for m < *count (d floats per row; grid sized for max_rows): the packed copy of the
+ * activation rows for the weight-gradient kernels that cannot gather their k-major B operand (exact / deterministic
+ * product modes; the pre-split kernel gathers in ick_presplit_weights instead). */
+int ick_gather_rows(const float* src, int64_t src_rs, const int32_t* rowmap, const int32_t* count, float* dst,
+                    int64_t dst_rs, int32_t max_rows, int32_t d, void* stream);
 
 #ifdef __cplusplus
 }
