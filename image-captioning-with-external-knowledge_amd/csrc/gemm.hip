@@ -60,6 +60,16 @@ namespace {
 // for anything out of bounds -- no address arithmetic, selects or branches in the loop, so the loads of
 // two slices stay in flight behind the MFMAs.  Only the last, partial K slice is masked (at LDS-store time).
 // !VEC is the generic element-wise fallback for ragged / unaligned operands.
+// k-major operands may gather their k lines through a device map (ick_gemm_args.a_kmap / b_kmap): reduction index k then
+// reads line kmap[k].  Only the address changes: the lane's k-line offset comes from the map instead of the scalar slice
+// offset.  Mapped problems run on instantiations of their own (MAP): behind a run-time branch of the one kernel, the
+// index registers became loop-carried values defined on one side of a branch, and the copies and waits the compiler
+// places at such joins made the unmapped loop wait for its loads a phase early.  In a MAP kernel register set SET keeps
+// the k lines of the next slice it will request (kx[SET]).  They are refilled right behind the data loads that consumed
+// them -- two slices ahead of their use, unconditionally and outside every branch, so the load lands in place -- and are
+// retired by the wait the LDS store of the slice in between needs anyway: the data loads never wait for an index load
+// issued in the same phase.  An operand without a map (or an unmapped problem of a grouped launch) rides along: its
+// refill reads a word that is not used and its k line is the reduction index (the map's presence is a uniform run-time value).
 // k-major planes (bank search): 64-row tiles take (2 R + 64)-byte k lines and swap neighbouring 16-row
 // blocks in k lines 8-15 / 24-31; 128-row tiles take (2 R + 32)-byte k lines (the 128 x 64 tile of Encoder.conv1 then
 // needs exactly 80 KB: two workgroups per CU) and swap blocks four apart.  kmajor_swap = log2 of the swap distance in
@@ -72,7 +82,7 @@ constexpr int kKmSwapOn = 0;
 constexpr int kKmSwapOn = 1;
 #endif
 
-template <int R, bool KM, bool VEC, int BKT, int NT = 256, bool SPL = false>
+template <int R, bool KM, bool VEC, int BKT, int NT = 256, bool SPL = false, bool MAP = false>
 struct Stager {
     static constexpr int NP = R * BKT / (4 * NT);    // float4 per thread (NT threads)
     static_assert(NP >= 1, "tile too small for the workgroup");
@@ -94,6 +104,9 @@ struct Stager {
     float4 v[2][NP];           // two register sets: the loads of slice i+2 fly while slice i+1 waits to be stored
     float4 cs;                 // SPL, k-major: this thread's share of the column sums (rows 4c..4c+3 over its k lines)
     bool want_cs;
+    const int32_t* kmap;       // MAP: the k-line map (uniform; nullptr: line k is reduction index k)
+    uint32_t rbase;            // MAP, VEC: byte offset of this thread's four rows in k line 0 (kOobOffset outside the matrix)
+    int kx[2][NP];             // MAP: the k lines of the next slice that register set SET will request
 
     __device__ __forceinline__ void init(const float* p, const RowMap& m, int64_t kstride, int tile_row0, int rows,
                                          int64_t extent) {
@@ -104,6 +117,8 @@ struct Stager {
         ok = 0;
         cs = float4{0.f, 0.f, 0.f, 0.f};
         want_cs = false;
+        kmap = nullptr;
+        rbase = kOobOffset;
         if constexpr (VEC) {
             rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), (short)0, (int)(extent * 4), 0x00020000);
             if constexpr (KM) {
@@ -112,6 +127,7 @@ struct Stager {
                 int64_t mo[1];
                 map_rows<1>(m, one, mo);
                 const uint32_t ro = (uint32_t)(mo[0] * 4);
+                rbase = gr < rows ? ro : kOobOffset;
 #pragma unroll
                 for (int j = 0; j < NP; ++j)
                     voff[j] = gr < rows ? ro + (uint32_t)((int64_t)(r0 + KP * j) * ks * 4) : kOobOffset;
@@ -142,9 +158,44 @@ struct Stager {
         }
     }
 
-    // Issue the global loads of slice [k0, k0+BK); nothing here depends on loaded data.
+    // MAP: request the k lines of slice [k0, k0+BK) for register set SET.  An index at or past kend is clamped to the
+    // last valid one (the map need not be readable beyond K'); the store masks those lines.
+    template <int SET>
+    __device__ __forceinline__ void refill(int k0, int kend) {
+        if constexpr (KM && MAP) {
+            // (an unmapped operand reads its own first word: some valid global address, the value is not used)
+            const int32_t* mp = kmap != nullptr ? kmap : reinterpret_cast<const int32_t*>(base);      // uniform
+#pragma unroll
+            for (int j = 0; j < NP; ++j) kx[SET][j] = mp[kmap != nullptr ? min(k0 + r0 + KP * j, kend - 1) : 0];
+        }
+    }
+    __device__ __forceinline__ void prime(const int32_t* km, int kbeg, int kend) {
+        if constexpr (KM && MAP) {
+            kmap = km;
+            refill<0>(kbeg, kend);
+            refill<1>(kbeg + BKT, kend);
+        }
+    }
+
+    // Issue the global loads of slice [k0, k0+BK); nothing here depends on data loaded in the same phase.
     template <int SET>
     __device__ __forceinline__ void load(int k0, int kend) {
+        if constexpr (KM && MAP) {
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                const int kl = kmap != nullptr ? kx[SET][j] : min(k0 + r0 + KP * j, kend - 1);
+                const int64_t ko = (int64_t)kl * ks;
+                if constexpr (VEC) {
+                    // kOobOffset + a line offset below 2 GiB stays out of range: rows outside the matrix read zeros
+                    const uint32_t vo = rbase + (uint32_t)ko * 4u;
+                    v[SET][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)vo, 0, 0));
+                } else {
+                    v[SET][j].x = base[off[0] + ko]; v[SET][j].y = base[off[1] + ko];
+                    v[SET][j].z = base[off[2] + ko]; v[SET][j].w = base[off[3] + ko];
+                }
+            }
+            return;
+        }
         if constexpr (VEC) {
             const int soff = KM ? (int)((int64_t)k0 * ks * 4) : k0 * 4;   // wave-uniform: scalar offset
 #pragma unroll
@@ -278,13 +329,13 @@ __device__ __forceinline__ bool split_major(int& bid, int& zid, int nt, int nspl
 }
 
 // One output tile: workgroup `bid` of the tiles_m x tiles_n grid of problem p, K slice `zid` of `nsplit`.
-template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, int BKT, bool SPL = false, int LSTG = 2>
+template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, int BKT, bool SPL = false, int LSTG = 2, bool MAP = false>
 __device__ __forceinline__ void gemm_tile(const ick_gemm_args& p, int tiles_m, int tiles_n, int kchunk, int bid,
                                           int zid, int nsplit, float* smem, bool xcd_remap = true) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     constexpr int BK = BKT;
-    using SA = Stager<BM, AKM, VEC, BKT, WM * WN * 64, SPL>;
-    using SB = Stager<BN, BKM, VEC, BKT, WM * WN * 64, SPL>;
+    using SA = Stager<BM, AKM, VEC, BKT, WM * WN * 64, SPL, MAP>;
+    using SB = Stager<BN, BKM, VEC, BKT, WM * WN * 64, SPL, MAP>;
     constexpr int STAGE = SA::FLOATS + SB::FLOATS;
 #ifdef ICK_GEMM_STAMPS
     const int stamp_id = bid + zid * tiles_m * tiles_n;
@@ -322,6 +373,8 @@ __device__ __forceinline__ void gemm_tile(const ick_gemm_args& p, int tiles_m, i
     sa.init(p.A, amap, p.a_ks, m0, Mr, p.a_extent);
     const bool only = (p.flags & ICK_GEMM_COLSUM_ONLY) != 0;   // uniform: column sums of A, no product
     sb.init(only ? p.A : p.B, bmap, p.b_ks, n0, p.N, p.b_extent);
+    sa.prime(p.a_kmap, kbeg, kend);
+    sb.prime(only ? nullptr : p.b_kmap, kbeg, kend);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -343,7 +396,9 @@ __device__ __forceinline__ void gemm_tile(const ick_gemm_args& p, int tiles_m, i
     if (nk > 0) {
         sa.template load<0>(kbeg, kend);
         if (!only) sb.template load<0>(kbeg, kend);
+        sa.template refill<0>(kbeg + 2 * BK, kend); sb.template refill<0>(kbeg + 2 * BK, kend);
         if (nk > 1) { sa.template load<1>(kbeg + BK, kend); if (!only) sb.template load<1>(kbeg + BK, kend); }
+        sa.template refill<1>(kbeg + 3 * BK, kend); sb.template refill<1>(kbeg + 3 * BK, kend);
         sa.template store<0>(smem, kbeg, kend);
         if (!only) sb.template store<0>(smem + SA::FLOATS, kbeg, kend);
     }
@@ -357,6 +412,7 @@ __device__ __forceinline__ void gemm_tile(const ick_gemm_args& p, int tiles_m, i
         const float* Bs = As + SA::FLOATS;
         const int k0 = kbeg + it * BK;
         if (it + 2 < nk) { sa.template load<CUR>(k0 + 2 * BK, kend); if (!only) sb.template load<CUR>(k0 + 2 * BK, kend); }
+        sa.template refill<CUR>(k0 + 4 * BK, kend); sb.template refill<CUR>(k0 + 4 * BK, kend);     // MAP only, outside the branch
         if constexpr (SPL) {
             if (!only) {
                 // one 16x16x32 block per tile and slice, six bf16 products (smallest first)
@@ -459,15 +515,15 @@ __device__ __forceinline__ void gemm_tile(const ick_gemm_args& p, int tiles_m, i
     ICK_GSTAMP(3);
 }
 
-template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, int BKT, bool SPL, int LSTG = 2>
+template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, int BKT, bool SPL, int LSTG = 2, bool MAP = false>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(ick_gemm_args p, int tiles_m, int tiles_n, int kchunk) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if constexpr (TM == 1) chain_priority();     // 32 x 32 tiles: the chain GEMMs (single launches, not the grouped weight gradients)
     const int nt = tiles_m * tiles_n;
     int bid = blockIdx.x, zid = blockIdx.z;
     const bool by_split = split_major(bid, zid, nt, gridDim.z);
-    gemm_tile<WM, WN, TM, TN, AKM, BKM, VEC, BKT, SPL, LSTG>(p, tiles_m, tiles_n, kchunk, bid, zid, (int)gridDim.z, smem,
-                                                             !by_split);
+    gemm_tile<WM, WN, TM, TN, AKM, BKM, VEC, BKT, SPL, LSTG, MAP>(p, tiles_m, tiles_n, kchunk, bid, zid, (int)gridDim.z,
+                                                                  smem, !by_split);
 }
 
 // Several independent problems of the same kernel configuration in one launch (the weight-gradient GEMMs of a
@@ -481,7 +537,7 @@ struct GroupArgs {
     ick_gemm_args g[kGroupMax];
 };
 
-template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, int BKT, bool SPL>
+template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, int BKT, bool SPL, bool MAP = false>
 __global__ __launch_bounds__(256) void gemm_group_kernel(GroupArgs ga) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int gi = 0;
@@ -491,8 +547,8 @@ __global__ __launch_bounds__(256) void gemm_group_kernel(GroupArgs ga) {
     if (local >= nt * ga.split[gi]) return;      // padding
     int zid = local / nt, bid = local - zid * nt;
     const bool by_split = split_major(bid, zid, nt, ga.split[gi]);
-    gemm_tile<WM, WN, TM, TN, AKM, BKM, VEC, BKT, SPL>(ga.g[gi], ga.tiles_m[gi], ga.tiles_n[gi], ga.kchunk[gi], bid, zid,
-                                                       ga.split[gi], smem, !by_split);
+    gemm_tile<WM, WN, TM, TN, AKM, BKM, VEC, BKT, SPL, 2, MAP>(ga.g[gi], ga.tiles_m[gi], ga.tiles_n[gi], ga.kchunk[gi], bid,
+                                                               zid, ga.split[gi], smem, !by_split);
 }
 
 // Host-side plan of one problem: validated arguments + kernel configuration.
@@ -505,10 +561,11 @@ struct Plan {
     bool xl;                     // 128 x 128 tiles, 8 waves, split products only (single launches only; implies wide)
     bool ps;                     // B read from its pre-split copy (gemm_ps.hip) ...
     int ps_tile, ps_nt;          // ... on tile shape ps_tile (gemm_ps_tile_dims), A loads non-temporal when ps_nt
+    bool kmap;                   // an operand gathers its k lines through a map: the MAP instantiations (four-wave tiles)
     int tiles_m, tiles_n, kchunk, split;
 };
 
-template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, bool SPL, int LSTG = 2>
+template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, bool SPL, int LSTG = 2, bool MAP = false>
 int launch_tile_s(const Plan& pl, hipStream_t s) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16, NT = WM * WN * 64;
     constexpr int STAGE = Stager<BM, AKM, VEC, 32, NT, SPL>::FLOATS + Stager<BN, BKM, VEC, 32, NT, SPL>::FLOATS;
@@ -517,30 +574,30 @@ int launch_tile_s(const Plan& pl, hipStream_t s) {
     const size_t lds = smem;
     if (lds > 64 * 1024) {
         static LdsAttrOnce attr;
-        if (int e = attr.ensure(reinterpret_cast<const void*>(gemm_kernel<WM, WN, TM, TN, AKM, BKM, VEC, 32, SPL, LSTG>), 160 * 1024))
+        if (int e = attr.ensure(reinterpret_cast<const void*>(gemm_kernel<WM, WN, TM, TN, AKM, BKM, VEC, 32, SPL, LSTG, MAP>), 160 * 1024))
             return e;
     }
     const int gx = pl.tiles_m * pl.tiles_n;
-    hipLaunchKernelGGL((gemm_kernel<WM, WN, TM, TN, AKM, BKM, VEC, 32, SPL, LSTG>), dim3(gx, 1, pl.split),
+    hipLaunchKernelGGL((gemm_kernel<WM, WN, TM, TN, AKM, BKM, VEC, 32, SPL, LSTG, MAP>), dim3(gx, 1, pl.split),
                        dim3(NT), lds, s, pl.a, pl.tiles_m, pl.tiles_n, pl.kchunk);
     ICK_LAUNCH_RET();
 }
-template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC>
+template <int WM, int WN, int TM, int TN, bool AKM, bool BKM, bool VEC, bool MAP = false>
 int launch_tile(const Plan& pl, hipStream_t s) {
     if constexpr (VEC && TM > 1) {
-        if (pl.spl) return launch_tile_s<WM, WN, TM, TN, AKM, BKM, VEC, true>(pl, s);
+        if (pl.spl) return launch_tile_s<WM, WN, TM, TN, AKM, BKM, VEC, true, 2, MAP>(pl, s);
     }
-    return launch_tile_s<WM, WN, TM, TN, AKM, BKM, VEC, false>(pl, s);
+    return launch_tile_s<WM, WN, TM, TN, AKM, BKM, VEC, false, 2, MAP>(pl, s);
 }
-template <int TM, int TN, bool AKM, bool BKM, bool VEC>
-int launch_one(const Plan& pl, hipStream_t s) { return launch_tile<2, 2, TM, TN, AKM, BKM, VEC>(pl, s); }
+template <int TM, int TN, bool AKM, bool BKM, bool VEC, bool MAP = false>
+int launch_one(const Plan& pl, hipStream_t s) { return launch_tile<2, 2, TM, TN, AKM, BKM, VEC, MAP>(pl, s); }
 template <int TM, int TN, bool AKM, bool BKM, bool VEC>
 int launch_wide(const Plan& pl, hipStream_t s) { return launch_tile<4, 2, TM, TN, AKM, BKM, VEC>(pl, s); }   // 8 waves
 // 128 x 128, four waves of 64 x 64, one LDS buffer: two workgroups per CU
 template <int TM, int TN, bool AKM, bool BKM, bool VEC>
 int launch_xl4(const Plan& pl, hipStream_t s) { return launch_tile_s<2, 2, TM, TN, AKM, BKM, VEC, true, 1>(pl, s); }
 
-template <int TM, int TN, bool AKM, bool BKM, bool SPL>
+template <int TM, int TN, bool AKM, bool BKM, bool SPL, bool MAP>
 int launch_group_s(const Plan* const* pls, int n, hipStream_t s) {
     constexpr int BM = 2 * TM * 16, BN = 2 * TN * 16;
     constexpr int STAGE = Stager<BM, AKM, true, 32, 256, SPL>::FLOATS + Stager<BN, BKM, true, 32, 256, SPL>::FLOATS;
@@ -562,18 +619,18 @@ int launch_group_s(const Plan* const* pls, int n, hipStream_t s) {
     const size_t lds = smem;
     if (lds > 64 * 1024) {      // split planes of two k-major operands: 72 KB, above the default dynamic-LDS limit
         static LdsAttrOnce attr;
-        if (int e = attr.ensure(reinterpret_cast<const void*>(gemm_group_kernel<2, 2, TM, TN, AKM, BKM, true, 32, SPL>), 160 * 1024))
+        if (int e = attr.ensure(reinterpret_cast<const void*>(gemm_group_kernel<2, 2, TM, TN, AKM, BKM, true, 32, SPL, MAP>), 160 * 1024))
             return e;
     }
-    hipLaunchKernelGGL((gemm_group_kernel<2, 2, TM, TN, AKM, BKM, true, 32, SPL>), dim3(total), dim3(256), lds, s, ga);
+    hipLaunchKernelGGL((gemm_group_kernel<2, 2, TM, TN, AKM, BKM, true, 32, SPL, MAP>), dim3(total), dim3(256), lds, s, ga);
     ICK_LAUNCH_RET();
 }
-template <int TM, int TN, bool AKM, bool BKM>
+template <int TM, int TN, bool AKM, bool BKM, bool MAP = false>
 int launch_group(const Plan* const* pls, int n, hipStream_t s) {
     if constexpr (TM > 1) {
-        if (pls[0]->spl) return launch_group_s<TM, TN, AKM, BKM, true>(pls, n, s);
+        if (pls[0]->spl) return launch_group_s<TM, TN, AKM, BKM, true, MAP>(pls, n, s);
     }
-    return launch_group_s<TM, TN, AKM, BKM, false>(pls, n, s);
+    return launch_group_s<TM, TN, AKM, BKM, false, MAP>(pls, n, s);
 }
 
 // Split-bf16 products for the 64 x 64 / 128 x 64 / 128 x 128 tiles.  Mode 1 (the DEFAULT since round 4: the reference-pinned
@@ -603,6 +660,7 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
         a.B = a.A; a.C = a.colsum_a; a.bias = nullptr; a.gate = nullptr;
         a.N = 1; a.b_rs = 1; a.b_ks = a.a_ks; a.c_rs = 1; a.c_grp = 0; a.hs_dh = 0; a.b_extent = a.a_extent;
         a.drop_p = 0.f;
+        a.b_kmap = nullptr;
         a.flags = ICK_GEMM_COLSUM_ONLY | ICK_GEMM_ATOMIC;
     }
     ICK_CHECK_ARG(a.A && a.B && a.C);
@@ -612,6 +670,11 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
     ICK_CHECK_ARG((a.b_rs == 1) || (a.b_ks == 1));
     if (a.split_k > 1) ICK_CHECK_ARG(a.flags & ICK_GEMM_ATOMIC);
     if (a.colsum_a) ICK_CHECK_ARG(akm);       // column sums come from the k-major A tile
+    // k-line maps: k-major operands only (a k-contiguous operand has no k lines to gather), and not beside a pre-split B,
+    // whose copy was gathered when it was made (ick_presplit_item.k_map)
+    if (a.a_kmap) ICK_CHECK_ARG(akm);
+    if (a.b_kmap) ICK_CHECK_ARG(bkm);
+    if (a.a_kmap || a.b_kmap) ICK_CHECK_ARG(a.b_ps == nullptr);
     if (a.gate) ICK_CHECK_ARG(a.hs_dh <= 0 && a.c_grp <= 0 && a.split_k <= 1 && !(a.flags & (ICK_GEMM_ATOMIC | ICK_GEMM_ACCUM)));
     if (a.hs_dh > 0) {
         ICK_CHECK_ARG(a.hs_dhp >= a.hs_dh && a.hs_H > 0 && a.hs_S > 0 && a.hs_s0 >= 0);
@@ -635,24 +698,25 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
     else if (bkm) bvec = aligned16(a.B) && a.b_ks % 4 == 0 && a.N % 4 == 0;
     else bvec = aligned16(a.B) && a.b_rs % 4 == 0 && a.K % 4 == 0;
     // operand extents (elements addressable from the base pointer) bound the buffer descriptors of the vector
-    // path; without a group map they follow from the strides, with one the caller must state them
+    // path; without a group or k-line map they follow from the strides, with one the caller must state them
     auto extent_of = [](int64_t rows, int64_t rs, int64_t K, int64_t ks, int grp, int64_t gs, bool has_map) -> int64_t {
         if (has_map) return 0;
         if (grp <= 0) return (rows - 1) * rs + (K - 1) * ks + 1;
         const int64_t ng = (rows + grp - 1) / grp;
         return (ng - 1) * gs + (std::min<int64_t>(grp, rows) - 1) * rs + (K - 1) * ks + 1;
     };
-    if (a.a_extent <= 0) a.a_extent = extent_of(a.M, a.a_rs, a.K, a.a_ks, a.a_grp, a.a_gs, a.a_gmap != nullptr);
-    if (a.b_extent <= 0) a.b_extent = extent_of(a.N, a.b_rs, a.K, a.b_ks, 0, 0, false);
+    if (a.a_extent <= 0) a.a_extent = extent_of(a.M, a.a_rs, a.K, a.a_ks, a.a_grp, a.a_gs, a.a_gmap != nullptr || a.a_kmap != nullptr);
+    if (a.b_extent <= 0) a.b_extent = extent_of(a.N, a.b_rs, a.K, a.b_ks, 0, 0, a.b_kmap != nullptr);
     const int64_t kMaxExtent = ((int64_t)1 << 29) - 64;   // < 2 GiB of floats, so kOobOffset is out of range
     // every float4 of the vector path starts at a multiple of 4 floats, so a bound rounded down to one
     // (views into a larger buffer, e.g. the flat parameter bucket) and capped below 2 GiB never cuts a valid one
     a.a_extent = std::min(a.a_extent & ~(int64_t)3, kMaxExtent - 4);
     a.b_extent = std::min(a.b_extent & ~(int64_t)3, kMaxExtent - 4);
-    const int64_t a_need = extent_of(a.M, a.a_rs, a.K, a.a_ks, a.a_grp, a.a_gs, a.a_gmap != nullptr);
-    const int64_t b_need = extent_of(a.N, a.b_rs, a.K, a.b_ks, 0, 0, false);
+    const int64_t a_need = extent_of(a.M, a.a_rs, a.K, a.a_ks, a.a_grp, a.a_gs, a.a_gmap != nullptr || a.a_kmap != nullptr);
+    const int64_t b_need = extent_of(a.N, a.b_rs, a.K, a.b_ks, 0, 0, a.b_kmap != nullptr);
     pl.vec = avec && bvec && a.a_extent >= 4 && a.b_extent >= 4 && a_need <= a.a_extent + 3 && b_need <= a.b_extent + 3;
     pl.akm = akm; pl.bkm = bkm;
+    pl.kmap = a.a_kmap != nullptr || a.b_kmap != nullptr;
     a.flags &= 0xff;
     // Tile selection, measured on MI355X (tools/probes/probe_ops, profiles/r01_*): with exact-fp32 MFMA a 64x64
     // wave tile alone needs ~18 us for K = 300, so latency and occupancy favour 64x64 workgroup tiles (32x32 per
@@ -667,14 +731,14 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
     if (force_big > 0) pl.big = true;
     // 128 x 64 tiles, 8 waves: measured +4 % on the feature projection (k-major A, K = 2048, N = 300: 157 -> 151 us),
     // -3 % on the K = 300 shapes, so it is reserved for long-K, narrow-N problems
-    pl.wide = pl.vec && pl.big && a.M >= 128 && akm && !bkm && a.N <= 320 && a.M >= 4096 && a.K >= 1024 && split_req == 1;
+    pl.wide = pl.vec && pl.big && a.M >= 128 && akm && !bkm && a.N <= 320 && a.M >= 4096 && a.K >= 1024 && split_req == 1 && !pl.kmap;
     pl.spl = pl.vec && pl.big && (gemm_split_mode() == 2 || (gemm_split_mode() == 1 && !bkm));
     pl.xl = false;
     if (pl.spl) {
         // 128 x 128 tiles: twice the products per staged (and split) element.  One workgroup per CU (98 KB of LDS), so
         // the problem must bring several rounds of tiles and waste little of its last tile column
         const int64_t t128 = (int64_t)ceil_div(a.M, 128) * ceil_div(a.N, 128);
-        const bool fits = split_req == 1 && a.M >= 128 && a.N >= 128 && t128 >= 512 && ceil_div(a.N, 128) * 128 <= a.N + a.N / 8;
+        const bool fits = !pl.kmap && split_req == 1 && a.M >= 128 && a.N >= 128 && t128 >= 512 && ceil_div(a.N, 128) * 128 <= a.N + a.N / 8;
         pl.xl = fits;
         if (pl.xl) pl.wide = true;
     }
@@ -731,6 +795,13 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
     return ICK_OK;
 }
 
+// (kmap: the MAP instantiations exist for the four-wave tiles; a map needs a k-major operand, make_plan)
+#define ICK_BY_LAYOUT_MAP(FN, TM, TN, VECARGS, ...)                                           \
+    do {                                                                                      \
+        if (pl.akm && !pl.bkm) return FN<TM, TN, true, false VECARGS, true>(__VA_ARGS__);     \
+        if (!pl.akm && pl.bkm) return FN<TM, TN, false, true VECARGS, true>(__VA_ARGS__);     \
+        return FN<TM, TN, true, true VECARGS, true>(__VA_ARGS__);                             \
+    } while (0)
 #define ICK_BY_LAYOUT(FN, TM, TN, VECARGS, ...)                                         \
     do {                                                                                \
         if (!pl.akm && !pl.bkm) return FN<TM, TN, false, false VECARGS>(__VA_ARGS__);   \
@@ -743,6 +814,11 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
 
 int launch_plan(const Plan& pl, hipStream_t s) {
     if (pl.ps) return launch_gemm_ps(pl.a, pl.akm, pl.ps_tile, pl.tiles_m, pl.tiles_n, pl.kchunk, pl.split, pl.ps_nt, s);
+    if (pl.kmap) {
+        if (!pl.vec) ICK_BY_LAYOUT_MAP(launch_one, 2, 2, ICK_COMMA_FALSE, pl, s);
+        if (pl.big) ICK_BY_LAYOUT_MAP(launch_one, 2, 2, ICK_COMMA_TRUE, pl, s);
+        ICK_BY_LAYOUT_MAP(launch_one, 1, 1, ICK_COMMA_TRUE, pl, s);
+    }
     if (!pl.vec) ICK_BY_LAYOUT(launch_one, 2, 2, ICK_COMMA_FALSE, pl, s);
     if (pl.xl) {
         // four waves of 64 x 64 and one LDS buffer: two workgroups per CU overlap their phases (against eight waves, two
@@ -756,6 +832,12 @@ int launch_plan(const Plan& pl, hipStream_t s) {
 
 int launch_plans_grouped(const Plan* const* pls, int n, hipStream_t s) {
     const Plan& pl = *pls[0];
+    bool kmap = false;      // one mapped problem puts the group on the MAP kernel; the others ride along unmapped
+    for (int i = 0; i < n; ++i) kmap = kmap || pls[i]->kmap;
+    if (kmap) {
+        if (pl.big) ICK_BY_LAYOUT_MAP(launch_group, 2, 2, , pls, n, s);
+        ICK_BY_LAYOUT_MAP(launch_group, 1, 1, , pls, n, s);
+    }
     if (pl.big) ICK_BY_LAYOUT(launch_group, 2, 2, , pls, n, s);
     ICK_BY_LAYOUT(launch_group, 1, 1, , pls, n, s);
 }

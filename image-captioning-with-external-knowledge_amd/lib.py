@@ -36,6 +36,7 @@ class GemmArgs(C.Structure):
         ("gate", vp), ("gate_rs", i64), ("gate_scale", f32),
         ("b_ps", vp),
         ("m_bound", vp), ("k_bound", vp),
+        ("a_kmap", vp), ("b_kmap", vp),
     ]
 
 

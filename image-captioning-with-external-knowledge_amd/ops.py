@@ -51,13 +51,16 @@ def _dargs(drop):
 
 def gemm_args(A, B, Cout, M, N, K, a_rs, a_ks, b_rs, b_ks, c_rs, bias=None, a_grp=0, a_gs=0, a_gmap=None,
               c_grp=0, c_gs=0, c_gmap=None, relu=False, accumulate=False, atomic=False, split_k=1, alpha=1.0,
-              drop=None, colsum_a=None, gate=None, gate_scale=1.0, b_ps=None, m_bound=None, k_bound=None):
+              drop=None, colsum_a=None, gate=None, gate_scale=1.0, b_ps=None, m_bound=None, k_bound=None,
+              a_kmap=None, b_kmap=None):
     """ick_gemm_args for C[m,n] = act(alpha * sum_k A(m,k) B(n,k) + bias[n]) with explicit element strides; A/B/Cout
     are tensors (only their data pointers are used -- the caller guarantees the strides stay in bounds).
     colsum_a (k-major A only): colsum_a[m] += sum_k A(m,k).  b_ps: the pre-split copy of the (N, K) matrix B
     (presplit_weights): large problems then run on the LDS-DMA kernel of csrc/gemm_ps.hip.
     m_bound / k_bound: one-element int32 device tensors that bound the rows / the reduction length below M / K (the
-    packed score head's row count; include/ick_amd.h)."""
+    packed score head's row count; include/ick_amd.h).
+    a_kmap / b_kmap: int32 device tensors, k-major operands only: reduction index k reads the operand's k line kmap[k]
+    (the weight gradients over the valid caption rows of logical-row operands)."""
     for t in (A, B, Cout):
         if t.dtype != torch.float32:
             raise L.IckError("ick_gemm operands must be float32, got %s" % t.dtype)
@@ -80,6 +83,10 @@ def gemm_args(A, B, Cout, M, N, K, a_rs, a_ks, b_rs, b_ks, c_rs, bias=None, a_gr
     for name, t in (("m_bound", m_bound), ("k_bound", k_bound)):
         if t is not None:
             assert t.dtype == torch.int32 and t.numel() == 1 and t.is_cuda, "%s is a one-element int32 device tensor" % name
+            setattr(a, name, _p(t))
+    for name, t in (("a_kmap", a_kmap), ("b_kmap", b_kmap)):
+        if t is not None:
+            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous(), "%s is an int32 device tensor" % name
             setattr(a, name, _p(t))
     _drop(a, drop)
     return a
@@ -185,6 +192,12 @@ def wgrad_split(rows, n_out, k_in, grouped=False):
     return max(1, min(cap, rows // 256, (1600 + tiles // 2) // tiles))
 
 
+# K slices of a decoder-layer weight gradient that reduces over the valid caption rows only (linear_bwd's valid=): the
+# split is sized from the host-side row count B * L, the reduction that runs is ~0.6 of it.  One against two slices inside
+# the captured step: profiles/valid_row_wgrad_ab.txt (ICK_VALID_ROW_WGRAD_SLICES is that sweep's knob).
+VALID_ROW_WGRAD_SLICES = max(1, int(os.environ.get("ICK_VALID_ROW_WGRAD_SLICES", "2") or 2))
+
+
 CONV1_TILE = (128, 64)   # workgroup tile ick_gemm picks for Encoder.conv1 at bench size on the exact fp32 MFMA
 
 
@@ -225,8 +238,14 @@ def gemm_raw(A, B, Cout, M, N, K, *args, **kwargs):
     return Cout
 
 
+# test hook: a list that receives the ick_gemm_args of every problem handed to gemm_grouped while it is set
+GROUP_LOG = None
+
+
 def gemm_grouped(problems):
     """Launch a list of ick_gemm_args; problems of one kernel configuration share a launch."""
+    if GROUP_LOG is not None:
+        GROUP_LOG.extend(problems)
     for i in range(0, len(problems), 64):
         chunk = problems[i:i + 64]
         arr = (L.GemmArgs * len(chunk))(*chunk)
@@ -1136,7 +1155,7 @@ SIDE = None   # set by training.TrainStep / backward_from_tape for the duration 
 
 
 def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, group_now=False, gate=None,
-               gate_scale=1.0, wt_ps=None, xt_ps=None, pack=None):
+               gate_scale=1.0, wt_ps=None, xt_ps=None, pack=None, valid=None):
     """Backward of y = x @ w.T + b for row-major 2-D views dy (M,N), x (M,K), w (N,K):
     dw += dy.T @ x (split-K over M, float atomics), db += colsum(dy), dx = dy @ w.
     With a SideStream installed the two parameter gradients run beside the data gradient.
@@ -1145,13 +1164,17 @@ def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, gro
     vocabulary: 10 000 x 300 outputs over 1 280 rows) and db becomes a column-sum problem of the same group.
     pack (HeadRows; the packed score head): dy holds the M' = pack.count valid rows packed at its top, x and dx keep their
     logical rows.  The reductions of dw / db run over M' rows (xt_ps must have been gathered through pack.rowmap; without
-    it a packed copy of x is made here), dx is computed for M' rows and scattered through pack.rowmap into a dx that the
-    caller zeroed (accumulate_dx): the rows of padded positions stay exactly zero."""
+    it the rows of x are read in place through the k-line map of csrc/gemm.hip, b_kmap), dx is computed for M' rows and scattered through pack.rowmap into a dx that the
+    caller zeroed (accumulate_dx): the rows of padded positions stay exactly zero.
+    valid (HeadRows; the decoder layers below a packed head): dy and x both keep their logical rows, and the rows of dy
+    that valid.rowmap does not list are exactly zero: dw / db reduce over the valid.count listed rows of
+    both operands, read in place through the k-line maps of csrc/gemm.hip.  The data gradient is not touched."""
     M, N = dy.shape
     K = x.shape[1]
-    kb = pack.count if pack is not None else None
-    xk = x
+    assert pack is None or valid is None
+    kb = pack.count if pack is not None else (valid.count if valid is not None else None)
     assert pack is None or (need_dx and dx is not None and accumulate_dx and gate is None)
+    assert valid is None or (xt_ps is None and valid.rowmap.numel() == M)
 
     # dw += dy.T @ x with db += colsum(dy) riding on the first tile column of the same kernel
     wg = None
@@ -1165,10 +1188,15 @@ def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, gro
         if db is not None:
             extra.append(colsum_problem(dy, db, split_k=max(1, min(16, M // 256)), k_bound=kb))
     elif dw is not None:
-        # (the kernels of csrc/gemm.hip cannot gather their k-major B operand: they read a packed copy of x)
-        xk = gather_rows(x, pack) if pack is not None else x
-        wg = gemm_args(dy, xk, dw, N, K, M, 1, dy.stride(0), 1, xk.stride(0), dw.stride(0), atomic=True,
-                       split_k=wgrad_split(M, N, K, grouped=SIDE is not None), colsum_a=db, k_bound=kb)
+        # pack: dy is packed, the k-major B operand gathers the logical rows of x through the row list; valid: both do
+        rows = pack if pack is not None else valid
+        split = wgrad_split(M, N, K, grouped=SIDE is not None)
+        if valid is not None:
+            split = min(split, VALID_ROW_WGRAD_SLICES)
+        wg = gemm_args(dy, x, dw, N, K, M, 1, dy.stride(0), 1, x.stride(0), dw.stride(0), atomic=True,
+                       split_k=split, colsum_a=db, k_bound=kb,
+                       a_kmap=valid.rowmap if valid is not None else None,
+                       b_kmap=rows.rowmap if rows is not None else None)
 
     def param_grads():
         if wg is not None and extra:
@@ -1189,7 +1217,7 @@ def linear_bwd(dy, x, w, dw, db, need_dx=True, dx=None, accumulate_dx=False, gro
     overlap = SIDE is not None and (dw is not None or db is not None)
     if overlap:
         if wg is not None:
-            SIDE.add_problem(wg, dy, x, xk, xt_ps)
+            SIDE.add_problem(wg, dy, x, xt_ps)
             for e in extra:
                 SIDE.add_problem(e, dy)
             if group_now:      # a large problem of its own (the vocabulary): runs beside its data gradient

@@ -268,7 +268,7 @@ def _g(grads, param):
 
 
 def _lin_bwd(grads, dy2, x2, lin_w, lin_b, w_rows=None, need_dx=True, dx=None, acc=False, group_now=False,
-             gate=None, gate_scale=1.0, wt_ps=None, xt_ps=None, pack=None):
+             gate=None, gate_scale=1.0, wt_ps=None, xt_ps=None, pack=None, valid=None):
     """Backward of a Linear whose weight is `lin_w` (optionally the row slice w_rows of it)."""
     gw, gb = _g(grads, lin_w), _g(grads, lin_b)
     w = _p(lin_w)
@@ -277,7 +277,7 @@ def _lin_bwd(grads, dy2, x2, lin_w, lin_b, w_rows=None, need_dx=True, dx=None, a
         gw = gw[w_rows] if gw is not None else None
         gb = gb[w_rows] if gb is not None else None
     return ops.linear_bwd(dy2, x2, w, gw, gb, need_dx=need_dx, dx=dx, accumulate_dx=acc, group_now=group_now,
-                          gate=gate, gate_scale=gate_scale, wt_ps=wt_ps, xt_ps=xt_ps, pack=pack)
+                          gate=gate, gate_scale=gate_scale, wt_ps=wt_ps, xt_ps=xt_ps, pack=pack, valid=valid)
 
 
 def _prezeroed(dec, captions, entities, facts):
@@ -378,11 +378,13 @@ def _context_encoder_bwd(dec, stack, tapes, dx, grads, pkb=None, tag="e", g_firs
     return dx
 
 
-def _decoder_layer_bwd_chain(dec, li, layer, t, state, dkv_rows, kv, S, grads, pkb, mem2=None, mem_t_ps=None):
+def _decoder_layer_bwd_chain(dec, li, layer, t, state, dkv_rows, kv, S, grads, pkb, mem2=None, mem_t_ps=None,
+                             valid=None):
     """Backward of decoder layer li as two ops.rowchain_bwd launches around the cross-attention backward + the
     self-attention backward.  state = (dz, g0, w0p): the residual-path gradient of this layer's output, and -- from the
     layer above -- the in_proj gradient whose data gradient rides on this layer's first launch.  Returns the state
-    for the layer below."""
+    for the layer below.  valid (ops.HeadRows, below a packed score head): the layer's weight gradients reduce over the
+    valid caption rows only -- every other row of their dy operands is exactly zero."""
     H, d = dec.num_heads, dec.emb_dim
     dh = d // H
     B, T, _ = t["x"].shape
@@ -401,10 +403,11 @@ def _decoder_layer_bwd_chain(dec, li, layer, t, state, dkv_rows, kv, S, grads, p
         ops.SIDE.flush()
     ops.ln_partials_reduce(n3["part"], _g(grads, layer.norm3.weight), _g(grads, layer.norm3.bias))
     ops.ln_partials_reduce(n2["part"], _g(grads, layer.norm2.weight), _g(grads, layer.norm2.bias))
-    _lin_bwd(grads, n3["do"], t["f"].view(M, -1), layer.linear2.weight, layer.linear2.bias, need_dx=False)
-    _lin_bwd(grads, dpre, t["x2"].view(M, d), layer.linear1.weight, layer.linear1.bias, need_dx=False)
+    _lin_bwd(grads, n3["do"], t["f"].view(M, -1), layer.linear2.weight, layer.linear2.bias, need_dx=False,
+             valid=valid)
+    _lin_bwd(grads, dpre, t["x2"].view(M, d), layer.linear1.weight, layer.linear1.bias, need_dx=False, valid=valid)
     _lin_bwd(grads, n2["do"], t["ca"].view(M, d), layer.multihead_attn.out_proj.weight,
-             layer.multihead_attn.out_proj.bias, need_dx=False)
+             layer.multihead_attn.out_proj.bias, need_dx=False, valid=valid)
     # The layer's weight gradients go out in two grouped launches: linear2 / linear1 / cross out-projection + the two
     # norms' partials right behind the chain launch above, the rest at the layer's end (the side stream finishes last:
     # starting its work earlier shortens the step, 651 -> 654 k decode-steps/s; a third launch right behind the
@@ -428,27 +431,27 @@ def _decoder_layer_bwd_chain(dec, li, layer, t, state, dkv_rows, kv, S, grads, p
         ops.SIDE.flush()
     ops.ln_partials_reduce(n1["part"], _g(grads, layer.norm1.weight), _g(grads, layer.norm1.bias))
     _lin_bwd(grads, dq.view(M, d), t["x1"].view(M, d), layer.multihead_attn.in_proj_weight,
-             layer.multihead_attn.in_proj_bias, w_rows=slice(0, d), need_dx=False)
+             layer.multihead_attn.in_proj_bias, w_rows=slice(0, d), need_dx=False, valid=valid)
     _lin_bwd(grads, n1["do"], t["sa"].view(M, d), layer.self_attn.out_proj.weight, layer.self_attn.out_proj.bias,
-             need_dx=False)
+             need_dx=False, valid=valid)
     dqkv = ops.attention_bwd_buffer((B, T, 3 * d), T, T, dh, dev)
     ops.attention_heads_bwd(t["qkv"], t["qkv"], t["sa"], dsa.view(B, T, d), t["lse_s"], dqkv[:, :, :d],
                             dqkv[:, :, d:2 * d], dqkv[:, :, 2 * d:], H, dh, T, T, 0, 1, 2, causal=True,
                             drop=t["d_sa"])
     if li > 0:
         _lin_bwd(grads, dqkv.view(M, 3 * d), t["x"].view(M, d), layer.self_attn.in_proj_weight,
-                 layer.self_attn.in_proj_bias, need_dx=False)
+                 layer.self_attn.in_proj_bias, need_dx=False, valid=valid)
         out = (dz_b, dqkv.view(M, 3 * d), pkb[("d", li, "siT")])
     else:
         dx0 = _lin_bwd(grads, dqkv.view(M, 3 * d), t["x"].view(M, d), layer.self_attn.in_proj_weight,
-                       layer.self_attn.in_proj_bias, dx=dz_b, acc=True).view(B, T, d)
+                       layer.self_attn.in_proj_bias, dx=dz_b, acc=True, valid=valid).view(B, T, d)
         out = (dx0, None, None)
     if ops.SIDE is not None:
         ops.SIDE.flush_group()          # this layer's weight gradients: one grouped launch
     return out
 
 
-def _decoder_layer_bwd(dec, li, layer, t, dx, dkv_rows, kv, S, grads, mem2=None, mem_t_ps=None):
+def _decoder_layer_bwd(dec, li, layer, t, dx, dkv_rows, kv, S, grads, mem2=None, mem_t_ps=None, valid=None):
     H, d = dec.num_heads, dec.emb_dim
     dh = d // H
     B, T, _ = t["x"].shape
@@ -456,13 +459,14 @@ def _decoder_layer_bwd(dec, li, layer, t, dx, dkv_rows, kv, S, grads, mem2=None,
     dz, do3 = ops.layernorm_bwd(dx, t["o3"], t["x2"], _p(layer.norm3.weight), t["m3"], t["r3"],
                                 _g(grads, layer.norm3.weight), _g(grads, layer.norm3.bias), drop=t["d3"])
     dpre = _lin_bwd(grads, do3.view(M, d), t["f"].view(M, -1), layer.linear2.weight, layer.linear2.bias,
-                    gate=t["f"].view(M, -1), gate_scale=_keep_scale(t["d_ff"]))       # ReLU' (+ dropout) fused
+                    gate=t["f"].view(M, -1), gate_scale=_keep_scale(t["d_ff"]),       # ReLU' (+ dropout) fused
+                    valid=valid)
     dx2 = _lin_bwd(grads, dpre, t["x2"].view(M, d), layer.linear1.weight, layer.linear1.bias, dx=dz.view(M, d),
-                   acc=True)
+                   acc=True, valid=valid)
     dz, do2 = ops.layernorm_bwd(dx2.view(B, T, d), t["o2"], t["x1"], _p(layer.norm2.weight), t["m2"], t["r2"],
                                 _g(grads, layer.norm2.weight), _g(grads, layer.norm2.bias), drop=t["d2"])
     dca = _lin_bwd(grads, do2.view(M, d), t["ca"].view(M, d), layer.multihead_attn.out_proj.weight,
-                   layer.multihead_attn.out_proj.bias)
+                   layer.multihead_attn.out_proj.bias, valid=valid)
     dq = torch.empty(B, T, d, device=dx.device, dtype=torch.float32)
     c0 = 2 * li * d
     ops.attention_heads_bwd(t["qc"], kv, t["ca"], dca.view(B, T, d), t["lse_c"], dq, dkv_rows[:, :, c0:c0 + d],
@@ -472,17 +476,17 @@ def _decoder_layer_bwd(dec, li, layer, t, dx, dkv_rows, kv, S, grads, mem2=None,
         # all B * S memory rows joins this layer's group instead of waiting for the whole decoder stack
         _kv_proj_param_grads(layer, li, dkv_rows, mem2, grads, d, mem_t_ps)
     dx1 = _lin_bwd(grads, dq.view(M, d), t["x1"].view(M, d), layer.multihead_attn.in_proj_weight,
-                   layer.multihead_attn.in_proj_bias, w_rows=slice(0, d), dx=dz.view(M, d), acc=True)
+                   layer.multihead_attn.in_proj_bias, w_rows=slice(0, d), dx=dz.view(M, d), acc=True, valid=valid)
     dz, do1 = ops.layernorm_bwd(dx1.view(B, T, d), t["o1"], t["x"], _p(layer.norm1.weight), t["m1"], t["r1"],
                                 _g(grads, layer.norm1.weight), _g(grads, layer.norm1.bias), drop=t["d1"])
     dsa = _lin_bwd(grads, do1.view(M, d), t["sa"].view(M, d), layer.self_attn.out_proj.weight,
-                   layer.self_attn.out_proj.bias)
+                   layer.self_attn.out_proj.bias, valid=valid)
     dqkv = ops.attention_bwd_buffer((B, T, 3 * d), T, T, dh, dx.device)
     ops.attention_heads_bwd(t["qkv"], t["qkv"], t["sa"], dsa.view(B, T, d), t["lse_s"], dqkv[:, :, :d],
                             dqkv[:, :, d:2 * d], dqkv[:, :, 2 * d:], H, dh, T, T, 0, 1, 2, causal=True,
                             drop=t["d_sa"])
     dx0 = _lin_bwd(grads, dqkv.view(M, 3 * d), t["x"].view(M, d), layer.self_attn.in_proj_weight,
-                   layer.self_attn.in_proj_bias, dx=dz.view(M, d), acc=True).view(B, T, d)
+                   layer.self_attn.in_proj_bias, dx=dz.view(M, d), acc=True, valid=valid).view(B, T, d)
     if ops.SIDE is not None:
         ops.SIDE.flush_group()          # this layer's weight gradients: one grouped launch
     return dx0
@@ -655,6 +659,11 @@ def _backward_phases(dec, tape, dscores, grads, want_image_grad=False):
     # the vocabulary weight gradient is a large problem of its own: it starts beside its data gradient
     dhv0 = pre.get("dhv")
     pack = m.get("pack")        # packed score head: dscores holds the valid rows only, packed at its top
+    # below a packed head the gradient at every padded position is exactly zero all the way down the decoder stack: the
+    # layers' weight gradients reduce over the valid rows only (ICK_NO_VALID_ROW_WGRAD=1: over all B * L).
+    # Not in deterministic mode: there every gradient below the head is pinned bit-identical to the unpacked head's
+    # (tests/test_packed_head_gpu.py), and packed rows fall into other 4-row MFMA groups than logical ones
+    valid = pack if os.environ.get("ICK_NO_VALID_ROW_WGRAD", "0") in ("", "0") and not ops.is_deterministic() else None
     hv_t_ps = _rows_t_presplit(hv.view(M, d), pack) if _g(grads, dec.fc_vocab.weight) is not None else None
     if pack is not None:
         # M' rows of data gradient, scattered into the zeroed logical buffer: the padded positions stay exactly zero
@@ -698,13 +707,14 @@ def _backward_phases(dec, tape, dscores, grads, want_image_grad=False):
         state = (dh.view(M, d), None, None)
         for li in reversed(range(len(layers))):
             state = _decoder_layer_bwd_chain(dec, li, layers[li], tape.dec_layers[li], state, dkv_rows, m["kv"], S,
-                                             grads, pkb, mem2=m["mem"].view(B * S, d), mem_t_ps=mem_t_ps)
+                                             grads, pkb, mem2=m["mem"].view(B * S, d), mem_t_ps=mem_t_ps,
+                                             valid=valid)
             ops.stamp("bwd: decoder layer %d done" % li)
         dx = state[0]
     else:
         for li in reversed(range(len(layers))):
             dx = _decoder_layer_bwd(dec, li, layers[li], tape.dec_layers[li], dx, dkv_rows, m["kv"], S, grads,
-                                    mem2=m["mem"].view(B * S, d), mem_t_ps=mem_t_ps)
+                                    mem2=m["mem"].view(B * S, d), mem_t_ps=mem_t_ps, valid=valid)
             ops.stamp("bwd: decoder layer %d done" % li)
     yield    # ---- end of the early phase: every gradient of early_parameters() has been enqueued
     # ---- cross K/V projection: the weight gradients went out with the decoder layers; data gradient for the

@@ -93,6 +93,14 @@ typedef struct {
                                      K' = 0: C and colsum_a stay untouched.  Both bounds are read once per workgroup through
                                      the scalar cache (training: the number of valid caption rows of a captured step, whose
                                      lengths are a device input -- the packed score head) */
+    const int32_t* a_kmap;
+    const int32_t* b_kmap;        /* optional DEVICE arrays of at least min(K, *k_bound) int32, k-major operands only (a_rs == 1 /
+                                     b_rs == 1): reduction index k reads the operand's k line a_kmap[k] / b_kmap[k] instead of k
+                                     (element (m, k) at A[... + a_kmap[k] * a_ks]).  k_bound keeps its meaning: the K slices
+                                     partition [0, K'), colsum_a sums the K' gathered lines.  The entries must name lines inside
+                                     a_extent / b_extent.  Not with b_ps (the pre-split copy is gathered when it is made:
+                                     ick_presplit_item.k_map).  Training: the weight gradients of the decoder layers reduce over
+                                     the valid caption rows of the logical (B * L)-row operands, DESIGN.md 3.1f */
 } ick_gemm_args;
 
 #define ICK_GEMM_RELU 1
