@@ -404,6 +404,167 @@ __global__ __launch_bounds__(256) void packed_ce_reduce_kernel(const float* __re
     if (threadIdx.x == 0) { loss_sum[0] = s; count[0] = c; }
 }
 
+// Caption scoring (ick_row_logprob_rank): what a scorer needs of one packed score row -- the target's
+// log-probability, its rank in a stable descending sort and the row's argmax -- from ONE read of the row.
+struct RowScan {
+    float m, s;      // running maximum and sum of exp(x - m); m is also the value of the running argmax
+    float cnt;       // columns that beat the target (a count below 2^24: exact in fp32 in any order)
+    int bi;          // lowest column that holds m
+};
+__device__ __forceinline__ void row_scan_push(RowScan& a, float x, int c, float st, int target) {
+    a.s += __expf(x - a.m);       // a.m >= x: the caller has moved the maximum over the whole batch first
+    a.cnt += (x > st || (x == st && c < target)) ? 1.f : 0.f;
+}
+// (a thread meets its columns in ascending order, so `>` alone keeps the lowest column of a tie)
+__device__ __forceinline__ void row_scan_best(float& bv, int& bi, float x, int c) {
+    if (x > bv) { bv = x; bi = c; }
+}
+
+// One workgroup per packed row m < *count of the (L, R) grid; the row belongs to position rowmap[m] = b * L + t and its
+// results go to the LOGICAL element (b, t) of the (R, L - 1) outputs.  Same validity rule as packed_ce_rows_kernel: a
+// target that is <pad> or outside [0, Vx) gives 0 / -1 / -1.  Scores are taken to be finite (the head's are): -inf is
+// the padding of the lanes past the row, and a batch that holds nothing else is skipped.
+__global__ __launch_bounds__(256) void row_logprob_rank_kernel(const float* __restrict__ scores, int64_t ld,
+                                                               const int64_t* __restrict__ caps,
+                                                               const int32_t* __restrict__ rowmap,
+                                                               const int32_t* __restrict__ count, int L, int Vx, int pad,
+                                                               float* __restrict__ tlp, int32_t* __restrict__ rank,
+                                                               int32_t* __restrict__ best) {
+    __shared__ float4 red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t row = (int64_t)blockIdx.y * L + blockIdx.x;
+    if (row >= device_bound((int)gridDim.y * L, count)) return;      // uniform
+    const int lr = rowmap[row];
+    const int b = lr / L, t = lr - b * L;
+    if (b >= (int)gridDim.y || t >= L - 1) return;                   // (never, for a row list of ick_head_rowmap)
+    const int64_t o = (int64_t)b * (L - 1) + t;
+    const int64_t target64 = caps[(int64_t)b * L + t + 1];
+    if (target64 == pad || target64 < 0 || target64 >= Vx) {         // uniform
+        if (tid == 0) { tlp[o] = 0.f; rank[o] = -1; best[o] = -1; }
+        return;
+    }
+    const int target = (int)target64;
+    const float* r = scores + row * ld;
+    const float st = r[target];
+    const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(scores) & 15) == 0;
+    const int n4 = vec ? (Vx >> 2) : 0;             // float4 elements of the aligned bulk; [4 n4, Vx) is the scalar tail
+    const float4* r4 = reinterpret_cast<const float4*>(r);
+    RowScan a{-INFINITY, 0.f, 0.f, 0x7fffffff};
+    for (int i0 = 0; i0 < n4; i0 += 256 * 4) {
+        float4 x[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = i0 + tid + 256 * j;
+            x[j] = i < n4 ? r4[i] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        }
+        float bm = a.m;
+        int bi = a.bi;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = 4 * (i0 + tid + 256 * j);
+            row_scan_best(bm, bi, x[j].x, c); row_scan_best(bm, bi, x[j].y, c + 1);
+            row_scan_best(bm, bi, x[j].z, c + 2); row_scan_best(bm, bi, x[j].w, c + 3);
+        }
+        if (bm > -INFINITY) {
+            a.s *= __expf(a.m - bm);                // a.m = -inf: s is 0 and stays 0
+            a.m = bm; a.bi = bi;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {           // (columns past the row hold -inf: exp gives 0, no comparison holds)
+                const int c = 4 * (i0 + tid + 256 * j);
+                row_scan_push(a, x[j].x, c, st, target); row_scan_push(a, x[j].y, c + 1, st, target);
+                row_scan_push(a, x[j].z, c + 2, st, target); row_scan_push(a, x[j].w, c + 3, st, target);
+            }
+        }
+    }
+    for (int i0 = 4 * n4; i0 < Vx; i0 += 256 * 8) {
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = i0 + tid + 256 * j;
+            x[j] = i < Vx ? r[i] : -INFINITY;
+        }
+        float bm = a.m;
+        int bi = a.bi;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) row_scan_best(bm, bi, x[j], i0 + tid + 256 * j);
+        if (bm > -INFINITY) {
+            a.s *= __expf(a.m - bm);
+            a.m = bm; a.bi = bi;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) row_scan_push(a, x[j], i0 + tid + 256 * j, st, target);
+        }
+    }
+    // merge: within the wave by the DPP reductions, then the four waves' results by thread 0 in wave order.  Column
+    // numbers are below 2^24 (checked by the entry point), so the lowest column of the maximum is a float maximum of -c.
+    const float wm = wave_max(a.m);
+    const float ws = wave_sum(a.m > -INFINITY ? a.s * __expf(a.m - wm) : 0.f);
+    const float wc = wave_sum(a.cnt);
+    const float wi = wave_max(a.m == wm && a.bi != 0x7fffffff ? -(float)a.bi : -INFINITY);
+    if (lane == 0) red[wave] = make_float4(wm, ws, wc, wi);
+    __syncthreads();
+    if (tid == 0) {
+        float m = red[0].x;
+#pragma unroll
+        for (int w = 1; w < 4; ++w) m = fmaxf(m, red[w].x);
+        float s = 0.f, c = 0.f, bi = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (red[w].x > -INFINITY) s += red[w].y * __expf(red[w].x - m);
+            c += red[w].z;
+            if (red[w].x == m) bi = fmaxf(bi, red[w].w);
+        }
+        tlp[o] = st - (m + __logf(s));
+        rank[o] = (int32_t)c;
+        best[o] = (int32_t)(-bi);
+    }
+}
+
+// One wave per caption r (ick_caption_score_sums): the caption's valid rows are positions t < n = rowstart[r + 1] -
+// rowstart[r]; the positions from n on get their fill values here (so no memset precedes the row kernel), the token
+// log-probabilities are summed in position order by lane 0.
+__global__ __launch_bounds__(256) void caption_sums_kernel(const int32_t* __restrict__ rowstart, int R, int L,
+                                                           float* __restrict__ tlp, int32_t* __restrict__ rank,
+                                                           int32_t* __restrict__ best, float* __restrict__ log_prob,
+                                                           int32_t* __restrict__ tokens) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (r >= R) return;
+    const int n = min(max(rowstart[r + 1] - rowstart[r], 0), L - 1);
+    const int64_t o = (int64_t)r * (L - 1);
+    for (int t = n + lane; t < L - 1; t += 64) { tlp[o + t] = 0.f; rank[o + t] = -1; best[o + t] = -1; }
+    if (lane == 0) {
+        float s = 0.f;
+        int c = 0;
+        for (int t = 0; t < n; ++t) {
+            if (rank[o + t] >= 0) { s += tlp[o + t]; ++c; }
+        }
+        log_prob[r] = s;
+        tokens[r] = c;
+    }
+}
+
+// The four totals over all R * (L - 1) positions in a fixed order (one workgroup, no float atomics).
+__global__ __launch_bounds__(256) void caption_totals_kernel(const float* __restrict__ tlp, const int32_t* __restrict__ rank,
+                                                             int64_t n, int top_k, float* __restrict__ loss_sum,
+                                                             float* __restrict__ count, float* __restrict__ top1,
+                                                             float* __restrict__ topk) {
+    __shared__ float red[4];
+    float s = 0.f, c = 0.f, h1 = 0.f, hk = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        const int rk = rank[i];
+        if (rk >= 0) {
+            s -= tlp[i];
+            c += 1.f;
+            h1 += rk == 0 ? 1.f : 0.f;
+            hk += rk < top_k ? 1.f : 0.f;
+        }
+    }
+    s = block_sum<4>(s, red);
+    c = block_sum<4>(c, red);
+    h1 = block_sum<4>(h1, red);
+    hk = block_sum<4>(hk, red);
+    if (threadIdx.x == 0) { loss_sum[0] = s; count[0] = c; top1[0] = h1; topk[0] = hk; }
+}
+
 // The packed row list of the training step's score head (ick_head_rowmap): one workgroup scans the B lengths.
 __global__ __launch_bounds__(256) void head_rowmap_kernel(const int64_t* __restrict__ lengths, int B, int L,
                                                           int32_t* __restrict__ decode_len, int32_t* __restrict__ rowstart,
@@ -578,6 +739,32 @@ extern "C" int ick_packed_ce_packed(const float* scores, int64_t ld, const int64
         hipLaunchKernelGGL(packed_ce_reduce_kernel<false>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, nullptr, loss_sum,
                            count_out, rowmap, count);
     }
+    ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_row_logprob_rank(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                                    const int32_t* count, int32_t R, int32_t L, int32_t Vx, int32_t pad_token,
+                                    float* token_log_prob, int32_t* rank, int32_t* best, void* stream) {
+    using namespace ick;
+    ICK_CHECK_ARG(scores && captions && rowmap && count && token_log_prob && rank && best);
+    ICK_CHECK_ARG(R > 0 && R <= 65535 && L > 1 && Vx > 0 && Vx <= (1 << 24) && ld >= Vx && (int64_t)R * L <= INT32_MAX);
+    hipLaunchKernelGGL(row_logprob_rank_kernel, dim3(L, R), dim3(256), 0, (hipStream_t)stream, scores, ld, captions,
+                       rowmap, count, L, Vx, pad_token, token_log_prob, rank, best);
+    ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_caption_score_sums(const int32_t* rowstart, int32_t R, int32_t L, int32_t top_k, float* token_log_prob,
+                                      int32_t* rank, int32_t* best, float* log_prob, int32_t* tokens, float* loss_sum,
+                                      float* count, float* top1_hits, float* topk_hits, void* stream) {
+    using namespace ick;
+    ICK_CHECK_ARG(rowstart && token_log_prob && rank && best && log_prob && tokens && loss_sum && count && top1_hits &&
+                  topk_hits);
+    ICK_CHECK_ARG(R > 0 && L > 1 && top_k >= 1 && (int64_t)R * L <= INT32_MAX);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(caption_sums_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, s, rowstart, R, L, token_log_prob, rank,
+                       best, log_prob, tokens);
+    hipLaunchKernelGGL(caption_totals_kernel, dim3(1), dim3(256), 0, s, token_log_prob, rank, (int64_t)R * (L - 1), top_k,
+                       loss_sum, count, top1_hits, topk_hits);
     ICK_LAUNCH_RET();
 }
 

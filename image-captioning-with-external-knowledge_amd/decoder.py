@@ -12,9 +12,11 @@ checkpoints (geo-aware/utils.py:32-49) unpickle into these classes and state_dic
 torch.nn modules are used ONLY as parameter containers; every forward computation below runs
 in libick_amd.so (HIP, gfx950) through ops.py.  There is no CPU / PyTorch fallback.
 """
+import dataclasses
 import math
 import os
 import struct
+import weakref
 
 import torch
 from torch import nn
@@ -203,6 +205,68 @@ def check_force(what, B, Vx, special, force_tokens=None, num_beam_groups=1):
     return out
 
 
+def check_score_args(what, has_facts, captions, encoder_out, caption_masks, caption_lengths, entities, facts=None,
+                     image_index=None, top_k=5):
+    """Validate the arguments of score_captions (IckError); shapes only, so it runs on tensors of any device.  Returns
+    (R, L, n_img): captions, caption length, image rows."""
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1:
+        raise IckError("%s needs an integer top_k >= 1" % what)
+    if captions.dim() != 2 or captions.shape[0] < 1 or captions.shape[1] < 2:
+        raise IckError("%s needs captions (R, L) with R >= 1 and L >= 2, got %s" % (what, tuple(captions.shape)))
+    R, Lc = captions.shape
+    if tuple(caption_masks.shape) != (R, Lc):
+        raise IckError("%s: caption_masks must have the captions' shape (%d, %d), got %s"
+                       % (what, R, Lc, tuple(caption_masks.shape)))
+    if caption_lengths.numel() != R:
+        raise IckError("%s: caption_lengths must hold %d lengths, got %s" % (what, R, tuple(caption_lengths.shape)))
+    if encoder_out.dim() not in (3, 4):
+        raise IckError("%s needs a token-major encoder_out (B, d, P) or a 4-D feature map" % what)
+    n_img = encoder_out.shape[0]
+    if entities.dim() != 3 or entities.shape[0] != n_img:
+        raise IckError("%s: entities must be (%d, K, features), got %s" % (what, n_img, tuple(entities.shape)))
+    if has_facts and (facts is None or facts.dim() != 3 or facts.shape[0] != n_img or facts.shape[2] != 3):
+        raise IckError("%s: facts must be (%d, F, 3)" % (what, n_img))
+    if image_index is None:
+        if n_img != R:
+            raise IckError("%s: %d captions over %d image rows need image_index" % (what, R, n_img))
+    else:
+        if encoder_out.dim() == 4:
+            raise IckError("image_index needs a token-major encoder_out (B, d, P), not a 4-D feature map")
+        if not torch.is_tensor(image_index) or image_index.dtype not in (torch.int32, torch.int64) or \
+                tuple(image_index.shape) != (R,):
+            raise IckError("image_index must be an integer tensor of shape (%d,)" % R)
+    return R, Lc, n_img
+
+
+@dataclasses.dataclass
+class CaptionScores:
+    """score_captions' result, device tensors in the caller's caption order: log_prob (R,) = sum of the caption's token
+    log-probabilities, tokens (R,) int32 = how many were scored, token_log_probs / rank / best (R, L-1) per position
+    (0 / -1 / -1 past the caption; rank 0 = the target is the argmax, best = the argmax column), and the totals over all
+    captions loss_sum (= -sum of log-probabilities), count, top1_hits, topk_hits, (1,) float32 each."""
+    log_prob: torch.Tensor
+    tokens: torch.Tensor
+    token_log_probs: torch.Tensor
+    rank: torch.Tensor
+    best: torch.Tensor
+    loss_sum: torch.Tensor
+    count: torch.Tensor
+    top1_hits: torch.Tensor
+    topk_hits: torch.Tensor
+
+
+def _caption_scores(flat, R, T):
+    """CaptionScores as views of one flat float32 buffer of 3 * R * T + 2 * R + 4 words (one allocation, one copy out of
+    a graph's static result)."""
+    n = R * T
+    i32 = flat.view(torch.int32)
+    return CaptionScores(log_prob=flat[3 * n:3 * n + R], tokens=i32[3 * n + R:3 * n + 2 * R],
+                         token_log_probs=flat[:n].view(R, T), rank=i32[n:2 * n].view(R, T),
+                         best=i32[2 * n:3 * n].view(R, T), loss_sum=flat[3 * n + 2 * R:][0:1],
+                         count=flat[3 * n + 2 * R:][1:2], top1_hits=flat[3 * n + 2 * R:][2:3],
+                         topk_hits=flat[3 * n + 2 * R:][3:4])
+
+
 def rules_tensor(max_len, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0, device="cuda"):
     """The device input of the rules (lib.DecodeRules): int32 (4 + max_len + 1) = the rule words
     {no_repeat_ngram_size, min_len, length penalty on, 0} followed by the fp32 bits of length_penalty_table()."""
@@ -271,7 +335,8 @@ class CaptionEmbedder(nn.Module):
 # never part of a pickle (checkpoints pickle whole modules, geo-aware/utils.py:32-46) or of a deep copy -- they are rebuilt
 # on first use.
 _CACHE_KEYS = ("_graphs", "_kv_pack", "_pred_wt_cache", "_len_pin", "_idx_pin", "_plist", "_pin_ev", "_dec_pack",
-               "_chain_cache", "_chain_cache_bwd", "_chain_ok", "_chain_bwd_ok", "_ps_cache", "_last_static", "_enc")
+               "_chain_cache", "_chain_cache_bwd", "_chain_ok", "_chain_bwd_ok", "_ps_cache", "_last_static", "_enc",
+               "_score_gmap_checked")
 
 
 def _state_without_caches(module):
@@ -966,8 +1031,9 @@ class DecoderTransformer(nn.Module):
         return encoder_out.to(dev), entities, facts
 
     # ------------------------------------------------------------------ forward (teacher forced)
-    def _forward_device(self, captions, caption_masks, entities, facts, enc_tok, gmap, stages=None):
-        """Device-only part of forward() on length-sorted inputs (no host synchronisation inside)."""
+    def _forward_device(self, captions, caption_masks, entities, facts, enc_tok, gmap, stages=None, head=None):
+        """Device-only part of forward() on length-sorted inputs (no host synchronisation inside).  head: callable
+        (h, ee, fe, eib, hv) -> result that takes the place of the dense score head (score_captions)."""
         d, V = self.emb_dim, self.vocab_size
         K = entities.shape[1]
         ops.stamp("forward: start")
@@ -997,6 +1063,8 @@ class DecoderTransformer(nn.Module):
             eib, gate = ops.context_indicators(captions, facts, K, V, self._pred_wt(),
                                                self.fc_predicate.bias.detach(), mode=0)
             hv = ops.mul(x, gate)
+        if head is not None:
+            return head(x, ee, fe, eib, hv)
         scores = torch.empty(B, T, V + K + (0 if fe is None else fe.shape[1]), device=x.device, dtype=torch.float32)
         self._score_head(x, ee, fe, eib, hv, scores, self._vocab_presplit(B * T))
         ops.stamp("forward: scores done")
@@ -1015,11 +1083,12 @@ class DecoderTransformer(nn.Module):
                 enc.__dict__.get("_param_epoch", 0))
 
     def input_buffers(self):
-        """The static input tensors of the graph the last forward() / predict() / predict_beam() call replayed (None
-        before the first graphed call), in that call's order -- forward: [captions, caption_masks, entities, facts,
-        image input]; predict*: [image input, entities, facts].  A loader that copies the next batch straight into them
-        and passes them back in saves the device-to-device input copy of every call (the feature map is 103 MB at
-        B = 64)."""
+        """The static input tensors of the graph the last forward() / predict() / predict_beam() / score_captions() call
+        replayed (None before the first graphed call), in that call's order -- forward: [captions, caption_masks,
+        entities, facts, image input]; predict*: [image input, entities, facts]; score_captions: [captions,
+        caption_masks, lengths, entities, facts, image input, image_index].  A loader that copies the next batch
+        straight into them and passes them back in saves the device-to-device input copy of every call (the feature map
+        is 103 MB at B = 64)."""
         return self.__dict__.get("_last_static")
 
     def _graphed(self, kind, key, fn, inputs):
@@ -1107,6 +1176,100 @@ class DecoderTransformer(nn.Module):
             return scores, captions, decode_lengths
         return self._forward_device(captions, caption_masks, entities, facts, enc_tok, gmap, stages), captions, \
             decode_lengths
+
+    # ------------------------------------------------------------------ scoring of given captions
+    def _score_device(self, captions, caption_masks, lengths, entities, facts, enc_tok, gmap, top_k):
+        """Device-only part of score_captions, in the caller's order: forward()'s layers, then the packed score head over
+        the valid rows (ops.HeadRows from the device lengths) and the two reduction launches.  -> the flat result buffer of
+        _caption_scores.  gmap (R,) int32: caption r reads image / entity / fact row gmap[r] (gathered copies)."""
+        if gmap is not None:
+            idx = gmap.long()
+            enc_tok, entities = enc_tok.index_select(0, idx), entities.index_select(0, idx)
+            facts = None if facts is None else facts.index_select(0, idx)
+        R, Lc = captions.shape
+        V, K = self.vocab_size, entities.shape[1]
+
+        def head(x, ee, fe, eib, hv):
+            pack = ops.HeadRows(lengths, R, Lc)
+            Vx = V + K + (0 if fe is None else fe.shape[1])
+            ld = (Vx + 3) // 4 * 4          # 16-byte aligned rows for the reduction's float4 loads
+            scores = torch.empty(R, Lc, ld, device=x.device, dtype=torch.float32)[:, :, :Vx]
+            self._score_head(x, ee, fe, eib, hv, scores, self._vocab_presplit(R * Lc), pack=pack)
+            ops.stamp("score: packed scores done")
+            T = Lc - 1
+            flat = torch.empty(3 * R * T + 2 * R + 4, device=x.device, dtype=torch.float32)
+            v = _caption_scores(flat, R, T)
+            ops.row_logprob_rank(scores, captions, pack, self.word_map["<pad>"], out=(v.token_log_probs, v.rank, v.best))
+            ops.caption_score_sums(pack, v.token_log_probs, v.rank, v.best, top_k,
+                                   out=(v.log_prob, v.tokens, flat[3 * R * T + 2 * R:]))
+            return flat
+
+        return self._forward_device(captions, caption_masks, entities, facts, enc_tok, None, head=head)
+
+    @torch.no_grad()
+    def score_captions(self, captions, encoder_out, caption_masks, caption_lengths, entities, facts=None,
+                       image_index=None, top_k=5):
+        """How likely the GIVEN captions are (teacher forced, forward()'s argument order) -> CaptionScores, in the caller's
+        caption order: per caption the summed log-probability and token count, per position the target's
+        log-probability, its rank among the V+K[+F] columns (0 = argmax) and the argmax column, and the batch totals a
+        validation loop accumulates (loss_sum, count, top1_hits, topk_hits with rank < top_k).
+        Runs without dropout and without gradients whatever the module's mode.  No length sort and no host
+        synchronisation: the lengths stay on the device, the score head runs over the valid positions only
+        (ops.HeadRows) and each packed score row is read once (ick_row_logprob_rank); the (R, L, V+K+F) score matrix is
+        never returned.  image_index (R,) int: caption r reads row image_index[r] of a token-major encoder_out, of
+        entities and of facts (several captions of one image; as TrainStep's image_index).  With use_hip_graphs the call
+        replays a captured graph per input shape (kind "score"); the result tensors are the caller's own."""
+        R, Lc, n_img = check_score_args("score_captions", self.has_facts, captions, encoder_out, caption_masks,
+                                        caption_lengths, entities, facts, image_index, top_k)
+        if image_index is not None:
+            # range check as TrainStep's: skipped for the very tensor object validated last time, unmodified
+            ok = self.__dict__.get("_score_gmap_checked")
+            if ok is None or ok[0]() is not image_index or ok[1:] != (image_index._version, n_img):
+                lo, hi = (int(v) for v in torch.aminmax(image_index.reshape(-1)))
+                if lo < 0 or hi >= n_img:
+                    raise IckError("image_index values must lie in [0, %d), got [%d, %d]" % (n_img, lo, hi))
+                self.__dict__["_score_gmap_checked"] = (weakref.ref(image_index), image_index._version, n_img)
+        return self._score_captions(captions, encoder_out, caption_masks, caption_lengths, entities, facts, image_index,
+                                    top_k)
+
+    def _score_captions(self, captions, encoder_out, caption_masks, caption_lengths, entities, facts, image_index, top_k):
+        """score_captions behind its argument checks (image_index is known to be in range)."""
+        R, Lc = captions.shape
+        encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
+        dev = encoder_out.device
+        gmap = None if image_index is None else image_index.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
+        captions = captions.to(dev, torch.int64, non_blocking=True).contiguous()
+        caption_masks = caption_masks.to(dev, torch.int64, non_blocking=True).contiguous()
+        lengths = caption_lengths.detach().reshape(-1).to(dev, torch.int64, non_blocking=True).contiguous()
+        enc_tok, _ = self._image_input(encoder_out)
+        inputs = [captions, caption_masks, lengths, entities, facts, enc_tok, gmap]
+        fn = lambda c, m, l, e, f, t, g: self._score_device(c, m, l, e, f, t, g, top_k)     # noqa: E731
+        if self.use_hip_graphs:
+            key = tuple(None if t is None else tuple(t.shape) for t in inputs) + (top_k,) + self._enc_key(enc_tok)
+            flat = self._graphed("score", key, fn, inputs).clone()      # the graph's static result stays the graph's
+        else:
+            flat = fn(*inputs)
+        return _caption_scores(flat, R, Lc - 1)
+
+    @torch.no_grad()
+    def score_tokens(self, tokens, encoder_out, entities, facts=None, samples_per_image=1, top_k=5):
+        """score_captions of decode output: tokens (max_len, R) int64 as predict / predict_beam / predict_sample return
+        them, column b * n + j belonging to image b (n = samples_per_image).  The rows become teacher-forcing captions
+        [<start>, w_1 .. <end>, <pad> ..] on the device (ops.samples_to_captions); position t of the result scores w_{t+1}."""
+        n = samples_per_image
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise IckError("score_tokens needs an integer samples_per_image >= 1")
+        if not torch.is_tensor(tokens) or tokens.dim() != 2 or tokens.shape[1] != encoder_out.shape[0] * n:
+            raise IckError("score_tokens needs tokens (max_len, %d images x %d), got %s"
+                           % (encoder_out.shape[0], n, tuple(tokens.shape) if torch.is_tensor(tokens) else type(tokens)))
+        dev = self.fc_vocab.weight.device
+        rows = tokens.to(dev, torch.int64).t().contiguous()
+        wm = self.word_map
+        caps, masks, lengths = ops.samples_to_captions(rows, self.vocab_size, entities.shape[1], self.has_facts,
+                                                       wm["<start>"], wm["<end>"], wm["<pad>"])
+        index = torch.arange(rows.shape[0], device=dev, dtype=torch.int32) // n if n > 1 else None
+        check_score_args("score_tokens", self.has_facts, caps, encoder_out, masks, lengths, entities, facts, index, top_k)
+        return self._score_captions(caps, encoder_out, masks, lengths, entities, facts, index, top_k)
 
     # ------------------------------------------------------------------ greedy decode (KV cached)
     def _decode_pack(self):

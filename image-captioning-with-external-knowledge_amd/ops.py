@@ -776,6 +776,46 @@ def packed_ce_rows(scores, captions, pack, pad_token, weights=None, want_grad=Fa
     return loss_sum, count, dscores
 
 
+def row_logprob_rank(scores, captions, pack, pad_token, out=None):
+    """Per-token log-probability, rank and argmax of the PACKED score rows (scores (R, L, Vx) as _score_head(pack=) writes
+    them; ick_row_logprob_rank) -> (token_log_probs f32, rank i32, best i32), each (R, L - 1) in LOGICAL order.  Only the
+    elements of the pack's rows are written: caption_score_sums defines the rest.  out: the three tensors to write."""
+    R, Lc, Vx = scores.shape
+    dev = scores.device
+    if captions.dtype != torch.int64 or not captions.is_contiguous() or tuple(captions.shape) != (R, Lc):
+        raise L.IckError("row_logprob_rank needs contiguous int64 captions (%d, %d)" % (R, Lc))
+    assert scores.stride(0) == Lc * scores.stride(1) and scores.stride(2) == 1 and pack.rowmap.numel() == R * Lc
+    if out is None:
+        out = (torch.empty(R, Lc - 1, device=dev, dtype=torch.float32),
+               torch.empty(R, Lc - 1, device=dev, dtype=torch.int32),
+               torch.empty(R, Lc - 1, device=dev, dtype=torch.int32))
+    tlp, rank, best = out
+    assert all(t.shape == (R, Lc - 1) and t.is_contiguous() for t in out)
+    assert tlp.dtype == torch.float32 and rank.dtype == torch.int32 and best.dtype == torch.int32
+    L.check(L.load().ick_row_logprob_rank(_p(scores), scores.stride(1), _p(captions), _p(pack.rowmap), _p(pack.count), R,
+                                          Lc, Vx, pad_token, _p(tlp), _p(rank), _p(best), _stream()),
+            "ick_row_logprob_rank")
+    return tlp, rank, best
+
+
+def caption_score_sums(pack, tlp, rank, best, top_k=5, out=None):
+    """After row_logprob_rank: fills the positions past every caption, -> (log_prob (R,) f32, tokens (R,) i32, loss_sum,
+    count, top1_hits, topk_hits (1,) f32 each) (ick_caption_score_sums).  out: (log_prob, tokens, totals (4,) f32)."""
+    R, T = tlp.shape
+    dev = tlp.device
+    if out is None:
+        out = (torch.empty(R, device=dev, dtype=torch.float32), torch.empty(R, device=dev, dtype=torch.int32),
+               torch.empty(4, device=dev, dtype=torch.float32))
+    log_prob, tokens, totals = out
+    assert log_prob.shape == tokens.shape == (R,) and totals.shape == (4,) and totals.is_contiguous()
+    assert log_prob.dtype == totals.dtype == torch.float32 and tokens.dtype == torch.int32
+    assert pack.rowstart.numel() == R + 1 and tlp.is_contiguous() and rank.is_contiguous() and best.is_contiguous()
+    L.check(L.load().ick_caption_score_sums(_p(pack.rowstart), R, T + 1, int(top_k), _p(tlp), _p(rank), _p(best),
+                                            _p(log_prob), _p(tokens), _p(totals[0:1]), _p(totals[1:2]), _p(totals[2:3]),
+                                            _p(totals[3:4]), _stream()), "ick_caption_score_sums")
+    return log_prob, tokens, totals[0:1], totals[1:2], totals[2:3], totals[3:4]
+
+
 def packed_ce(scores, captions_sorted, decode_len, pad_token, want_grad=False, out_sum=None, out_count=None):
     """Returns (loss_sum (1,), count (1,), dscores or None): token-mean loss = loss_sum / count.  out_sum / out_count:
     one-element float tensors to receive the two scalars (the tail of TrainStep's gradient bucket)."""

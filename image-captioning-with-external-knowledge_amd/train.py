@@ -16,6 +16,7 @@ captions), the batch's own captions as the references (one per image in this dat
 cross-entropy step.  It uses the plain fused loop, not the prefetch pipeline; validation (the cross-entropy loss) and
 checkpointing are unchanged."""
 import json
+import math
 import os
 import time
 from dataclasses import dataclass
@@ -70,6 +71,8 @@ class Config:
     scst: bool = False                                 # self-critical fine-tuning with a device CIDEr-D reward
     scst_samples: int = 5                              # sampled captions per image
     scst_baseline: str = "greedy"                      # "greedy" | "mean" (leave-one-out)
+    val_token_metrics: bool = False                    # validate() through decoder.score_captions: also perplexity and
+                                                       # top-1 / top-5 token accuracy (STATS["val_perplexity"], ...)
 
 
 def _batch_to_device(batch, device, has_facts):
@@ -336,6 +339,8 @@ def validate(loader, encoder, decoder, criterion, cfg, device):
     same best-checkpoint / lr-decay / early-stop decisions."""
     decoder.eval()
     encoder.eval()
+    if cfg.val_token_metrics:
+        return _validate_token_metrics(loader, encoder, decoder, cfg, device)
     losses = ut.AverageMeter()
     has_facts = decoder.has_facts
     with torch.no_grad():
@@ -348,6 +353,29 @@ def validate(loader, encoder, decoder, criterion, cfg, device):
                 break
     total, count = dp.reduce_sum_count(losses.sum, losses.count, device=device)
     return total / max(count, 1.0)
+
+
+def _validate_token_metrics(loader, encoder, decoder, cfg, device):
+    """validate() with Config.val_token_metrics: every batch goes through decoder.score_captions (the score head over the
+    valid positions only, no (B, L, V+K+F) matrix, no per-batch .item()); the four totals are accumulated on the device
+    and read once at the end.  Same token-weighted loss; also prints and records perplexity and top-1 / top-5 accuracy."""
+    acc = torch.zeros(4, device=device, dtype=torch.float64)
+    with torch.no_grad():
+        for i, batch in enumerate(loader):
+            imgs, caps, caplens, capmasks, ent, facts = _batch_to_device(batch, device, decoder.has_facts)
+            s = decoder.score_captions(caps, encoder(imgs), capmasks, caplens, ent, facts, top_k=5)
+            acc += torch.cat([s.loss_sum, s.count, s.top1_hits, s.topk_hits]).double()
+            if cfg.max_batches and i + 1 >= cfg.max_batches:
+                break
+    loss_sum, count, top1, top5 = acc.tolist()                  # the one synchronisation
+    total, count = dp.reduce_sum_count(loss_sum, count, device=device)
+    top1, top5 = dp.reduce_sum_count(top1, top5, device=device)
+    loss = total / max(count, 1.0)
+    STATS["val_perplexity"] = math.exp(loss) if loss < 700.0 else float("inf")
+    STATS["val_top1"], STATS["val_top5"] = top1 / max(count, 1.0), top5 / max(count, 1.0)
+    print("Validation: perplexity %.3f\ttop-1 accuracy %.4f\ttop-5 accuracy %.4f (%d tokens)"
+          % (STATS["val_perplexity"], STATS["val_top1"], STATS["val_top5"], int(count)))
+    return loss
 
 
 class ShardSampler(torch.utils.data.Sampler):

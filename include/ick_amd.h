@@ -737,6 +737,27 @@ int ick_pointer_scores_bwd_packed(const float* ds, int64_t ds_ld, int32_t col0, 
 int ick_gather_rows(const float* src, int64_t src_rs, const int32_t* rowmap, const int32_t* count, float* dst,
                     int64_t dst_rs, int32_t max_rows, int32_t d, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Caption scoring: how likely a GIVEN caption is, from the packed score rows of the head above.
+ *
+ * ick_row_logprob_rank: one read of packed score row m < *count (position (b, t) = (rowmap[m] / L, rowmap[m] % L), target
+ *   c* = captions[b, t + 1]) gives, at the LOGICAL element (b, t) of the (R, L - 1) outputs,
+ *     token_log_prob = s[c*] - logsumexp(s),
+ *     rank = #{c : s[c] > s[c*], or s[c] == s[c*] and c < c*}  (the target's place in a stable descending sort: 0 = argmax),
+ *     best = the lowest column that holds the row's maximum.
+ *   A target that is <pad> or outside [0, Vx) gives 0 / -1 / -1.  Elements of positions that are no packed row are not
+ *   written here.  Vx <= 2^24, L >= 2, R <= 65535.
+ * ick_caption_score_sums, after it: fills every element past a caption's valid rows (t >= rowstart[r + 1] - rowstart[r])
+ *   with 0 / -1 / -1, log_prob[r] = the caption's token log-probabilities summed in position order, tokens[r] = how many
+ *   were scored, and the totals over all captions in a fixed order (bit-identical from run to run): loss_sum = -sum of
+ *   log-probabilities, count, top1_hits (rank == 0), topk_hits (rank < top_k), one float each. */
+int ick_row_logprob_rank(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                         const int32_t* count, int32_t R, int32_t L, int32_t Vx, int32_t pad_token, float* token_log_prob,
+                         int32_t* rank, int32_t* best, void* stream);
+int ick_caption_score_sums(const int32_t* rowstart, int32_t R, int32_t L, int32_t top_k, float* token_log_prob,
+                           int32_t* rank, int32_t* best, float* log_prob, int32_t* tokens, float* loss_sum, float* count,
+                           float* top1_hits, float* topk_hits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
