@@ -209,13 +209,22 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restr
 // kPacked (ick_packed_ce_packed): scores / row_loss / dscores hold the PACKED rows of the valid positions; workgroup m takes
 // packed row m, which belongs to position rowmap[m] = b * L + t (valid by construction: t < min(length - 1, L - 1)); dl is
 // the device row count, and workgroups at or past it exit without writing anything.
-template <bool kWeighted, bool kPacked = false>
+// kSmooth (ick_packed_ce_smooth): label smoothing with eps = eps_arg.word[0], a device word, uniform
+// per launch -- row_loss = (1 - eps) * (lse - x[target]) + eps * (lse - mean(x)) and the gradient is
+// w * (softmax - (1 - eps) * onehot - eps / Vx).  The row's sum is gathered in the pass that reads the row anyway.  The
+// terms are written so that eps == 0 leaves the plain kernels' bits: the uniform term enters as + w * (0 - eps / Vx) (a
+// zero of w's sign, which also keeps the sign of a gradient that underflowed to zero), the target's as - w * (1 - eps).
+template <bool kSmooth>
+struct CeEps { const float* word; };          // the device word holding eps
+template <>
+struct CeEps<false> {};                       // the plain kernels take no such argument
+template <bool kWeighted, bool kPacked = false, bool kSmooth = false>
 __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __restrict__ scores, int64_t ld,
                                                              const int64_t* __restrict__ caps,
                                                              const int32_t* __restrict__ dl, int L, int Vx, int pad,
                                                              float* __restrict__ row_loss, float* __restrict__ dscores,
                                                              const float* __restrict__ weight,
-                                                             const int32_t* __restrict__ rowmap) {
+                                                             const int32_t* __restrict__ rowmap, CeEps<kSmooth> eps_arg) {
     __shared__ float red[4];
     int t = blockIdx.x, b = blockIdx.y;
     const int tid = threadIdx.x;
@@ -246,6 +255,12 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
         }
         return;
     }
+    float eps = 0.f, keep = 1.f, nsub = 0.f, rs = 0.f;      // kSmooth: eps, 1 - eps, 0 - eps / Vx, the row's sum
+    if constexpr (kSmooth) {
+        eps = eps_arg.word[0];                              // uniform
+        keep = 1.f - eps;
+        nsub = 0.f - eps / (float)Vx;
+    }
     // Rows of up to 256 * 4 * kCeVec floats (16-byte aligned) stay in registers between the passes: one read
     // of the logits and one write of the gradient instead of three reads; longer / unaligned rows re-read.
     constexpr int kCeVec = 10;
@@ -262,8 +277,12 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
             const int i = tid + 256 * j;
             x[j] = i < n4 ? r4[i] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
             m = fmaxf(m, fmaxf(fmaxf(x[j].x, x[j].y), fmaxf(x[j].z, x[j].w)));
+            if constexpr (kSmooth) {
+                if (i < n4) rs += (x[j].x + x[j].y) + (x[j].z + x[j].w);
+            }
         }
         m = block_max<4>(m, red);
+        if constexpr (kSmooth) rs = block_sum<4>(rs, red);
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < kCeVec; ++j) {
@@ -272,10 +291,18 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
             s += (x[j].x + x[j].y) + (x[j].z + x[j].w);
         }
         s = block_sum<4>(s, red);
-        if (tid == 0) row_loss[row] = m + __logf(s) - r[target];
+        if (tid == 0) {
+            if constexpr (kSmooth) {
+                const float lse = m + __logf(s);
+                row_loss[row] = keep * (lse - r[target]) + eps * (lse - rs / (float)Vx);
+            } else {
+                row_loss[row] = m + __logf(s) - r[target];
+            }
+        }
         if (dr) {
             const float wr = kWeighted ? weight[b] : 1.f;
             const float inv = wr / s;
+            const float wt = kSmooth ? wr * keep : wr, wu = wr * nsub;
             float4* d4 = reinterpret_cast<float4*>(dr);
             const int tq = (int)(target >> 2), tr = (int)(target & 3);
 #pragma unroll
@@ -283,8 +310,9 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
                 const int i = tid + 256 * j;
                 if (i < n4) {
                     float4 g = make_float4(x[j].x * inv, x[j].y * inv, x[j].z * inv, x[j].w * inv);
+                    if constexpr (kSmooth) { g.x += wu; g.y += wu; g.z += wu; g.w += wu; }
                     if (i == tq) {
-                        if (tr == 0) g.x -= wr; else if (tr == 1) g.y -= wr; else if (tr == 2) g.z -= wr; else g.w -= wr;
+                        if (tr == 0) g.x -= wt; else if (tr == 1) g.y -= wt; else if (tr == 2) g.z -= wt; else g.w -= wt;
                     }
                     d4[i] = g;
                 }
@@ -308,6 +336,9 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
         for (int j = 0; j < 4; ++j) {
             const int i = i0 + tid + 256 * j;
             x[j] = i < n4 ? r4[i] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+            if constexpr (kSmooth) {
+                if (i < n4) rs += (x[j].x + x[j].y) + (x[j].z + x[j].w);
+            }
         }
         float bm = m;
 #pragma unroll
@@ -326,6 +357,9 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
         for (int j = 0; j < 8; ++j) {
             const int i = i0 + tid + 256 * j;
             x[j] = i < Vx ? r[i] : -INFINITY;
+            if constexpr (kSmooth) {
+                if (i < Vx) rs += x[j];
+            }
         }
         float bm = m;
 #pragma unroll
@@ -341,10 +375,16 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
     m = block_max<4>(m, red);
     s = block_sum<4>(mt > -INFINITY ? s * __expf(mt - m) : 0.f, red);
     const float lse = m + __logf(s);
-    if (tid == 0) row_loss[row] = lse - r[target];
+    if constexpr (kSmooth) {
+        rs = block_sum<4>(rs, red);
+        if (tid == 0) row_loss[row] = keep * (lse - r[target]) + eps * (lse - rs / (float)Vx);
+    } else {
+        if (tid == 0) row_loss[row] = lse - r[target];
+    }
     if (dr) {
         const float wr = kWeighted ? weight[b] : 1.f;
         const float inv = wr / s;
+        const float wt = kSmooth ? wr * keep : wr, wu = wr * nsub;
         float4* d4 = reinterpret_cast<float4*>(dr);
         const int tq = (int)(target >> 2), tr = (int)(target & 3);
         for (int i0 = 0; i0 < n4; i0 += 256 * 4) {
@@ -360,8 +400,9 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
                 if (i < n4) {
                     float4 gq = make_float4(__expf(x[j].x - m) * inv, __expf(x[j].y - m) * inv, __expf(x[j].z - m) * inv,
                                             __expf(x[j].w - m) * inv);
+                    if constexpr (kSmooth) { gq.x += wu; gq.y += wu; gq.z += wu; gq.w += wu; }
                     if (i == tq) {
-                        if (tr == 0) gq.x -= wr; else if (tr == 1) gq.y -= wr; else if (tr == 2) gq.z -= wr; else gq.w -= wr;
+                        if (tr == 0) gq.x -= wt; else if (tr == 1) gq.y -= wt; else if (tr == 2) gq.z -= wt; else gq.w -= wt;
                     }
                     d4[i] = gq;
                 }
@@ -377,7 +418,10 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int i = i0 + tid + 256 * j;
-                if (i < Vx) dr[i] = __expf(x[j] - m) * inv - (i == target ? wr : 0.f);
+                if (i < Vx) {
+                    if constexpr (kSmooth) dr[i] = (__expf(x[j] - m) * inv + wu) - (i == target ? wt : 0.f);
+                    else dr[i] = __expf(x[j] - m) * inv - (i == target ? wr : 0.f);
+                }
             }
         }
     }
@@ -714,7 +758,7 @@ extern "C" int ick_packed_ce(const float* scores, int64_t ld, const int64_t* cap
     ICK_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Vx > 0 && ld >= Vx);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(packed_ce_rows_kernel<false>, dim3(L, B), dim3(256), 0, s, scores, ld, captions_sorted, decode_len,
-                       L, Vx, pad_token, row_loss, dscores, nullptr, nullptr);
+                       L, Vx, pad_token, row_loss, dscores, nullptr, nullptr, CeEps<false>{});
     hipLaunchKernelGGL(packed_ce_reduce_kernel<false>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, nullptr, loss_sum,
                        count, nullptr, nullptr);
     ICK_LAUNCH_RET();
@@ -730,15 +774,42 @@ extern "C" int ick_packed_ce_packed(const float* scores, int64_t ld, const int64
     hipStream_t s = (hipStream_t)stream;
     if (weights != nullptr) {
         hipLaunchKernelGGL((packed_ce_rows_kernel<true, true>), dim3(L, B), dim3(256), 0, s, scores, ld, captions, count, L,
-                           Vx, pad_token, row_loss, dscores, weights, rowmap);
+                           Vx, pad_token, row_loss, dscores, weights, rowmap, CeEps<false>{});
         hipLaunchKernelGGL(packed_ce_reduce_kernel<true>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, weights, loss_sum,
                            count_out, rowmap, count);
     } else {
         hipLaunchKernelGGL((packed_ce_rows_kernel<false, true>), dim3(L, B), dim3(256), 0, s, scores, ld, captions, count, L,
-                           Vx, pad_token, row_loss, dscores, nullptr, rowmap);
+                           Vx, pad_token, row_loss, dscores, nullptr, rowmap, CeEps<false>{});
         hipLaunchKernelGGL(packed_ce_reduce_kernel<false>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, nullptr, loss_sum,
                            count_out, rowmap, count);
     }
+    ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_packed_ce_smooth(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                                    const int32_t* count, const int32_t* decode_len, const float* weights,
+                                    const float* eps, int32_t B, int32_t L, int32_t Vx, int32_t pad_token,
+                                    float* row_loss, float* loss_sum, float* count_out, float* dscores, void* stream) {
+    using namespace ick;
+    ICK_CHECK_ARG(scores && captions && eps && row_loss && loss_sum && count_out);
+    ICK_CHECK_ARG((rowmap != nullptr) == (count != nullptr) && (rowmap != nullptr || decode_len != nullptr));
+    ICK_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Vx > 0 && ld >= Vx && (int64_t)B * L <= INT32_MAX);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(L, B), block(256);
+    const int32_t* dl = rowmap ? count : decode_len;
+#define ICK_CE_SMOOTH(W, P)                                                                                            \
+    hipLaunchKernelGGL((packed_ce_rows_kernel<W, P, true>), grid, block, 0, s, scores, ld, captions, dl, L, Vx,         \
+                       pad_token, row_loss, dscores, weights, rowmap, CeEps<true>{eps})
+    if (weights != nullptr) {
+        if (rowmap) { ICK_CE_SMOOTH(true, true); } else { ICK_CE_SMOOTH(true, false); }
+        hipLaunchKernelGGL(packed_ce_reduce_kernel<true>, dim3(1), block, 0, s, row_loss, B * L, L, weights, loss_sum,
+                           count_out, rowmap, count);
+    } else {
+        if (rowmap) { ICK_CE_SMOOTH(false, true); } else { ICK_CE_SMOOTH(false, false); }
+        hipLaunchKernelGGL(packed_ce_reduce_kernel<false>, dim3(1), block, 0, s, row_loss, B * L, L, nullptr, loss_sum,
+                           count_out, rowmap, count);
+    }
+#undef ICK_CE_SMOOTH
     ICK_LAUNCH_RET();
 }
 
@@ -777,7 +848,7 @@ extern "C" int ick_packed_ce_weighted(const float* scores, int64_t ld, const int
     ICK_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Vx > 0 && ld >= Vx && (int64_t)B * L <= INT32_MAX);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(packed_ce_rows_kernel<true>, dim3(L, B), dim3(256), 0, s, scores, ld, captions_sorted, decode_len,
-                       L, Vx, pad_token, row_loss, dscores, weights, nullptr);
+                       L, Vx, pad_token, row_loss, dscores, weights, nullptr, CeEps<false>{});
     hipLaunchKernelGGL(packed_ce_reduce_kernel<true>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, weights, loss_sum,
                        count, nullptr, nullptr);
     ICK_LAUNCH_RET();

@@ -236,6 +236,7 @@ SIGNATURES = {
     "ick_head_rowmap": [vp, i32, i32, vp, vp, vp, vp],
     "ick_pointer_scores_packed": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i32, vp, vp, vp],
     "ick_packed_ce_packed": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+    "ick_packed_ce_smooth": [vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "ick_pointer_scores_bwd_packed": [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],
     "ick_gather_rows": [vp, i64, vp, vp, vp, i64, i32, i32, vp],
     "ick_row_logprob_rank": [vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp],

@@ -857,6 +857,37 @@ def packed_ce_weighted(scores, captions_sorted, decode_len, weights, pad_token, 
     return loss_sum, count, dscores
 
 
+def packed_ce_smooth(scores, captions, decode_len_or_pack, pad_token, eps, weights=None, want_grad=False, out_sum=None,
+                     out_count=None):
+    """The packed cross entropy with label smoothing (ick_packed_ce_smooth; torch's CrossEntropyLoss(label_smoothing=)):
+    row loss (1 - eps) * (lse - x[t]) + eps * (lse - mean(x)), gradient w * (softmax - (1 - eps) * onehot - eps / Vx).
+    decode_len_or_pack: the int32 decode lengths (scores are the (B, L) rows, as packed_ce / packed_ce_weighted take them)
+    or a HeadRows (scores hold its packed rows, as packed_ce_rows takes them).  eps: a ONE-element float32 device tensor,
+    read by the kernel, so a captured launch follows the value written into it; 0.0 there gives the plain wrappers'
+    bits."""
+    B, Lc, Vx = scores.shape
+    dev = scores.device
+    if not isinstance(eps, torch.Tensor) or eps.numel() != 1 or eps.dtype != torch.float32 or not eps.is_cuda:
+        raise L.IckError("packed_ce_smooth needs eps as a one-element float32 tensor on the device")
+    if weights is not None and (weights.shape != (B,) or weights.dtype != torch.float32 or not weights.is_cuda or
+                                not weights.is_contiguous()):
+        raise L.IckError("packed_ce_smooth needs contiguous (B,) float32 weights on the device")
+    pack = decode_len_or_pack if isinstance(decode_len_or_pack, HeadRows) else None
+    row_loss = torch.empty(B * Lc, device=dev, dtype=torch.float32)
+    loss_sum = out_sum if out_sum is not None else torch.empty(1, device=dev, dtype=torch.float32)
+    count = out_count if out_count is not None else torch.empty(1, device=dev, dtype=torch.float32)
+    dscores = None
+    if pack is not None or want_grad:
+        assert scores.stride(0) == Lc * scores.stride(1) and scores.stride(2) == 1
+    if want_grad:
+        dscores = torch.empty(B, Lc, scores.stride(1), device=dev, dtype=torch.float32)[:, :, :Vx]
+    rowmap, rows, dl = (pack.rowmap, pack.count, None) if pack is not None else (None, None, decode_len_or_pack)
+    L.check(L.load().ick_packed_ce_smooth(_p(scores), scores.stride(1), _p(captions), _p(rowmap), _p(rows), _p(dl),
+                                          _p(weights), _p(eps), B, Lc, Vx, pad_token, _p(row_loss), _p(loss_sum),
+                                          _p(count), _p(dscores), _stream()), "ick_packed_ce_smooth")
+    return loss_sum, count, dscores
+
+
 def samples_to_captions(tokens, V, K, has_facts, start, end, pad, out=None):
     """Sampled rows tokens (R, T) int64 -> (captions (R, T+1), masks (R, T+1), lengths (R,)) int64 training rows
     (ick_samples_to_captions): [<start>, w_1 .. w_m, <end>, <pad> ..], length m + 2 (T + 1 without <end>); masks by

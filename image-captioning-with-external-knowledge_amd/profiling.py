@@ -123,6 +123,12 @@ def classify(name, args):
         B, Lc, Vx = args[6], args[7], args[8]
         return (("weighted " if args[5] else "") + "packed cross entropy (+ gradient)",
                 4.0 * B * Lc * Vx * (2 if args[13] else 1), "byte")
+    if name == "ick_packed_ce_smooth":
+        # the same bytes as its plain siblings: one read of the scores, one write of the gradient (packed rows: priced
+        # at all B * L, as above)
+        B, Lc, Vx = args[8], args[9], args[10]
+        return (("weighted " if args[6] else "") + "packed cross entropy, label smoothing (+ gradient)",
+                4.0 * B * Lc * Vx * (2 if args[15] else 1), "byte")
     if name == "ick_adam_clamp":
         return "clamp + Adam", 4.0 * args[4] * 7, "byte"
     if name == "ick_adam_clamp_derive":

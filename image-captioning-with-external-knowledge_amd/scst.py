@@ -47,7 +47,9 @@ class SelfCriticalStep:
     (samples, rewards, advantages, greedy, greedy_rewards) and the step never synchronises with the host.
     Advantages: "greedy" a_bj = r_bj - r_greedy_b; "mean" the leave-one-out mean a_bj = r_bj - (sum_k r_bk - r_bj)/(n-1).
     encoder_out: (B, d, P) encoder output, or the (B, 2048, 14, 14) feature map with an encoder attached to the decoder or
-    given to the TrainStep (Encoder.conv1 then runs once per step at B rows)."""
+    given to the TrainStep (Encoder.conv1 then runs once per step at B rows).
+    A TrainStep built with label_smoothing= composes as the weighted formula says: each sampled row's SMOOTHED loss and
+    gradient are multiplied by its caption's advantage (the count stays unweighted); nothing here changes."""
 
     def __init__(self, train_step, reward_fn, num_samples=5, baseline="greedy", max_len=20, temperature=1.0, top_k=0,
                  top_p=1.0, seed=0):

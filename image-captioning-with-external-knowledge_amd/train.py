@@ -54,6 +54,11 @@ class Config:
     encoder_lr: float = 1e-4                           # geo-aware/train.py:47
     fine_tune_encoder: bool = False                    # geo-aware/train.py:52; True trains conv1 (+ trunk blocks 2-4)
     grad_clip: float = 5.0
+    label_smoothing: float = 0.0                       # eps of the TRAINING loss, 0 <= eps < 1 (Szegedy et al. 2016; 0.1
+                                                       # is usual): fused, TrainStep(label_smoothing=); unfused, torch's
+                                                       # CrossEntropyLoss(label_smoothing=).  Validation stays the plain
+                                                       # negative log-likelihood on both paths (val_token_metrics too), so
+                                                       # early stopping and perplexity compare across values of eps
     print_freq: int = 100
     checkpoint: str = ""
     zero_out_epochs_since_improvement: bool = False
@@ -219,6 +224,13 @@ class Prefetcher:
                 t.record_stream(cur)
         self._load()
         return tensors, n_tok
+
+
+def make_criteria(pad_token, label_smoothing=0.0):
+    """(training criterion, validation criterion) of the unfused path: the training loss carries Config.label_smoothing,
+    validation is always the plain negative log-likelihood."""
+    return (nn.CrossEntropyLoss(ignore_index=pad_token, label_smoothing=float(label_smoothing)),
+            nn.CrossEntropyLoss(ignore_index=pad_token))
 
 
 def packed_loss(criterion, scores, caps_sorted, decode_lengths):
@@ -485,7 +497,7 @@ def main(cfg=None):
                          encoder=encoder if pipelined else None, deterministic=det,
                          # the pipelined loop lets step i's optimizer update run at the head of step i + 1's graph beside
                          # Encoder.conv1; _train_fused_pipelined() flushes the last one of an epoch
-                         lazy_update=bool(pipelined))
+                         lazy_update=bool(pipelined), label_smoothing=cfg.label_smoothing)
         if decoder_optimizer is not None:
             # resume: Adam moments, step count (bias correction + dropout stream position) and the decayed lr come
             # back from the pickled optimizer (ours or one written by the reference, geo-aware/utils.py:32-46)
@@ -496,7 +508,7 @@ def main(cfg=None):
         dp.broadcast_module_state([encoder, decoder], _bucket_range(step))
     elif decoder_optimizer is None:
         decoder_optimizer = torch.optim.Adam([p for p in decoder.parameters() if p.requires_grad], lr=cfg.decoder_lr)
-    criterion = nn.CrossEntropyLoss(ignore_index=word_map["<pad>"]).to(device)
+    criterion, val_criterion = (c.to(device) for c in make_criteria(word_map["<pad>"], cfg.label_smoothing))
     loaders, samplers, shuffle_gen = make_loaders(cfg, rank, world, fused)
     sc = None
     if cfg.scst:
@@ -526,7 +538,7 @@ def main(cfg=None):
         else:
             tr = train(loaders["TRAIN"], encoder, decoder, criterion, decoder_optimizer, step, epoch, cfg, device,
                        encoder_optimizer)
-        last_loss = validate(loaders["VAL"], encoder, decoder, criterion, cfg, device)   # identical on every rank
+        last_loss = validate(loaders["VAL"], encoder, decoder, val_criterion, cfg, device)   # identical on every rank
         is_best = last_loss < best_loss
         best_loss = min(last_loss, best_loss)
         epochs_since_improvement = 0 if is_best else epochs_since_improvement + 1

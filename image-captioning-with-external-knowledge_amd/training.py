@@ -816,8 +816,16 @@ class TrainStep:
     replays advance without re-capturing."""
 
     def __init__(self, decoder, lr=4e-4, grad_clip=5.0, betas=(0.9, 0.999), eps=1e-8, process_group=None, seed=0,
-                 use_graph=True, encoder=None, deterministic=None, lazy_update=False):
+                 use_graph=True, encoder=None, deterministic=None, lazy_update=False, label_smoothing=0.0):
         self.dec = decoder
+        # label_smoothing (0 <= eps < 1; DESIGN.md 3.1g): the loss of torch's CrossEntropyLoss(label_smoothing=eps), and
+        # the returned loss is that smoothed loss.  Exactly 0.0 launches the plain cross entropy; a non-zero value lives
+        # in a one-float device word the smoothed kernel reads, so set_label_smoothing() between two non-zero values
+        # replays the captured graphs.  With caption_weights (SelfCriticalStep) the row's smoothed loss and gradient are
+        # multiplied by the caption's weight, the count stays unweighted.  A hyper-parameter like grad_clip: not part of
+        # state_dict().
+        self.label_smoothing = self._check_smoothing(label_smoothing)
+        self._eps_word = None
         # lazy_update: the optimizer update of step i runs at the head of step i + 1's graph, on the side stream beside
         # Encoder.conv1 (see forward_with_tape's pre_side) instead of as a graph of its own at the end of step i, where
         # nothing overlaps its ~85 us of HBM streaming.  Between two calls the parameters then lag one update behind the
@@ -878,6 +886,8 @@ class TrainStep:
                 self.grads[id(p)] = self.flat_g[off:off + k].view(p.shape)
                 off += pad(k)
         self.params = params
+        if self.label_smoothing != 0.0:
+            self._eps_word = torch.full((1,), self.label_smoothing, device=dev, dtype=torch.float32)
         self._graphs = {}
         # the re-laid-out copies of the weights (packed row-chain images, cross K/V gather, bf16 planes) that the optimizer
         # kernel keeps current itself: built on the first call (DerivedWeights); ICK_ADAM_DERIVE=0 keeps the per-step
@@ -920,12 +930,35 @@ class TrainStep:
             return dict(enc_tok=None, feats=enc_in, conv1=(c1.weight.detach(), c1.bias.detach(), self.enc.conv1_presplit()))
         return dict(enc_tok=enc_in)
 
+    @staticmethod
+    def _check_smoothing(eps):
+        eps = float(eps)
+        if not 0.0 <= eps < 1.0:          # (NaN fails both compares)
+            raise IckError("label_smoothing must lie in [0, 1), got %r" % (eps,))
+        return eps
+
+    def set_label_smoothing(self, eps):
+        """A new label-smoothing value.  Between two non-zero values only the device word is written and the captured
+        graphs replay; moving between zero and non-zero changes the loss kernel, which is part of the graph key, so the
+        next step captures once for the new kind (graphs of the other kind are kept).  No flush(): eps shapes the
+        gradients of the steps to come, not a pending update."""
+        eps = self._check_smoothing(eps)
+        if eps != 0.0:
+            if self._eps_word is None:
+                self._eps_word = torch.empty(1, device=self.flat_p.device, dtype=torch.float32)
+            self._eps_word.fill_(eps)
+        self.label_smoothing = eps
+
     def _loss(self, scores, captions, decode_len, weights, pack=None):
         """Packed cross entropy into the tail of the gradient bucket (it was zeroed by the side tail; nothing else touches
         those two floats); with per-caption weights (SelfCriticalStep's advantages) the weighted form.  pack: the scores
-        are the packed rows of the valid positions, and so are the score gradients."""
+        are the packed rows of the valid positions, and so are the score gradients.  With label smoothing on, the
+        smoothed entry in the same layout."""
         tail = dict(want_grad=True, out_sum=self.flat_g[self.n:self.n + 1], out_count=self.flat_g[self.n + 1:])
         pad = self.dec.word_map["<pad>"]
+        if self.label_smoothing != 0.0:
+            return ops.packed_ce_smooth(scores, captions, pack if pack is not None else decode_len, pad, self._eps_word,
+                                        weights=weights, **tail)
         if pack is not None:
             return ops.packed_ce_rows(scores, captions, pack, pad, weights=weights, **tail)
         if weights is None:
@@ -1230,6 +1263,8 @@ class TrainStep:
                            % (ops.is_deterministic(), self.deterministic))
         # the large GEMM tiles' product mode is baked into a capture as well
         key = tuple(None if t is None else tuple(t.shape) for t in inputs) + (ops.gemm_split_mode(),)
+        if self.label_smoothing != 0.0:
+            key += ("label_smoothing",)     # another loss kernel; the value itself is read from the device word
         if not self._derived_tried:
             self._derived_tried = True
             if os.environ.get("ICK_ADAM_DERIVE", "1") != "0":

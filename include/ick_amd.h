@@ -725,6 +725,20 @@ int ick_pointer_scores_packed(const float* h, const float* ctx, const float* w, 
 int ick_packed_ce_packed(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
                          const int32_t* count, const float* weights, int32_t B, int32_t L, int32_t Vx, int32_t pad_token,
                          float* row_loss, float* loss_sum, float* count_out, float* dscores, void* stream);
+/* The packed cross entropy with label smoothing (Szegedy et al. 2016; torch's CrossEntropyLoss(label_smoothing=eps);
+ * DESIGN.md 3.1g).  For a contributing row with scores x[0 .. Vx), target t and lse = logsumexp(x):
+ *     loss = (1 - eps) * (lse - x[t]) + eps * (lse - mean(x)),
+ *     d loss / d x[c] = softmax(x)[c] - (1 - eps) * [c == t] - eps / Vx,
+ * every column of the row counting, pointer columns included.  Which rows contribute, loss_sum, count_out, weights (may
+ * be NULL) and the layout are those of the plain entries: with rowmap and count the scores are PACKED rows as in
+ * ick_packed_ce_packed (decode_len is not read); with both NULL they are the (B, L) rows of ick_packed_ce[_weighted] and
+ * decode_len is required.  eps: ONE float in device memory, 0 <= eps < 1, read by the kernel at run time -- a captured
+ * launch follows a new value written to the word.  NULL eps: ICK_EINVAL.  With 0.0 in the word every output has the bits
+ * of the plain entry of the same layout and weights. */
+int ick_packed_ce_smooth(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                         const int32_t* count, const int32_t* decode_len, const float* weights, const float* eps,
+                         int32_t B, int32_t L, int32_t Vx, int32_t pad_token, float* row_loss, float* loss_sum,
+                         float* count_out, float* dscores, void* stream);
 /* ick_pointer_scores_bwd reading PACKED score-gradient rows (sample b's rows are rowstart[b] .. rowstart[b + 1] - 1, in
  * position order); h, ind and dh keep their logical (B, T) rows; dh rows of padded positions are not touched. */
 int ick_pointer_scores_bwd_packed(const float* ds, int64_t ds_ld, int32_t col0, const float* h, const float* ctx,
