@@ -229,6 +229,35 @@ __device__ __forceinline__ void mark_bans(const Tok* hist, int t, int n, int m, 
     __syncthreads();
 }
 
+// What the host entry points of the rules variants ask of their arguments.  beam: beam search also reads the length
+// penalty table and the token counts, and bans <end> by its column.
+inline bool rules_ok(const ick_decode_ctx* c, const ick_decode_rules* rules, bool beam) {
+    if (!(c && rules && rules->words && ((uintptr_t)rules->words & 15) == 0 && c->max_len <= kRuleHistMax)) return false;
+    return !beam || (rules->lp && rules->len && c->end_token >= 0 && c->end_token < c->V);
+}
+
+// The next input token of a decode step: its kind (0 word, 1 entity, 2 fact: the caption mask CaptionEmbedder reads) and
+// the embedding row of caption b it stands for, out-of-range indices clamped (geo-aware/models.py:155-181).
+template <typename T>
+__device__ __forceinline__ int token_kind(T tok, int V, int K, bool has_facts) {
+    return (has_facts && tok >= V + K) ? 2 : (tok >= V ? 1 : 0);
+}
+template <typename T>
+__device__ __forceinline__ const float* token_row(T tok, int kind, int64_t b, const float* word_emb, const float* ee,
+                                                  const float* fe, int V, int K, int F, int d, int pad_token) {
+    if (kind == 1) {
+        T e = tok - V;
+        if (e < 0 || e >= K) e = K - 1;
+        return ee + (b * K + e) * d;
+    }
+    if (kind == 2 && fe != nullptr) {
+        T e = tok - V - K;
+        if (e < 0 || e >= F) e = F - 1;
+        return fe + (b * F + e) * d;
+    }
+    return word_emb + (int64_t)(tok >= 0 && tok < V ? tok : (T)pad_token) * d;
+}
+
 struct DropArg {
     float p;
     uint32_t seed, site;

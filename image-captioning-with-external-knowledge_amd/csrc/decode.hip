@@ -590,7 +590,7 @@ __device__ __forceinline__ void fused_select(const SelFuse& f, int64_t r0, int R
                 cur = second; rw1 = ph[0]; rw2 = ph[1]; rw3 = ph[2]; nrw = 3;
             }
             tok = cur;
-            msk = (f.has_facts && cur >= f.V + f.K) ? 2 : (cur >= f.V ? 1 : 0);
+            msk = token_kind(cur, f.V, f.K, f.has_facts);
         }
     }
     if (recorder && r0 + g < R && lane == 0) {
@@ -613,19 +613,8 @@ __device__ __forceinline__ void fused_select(const SelFuse& f, int64_t r0, int R
         so[8] = nfin;
     }
     // CaptionEmbedder + sqrt(d) scale + PositionEncoder of the token (geo-aware/models.py:155-181,355-357)
-    const int64_t b = row / f.rows_per_sample;
-    const float* src;
-    if (msk == 1) {
-        int e = tok - f.V;
-        if (e < 0 || e >= f.K) e = f.K - 1;
-        src = f.ee + (b * f.K + e) * d;
-    } else if (msk == 2 && f.fe != nullptr) {
-        int e = tok - f.V - f.K;
-        if (e < 0 || e >= f.F) e = f.F - 1;
-        src = f.fe + (b * f.F + e) * d;
-    } else {
-        src = f.word_emb + (int64_t)(tok >= 0 && tok < f.V ? tok : f.pad_token) * d;
-    }
+    const float* src = token_row(tok, msk, row / f.rows_per_sample, f.word_emb, f.ee, f.fe, f.V, f.K, f.F, d,
+                                 f.pad_token);
     const float* pe = f.pe + (int64_t)pos * d;
     const int d4 = d >> 2;
     const bool ok0 = lane < d4, ok1 = 64 + lane < d4;
@@ -1465,7 +1454,7 @@ __global__ __launch_bounds__(256) void dec_select_kernel(SelectArgs a) {
                 }
                 o[i] = cur;
                 tok = cur;
-                msk = (a.has_facts && cur >= a.V + a.K) ? 2 : (cur >= a.V ? 1 : 0);
+                msk = token_kind(cur, a.V, a.K, a.has_facts);
             }
         }
         a.next_token[r] = tok;
@@ -1478,19 +1467,8 @@ __global__ __launch_bounds__(256) void dec_select_kernel(SelectArgs a) {
     if (i + 1 >= a.max_len) return;
     // CaptionEmbedder + sqrt(d) scale + PositionEncoder of the next input token (geo-aware/models.py:155-181,355-357)
     const int64_t tok = tok_sh[0], msk = tok_sh[1];
-    const int64_t b = r / a.rows_per_sample;
-    const float* src;
-    if (msk == 1) {
-        int64_t e = tok - a.V;
-        if (e < 0 || e >= a.K) e = a.K - 1;
-        src = a.ee + (b * a.K + e) * a.d;
-    } else if (msk == 2 && a.fe != nullptr) {
-        int64_t e = tok - a.V - a.K;
-        if (e < 0 || e >= a.F) e = a.F - 1;
-        src = a.fe + (b * a.F + e) * a.d;
-    } else {
-        src = a.word_emb + (tok >= 0 && tok < a.V ? tok : (int64_t)a.pad_token) * a.d;
-    }
+    const float* src = token_row(tok, (int)msk, r / a.rows_per_sample, a.word_emb, a.ee, a.fe, a.V, a.K, a.F, a.d,
+                                 a.pad_token);
     const float* pe = a.pe + (int64_t)(i + 1) * a.d;
     for (int c = tid; c < a.d; c += 256) a.x0[r * a.d + c] = fmaf(src[c], a.emb_scale, pe[c]);
 }
@@ -1690,6 +1668,68 @@ void dec_beam_partial_kernel(std::conditional_t<FORCED, BeamPartForcedArgs, Beam
     }
 }
 
+// The LDS tables of one caption's selection step, by hypothesis (force: by forced slot).  met, force, nmet belong to the
+// FORCED variant and xtok to the DIVERSE one.
+struct BeamRows {
+    float *cum, *lse;
+    int *fin, *len, *parent, *tok, *nfin, *met, *force, *nmet, *xtok;
+};
+
+// One selection round: the block-wide arg-best (bv, bc) of every thread's candidates; the winner leaves the pool.
+template <int N>
+__device__ __forceinline__ void beam_round(float (&v)[N], int (&c)[N], float& bv, int& bc, float* shv, int* shc) {
+    bv = -INFINITY; bc = kNone;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        const bool take = v[q] > bv || (v[q] == bv && c[q] < bc);
+        bv = take ? v[q] : bv;
+        bc = take ? c[q] : bc;
+    }
+    block_best(bv, bc, shv, shc);
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+        if (c[q] == bc) { v[q] = -INFINITY; c[q] = kNone; }
+}
+
+// The winner of a round (code c, key `key`) becomes hypothesis h: thread 0 decides parent, token and ended-or-not and
+// stores the step's bookkeeping.  cum is the raw summed log-probability: where the key is not that (length penalty,
+// diversity penalty, banks) it is derived again from the step's score row, by the expression that made the key.
+template <bool DIVERSE, bool FORCED>
+__device__ __forceinline__ void beam_winner(const BeamArgs& a, const BeamRows& s, int64_t r0, bool lp_on, int h,
+                                            float key, int c) {
+    const int np = a.K + a.F, Vx = a.V + np;
+    const bool rederive = DIVERSE || FORCED || lp_on;
+    float v = rederive || c == kNone ? -INFINITY : key;         // fewer candidates than beams: a dead slot
+    int parent = 0, tok = a.pad_token, nf = 1, len = 0, met = 0;
+    if (c != kNone) {
+        parent = c / Vx;
+        if constexpr (FORCED) met = s.met[parent];
+        if (s.fin[parent]) {                                    // an ended hypothesis is carried as it is
+            if (rederive) v = s.cum[parent];
+            if (lp_on) len = s.len[parent];
+        } else {
+            tok = c - parent * Vx; nf = tok == a.end_token;
+            if (rederive) {
+                const float x = tok < a.V ? a.scores[(r0 + parent) * a.ld + tok]
+                                          : a.ptr[(r0 + parent) * np + (tok - a.V)];
+                v = s.cum[parent] - s.lse[parent] + x;
+            }
+            len = a.step + 1;
+            if constexpr (FORCED)
+                for (int f = 0; f < kForceMax; ++f) met |= s.force[f] == tok ? 1 << f : 0;
+        }
+    }
+    s.parent[h] = parent; s.tok[h] = tok; s.nfin[h] = nf;
+    if constexpr (FORCED) s.nmet[h] = met;
+    if constexpr (DIVERSE) s.xtok[h] = c != kNone && !s.fin[parent] ? tok : -1;
+    if (lp_on) a.len[r0 + h] = len;
+    a.cum[r0 + h] = v;
+    a.fin[r0 + h] = nf;
+    const bool live = c != kNone && !nf;
+    a.next_token[r0 + h] = live ? tok : 0;
+    a.next_mask[r0 + h] = live ? token_kind(tok, a.V, a.K, a.has_facts) : 0;
+}
+
 // DIVERSE: diverse beam search (ick_decode_select_beam_diverse); FORCED: constrained beam search
 // (ick_decode_select_beam_forced)
 template <bool RULES, bool DIVERSE = false, bool FORCED = false>
@@ -1706,6 +1746,8 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     __shared__ float lpf_s[kBeamMax];
     __shared__ int met_s[FORCED ? kBeamMax : 1], force_s[FORCED ? kForceMax : 1], nmet_s[FORCED ? kBeamMax : 1];
     __shared__ int shp[FORCED ? 4 : 1];
+    __shared__ int xtok_s[DIVERSE ? kBeamMax : 1];          // column expanded into slot j at this step, or -1
+    const BeamRows rows{cum_s, lse_s, fin_s, len_s, parent_s, tok_s, nfin_s, met_s, force_s, nmet_s, xtok_s};
     const int tid = threadIdx.x, k = a.k;
     const int64_t r0 = (int64_t)blockIdx.x * k;
     const int np = a.K + a.F, Vx = a.V + np;
@@ -1826,86 +1868,21 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
             for (int q = 0; q < NF; ++q)
                 if (fc[q] == bc) { fv[q] = -INFINITY; fc[q] = kNone; fb[q] = -32; }
             if (bc != kNone) turn = bp >= 16 ? bp - 16 : bp;
-            if (tid != 0) continue;
-            const int c = bc;
-            float v = -INFINITY;                                    // fewer candidates than beams: a dead slot
-            int parent = 0, tok = a.pad_token, nf = 1, len = 0, met = 0;
-            if (c != kNone) {
-                parent = c / Vx;
-                met = met_s[parent];
-                if (fin_s[parent]) {
-                    v = cum_s[parent]; len = lp_on ? len_s[parent] : 0;
-                } else {
-                    tok = c - parent * Vx; nf = tok == a.end_token;
-                    const float x = tok < a.V ? a.scores[(r0 + parent) * a.ld + tok]
-                                              : a.ptr[(r0 + parent) * np + (tok - a.V)];
-                    v = cum_s[parent] - lse_s[parent] + x;          // the expression that made the key
-                    len = a.step + 1;
-                    for (int s = 0; s < kForceMax; ++s) met |= force_s[s] == tok ? 1 << s : 0;
-                }
-            }
-            parent_s[round] = parent; tok_s[round] = tok; nfin_s[round] = nf; nmet_s[round] = met;
-            if (lp_on) a.len[r0 + round] = len;
-            a.cum[r0 + round] = v;
-            a.fin[r0 + round] = nf;
-            const bool live = c != kNone && !nf;
-            a.next_token[r0 + round] = live ? tok : 0;
-            a.next_mask[r0 + round] = !live ? 0 : ((a.has_facts && tok >= a.V + a.K) ? 2 : (tok >= a.V ? 1 : 0));
+            if (tid == 0) beam_winner<false, true>(a, rows, r0, lp_on, round, bv, bc);
         }
         __syncthreads();
         if (tid < k) a.met[r0 + tid] = nmet_s[tid];
-    } else
-    if constexpr (!DIVERSE) {
-    for (int round = 0; round < k; ++round) {
-        float bv = -INFINITY; int bc = kNone;
-#pragma unroll
-        for (int q = 0; q < NC; ++q) {
-            const bool take = cv[q] > bv || (cv[q] == bv && cc[q] < bc);
-            bv = take ? cv[q] : bv;
-            bc = take ? cc[q] : bc;
+    } else if constexpr (!DIVERSE) {
+        for (int round = 0; round < k; ++round) {
+            float bv; int bc;
+            beam_round(cv, cc, bv, bc, shv, shc);
+            if (tid == 0) beam_winner<false, false>(a, rows, r0, lp_on, round, bv, bc);
         }
-        block_best(bv, bc, shv, shc);
-#pragma unroll
-        for (int q = 0; q < NC; ++q)
-            if (cc[q] == bc) { cv[q] = -INFINITY; cc[q] = kNone; }
-        if (tid == 0) {
-            float v = bv; const int c = bc;
-            int parent = 0, tok = a.pad_token, nf = 1, len = 0;
-            if (c != kNone) {
-                parent = c / Vx;
-                if (fin_s[parent]) { nf = 1; tok = a.pad_token; }
-                else { tok = c - parent * Vx; nf = tok == a.end_token; }
-                if (lp_on) {       // v is the key: the raw log-probability again, by the expression that made the key
-                    if (fin_s[parent]) {
-                        v = cum_s[parent]; len = len_s[parent];
-                    } else {
-                        const float* rc = a.rec + ((r0 + parent) * nchunk + tok / kBeamChunk) * kBeamRec;
-                        int slot = 0;
-                        while (slot + 1 < k && __float_as_int(rc[3 + 2 * slot]) != tok) ++slot;
-                        v = cum_s[parent] - lse_s[parent] + rc[2 + 2 * slot];
-                        len = a.step + 1;
-                    }
-                }
-            } else {
-                v = -INFINITY;                                      // fewer candidates than beams: a dead slot
-            }
-            parent_s[round] = parent; tok_s[round] = tok; nfin_s[round] = nf;
-            if (lp_on) a.len[r0 + round] = len;
-            a.cum[r0 + round] = v;
-            a.fin[r0 + round] = nf;
-            const bool live = c != kNone && !nf;
-            a.next_token[r0 + round] = live ? tok : 0;
-            a.next_mask[r0 + round] = !live ? 0 : ((a.has_facts && tok >= a.V + a.K) ? 2 : (tok >= a.V ? 1 : 0));
-        }
-    }
     } else {
         // Diverse beam search: the groups choose in order.  Group g ranks the candidates of its own rows g*kg ..
         // (g+1)*kg - 1 by key - lambda * n, n = the number of hypotheses of groups 0 .. g-1 expanded with the
         // candidate's column at this step (an ended hypothesis competes with its key as it is), and its kg rounds fill
-        // slots g*kg + round: k rounds in all, as without groups.  The winner's bookkeeping is the loop's above (kept
-        // apart so that the instantiations without groups keep their instructions), with the raw log-probability
-        // always re-derived, since the key is penalised.
-        __shared__ int xtok_s[kBeamMax];                    // column expanded into slot j at this step, or -1
+        // slots g*kg + round: k rounds in all, as without groups.
         const int kg = k / a.groups;
         const float lam = diversity_penalty(a.penalty);
         for (int g = 0; g < a.groups; ++g) {
@@ -1923,42 +1900,9 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
                 }
             }
             for (int round = 0; round < kg; ++round) {
-                float bv = -INFINITY; int bc = kNone;
-#pragma unroll
-                for (int q = 0; q < NC; ++q) {
-                    const bool take = gv[q] > bv || (gv[q] == bv && gc[q] < bc);
-                    bv = take ? gv[q] : bv;
-                    bc = take ? gc[q] : bc;
-                }
-                block_best(bv, bc, shv, shc);
-#pragma unroll
-                for (int q = 0; q < NC; ++q)
-                    if (gc[q] == bc) { gv[q] = -INFINITY; gc[q] = kNone; }
-                if (tid != 0) continue;
-                const int h = g * kg + round, c = bc;
-                float v = -INFINITY;                                // fewer candidates than beams: a dead slot
-                int parent = 0, tok = a.pad_token, nf = 1, len = 0;
-                if (c != kNone) {
-                    parent = c / Vx;
-                    if (fin_s[parent]) {
-                        v = cum_s[parent]; len = lp_on ? len_s[parent] : 0;
-                    } else {
-                        tok = c - parent * Vx; nf = tok == a.end_token;
-                        const float* rc = a.rec + ((r0 + parent) * nchunk + tok / kBeamChunk) * kBeamRec;
-                        int slot = 0;
-                        while (slot + 1 < k && __float_as_int(rc[3 + 2 * slot]) != tok) ++slot;
-                        v = cum_s[parent] - lse_s[parent] + rc[2 + 2 * slot];
-                        len = a.step + 1;
-                    }
-                }
-                parent_s[h] = parent; tok_s[h] = tok; nfin_s[h] = nf;
-                xtok_s[h] = c != kNone && !fin_s[parent] ? tok : -1;
-                if (lp_on) a.len[r0 + h] = len;
-                a.cum[r0 + h] = v;
-                a.fin[r0 + h] = nf;
-                const bool live = c != kNone && !nf;
-                a.next_token[r0 + h] = live ? tok : 0;
-                a.next_mask[r0 + h] = !live ? 0 : ((a.has_facts && tok >= a.V + a.K) ? 2 : (tok >= a.V ? 1 : 0));
+                float bv; int bc;
+                beam_round(gv, gc, bv, bc, shv, shc);
+                if (tid == 0) beam_winner<true, false>(a, rows, r0, lp_on, g * kg + round, bv, bc);
             }
             __syncthreads();                                // xtok_s of this group before the next group reads it
         }
@@ -1986,19 +1930,9 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     for (int idx = tid; idx < k * a.d; idx += 256) {
         const int j = idx / a.d, c = idx - j * a.d;
         const int tok = nfin_s[j] ? 0 : tok_s[j];
-        const int64_t b = blockIdx.x;
-        const float* src;
-        if (tok >= a.V + a.K && a.has_facts && a.fe != nullptr) {
-            int e = tok - a.V - a.K;
-            if (e >= a.F) e = a.F - 1;
-            src = a.fe + (b * a.F + e) * a.d;
-        } else if (tok >= a.V) {
-            int e = tok - a.V;
-            if (e >= a.K) e = a.K - 1;
-            src = a.ee + (b * a.K + e) * a.d;
-        } else {
-            src = a.word_emb + (int64_t)tok * a.d;
-        }
+        // (tok is in [0, Vx), has_facts is F > 0 and fe is non-null exactly then: no clamp of token_row() acts here)
+        const float* src = token_row(tok, token_kind(tok, a.V, a.K, a.has_facts), (int64_t)blockIdx.x, a.word_emb, a.ee,
+                                     a.fe, a.V, a.K, a.F, a.d, a.pad_token);
         a.x0[(r0 + j) * a.d + c] = fmaf(src[c], a.emb_scale, pe[c]);
     }
 }
@@ -2348,8 +2282,7 @@ extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_st
 
 extern "C" int ick_decode_select_beam_rules(const ick_decode_ctx* c, const ick_beam_state* bs,
                                             const ick_decode_rules* rules, int32_t pos, void* stream) {
-    ICK_CHECK_ARG(c && rules && rules->words && rules->lp && rules->len && ((uintptr_t)rules->words & 15) == 0);
-    ICK_CHECK_ARG(c->max_len <= kRuleHistMax && c->end_token >= 0 && c->end_token < c->V);
+    ICK_CHECK_ARG(rules_ok(c, rules, true));
     return select_beam_impl(c, bs, rules, nullptr, nullptr, pos, stream);
 }
 
@@ -2358,10 +2291,7 @@ extern "C" int ick_decode_select_beam_diverse(const ick_decode_ctx* c, const ick
                                               int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && div && div->penalty && div->groups >= 1 && c->rows_per_sample >= 1 &&
                   c->rows_per_sample % div->groups == 0);
-    if (rules != nullptr) {
-        ICK_CHECK_ARG(rules->words && rules->lp && rules->len && ((uintptr_t)rules->words & 15) == 0);
-        ICK_CHECK_ARG(c->max_len <= kRuleHistMax && c->end_token >= 0 && c->end_token < c->V);
-    }
+    ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
     return select_beam_impl(c, bs, rules, div, nullptr, pos, stream);
 }
 
@@ -2369,9 +2299,6 @@ extern "C" int ick_decode_select_beam_forced(const ick_decode_ctx* c, const ick_
                                              const ick_decode_rules* rules, const ick_decode_constraints* fc,
                                              int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && fc && fc->force && fc->met && c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax);
-    if (rules != nullptr) {
-        ICK_CHECK_ARG(rules->words && rules->lp && rules->len && ((uintptr_t)rules->words & 15) == 0);
-        ICK_CHECK_ARG(c->max_len <= kRuleHistMax && c->end_token >= 0 && c->end_token < c->V);
-    }
+    ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
     return select_beam_impl(c, bs, rules, nullptr, fc, pos, stream);
 }

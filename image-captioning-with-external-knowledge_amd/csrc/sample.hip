@@ -352,7 +352,7 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
                 atomicAdd(a.n_done, 1);
             } else {
                 tok = bc;
-                msk = (a.has_facts && bc >= a.V + a.K) ? 2 : (bc >= a.V ? 1 : 0);
+                msk = token_kind(bc, a.V, a.K, a.has_facts);
             }
             tok_sh[0] = tok;
             tok_sh[1] = msk;
@@ -370,19 +370,8 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
     }
     if (i + 1 >= a.max_len) return;
     // CaptionEmbedder + sqrt(d) scale + PositionEncoder of the next input token (as dec_select_kernel)
-    const int64_t b = r / a.rows_per_sample;
-    const float* src;
-    if (msk == 1) {
-        int64_t e = tok - a.V;
-        if (e < 0 || e >= a.K) e = a.K - 1;
-        src = a.ee + (b * a.K + e) * a.d;
-    } else if (msk == 2 && a.fe != nullptr) {
-        int64_t e = tok - a.V - a.K;
-        if (e < 0 || e >= a.F) e = a.F - 1;
-        src = a.fe + (b * a.F + e) * a.d;
-    } else {
-        src = a.word_emb + (tok >= 0 && tok < a.V ? tok : (int64_t)a.pad_token) * a.d;
-    }
+    const float* src = token_row(tok, (int)msk, r / a.rows_per_sample, a.word_emb, a.ee, a.fe, a.V, a.K, a.F, a.d,
+                                 a.pad_token);
     const float* pe = a.pe + (int64_t)(i + 1) * a.d;
     for (int c = tid; c < a.d; c += kSNT) a.x0[r * a.d + c] = fmaf(src[c], a.emb_scale, pe[c]);
 }
@@ -430,6 +419,6 @@ extern "C" int ick_decode_select_sample(const ick_decode_ctx* c, const ick_sampl
 
 extern "C" int ick_decode_select_sample_rules(const ick_decode_ctx* c, const ick_sample_state* s,
                                               const ick_decode_rules* rules, int32_t pos, void* stream) {
-    ICK_CHECK_ARG(c && rules && rules->words && ((uintptr_t)rules->words & 15) == 0 && c->max_len <= kRuleHistMax);
+    ICK_CHECK_ARG(rules_ok(c, rules, false));
     return select_sample_impl(c, s, rules, pos, stream);
 }

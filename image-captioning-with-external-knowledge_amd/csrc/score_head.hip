@@ -171,7 +171,7 @@ __device__ __forceinline__ void greedy_update_one(int b, int best_b, int second_
     out = o[i];
     if (i < max_len - 1) {
         next_token[b] = out;
-        next_mask[b] = (has_facts && out >= V + K) ? 2 : (out >= V ? 1 : 0);
+        next_mask[b] = token_kind(out, V, K, has_facts);
     }
 }
 

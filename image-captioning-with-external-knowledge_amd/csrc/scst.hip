@@ -33,7 +33,7 @@ __global__ __launch_bounds__(64) void samples_to_captions_kernel(const int64_t* 
             len = t + 2;
         }
         cap[t + 1] = w;
-        msk[t + 1] = ended ? 0 : (has_facts && w >= (int64_t)V + K) ? 2 : (w >= V ? 1 : 0);
+        msk[t + 1] = ended ? 0 : token_kind(w, V, K, has_facts);
     }
     lengths[r] = len;
 }

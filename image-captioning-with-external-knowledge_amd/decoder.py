@@ -17,6 +17,7 @@ import math
 import os
 import struct
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -101,6 +102,19 @@ _NO_DROPOUT = DropSites(0, False)
 
 # return_attention: the largest weight buffer a decode call may allocate, (max_len, rows, layers, H, S) fp32
 ATTENTION_MAX_BYTES = 1 << 30
+
+
+class _BeamResult(NamedTuple):
+    """What DecoderTransformer._predict_beam_device returns; None: not part of this search."""
+    best: torch.Tensor                  # (B, max_len) the best hypothesis of every caption
+    score: torch.Tensor                 # (B) its log-probability
+    all: torch.Tensor                   # (B, beam, max_len) every final hypothesis
+    all_scores: torch.Tensor            # (B, beam)
+    attn: Optional[torch.Tensor] = None             # cross-attention weights of the best (attention=True)
+    all_attn: Optional[torch.Tensor] = None         # ... of every final hypothesis
+    group: Optional[torch.Tensor] = None            # (B * G, max_len) the best of each group (groups > 1)
+    group_score: Optional[torch.Tensor] = None      # (B * G)
+    group_attn: Optional[torch.Tensor] = None
 
 
 def _attention_check(what, max_len, rows, layers, H, S):
@@ -1400,11 +1414,46 @@ class DecoderTransformer(nn.Module):
         ops.decode_init(c, self.word_map["<start>"], n_done_init)
         return c, t
 
+    def _decode_front(self, what, encoder_out, entities, facts, max_pred_len, rows=1, attention=False, needs=None,
+                      fits=None):
+        """The front end predict(), predict_beam() and predict_sample() share: the inputs as the device loops read them,
+        S_all = P + K + F memory rows and Vx = V + K + F score columns.  needs: the IckError text of a call the fused
+        decode kernels cannot run -- their own size limits, or fits(B, Vx), the caller's -- or None for no such check;
+        attention: the weight buffer of `rows` rows per caption must fit.  Returns (enc_tok, entities, facts, S_all, Vx)."""
+        encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
+        entities = entities.contiguous()
+        enc_tok, P = self._image_input(encoder_out)
+        enc_tok = enc_tok.contiguous()
+        S_all = P + entities.shape[1] + (facts.shape[1] if facts is not None else 0)
+        Vx = self.vocab_size + S_all - P
+        FF = self.transformer_decoder.layers[0].linear1.out_features
+        if needs is not None and not (fits(enc_tok.shape[0], Vx) and
+                                      ops.decode_supported(self.emb_dim, self.num_heads, FF, S_all, max_pred_len)):
+            raise IckError(needs)
+        if attention:
+            _attention_check(what, max_pred_len, enc_tok.shape[0] * rows, len(self.transformer_decoder.layers),
+                             self.num_heads, S_all)
+        return enc_tok, entities, facts, S_all, Vx
+
+    def _decode_step(self, c, t, cap, facts, K, i, attn=None, part=0):
+        """The layers of decode step i on the fused kernels (part: as ops.decode_layers_part, 0 = the whole step): the
+        context indicators of the caption buffer `cap` (a model with facts), then the decoder stack and the score head,
+        which also writes the step's cross-attention weights when attn is given."""
+        if self.has_facts:
+            ops.context_indicators(cap, facts, K, self.vocab_size, self._pred_wt(), self.fc_predicate.bias.detach(),
+                                   mode=1, eib=t["eib"], gate=t["gate"])
+        if attn is not None:
+            ops.decode_layers_attn(c, attn, i, part)
+        elif part:
+            ops.decode_layers_part(c, i, part)
+        else:
+            ops.decode_layers(c, i)
+
     def _predict_fused(self, enc_tok, entities, facts, max_pred_len, attention=False):
         """predict() on the fused decode kernels (csrc/decode.hip): 12 launches per token (13 with facts).  attention:
         also return the cross-attention weights (max_len, B, layers, H, S), zero after each row's <end>."""
         B = enc_tok.shape[0]
-        d, V, K = self.emb_dim, self.vocab_size, entities.shape[1]
+        K = entities.shape[1]
         ee, fe, kv, _, side = self._encode_context(enc_tok, entities, facts, None)
         side.join()
         S = kv.shape[3]
@@ -1413,27 +1462,11 @@ class DecoderTransformer(nn.Module):
         fuse = self.fuse_select
         c, t = self._decode_ctx(kv, ee, fe, 1, max_pred_len, S, fuse_select=fuse)
         attn = torch.zeros(max_pred_len, B, c.layers, c.H, S, device=kv.device) if attention else None
-
-        def indicators():
-            ops.context_indicators(t["cap_buf"], facts, K, V, self._pred_wt(), self.fc_predicate.bias.detach(),
-                                   mode=1, eib=t["eib"], gate=t["gate"])
-
         for i in range(max_pred_len):
-            if fuse and i > 0:
+            fused = fuse and i > 0
+            if fused:
                 ops.decode_layers_part(c, i, 1)           # selection of step i - 1 + first self-attention block
-                if self.has_facts:
-                    indicators()
-                if attention:
-                    ops.decode_layers_attn(c, attn, i, 2)
-                else:
-                    ops.decode_layers_part(c, i, 2)
-            else:
-                if self.has_facts:
-                    indicators()
-                if attention:
-                    ops.decode_layers_attn(c, attn, i)
-                else:
-                    ops.decode_layers(c, i)
+            self._decode_step(c, t, t.get("cap_buf"), facts, K, i, attn, 2 if fused else 0)
             if not fuse or i == max_pred_len - 1:
                 ops.decode_select_greedy(c, i)
         if attention:
@@ -1444,13 +1477,14 @@ class DecoderTransformer(nn.Module):
                              penalty=None, force=None):
         """Beam search on the fused decode kernels: R = B * beam rows share their caption's cross K/V; the
         self-attention cache is never reordered -- an ancestry table says which cache row holds position p of a
-        hypothesis.  Returns (best sequence (B, max_len), its log-probability (B), all sequences, all scores); with
-        attention also the cross-attention weights of the best (max_len, B, layers, H, S) and of every final hypothesis
-        (max_len, B, beam, layers, H, S).  rules: a rules_tensor() (device input read at run time) or None; with it the
-        best hypothesis is the argmax of cum / lp[length].  groups > 1: diverse beam search with the
-        penalty lambda read from the (1) fp32 device tensor `penalty`; every group starts from the <start> hypothesis,
-        and the best hypothesis of each group (by the unpenalised key) follows: (its sequence (B * G, max_len), its
-        log-probability (B * G)), and with attention its weights (max_len, B * G, layers, H, S).  force: the (B, 8) int32
+        hypothesis.  Returns a _BeamResult: the best sequence (B, max_len), its log-probability (B), all sequences, all
+        scores; with attention also the cross-attention weights of the best (max_len, B, layers, H, S) and of every
+        final hypothesis (max_len, B, beam, layers, H, S).  rules: a rules_tensor() (device input read at run time) or
+        None; with it the best hypothesis is the argmax of cum / lp[length].  groups > 1: diverse beam search (DESIGN.md
+        §3.2f) with the penalty lambda read from the (1) fp32 device tensor `penalty`; every group starts from the
+        <start> hypothesis, and the result also holds the best hypothesis of each group (by the unpenalised key): its
+        sequence (B * G, max_len), its log-probability (B * G), and with attention its weights (max_len, B * G, layers,
+        H, S).  force: the (B, 8) int32
         device tensor of check_force() (read at run time) or None; with it the search is the constrained one of
         DESIGN.md §3.2g and the best hypothesis is the best by (met slots, key)."""
         from . import lib as L
@@ -1480,7 +1514,7 @@ class DecoderTransformer(nn.Module):
         rec = torch.empty(R, (Vx + 1023) // 1024, 18, device=dev, dtype=torch.float32)
         bs.rec = rec.data_ptr()
         attn = torch.zeros(max_pred_len, R, c.layers, c.H, S, device=dev) if attention else None
-        rs = None
+        rs = dv = fc = None
         if rules is not None:
             lens = torch.zeros(R, dtype=torch.int32, device=dev)
             rs = _rules_struct(rules, lens)
@@ -1495,23 +1529,11 @@ class DecoderTransformer(nn.Module):
             cur, nxt = i & 1, (i + 1) & 1
             c.anc = anc[cur].data_ptr()
             if self.has_facts:
-                ops.context_indicators(cap[cur], facts_r, K, V, self._pred_wt(), self.fc_predicate.bias.detach(), mode=1,
-                                       eib=t["eib"], gate=t["gate"])
                 bs.cap_in, bs.cap_out = cap[cur].data_ptr(), cap[nxt].data_ptr()
-            if attention:
-                ops.decode_layers_attn(c, attn, i)
-            else:
-                ops.decode_layers(c, i)
+            self._decode_step(c, t, cap and cap[cur], facts_r, K, i, attn)
             bs.seq_in, bs.seq_out = seq[cur].data_ptr(), seq[nxt].data_ptr()
             bs.anc_in, bs.anc_out = anc[cur].data_ptr(), anc[nxt].data_ptr()
-            if force is not None:
-                ops.decode_select_beam_forced(c, bs, rs, fc, i)
-            elif groups > 1:
-                ops.decode_select_beam_diverse(c, bs, rs, dv, i)
-            elif rules is None:
-                ops.decode_select_beam(c, bs, i)
-            else:
-                ops.decode_select_beam_rules(c, bs, rs, i)
+            ops.decode_select_beam(c, bs, i, rs, dv, fc)
         final = seq[max_pred_len & 1].view(B, beam, max_pred_len)
         if rules is None:
             key = cum
@@ -1524,23 +1546,23 @@ class DecoderTransformer(nn.Module):
             bank = ((met.view(B, beam, 1) >> torch.arange(FORCE_MAX, device=dev, dtype=torch.int32)) & 1).sum(dim=2)
             top = bank == bank.max(dim=1, keepdim=True).values
             best = torch.where(top, key, torch.full_like(key, float("-inf"))).argmax(dim=1)
-        out = final[torch.arange(B, device=dev), best]
-        group_res = ()
+        rows = torch.arange(B, device=dev)
+        res = _BeamResult(final[rows, best], cum.gather(1, best.view(B, 1)).view(B), final, cum)
         if groups > 1:                                    # the best of each group by the same key (no penalty)
             gbest = key.view(B, groups, kg).argmax(dim=2) + torch.arange(0, beam, kg, device=dev)      # (B, G)
-            bidx = torch.arange(B, device=dev).view(B, 1)
-            group_res = (final[bidx, gbest].reshape(B * groups, max_pred_len), cum.gather(1, gbest).reshape(B * groups))
+            bidx = rows.view(B, 1)
+            res = res._replace(group=final[bidx, gbest].reshape(B * groups, max_pred_len),
+                               group_score=cum.gather(1, gbest).reshape(B * groups))
         if not attention:
-            return (out, cum.gather(1, best.view(B, 1)).view(B), final, cum) + group_res
+            return res
         # rows are never reordered: position p of a final hypothesis was computed by row anc[hyp, p] (global row index)
         anc_fin = anc[max_pred_len & 1].t().long()                                        # (max_len, R)
         steps = torch.arange(max_pred_len, device=dev).view(-1, 1)
         hyp = _zero_after_end(attn[steps, anc_fin], final.view(R, max_pred_len), self.word_map["<end>"])
         hyp = hyp.view(max_pred_len, B, beam, *hyp.shape[2:])
         if groups > 1:
-            group_res += (hyp[:, bidx, gbest].reshape(max_pred_len, B * groups, *hyp.shape[3:]),)
-        return (out, cum.gather(1, best.view(B, 1)).view(B), final, cum, hyp[:, torch.arange(B, device=dev), best],
-                hyp) + group_res
+            res = res._replace(group_attn=hyp[:, bidx, gbest].reshape(max_pred_len, B * groups, *hyp.shape[3:]))
+        return res._replace(attn=hyp[:, rows, best], all_attn=hyp)
 
     @torch.no_grad()
     def predict_beam(self, encoder_out, max_pred_len, entities, facts=None, beam_size=5, return_all=False,
@@ -1594,62 +1616,40 @@ class DecoderTransformer(nn.Module):
         if beam_size == 1 and not rules_on and force is None:
             return DecoderTransformer.predict(self, encoder_out, max_pred_len, entities, facts,
                                               return_attention=return_attention)
-        encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
-        entities = entities.contiguous()
-        enc_tok, P = self._image_input(encoder_out)
-        enc_tok = enc_tok.contiguous()
-        FF = self.transformer_decoder.layers[0].linear1.out_features
-        S_all = P + entities.shape[1] + (facts.shape[1] if facts is not None else 0)
-        Vx = self.vocab_size + S_all - P
-        if not (1 <= beam_size <= 8) or not ops.decode_supported(self.emb_dim, self.num_heads, FF, S_all, max_pred_len) \
-                or not ops.decode_beam_supported(Vx, beam_size):
-            raise IckError("predict_beam needs 1 <= beam_size <= 8, beam_size^2 * ceil((V+K+F)/1024) <= 4096 and sizes "
-                           "the fused decode kernels support")
-        if return_attention:
-            _attention_check("predict_beam", max_pred_len, enc_tok.shape[0] * beam_size,
-                             len(self.transformer_decoder.layers), self.num_heads, S_all)
+        enc_tok, entities, facts, _, _ = self._decode_front(
+            "predict_beam", encoder_out, entities, facts, max_pred_len, beam_size, return_attention,
+            "predict_beam needs 1 <= beam_size <= 8, beam_size^2 * ceil((V+K+F)/1024) <= 4096 and sizes the fused decode "
+            "kernels support", lambda B, Vx: 1 <= beam_size <= 8 and ops.decode_beam_supported(Vx, beam_size))
         rules = rules_tensor(max_pred_len, length_penalty, no_repeat_ngram_size, min_len, enc_tok.device) \
             if rules_on else None
         G = num_beam_groups
-        penalty = torch.tensor([diversity_penalty], dtype=torch.float32).to(enc_tok.device) if diverse else None
+        forced = force is not None
+        # the variant's own device input: the forced columns, or the diversity penalty
+        extra = force.to(enc_tok.device) if forced else \
+            torch.tensor([diversity_penalty], dtype=torch.float32).to(enc_tok.device) if diverse else None
+        inputs = [enc_tok, entities, facts] + ([rules, extra] if extra is not None else [rules] if rules_on else [])
+
+        def run(t, e, f, r=None, x=None):
+            return self._predict_beam_device(t, e, f, max_pred_len, beam_size, return_attention, r, G,
+                                             x if diverse else None, x if forced else None)
+
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
-                   max_pred_len, beam_size) + self._enc_key(enc_tok)
-            if force is not None:
-                force = force.to(enc_tok.device)
-                kind = ("beam_force_rules" if rules_on else "beam_force") + ("_attn" if return_attention else "")
-                res = self._graphed(kind, key,
-                                    lambda t, e, f, r, ft: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
-                                                                                     return_attention, r, force=ft),
-                                    [enc_tok, entities, facts, rules, force])
-            elif diverse:
-                kind = ("beam_div_rules" if rules_on else "beam_div") + ("_attn" if return_attention else "")
-                res = self._graphed(kind, key + (G,),
-                                    lambda t, e, f, r, lam: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
-                                                                                      return_attention, r, G, lam),
-                                    [enc_tok, entities, facts, rules, penalty])
-            elif rules_on:
-                res = self._graphed("beam_rules_attn" if return_attention else "beam_rules", key,
-                                    lambda t, e, f, r: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
-                                                                                 return_attention, r),
-                                    [enc_tok, entities, facts, rules])
-            else:
-                res = self._graphed("beam_attn" if return_attention else "beam", key,
-                                    lambda t, e, f: self._predict_beam_device(t, e, f, max_pred_len, beam_size,
-                                                                              return_attention),
-                                    [enc_tok, entities, facts])
+                   max_pred_len, beam_size) + self._enc_key(enc_tok) + ((G,) if diverse else ())
+            kind = "beam" + ("_force" if forced else "_div" if diverse else "") + ("_rules" if rules_on else "") + \
+                ("_attn" if return_attention else "")
+            res = self._graphed(kind, key, run, inputs)
         else:
-            res = self._predict_beam_device(enc_tok, entities, facts, max_pred_len, beam_size, return_attention, rules,
-                                            G, penalty, None if force is None else force.to(enc_tok.device))
+            res = run(*inputs)
+        seq, score, attn = res.best, res.score, res.attn
         if return_groups and diverse:       # the best of each group in place of the best of the caption
-            n = 6 if return_attention else 4
-            res = (res[n], res[n + 1], res[2], res[3]) + ((res[n + 2], res[5]) if return_attention else ())
-        out = res[0].t().contiguous()
+            seq, score, attn = res.group, res.group_score, res.group_attn
+        out = seq.t().contiguous()
         if not return_attention:
-            return (out, res[1], res[2], res[3]) if return_all else out
+            return (out, score, res.all, res.all_scores) if return_all else out
         if return_all:
-            return out, res[1], res[2], res[3], res[4].clone(), res[5].clone()
-        return out, res[4].clone()
+            return out, score, res.all, res.all_scores, attn.clone(), res.all_attn.clone()
+        return out, attn.clone()
 
     def _predict_sample_device(self, enc_tok, entities, facts, knobs, max_pred_len, n, attention=False, rules=None):
         """Sampled decode on the fused decode kernels: R = B * n rows, the n samples of a caption share its cross K/V
@@ -1659,7 +1659,7 @@ class DecoderTransformer(nn.Module):
         S)])."""
         from . import lib as L
         dev = enc_tok.device
-        V, K = self.vocab_size, entities.shape[1]
+        K = entities.shape[1]
         ee, fe, kv, _, side = self._encode_context(enc_tok, entities, facts, None)
         side.join()
         c, t = self._decode_ctx(kv, ee, fe, n, max_pred_len, kv.shape[3], want_scores=True)
@@ -1671,17 +1671,8 @@ class DecoderTransformer(nn.Module):
         attn = torch.zeros(max_pred_len, c.R, c.layers, c.H, c.S, device=dev) if attention else None
         rs = None if rules is None else _rules_struct(rules)
         for i in range(max_pred_len):
-            if self.has_facts:
-                ops.context_indicators(t["cap_buf"], facts_r, K, V, self._pred_wt(), self.fc_predicate.bias.detach(),
-                                       mode=1, eib=t["eib"], gate=t["gate"])
-            if attention:
-                ops.decode_layers_attn(c, attn, i)
-            else:
-                ops.decode_layers(c, i)
-            if rs is None:
-                ops.decode_select_sample(c, st, i)
-            else:
-                ops.decode_select_sample_rules(c, st, rs, i)
+            self._decode_step(c, t, t.get("cap_buf"), facts_r, K, i, attn)
+            ops.decode_select_sample(c, st, i, rs)
         if attention:
             return t["output"], log_prob, _zero_after_end(attn, t["output"], self.word_map["<end>"])
         return t["output"], log_prob
@@ -1721,21 +1712,10 @@ class DecoderTransformer(nn.Module):
             raise IckError("predict_sample needs an integer top_k >= 0 (0 = off)")
         if not (0 < top_p <= 1):
             raise IckError("predict_sample needs 0 < top_p <= 1")
-        encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
-        entities = entities.contiguous()
-        enc_tok, P = self._image_input(encoder_out)
-        enc_tok = enc_tok.contiguous()
-        B = enc_tok.shape[0]
-        FF = self.transformer_decoder.layers[0].linear1.out_features
-        S_all = P + entities.shape[1] + (facts.shape[1] if facts is not None else 0)
-        Vx = self.vocab_size + S_all - P
-        if B * num_samples > 65535 or not ops.decode_supported(self.emb_dim, self.num_heads, FF, S_all, max_pred_len) \
-                or not ops.decode_sample_supported(Vx, num_samples):
-            raise IckError("predict_sample needs B * num_samples <= 65535, V+K+F <= 65536 and sizes the fused decode "
-                           "kernels support")
-        if return_attention:
-            _attention_check("predict_sample", max_pred_len, B * num_samples, len(self.transformer_decoder.layers),
-                             self.num_heads, S_all)
+        enc_tok, entities, facts, _, _ = self._decode_front(
+            "predict_sample", encoder_out, entities, facts, max_pred_len, num_samples, return_attention,
+            "predict_sample needs B * num_samples <= 65535, V+K+F <= 65536 and sizes the fused decode kernels support",
+            lambda B, Vx: B * num_samples <= 65535 and ops.decode_sample_supported(Vx, num_samples))
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (), dtype=torch.int64))
         seed = int(seed) & (2 ** 64 - 1)
@@ -1743,22 +1723,18 @@ class DecoderTransformer(nn.Module):
         tp = struct.unpack("<q", struct.pack("<ff", temperature, top_p))[0]
         knobs = torch.tensor([seed, tp, min(top_k, 2 ** 31 - 1)], dtype=torch.int64).to(enc_tok.device)
         rules = rules_tensor(max_pred_len, 0.0, no_repeat_ngram_size, min_len, enc_tok.device) if rules_on else None
+        inputs = [enc_tok, entities, facts, knobs] + ([rules] if rules_on else [])
+
+        def run(t, e, f, k, r=None):
+            return self._predict_sample_device(t, e, f, k, max_pred_len, num_samples, return_attention, r)
+
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, num_samples) + self._enc_key(enc_tok)
-            if rules_on:
-                res = self._graphed("sample_rules_attn" if return_attention else "sample_rules", key,
-                                    lambda t, e, f, k, r: self._predict_sample_device(t, e, f, k, max_pred_len,
-                                                                                      num_samples, return_attention, r),
-                                    [enc_tok, entities, facts, knobs, rules])
-            else:
-                res = self._graphed("sample_attn" if return_attention else "sample", key,
-                                    lambda t, e, f, k: self._predict_sample_device(t, e, f, k, max_pred_len,
-                                                                                   num_samples, return_attention),
-                                    [enc_tok, entities, facts, knobs])
+            kind = "sample" + ("_rules" if rules_on else "") + ("_attn" if return_attention else "")
+            res = self._graphed(kind, key, run, inputs)
         else:
-            res = self._predict_sample_device(enc_tok, entities, facts, knobs, max_pred_len, num_samples, return_attention,
-                                              rules)
+            res = run(*inputs)
         out = res[0].t().contiguous()
         ret = (out, res[1].t().contiguous()) if return_log_probs else (out,)
         if return_attention:
@@ -1822,18 +1798,10 @@ class DecoderTransformer(nn.Module):
         token i) over the S = P + K + F memory rows [image ; entities ; facts] (split_attention() cuts that axis).  Steps
         after a row's <end> are zero (the <end> step keeps the weights that chose it).  Needs the fused decode kernels
         and a buffer of at most ATTENTION_MAX_BYTES; the tokens are the same bits as without it."""
-        encoder_out, entities, facts = self._prepare_inputs(encoder_out, entities, facts)
-        entities = entities.contiguous()
-        enc_tok, P = self._image_input(encoder_out)
-        enc_tok = enc_tok.contiguous()
-        if return_attention:
-            FF = self.transformer_decoder.layers[0].linear1.out_features
-            S_all = P + entities.shape[1] + (facts.shape[1] if facts is not None else 0)
-            if not self.fused_decode or not ops.decode_supported(self.emb_dim, self.num_heads, FF, S_all, max_pred_len):
-                raise IckError("predict(return_attention=True) needs fused_decode and sizes the fused decode kernels "
-                               "support")
-            _attention_check("predict", max_pred_len, enc_tok.shape[0], len(self.transformer_decoder.layers),
-                             self.num_heads, S_all)
+        enc_tok, entities, facts, _, _ = self._decode_front(
+            "predict", encoder_out, entities, facts, max_pred_len, 1, return_attention,
+            "predict(return_attention=True) needs fused_decode and sizes the fused decode kernels support"
+            if return_attention else None, lambda B, Vx: self.fused_decode)
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len) + self._enc_key(enc_tok)

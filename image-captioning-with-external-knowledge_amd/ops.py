@@ -687,42 +687,32 @@ def decode_select_greedy(ctx, pos):
     L.check(L.load().ick_decode_select_greedy(C.byref(ctx), pos, _stream()), "ick_decode_select_greedy")
 
 
-def decode_select_beam(ctx, beam_state, pos):
-    L.check(L.load().ick_decode_select_beam(C.byref(ctx), C.byref(beam_state), pos, _stream()), "ick_decode_select_beam")
+def _ref(s):
+    return None if s is None else C.byref(s)
 
 
-def decode_select_beam_rules(ctx, beam_state, rules, pos):
-    """ick_decode_select_beam under decoding rules (lib.DecodeRules): n-gram / min-length bans, length penalty."""
-    L.check(L.load().ick_decode_select_beam_rules(C.byref(ctx), C.byref(beam_state), C.byref(rules), pos, _stream()),
-            "ick_decode_select_beam_rules")
-
-
-def decode_select_beam_diverse(ctx, beam_state, rules, diversity, pos):
-    """ick_decode_select_beam_diverse: diverse beam search (lib.DecodeDiversity: groups, penalty), under decoding rules
-    (lib.DecodeRules) or none (rules=None)."""
-    L.check(L.load().ick_decode_select_beam_diverse(C.byref(ctx), C.byref(beam_state),
-                                                    None if rules is None else C.byref(rules), C.byref(diversity),
-                                                    pos, _stream()), "ick_decode_select_beam_diverse")
+def decode_select_beam(ctx, beam_state, pos, rules=None, diversity=None, constraints=None):
+    """Beam selection of step `pos` (ick_decode_select_beam), under decoding rules (lib.DecodeRules: n-gram / min-length
+    bans, length penalty) or none, as plain, diverse (lib.DecodeDiversity: groups, penalty: ick_..._diverse) or
+    constrained beam search (lib.DecodeConstraints: force, met: ick_..._forced)."""
+    if constraints is not None:
+        name, extra = "ick_decode_select_beam_forced", (_ref(rules), C.byref(constraints))
+    elif diversity is not None:
+        name, extra = "ick_decode_select_beam_diverse", (_ref(rules), C.byref(diversity))
+    else:
+        name, extra = ("ick_decode_select_beam", ()) if rules is None else ("ick_decode_select_beam_rules", (_ref(rules),))
+    L.check(getattr(L.load(), name)(C.byref(ctx), C.byref(beam_state), *extra, pos, _stream()), name)
 
 
 def decode_select_beam_forced(ctx, beam_state, rules, constraints, pos):
-    """ick_decode_select_beam_forced: constrained beam search (lib.DecodeConstraints: force, met), under decoding rules
-    (lib.DecodeRules) or none (rules=None)."""
-    L.check(L.load().ick_decode_select_beam_forced(C.byref(ctx), C.byref(beam_state),
-                                                   None if rules is None else C.byref(rules), C.byref(constraints),
-                                                   pos, _stream()), "ick_decode_select_beam_forced")
+    decode_select_beam(ctx, beam_state, pos, rules, constraints=constraints)
 
 
-def decode_select_sample_rules(ctx, sample_state, rules, pos):
-    """ick_decode_select_sample under decoding rules (lib.DecodeRules): n-gram / min-length bans."""
-    L.check(L.load().ick_decode_select_sample_rules(C.byref(ctx), C.byref(sample_state), C.byref(rules), pos,
-                                                    _stream()), "ick_decode_select_sample_rules")
-
-
-def decode_select_sample(ctx, sample_state, pos):
-    """Sampled token of step `pos` for every live row (ick_decode_select_sample); sample_state: lib.SampleState."""
-    L.check(L.load().ick_decode_select_sample(C.byref(ctx), C.byref(sample_state), pos, _stream()),
-            "ick_decode_select_sample")
+def decode_select_sample(ctx, sample_state, pos, rules=None):
+    """Sampled token of step `pos` for every live row (ick_decode_select_sample); sample_state: lib.SampleState; rules:
+    lib.DecodeRules (n-gram / min-length bans: ick_decode_select_sample_rules) or None."""
+    name, extra = ("ick_decode_select_sample", ()) if rules is None else ("ick_decode_select_sample_rules", (_ref(rules),))
+    L.check(getattr(L.load(), name)(C.byref(ctx), C.byref(sample_state), *extra, pos, _stream()), name)
 
 
 class HeadRows:
