@@ -24,6 +24,7 @@ from torch import nn
 
 from . import ops
 from .lib import IckError
+from .weights import WeightImages, vocab_planes_wanted
 
 VARIANT_TYPE_OFFSET = {"geo": 4, "knowledge": 6, "news": 5}
 VARIANT_NUM_TYPES = {"geo": 1000, "knowledge": 1000, "news": 20}
@@ -348,9 +349,8 @@ class CaptionEmbedder(nn.Module):
 # Device-side caches a module keeps in its __dict__ (captured graphs, packed / pre-split weight copies, pinned staging):
 # never part of a pickle (checkpoints pickle whole modules, geo-aware/utils.py:32-46) or of a deep copy -- they are rebuilt
 # on first use.
-_CACHE_KEYS = ("_graphs", "_kv_pack", "_pred_wt_cache", "_len_pin", "_idx_pin", "_plist", "_pin_ev", "_dec_pack",
-               "_chain_cache", "_chain_cache_bwd", "_chain_ok", "_chain_bwd_ok", "_ps_cache", "_last_static", "_enc",
-               "_score_gmap_checked")
+_CACHE_KEYS = ("_graphs", "_images", "_len_pin", "_idx_pin", "_plist", "_pin_ev", "_chain_ok", "_chain_bwd_ok", "_ps_cache",
+               "_last_static", "_enc", "_score_gmap_checked")
 
 
 def _state_without_caches(module):
@@ -574,11 +574,10 @@ class DecoderTransformer(nn.Module):
 
     def invalidate_caches(self):
         """Call after parameters were modified outside torch's version tracking (the fused Adam kernel
-        writes the flat bucket directly): drops the packed cross-K/V weights, the transposed predicate
-        weights and every captured graph."""
+        writes the flat bucket directly): every captured graph is dropped and the re-laid-out weight copies
+        (weight_images) become stale -- they keep their buffers, which captured training and SCST graphs write."""
         self.__dict__["_param_epoch"] = self.__dict__.get("_param_epoch", 0) + 1
-        for k in ("_kv_pack", "_pred_wt_cache", "_graphs", "_plist", "_dec_pack", "_last_static"):   # (_chain_cache keeps its buffer:
-            # captured training graphs write it; its key holds _param_epoch, so the contents are refreshed)
+        for k in ("_graphs", "_plist", "_last_static"):
             self.__dict__.pop(k, None)
 
     def _token_major(self, encoder_out):
@@ -614,59 +613,33 @@ class DecoderTransformer(nn.Module):
         t = self._token_major(encoder_out)
         return t, t.shape[1]
 
-    def _packed_cross_kv(self):
-        """[K_0;V_0;K_1;V_1;...] rows of the decoder layers' cross-attention in_proj, so the memory is
-        projected for all layers by one GEMM (cached until a parameter changes)."""
-        layers = self.transformer_decoder.layers
-        key = tuple(l.multihead_attn.in_proj_weight._version for l in layers) + tuple(
-            l.multihead_attn.in_proj_bias._version for l in layers) + tuple(
-            l.multihead_attn.in_proj_weight.data_ptr() for l in layers)
-        cache = self.__dict__.get("_kv_pack")
-        if cache is None or cache[0] != key:
-            d = self.emb_dim
-            w = torch.cat([l.multihead_attn.in_proj_weight.detach()[d:] for l in layers]).contiguous()
-            b = torch.cat([l.multihead_attn.in_proj_bias.detach()[d:] for l in layers]).contiguous()
-            cache = (key, w, b)
-            self.__dict__["_kv_pack"] = cache
-        return cache[1], cache[2]
+    def weight_images(self):
+        """The owner of every re-laid-out copy of this decoder's weights (weights.WeightImages).  One object per parameter
+        storage: when a parameter has moved (.to(), a replaced Parameter) a new one is built and the captured graphs,
+        which read the old one's buffers, go with it."""
+        wi = self.__dict__.get("_images")
+        if wi is None or not wi.matches():
+            if wi is not None:
+                self.__dict__.get("_graphs", {}).clear()       # (in place: _graphed may be holding the dictionary)
+            wi = self.__dict__["_images"] = WeightImages(self)
+        return wi
 
-    def _cross_kv_presplit(self, wkv):
-        """Pre-split copy of the all-layer cross K/V weight (the image rows' projection reads it as b_ps)."""
-        layers = self.transformer_decoder.layers
-        key = tuple(l.multihead_attn.in_proj_weight._version for l in layers) + (
-            wkv.data_ptr(), self.__dict__.get("_param_epoch", 0))
-        return ops.presplit_cached(self, "wkv", wkv, key)
+    def _packed_cross_kv(self):
+        """[K_0;V_0;K_1;V_1;...] rows of the layers' cross-attention in_proj (weight, bias): one GEMM projects the memory."""
+        wi = self.weight_images().current("kv")
+        return wi.wkv, wi.bkv
 
     def _vocab_presplit(self, rows):
         """Pre-split copy of fc_vocab's weight for the vocabulary GEMM over `rows` rows (None below 256 rows)."""
-        if rows < 256:
-            return None
-        w = self.fc_vocab.weight
-        return ops.presplit_cached(self, "vocab", w.detach(), (w._version, w.data_ptr(), self.__dict__.get("_param_epoch", 0)))
+        return self.weight_images().planes("vocab_ps", rows)
 
-    def _chain_items(self):
-        """(key, weight view) of every nn.Linear that a row-chain launch (ops.rowchain_fwd) multiplies with: per layer
-        the self-attention out-projection, the cross-attention q-projection and out-projection, linear1, linear2,
-        and -- from the second layer of a stack on -- the self-attention in_proj, which rides on the previous layer's
-        linear2 + norm launch."""
-        d = self.emb_dim
-        items = []
-        for li, layer in enumerate(self.transformer_decoder.layers):
-            items += [(("d", li, "so"), layer.self_attn.out_proj.weight), (("d", li, "cq"), layer.multihead_attn.in_proj_weight[:d]),
-                      (("d", li, "co"), layer.multihead_attn.out_proj.weight), (("d", li, "l1"), layer.linear1.weight),
-                      (("d", li, "l2"), layer.linear2.weight)]
-            if li > 0:
-                items.append((("d", li, "si"), layer.self_attn.in_proj_weight))     # layer 0's in_proj is a plain GEMM
-        stacks = [("e", self.transformer_encoder_entities)]
-        if self.has_facts:
-            stacks.append(("f", self.transformer_encoder_facts))
-        for tag, stack in stacks:
-            for li, layer in enumerate(stack.layers):
-                items += [((tag, li, "so"), layer.self_attn.out_proj.weight), ((tag, li, "l1"), layer.linear1.weight),
-                          ((tag, li, "l2"), layer.linear2.weight)]
-                if li > 0:
-                    items.append(((tag, li, "si"), layer.self_attn.in_proj_weight))
-        return items
+    def _pred_wt(self):
+        return self.weight_images().current("pred_wt").pred_wt
+
+    def _decode_pack(self):
+        """Transposed out_proj / linear2 weights of the decoder layers for the fused decode kernels (one input
+        feature per row, so a workgroup's slice of the out-projection is read coalesced)."""
+        return self.weight_images().current("decode").decode
 
     def chain_supported(self):
         """Do the layer widths fit the row-chain kernel (ick_rowchain_supported)?  ICK_NO_ROWCHAIN=1 turns it off."""
@@ -679,57 +652,6 @@ class DecoderTransformer(nn.Module):
             self.__dict__["_chain_ok"] = cached
         return cached
 
-    def _chain_items_bwd(self):
-        """(key, transposed weight view) for the backward chains (ops.rowchain_bwd): the data gradient of a Linear
-        multiplies with W, i.e. the row-chain GEMM reads a packed copy of W.T."""
-        items = []
-        for key, w in self._chain_items():
-            items.append(((key[0], key[1], key[2] + "T"), w.t()))
-        return items
-
-    def _chain_pack(self, fresh=False, bwd=False, subset=None, extra=None, copies=()):
-        """Packed copies (ops.pack_weights) of the weights the row-chain launches read, as {key: tensor} views of one
-        persistent buffer (bwd: of the transposed weights, for the data-gradient chains).  Refreshed when a parameter's
-        version changed, or on every call with fresh=True (inside the captured training step, where the fused Adam
-        updates the weights behind torch's version counters); then `subset` (a predicate on the item key) limits the
-        launch to the copies the caller needs first -- the rest follows in a later call.  extra: (key, 2-D view) of
-        per-call tensors packed in the same launch into persistent buffers of their own (the transposed all-layer cross
-        K/V weight of the backward pass); their copies are returned under `key`.  copies: plain (src, dst) 2-D copies
-        that ride in the same launch (only with fresh=True)."""
-        items = self._chain_items_bwd() if bwd else self._chain_items()
-        name = "_chain_cache_bwd" if bwd else "_chain_cache"
-        cache = self.__dict__.get(name)
-        key = tuple(w._version for _, w in items) + (items[0][1].data_ptr(), self.__dict__.get("_param_epoch", 0))
-        if cache is None or cache["ptr"] != items[0][1].data_ptr() or cache["buf"].device != items[0][1].device:
-            sizes = [ops.packed_weight_floats(w.shape[0], w.shape[1]) for _, w in items]
-            buf = torch.empty(sum(sizes), device=items[0][1].device, dtype=torch.float32)
-            views, off = {}, 0
-            for (k, _), n in zip(items, sizes):
-                views[k] = buf[off:off + n]
-                off += n
-            cache = {"ptr": items[0][1].data_ptr(), "buf": buf, "views": views, "key": None}
-            self.__dict__[name] = cache
-        more = []
-        for k, w in (extra or []):
-            n = ops.packed_weight_floats(w.shape[0], w.shape[1])
-            buf = cache.setdefault("extra", {}).get(k)
-            if buf is None or buf.numel() != n or buf.device != w.device:
-                buf = cache["extra"][k] = torch.empty(n, device=w.device, dtype=torch.float32)
-            more.append((w.detach(), buf))
-        assert not copies or fresh
-        if fresh and subset is not None:
-            ops.pack_weights([(w.detach(), cache["views"][k]) for k, w in items if subset(k)] + more, copies)
-        elif fresh or cache["key"] != key:
-            ops.pack_weights([(w.detach(), cache["views"][k]) for k, w in items] + more, copies)
-            cache["key"] = key
-        elif more:
-            ops.pack_weights(more)
-        if extra:
-            views = dict(cache["views"])
-            views.update({k: cache["extra"][k] for k, _ in extra})
-            return views
-        return cache["views"]
-
     def chain_bwd_supported(self):
         cached = self.__dict__.get("_chain_bwd_ok")
         if cached is None:
@@ -740,15 +662,6 @@ class DecoderTransformer(nn.Module):
                 ops.rowchain_bwd_supported(max(3, 2 * len(self.transformer_decoder.layers)) * d, d, ff)
             self.__dict__["_chain_bwd_ok"] = cached
         return cached
-
-    def _pred_wt(self):
-        w = self.fc_predicate.weight
-        key = (w._version, w.data_ptr())
-        cache = self.__dict__.get("_pred_wt_cache")
-        if cache is None or cache[0] != key:
-            cache = (key, w.detach().t().contiguous())
-            self.__dict__["_pred_wt_cache"] = cache
-        return cache[1]
 
     def _encode_context(self, enc_tok, entities, facts, gmap):
         """Entity / fact encoders, context transformers and the all-layer cross K/V projection.
@@ -769,10 +682,10 @@ class DecoderTransformer(nn.Module):
         K = entities.shape[1]
         Fn = facts.shape[1] if self.has_facts else 0
         ee, fe = self._encode_entities(entities, facts)
-        wkv, bkv = self._packed_cross_kv()
-        wkv_ps = self._cross_kv_presplit(wkv)
         # refreshed (if stale) on the main stream, before the side stream forks
-        pk = self._chain_pack() if self.chain_supported() else None
+        wi = self.weight_images().current("kv", *(("chain",) if self.chain_supported() else ()))
+        wkv, bkv, wkv_ps = wi.wkv, wi.bkv, wi.planes("kv_ps")
+        pk = wi.chain if self.chain_supported() else None
         nseg = wkv.shape[0] // d
         S = P + K + Fn
         kv = torch.empty(B, nseg, H, S, ops.DHP, device=enc_tok.device, dtype=torch.float32)
@@ -829,7 +742,7 @@ class DecoderTransformer(nn.Module):
         return ee, fe, kv, (ctx_e, ctx_f), side
 
     # ------------------------------------------------------------------ layer forward (inference and training.py)
-    # Shared by the inference forward and training.forward_with_tape.  pk: the packed row-chain weights (_chain_pack) ->
+    # Shared by the inference forward and training.forward_with_tape.  pk: the packed row-chain weights (weight_images().chain) ->
     # each out-projection / linear2 runs in one ops.rowchain_fwd launch together with its add & norm and the next
     # projection; pk None -> the separate GEMM / add & norm kernels.  ds hands out the dropout sites (training only).
     # save: keep what the backward pass needs -- o_out, the norm statistics and the attention lse -- in the layer's dict.
@@ -1061,7 +974,7 @@ class DecoderTransformer(nn.Module):
         # the context chain, which is what the first cross-attention waits for: forward 0.694 -> 0.715 ms.)
         ee, fe, kv, ctx, side = self._encode_context(enc_tok, entities, facts, gmap)
         x, emb = embed(ee, fe)
-        pk = self._chain_pack() if self.chain_supported() else None     # as _encode_context refreshed it
+        pk = self.weight_images().current("chain").chain if self.chain_supported() else None    # as _encode_context refreshed it
         qkv = None
         S = kv.shape[3]
         for li, layer in enumerate(self.transformer_decoder.layers):
@@ -1286,57 +1199,20 @@ class DecoderTransformer(nn.Module):
         return self._score_captions(caps, encoder_out, masks, lengths, entities, facts, index, top_k)
 
     # ------------------------------------------------------------------ greedy decode (KV cached)
-    def _decode_pack(self):
-        """Transposed out_proj / linear2 weights of the decoder layers for the fused decode kernels (one input
-        feature per row, so a workgroup's slice of the out-projection is read coalesced); cached until a parameter
-        changes."""
-        layers = self.transformer_decoder.layers
-        src = [w for l in layers for w in (l.self_attn.out_proj.weight, l.multihead_attn.out_proj.weight, l.linear2.weight)]
-        key = tuple(w._version for w in src) + tuple(w.data_ptr() for w in src)
-        cache = self.__dict__.get("_dec_pack")
-        if cache is None or cache[0] != key:
-            cache = (key, [w.detach().t().contiguous() for w in src])
-            self.__dict__["_dec_pack"] = cache
-        return cache[1]
-
     def _refresh_decode_copies(self, rows):
         """Re-derive IN PLACE, from the live parameters, every re-laid-out weight copy the decode paths (predict,
         predict_sample over `rows` rows) read: the gathered cross K/V weight and bias, _decode_pack's transposed
         out_proj / linear2, the transposed predicate weight, the context encoders' packed row-chain images and the
         pre-split planes.  One ick_pack_weights launch (+ one ick_presplit_weights launch in the split product modes), so
         it can open a captured decode graph that must stay valid across optimizer steps which update the parameters
-        behind torch's version counters (SelfCriticalStep).  Returns the buffers: the caller keeps them alive while a graph
-        reads them (invalidate_caches() drops the decoder's own references)."""
-        d = self.emb_dim
-        layers = self.transformer_decoder.layers
-        wkv, bkv = self._packed_cross_kv()
-        dpack = self._decode_pack()
-        copies = []
-        for i, l in enumerate(layers):
-            copies.append((l.multihead_attn.in_proj_weight.detach()[d:], wkv[2 * d * i:2 * d * (i + 1)]))
-            copies.append((l.multihead_attn.in_proj_bias.detach()[d:].view(1, -1), bkv[2 * d * i:2 * d * (i + 1)].view(1, -1)))
-        src = [w for l in layers for w in (l.self_attn.out_proj.weight, l.multihead_attn.out_proj.weight, l.linear2.weight)]
-        copies += [(w.detach().t(), t) for w, t in zip(src, dpack)]
-        keep = [wkv, bkv] + list(dpack)
-        if self.has_facts:
-            pw = self._pred_wt()
-            copies.append((self.fc_predicate.weight.detach().t(), pw))
-            keep.append(pw)
-        if self.chain_supported():      # only the context encoders' images: the decode kernels read the layers directly
-            keep += list(self._chain_pack(fresh=True, subset=lambda k: k[0] != "d", copies=copies).values())
-        else:
-            ops.pack_weights([], copies)
-        ps = []
-        wkv_ps = self._cross_kv_presplit(wkv)
-        if wkv_ps is not None:
-            ps.append((wkv, wkv_ps))
-        vocab_ps = None if self.fused_decode else self._vocab_presplit(rows)
-        if vocab_ps is not None:       # the unfused greedy path's score head
-            ps.append((self.fc_vocab.weight.detach(), vocab_ps))
-        if ps:
-            ops.presplit_weights(ps)
-            keep += [b for _, b in ps]
-        return keep
+        behind torch's version counters (SelfCriticalStep)."""
+        groups = ("kv", "decode", "pred_wt") + (("chain",) if self.chain_supported() else ())
+        if ops.gemm_split_mode() != 0:
+            groups += ("kv_ps",)
+            if not self.fused_decode and vocab_planes_wanted(rows):      # the unfused greedy path's score head
+                groups += ("vocab_ps",)
+        # only the context encoders' chain images: the decode kernels read the layers directly
+        self.weight_images().refresh(*groups, subset=lambda k: k[0] != "d")
 
     def _decode_ctx(self, kv, ee, fe, rows_per_sample, max_len, S, anc=None, want_scores=False, fuse_select=False,
                     n_done_init=0):

@@ -88,19 +88,16 @@ class SelfCriticalStep:
         dec = self.dec
         full = (kind, key, ops.gemm_split_mode(), self.ts.flat_p.data_ptr())
         g = self._graphs.get(full)
-        if g is None:
-            keep = []
-
+        if g is None or g.images is not dec.__dict__.get("_images"):      # (a graph reads its owner's buffers, and holds it)
             def body(*ins):
-                keep.append(dec._refresh_decode_copies(rows))
+                dec._refresh_decode_copies(rows)
                 return fn(*ins)
 
             if len(self._graphs) >= 8:
                 self._graphs.clear()
             with torch.no_grad():
                 g = _GraphedCall(body, inputs)
-            g.keep = keep
-            self._graphs[full] = g
+            self._graphs[full], g.images = g, dec.weight_images()
             self.captures += 1
         with torch.no_grad():
             return g(*inputs)

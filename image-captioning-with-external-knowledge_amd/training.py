@@ -26,7 +26,7 @@ import torch
 from . import dp, ops
 from .decoder import DropSites
 from .lib import IckError
-from .weights import DerivedWeights      # noqa: F401  (the optimizer-maintained weight images; also imported from here)
+from .weights import DerivedWeights, first_stage, vocab_planes_wanted      # noqa: F401  (DerivedWeights is also imported from here)
 
 
 class Tape:
@@ -91,54 +91,34 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
         side_tail()
 
     chain = dec.chain_supported()
+    chain_t = chain and dec.chain_bwd_supported()
     staged = chain and fresh_pack and overlap and derived is None
-    first = lambda k: k[0] != "d" or (k[1] == 0 and k[2] in ("so", "cq", "si"))     # context encoders + layer 0's self block
     split_on = ops.gemm_split_mode() >= 1 and not ops.is_deterministic()
 
     lazy = pre_side is not None and side is not None and feats is not None and derived is not None
     if pre_side is not None and not lazy:
         pre_side()
     ee, fe = (None, None) if lazy else dec._encode_entities(entities, facts)
-    if derived is not None:
-        wkv, bkv, pk = derived.wkv, derived.bkv, derived.pk
-        m["pkb"] = derived.pkb
-        if split_on:
-            m["wkv_ps"] = derived.wkv_ps
-            if B * L >= 256:
-                m["vocab_ps"], m["vocab_t_ps"] = derived.vocab_ps, derived.vocab_t_ps
-    else:
-        copies = []
-        if fresh_pack:
-            layers_ = dec.transformer_decoder.layers
-            if chain:
-                # the all-layer cross K/V weight and bias gathered by the packing launch below (two torch.cat
-                # launches less in front of Encoder.conv1 and the context chain)
-                wkv = torch.empty(nseg * d, d, device=dev, dtype=torch.float32)
-                bkv = torch.empty(nseg * d, device=dev, dtype=torch.float32)
-                for i_, l in enumerate(layers_):
-                    copies.append((_p(l.multihead_attn.in_proj_weight)[d:], wkv[2 * d * i_:2 * d * (i_ + 1)]))
-                    copies.append((_p(l.multihead_attn.in_proj_bias)[d:].view(1, -1),
-                                   bkv[2 * d * i_:2 * d * (i_ + 1)].view(1, -1)))
-            else:
-                wkv = torch.cat([_p(l.multihead_attn.in_proj_weight)[d:] for l in layers_])
-                bkv = torch.cat([_p(l.multihead_attn.in_proj_bias)[d:] for l in layers_])
-        else:
-            wkv, bkv = dec._packed_cross_kv()
-        # packed weight copies of the row-chain launches.  Inside a captured step that does not keep them current itself
-        # (derived is None) they are refreshed in three launches placed where they cost least: the context encoders'
-        # copies now (the side chain needs them first), the decoder layers' after Encoder.conv1 has been enqueued, the
-        # transposed copies of the backward chains on the side stream once the context chain is done.
-        pk = dec._chain_pack(fresh=fresh_pack, subset=first if staged else None, copies=copies) if chain else None
+    # The re-laid-out weight copies.  `derived` keeps them current itself; a captured step without it (fresh_pack) re-fills
+    # them, the packed row-chain images in three launches placed where they cost least: the context encoders' now (the side
+    # chain needs them first; the cross K/V weight and bias ride along), the decoder layers' after Encoder.conv1 has been
+    # enqueued, the transposed images of the backward chains on the side stream once the context chain is done.
+    wi = dec.weight_images()
+    fill = None if derived is not None else wi.refresh if fresh_pack else wi.current
+    if staged:
+        wi.refresh("kv", "chain", subset=first_stage)
+    elif fill is not None:
+        fill("kv", *(("chain",) if chain else ()))
+    wkv, bkv = wi.wkv, wi.bkv
+    pk = wi.chain if chain else None
 
     def kv_presplit():
         # pre-split copy (three bf16 planes) of the all-layer cross K/V weight for the image rows' projection (ick_gemm's
         # b_ps, csrc/gemm_ps.hip); with a side stream it is made behind the fork: only the main stream reads it
-        if derived is None and split_on:
-            if fresh_pack:
-                m["wkv_ps"] = ops.presplit_buffer(nseg * d, d, dev)
-                ops.presplit_weights([(wkv, m["wkv_ps"])])
-            else:
-                m["wkv_ps"] = dec._cross_kv_presplit(wkv)
+        if split_on:
+            if fill is not None:
+                fill("kv_ps")
+            m["wkv_ps"] = wi.kv_ps
 
     if side is None:
         kv_presplit()
@@ -147,14 +127,12 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
         # fc_vocab's pre-split copies: nothing needs them before the score head, so they are made where the side stream
         # idles.  The transposed one is the B operand of the data gradient dh = dscores @ W on the pre-split kernel (128 x 80
         # tile, 40 tiles x 12 K slices: cfg2 train step 1.770 -> 1.741 ms, profiles/r04_y_ab_vocab_dgrad_ps.txt)
-        if derived is None and split_on and B * L >= 256:
-            if fresh_pack:
-                m["vocab_ps"] = ops.presplit_buffer(V, d, dev)
-                m["vocab_t_ps"] = ops.presplit_buffer(d, V, dev)
-                ops.presplit_weights([(_p(dec.fc_vocab.weight), m["vocab_ps"]),
-                                      (_p(dec.fc_vocab.weight).t(), m["vocab_t_ps"])])
-            else:
-                m["vocab_ps"] = dec._vocab_presplit(B * L)
+        if split_on and vocab_planes_wanted(B * L):
+            groups = ("vocab_ps", "vocab_t_ps") if derived is not None or fresh_pack else ("vocab_ps",)
+            if fill is not None:
+                fill(*groups)
+            for g in groups:
+                m[g] = getattr(wi, g)
 
     head = {}
 
@@ -175,8 +153,8 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
             side.signal("ctx")      # the first cross-attention waits for this point, not for the packing / zeroing below
         ops.stamp("side: context chain done")
         # bulk work nothing waits for before the score head / the backward pass
-        if staged and dec.chain_bwd_supported():
-            m["pkb"] = dec._chain_pack(fresh=True, bwd=True, extra=[(("kv", "T"), wkv.t())])
+        if staged and chain_t:
+            wi.refresh("chain_t")
         vocab_presplit()
         if side is not None and side_tail is not None:
             side_tail()
@@ -209,9 +187,11 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
             ee, fe = head["ee"], head["fe"]
         kv_presplit()
     if staged:
-        dec._chain_pack(fresh=True, subset=lambda k: not first(k))
-    elif derived is None and pk is not None and dec.chain_bwd_supported():
-        m["pkb"] = dec._chain_pack(fresh=fresh_pack, bwd=True, extra=[(("kv", "T"), wkv.t())])
+        wi.refresh("chain", subset=lambda k: not first_stage(k))
+    elif fill is not None and chain_t:
+        fill("chain_t")
+    if chain_t:
+        m["pkb"] = wi.chain_t
     if dec.has_facts:
         # on the main stream, beside the entity chain on the side stream: two chains of small kernels overlap well
         # (a chain beside the large projection below does not)
@@ -237,11 +217,9 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
     ops.stamp("fwd: decoder layers done")
     eib = gate = hv = None
     if dec.has_facts:
-        if derived is not None:
-            pred_wt = derived.pred_wt
-        else:
-            pred_wt = _p(dec.fc_predicate.weight).t().contiguous() if fresh_pack else dec._pred_wt()
-        eib, gate = ops.context_indicators(captions, facts, K, V, pred_wt, _p(dec.fc_predicate.bias), mode=0)
+        if fill is not None:
+            fill("pred_wt")
+        eib, gate = ops.context_indicators(captions, facts, K, V, wi.pred_wt, _p(dec.fc_predicate.bias), mode=0)
         hv = ops.mul(x, gate)
     Vx = V + K + Fn
     # rows padded to a multiple of 4 floats (knowledge: 50 000 + 20 + 51 = 50 071 columns): the vocabulary's data- and
@@ -301,7 +279,7 @@ def _norm_args(t, i, res, layer_norm, grads, M, d, dev):
 
 
 def _context_encoder_bwd(dec, stack, tapes, dx, grads, pkb=None, tag="e", g_first=None):
-    """pkb: packed transposed weights (dec._chain_pack(bwd=True)) -> one ops.rowchain_bwd launch per layer for
+    """pkb: packed transposed weights (dec.weight_images().chain_t) -> one ops.rowchain_bwd launch per layer for
     [in_proj data gradient of the layer above] + norm2' + linear2' + ReLU' + linear1' + norm1' + out_proj' instead
     of six kernels.  g_first = (g0 rows view, packed W0^T): the incoming gradient is g0 @ W0 (no dx tensor)."""
     H, d = dec.num_heads, dec.emb_dim
@@ -1271,7 +1249,7 @@ class TrainStep:
                 self.derived = DerivedWeights.build(self)
                 self._graphs.clear()
         if self.derived is not None:
-            self.derived.ensure_current()
+            self.derived.ensure_current(check=key not in self._graphs)
         if self.use_graph and key not in self._graphs:
             self.flush()                  # the warm-up runs below must not find gradients waiting to be applied
             if len(self._graphs) >= 4:

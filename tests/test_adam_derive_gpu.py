@@ -21,12 +21,11 @@ pytestmark = pytest.mark.gpu
 
 
 def _images(dw):
-    dec = dw.dec
-    out = {"pk": dec.__dict__["_chain_cache"]["buf"], "pkb": dec.__dict__["_chain_cache_bwd"]["buf"],
-           "kvT": dw.pkb[("kv", "T")], "wkv": dw.wkv, "bkv": dw.bkv, "wkv_ps": dw.wkv_ps, "vocab_ps": dw.vocab_ps,
-           "vocab_t_ps": dw.vocab_t_ps}
-    if dw.pred_wt is not None:
-        out["pred_wt"] = dw.pred_wt
+    wi = dw.owner
+    out = {"pk": wi.flat["chain"], "pkb": wi.flat["chain_t"], "kvT": wi.chain_t[("kv", "T")], "wkv": wi.wkv, "bkv": wi.bkv,
+           "wkv_ps": wi.kv_ps, "vocab_ps": wi.vocab_ps, "vocab_t_ps": wi.vocab_t_ps}
+    if wi.pred_wt is not None:
+        out["pred_wt"] = wi.pred_wt
     return out
 
 
@@ -62,10 +61,10 @@ def test_update_and_images_are_bit_identical_to_the_separate_kernels(variant, V)
     # ... and the images are the updated weights' (not the old ones'): spot checks against the parameters themselves
     d = dec.emb_dim
     l0 = dec.transformer_decoder.layers[0]
-    assert torch.equal(dw.wkv[:2 * d], l0.multihead_attn.in_proj_weight.detach()[d:])
-    assert torch.equal(dw.bkv[:2 * d], l0.multihead_attn.in_proj_bias.detach()[d:])
-    if dw.pred_wt is not None:
-        assert torch.equal(dw.pred_wt, dec.fc_predicate.weight.detach().t())
+    assert torch.equal(dw.owner.wkv[:2 * d], l0.multihead_attn.in_proj_weight.detach()[d:])
+    assert torch.equal(dw.owner.bkv[:2 * d], l0.multihead_attn.in_proj_bias.detach()[d:])
+    if dw.owner.pred_wt is not None:
+        assert torch.equal(dw.owner.pred_wt, dec.fc_predicate.weight.detach().t())
 
 
 def test_zero_token_batch_leaves_parameters_and_images_alone():

@@ -78,7 +78,9 @@ def test_row_chain_weight_items_cover_every_launch():
     for variant, stacks in (("geo", 1), ("knowledge", 2)):
         m = ick_amd.load_models(variant)
         dec = m.DecoderTransformer(synth.make_word_map(60), 300, 512, 512, 10, 3)
-        items = dict(dec._chain_items())
+        wi = dec.weight_images()
+        table = wi.groups
+        items = {e.key: e.src(wi) for e in table["chain"]}
         nl = 3
         assert len(items) == (6 * nl - 1) + stacks * (4 * nl - 1)
         d = dec.emb_dim
@@ -91,7 +93,8 @@ def test_row_chain_weight_items_cover_every_launch():
         # the q-projection item is the first d rows of the packed in_proj weight (a view, not a copy)
         w = dec.transformer_decoder.layers[0].multihead_attn.in_proj_weight
         assert items[("d", 0, "cq")].data_ptr() == w.data_ptr()
-        bwd = dict(dec._chain_items_bwd())
+        assert table["chain_t"][-1].key == ("kv", "T")       # made from the gathered cross K/V weight, not a parameter
+        bwd = {e.key: e.src(wi) for e in table["chain_t"][:-1]}
         assert set(bwd) == {(a, b, c + "T") for (a, b, c) in items}
         for (a, b, c), v in items.items():
             assert bwd[(a, b, c + "T")].shape == (v.shape[1], v.shape[0])
