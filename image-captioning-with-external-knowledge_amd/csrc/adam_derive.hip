@@ -15,20 +15,25 @@
 // The arithmetic is adam_clamp_kernel's, operation for operation (tests/test_adam_derive_gpu.py: bit-identical
 // parameters and moments; images bit-identical to ick_pack_weights / ick_presplit_weights of the updated weights).
 #include "gemm_common.h"
+#include "opt_words.h"
 
 namespace ick {
 namespace {
 
 struct AdamHyper {
-    float gscale, clip, b1, b2, c1, c2, eps, step, bc2_sqrt;
+    float gscale, clip, b1, b2, c1, c2, eps, step, bc2_sqrt, coef;
 };
 
+// kOpt (ick_adam_opt_derive): the gradient times the global-norm clip's coefficient between the scale and
+// the clamp, as an operation of its own (coef == 1: the plain instantiation's bits)
+template <bool kOpt>
 __device__ __forceinline__ void adam4(const AdamHyper& h, float4& p, float4& g, float4& m, float4& v) {
     float ga[4] = {g.x, g.y, g.z, g.w}, ma[4] = {m.x, m.y, m.z, m.w}, va[4] = {v.x, v.y, v.z, v.w};
     float pa[4] = {p.x, p.y, p.z, p.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {      // the arithmetic of adam_clamp_kernel (csrc/backward.hip), operation for operation
         float x = ga[k] * h.gscale;
+        if (kOpt) x = x * h.coef;
         if (h.clip > 0.f) x = fminf(fmaxf(x, -h.clip), h.clip);
         ga[k] = x;
         ma[k] = h.b1 * ma[k] + h.c1 * x;
@@ -44,12 +49,14 @@ __device__ __forceinline__ void adam4(const AdamHyper& h, float4& p, float4& g, 
 constexpr int kT = 64;        // tile edge
 constexpr int kLd = 68;       // LDS row stride of the tile (16-byte aligned rows, 4 banks of skew per row)
 
+template <bool kOpt>
 __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p, float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v,
                                                           const ick_adam_item* __restrict__ items,
                                                           const ick_adam_block* __restrict__ blocks, float gscale,
                                                           float clip, float lr, float b1, float b2, float eps, int step0,
-                                                          const uint32_t* step_ptr, const float* __restrict__ gscale_den) {
+                                                          const uint32_t* step_ptr, const float* __restrict__ gscale_den,
+                                                          float* words, ick_lr_schedule sched) {
     __shared__ __attribute__((aligned(16))) float tile[kT * kLd];
     const ick_adam_block blk = blocks[blockIdx.x];
     if (gscale_den) {
@@ -62,6 +69,12 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
         const float t = (float)(step0 + (step_ptr ? (int)*step_ptr : 0));
         const float bc1 = 1.f - powf(b1, t);
         h.bc2_sqrt = sqrtf(1.f - powf(b2, t));
+        h.coef = 1.f;
+        if (kOpt) {        // the step's rate from the base rate word and the schedule; workgroup 0 reports it
+            lr = lr_schedule(words[kWordBaseLr], sched, t);
+            h.coef = words[kWordCoef];
+            if (blockIdx.x == 0 && threadIdx.x == 0) words[kWordLrNow] = lr;
+        }
         h.step = lr / bc1;
         h.gscale = gscale; h.clip = clip; h.b1 = b1; h.b2 = b2; h.c1 = 1.f - b1; h.c2 = 1.f - b2; h.eps = eps;
     }
@@ -83,7 +96,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
         for (int i = 0; i < 4; ++i) {
             const int j = tid + 256 * i;
             if (j < blk.cnt4) {
-                adam4(h, pi[i], gi[i], mi[i], vi[i]);
+                adam4<kOpt>(h, pi[i], gi[i], mi[i], vi[i]);
                 g4[j] = gi[i]; m4[j] = mi[i]; v4[j] = vi[i]; p4[j] = pi[i];
                 if (blk.copy) reinterpret_cast<float4*>(blk.copy)[j] = pi[i];
             }
@@ -117,7 +130,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
             const int row = idx >> 4, c4 = idx & 15;
             float4 out = make_float4(0.f, 0.f, 0.f, 0.f);      // outside the item / the matrix: zeros (the images' padding)
             if (at[i] >= 0) {
-                adam4(h, pi[i], gi[i], mi[i], vi[i]);
+                adam4<kOpt>(h, pi[i], gi[i], mi[i], vi[i]);
                 *reinterpret_cast<float4*>(g + at[i]) = gi[i];
                 *reinterpret_cast<float4*>(m + at[i]) = mi[i];
                 *reinterpret_cast<float4*>(v + at[i]) = vi[i];
@@ -218,15 +231,33 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
 }  // namespace
 }  // namespace ick
 
-extern "C" int ick_adam_clamp_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
-                                     const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
-                                     float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                                     const float* gscale_den, void* stream) {
+template <bool kOpt>
+static int launch_adam_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
+                              const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
+                              float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                              const uint32_t* step_ptr, const float* gscale_den, void* stream) {
     using namespace ick;
     ICK_CHECK_ARG(p && g && m && v && blocks && n_blocks > 0 && (step >= 1 || step_ptr != nullptr));
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     if (!(al16(p) && al16(g) && al16(m) && al16(v))) return ICK_EALIGN;
-    hipLaunchKernelGGL(adam_derive_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, items, blocks,
-                       gscale, clip, lr, beta1, beta2, eps, step, step_ptr, gscale_den);
+    hipLaunchKernelGGL(adam_derive_kernel<kOpt>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, items,
+                       blocks, gscale, clip, lr, beta1, beta2, eps, step, step_ptr, gscale_den, words, sched);
     ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_adam_clamp_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
+                                     const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
+                                     float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
+                                     const float* gscale_den, void* stream) {
+    return launch_adam_derive<false>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr, nullptr, ick_lr_schedule{},
+                                     beta1, beta2, eps, step, step_ptr, gscale_den, stream);
+}
+
+extern "C" int ick_adam_opt_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
+                                   const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float* words,
+                                   ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                                   const uint32_t* step_ptr, const float* gscale_den, void* stream) {
+    ICK_CHECK_ARG(words != nullptr && ick::lr_schedule_ok(sched));
+    return launch_adam_derive<true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words, sched, beta1, beta2,
+                                    eps, step, step_ptr, gscale_den, stream);
 }

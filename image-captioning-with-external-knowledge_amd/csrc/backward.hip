@@ -5,6 +5,7 @@
 // embedding and encoder stages, the pointer-score head, the predicate gate, and the fused
 // clamp + Adam update.
 #include "common.h"
+#include "opt_words.h"
 
 namespace ick {
 namespace {
@@ -532,11 +533,16 @@ __global__ __launch_bounds__(256) void context_gate_bwd_kernel(const int64_t* __
 //   g = clamp(g * gscale [/ *gscale_den], -clip, clip);  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // ---------------------------------------------------------------------------------------------
+// kOpt (ick_adam_opt): lr = schedule(words[0], t) instead of the literal, the gradient times words[3]
+// (the global-norm clip's coefficient) between the scale and the clamp, as an operation of its own -- with coef == 1 and a
+// constant schedule the bits are the plain instantiation's; workgroup 0 leaves the rate it used in words[4].
+template <bool kOpt>
 __global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                          float gscale, float clip, float lr, float b1, float b2,
                                                          float eps, int step0, const uint32_t* step_ptr,
-                                                         const float* __restrict__ gscale_den) {
+                                                         const float* __restrict__ gscale_den, float* words,
+                                                         ick_lr_schedule sched) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     if (gscale_den) {
         // a (global) batch without a single contributing token has no mean loss: leave parameters and moments alone
@@ -547,9 +553,16 @@ __global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, 
     const float t = (float)(step0 + (step_ptr ? (int)*step_ptr : 0));
     const float bc1 = 1.f - powf(b1, t);
     const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
+    float coef = 1.f;
+    if (kOpt) {
+        lr = lr_schedule(words[kWordBaseLr], sched, t);
+        coef = words[kWordCoef];
+        if (blockIdx.x == 0 && threadIdx.x == 0) words[kWordLrNow] = lr;
+    }
     const float step = lr / bc1;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         float gi = g[i] * gscale;
+        if (kOpt) gi = gi * coef;
         if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
         g[i] = gi;
         const float mi = b1 * m[i] + (1.f - b1) * gi;
@@ -562,11 +575,13 @@ __global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, 
 
 // The same update on float4: seven 16-byte streams per lane (the scalar form reaches 0.66 of the HBM rate, 320 MB per
 // cfg2 step).  n4 = n / 4 elements of float4; the launcher sends a tail of n % 4 to the scalar kernel.
+template <bool kOpt>
 __global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict__ p, float4* __restrict__ g,
                                                               float4* __restrict__ m, float4* __restrict__ v, int64_t n4,
                                                               float gscale, float clip, float lr, float b1, float b2,
                                                               float eps, int step0, const uint32_t* step_ptr,
-                                                              const float* __restrict__ gscale_den) {
+                                                              const float* __restrict__ gscale_den, float* words,
+                                                              ick_lr_schedule sched) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     if (gscale_den) {
         if (!(gscale_den[0] > 0.f)) return;
@@ -575,6 +590,12 @@ __global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict
     const float t = (float)(step0 + (step_ptr ? (int)*step_ptr : 0));
     const float bc1 = 1.f - powf(b1, t);
     const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
+    float coef = 1.f;
+    if (kOpt) {
+        lr = lr_schedule(words[kWordBaseLr], sched, t);
+        coef = words[kWordCoef];
+        if (blockIdx.x == 0 && threadIdx.x == 0) words[kWordLrNow] = lr;
+    }
     const float step = lr / bc1;
     const float c1 = 1.f - b1, c2 = 1.f - b2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
@@ -587,6 +608,7 @@ __global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict
 #pragma unroll
         for (int k = 0; k < 4; ++k) {      // the arithmetic of adam_clamp_kernel, operation for operation
             float x = ga[k] * gscale;
+            if (kOpt) x = x * coef;
             if (clip > 0.f) x = fminf(fmaxf(x, -clip), clip);
             ga[k] = x;
             mn[k] = b1 * ma[k] + c1 * x;
@@ -746,25 +768,42 @@ extern "C" int ick_context_gate_bwd(const int64_t* captions, const int64_t* fact
     ICK_LAUNCH_RET();
 }
 
-extern "C" int ick_adam_clamp(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr,
-                              float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                              const float* gscale_den, void* stream) {
+// ick_adam_clamp and ick_adam_opt: the float4 kernel over the aligned bulk, the scalar kernel over the rest
+template <bool kOpt>
+static int launch_adam(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr, float* words,
+                       ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
+                       const float* gscale_den, void* stream) {
     ICK_CHECK_ARG(p && g && m && v && n > 0 && (step >= 1 || step_ptr != nullptr));
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     int64_t done = 0;
     if (n >= 4096 && al16(p) && al16(g) && al16(m) && al16(v)) {
         const int64_t n4 = n / 4;
-        hipLaunchKernelGGL(adam_clamp_vec4_kernel, dim3((int)std::min<int64_t>(ceil_div(n4, 256), 4096)), dim3(256), 0,
-                           (hipStream_t)stream, reinterpret_cast<float4*>(p), reinterpret_cast<float4*>(g),
+        hipLaunchKernelGGL(adam_clamp_vec4_kernel<kOpt>, dim3((int)std::min<int64_t>(ceil_div(n4, 256), 4096)), dim3(256),
+                           0, (hipStream_t)stream, reinterpret_cast<float4*>(p), reinterpret_cast<float4*>(g),
                            reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), n4, gscale, clip, lr, beta1, beta2,
-                           eps, step, step_ptr, gscale_den);
+                           eps, step, step_ptr, gscale_den, words, sched);
         done = 4 * n4;
         if (done == n) ICK_LAUNCH_RET();
     }
-    hipLaunchKernelGGL(adam_clamp_kernel, dim3((int)std::min<int64_t>(ceil_div(n - done, 256), 4096)), dim3(256), 0,
+    hipLaunchKernelGGL(adam_clamp_kernel<kOpt>, dim3((int)std::min<int64_t>(ceil_div(n - done, 256), 4096)), dim3(256), 0,
                        (hipStream_t)stream, p + done, g + done, m + done, v + done, n - done, gscale, clip, lr, beta1,
-                       beta2, eps, step, step_ptr, gscale_den);
+                       beta2, eps, step, step_ptr, gscale_den, words, sched);
     ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_adam_clamp(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr,
+                              float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
+                              const float* gscale_den, void* stream) {
+    return launch_adam<false>(p, g, m, v, n, gscale, clip, lr, nullptr, ick_lr_schedule{}, beta1, beta2, eps, step,
+                              step_ptr, gscale_den, stream);
+}
+
+extern "C" int ick_adam_opt(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float* words,
+                            ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                            const uint32_t* step_ptr, const float* gscale_den, void* stream) {
+    ICK_CHECK_ARG(words != nullptr && lr_schedule_ok(sched));
+    return launch_adam<true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step, step_ptr,
+                             gscale_den, stream);
 }
 
 extern "C" int ick_scale_by_ratio(float* x, int64_t n, const float* num, const float* den, void* stream) {

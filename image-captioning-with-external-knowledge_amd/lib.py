@@ -97,6 +97,14 @@ class AdamBlock(C.Structure):     # ick_adam_block: the work of one workgroup of
     _fields_ = [("item", i32), ("tn", i32), ("tk", i32), ("cnt4", i32), ("off4", i64), ("copy", vp)]
 
 
+class LrSchedule(C.Structure):    # ick_lr_schedule: passed BY VALUE to ick_adam_opt[_derive]
+    _fields_ = [("kind", i32), ("warmup", i32), ("total", i32), ("min_ratio", f32)]
+
+
+OPT_WORDS = 8                     # ICK_OPT_WORDS; slots: base lr, max_norm, norm, coef, lr used, sum of squares
+LR_KINDS = {"constant": 0, "inverse_sqrt": 1, "cosine": 2, "linear": 3}
+
+
 class AttnArgs(C.Structure):
     _fields_ = [
         ("Q", vp), ("K", vp), ("V", vp), ("O", vp), ("lse", vp),
@@ -228,6 +236,10 @@ SIGNATURES = {
     "ick_context_gate_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "ick_adam_clamp": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp],
     "ick_adam_clamp_derive": [vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp],
+    "ick_grad_sqnorm_plan": [i64, C.POINTER(i32)],
+    "ick_grad_sqnorm": [vp, i64, f32, vp, vp, i64, vp, vp],
+    "ick_adam_opt": [vp, vp, vp, vp, i64, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp],
+    "ick_adam_opt_derive": [vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp],
     "ick_counter_add": [vp, u32, vp],
     "ick_counter_add_if": [vp, u32, vp, vp],
     "ick_timestamp": [vp, vp],

@@ -1386,6 +1386,70 @@ def adam_clamp_derive(p, g, m, v, items_dev, blocks_dev, n_blocks, step, lr, cli
             "ick_adam_clamp_derive")
 
 
+def _opt_words(words, who):
+    if not isinstance(words, torch.Tensor) or words.dtype != torch.float32 or not words.is_cuda or \
+            words.numel() < L.OPT_WORDS or not words.is_contiguous() or words.data_ptr() % 16:
+        raise L.IckError("%s needs the optimizer words as a contiguous, 16-byte aligned float32 device tensor of %d "
+                         "elements (base lr, max_norm, norm, coef, lr used, sum of squares)" % (who, L.OPT_WORDS))
+    return words
+
+
+def lr_schedule_struct(schedule):
+    """dict(kind=, warmup_steps=, total_steps=, min_lr_ratio=) or None (constant, no warmup) -> lib.LrSchedule."""
+    if isinstance(schedule, L.LrSchedule):
+        return schedule
+    sch = schedule or {}
+    kind = sch.get("kind", "constant")
+    if kind not in L.LR_KINDS:
+        raise L.IckError("unknown lr schedule kind %r (one of %s)" % (kind, ", ".join(sorted(L.LR_KINDS))))
+    return L.LrSchedule(L.LR_KINDS[kind], int(sch.get("warmup_steps", 0)), int(sch.get("total_steps", 0)),
+                        float(sch.get("min_lr_ratio", 0.0)))
+
+
+def grad_sqnorm_plan(n):
+    """(workgroups of the partial pass, floats per workgroup and trip, floats of scratch) of ick_grad_sqnorm for n."""
+    plan = (L.i32 * 3)()
+    L.check(L.load().ick_grad_sqnorm_plan(n, plan), "ick_grad_sqnorm_plan")
+    return tuple(plan)
+
+
+def grad_sqnorm(g, words, scratch=None, gscale=1.0, gscale_den=None):
+    """The norm pass of the global-norm clip (ick_grad_sqnorm): words[5] = sum of squares of the flat fp32 bucket g,
+    words[2] = its L2 norm times |gscale (/ the device scalar gscale_den)|, words[3] = min(1, words[1] / (norm + 1e-6))
+    (1 while words[1] <= 0).  Fixed-order reduction; nothing is written while gscale_den is given and not > 0.  words: the
+    optimizer words ON THE DEVICE (a host max_norm would be baked into a captured launch); scratch: float32 device
+    tensor of grad_sqnorm_plan(n)[2] floats (allocated when None).  Returns words."""
+    _opt_words(words, "grad_sqnorm")
+    if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
+        raise L.IckError("grad_sqnorm needs a contiguous float32 device bucket")
+    if scratch is None:
+        scratch = torch.empty(grad_sqnorm_plan(g.numel())[2], device=g.device, dtype=torch.float32)
+    L.check(L.load().ick_grad_sqnorm(_p(g), g.numel(), gscale, _p(gscale_den), _p(scratch), scratch.numel(), _p(words),
+                                     _stream()), "ick_grad_sqnorm")
+    return words
+
+
+def adam_opt(p, g, m, v, step, words, schedule=None, clip=5.0, gscale=1.0, beta1=0.9, beta2=0.999, eps=1e-8,
+             step_tensor=None, gscale_den=None):
+    """adam_clamp with the base rate in words[0] shaped by `schedule` on the step count, and the gradient multiplied by
+    words[3] (the global-norm clip's coefficient) between the scale and the clamp (ick_adam_opt); words[4] receives the
+    rate used.  words: the optimizer words on the device -- a host scalar is refused."""
+    _opt_words(words, "adam_opt")
+    L.check(L.load().ick_adam_opt(_p(p), _p(g), _p(m), _p(v), p.numel(), gscale, clip, _p(words),
+                                  lr_schedule_struct(schedule), beta1, beta2, eps, step, _p(step_tensor), _p(gscale_den),
+                                  _stream()), "ick_adam_opt")
+
+
+def adam_opt_derive(p, g, m, v, items_dev, blocks_dev, n_blocks, step, words, schedule=None, clip=5.0, gscale=1.0,
+                    beta1=0.9, beta2=0.999, eps=1e-8, step_tensor=None, gscale_den=None, nbytes=0):
+    """adam_clamp_derive in the form of adam_opt (ick_adam_opt_derive)."""
+    _opt_words(words, "adam_opt_derive")
+    L.ADAM_DERIVE_BYTES = nbytes
+    L.check(L.load().ick_adam_opt_derive(_p(p), _p(g), _p(m), _p(v), _p(items_dev), _p(blocks_dev), n_blocks, gscale, clip,
+                                         _p(words), lr_schedule_struct(schedule), beta1, beta2, eps, step,
+                                         _p(step_tensor), _p(gscale_den), _stream()), "ick_adam_opt_derive")
+
+
 def counter_add(counter, inc=1):
     L.check(L.load().ick_counter_add(_p(counter), inc, _stream()), "ick_counter_add")
 

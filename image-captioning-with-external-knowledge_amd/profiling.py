@@ -134,6 +134,13 @@ def classify(name, args):
     if name == "ick_adam_clamp_derive":
         # the seven streams of the update + every image of the updated weights (packed, transposed, bf16 planes)
         return "clamp + Adam + re-laid-out weight copies", float(getattr(L, "ADAM_DERIVE_BYTES", 0)), "byte"
+    if name == "ick_adam_opt":
+        return "clamp + Adam", 4.0 * args[4] * 7, "byte"
+    if name == "ick_adam_opt_derive":
+        return "clamp + Adam + re-laid-out weight copies", float(getattr(L, "ADAM_DERIVE_BYTES", 0)), "byte"
+    if name == "ick_grad_sqnorm":
+        # one read of the gradient bucket (the partials and the words are a few KiB)
+        return "gradient norm (global-norm clip)", 4.0 * args[1], "byte"
     if name == "ick_decode_layers":
         c = _struct(args[0])
         kv = 4.0 * c.R * c.layers * 2 * c.H * c.S * 32

@@ -31,7 +31,7 @@ from . import utils as ut
 from .cider import CiderD
 from .datasets import CaptionDataset
 from .scst import SelfCriticalStep
-from .training import TrainStep
+from .training import TrainStep, check_lr_schedule, check_max_grad_norm, lr_at
 
 
 @dataclass
@@ -59,6 +59,12 @@ class Config:
                                                        # CrossEntropyLoss(label_smoothing=).  Validation stays the plain
                                                        # negative log-likelihood on both paths (val_token_metrics too), so
                                                        # early stopping and perplexity compare across values of eps
+    max_grad_norm: object = None                       # float > 0: global-norm clip of the decoder's gradient before the
+                                                       # element clamp grad_clip (fused, TrainStep(max_grad_norm=);
+                                                       # unfused, torch.nn.utils.clip_grad_norm_); None: off
+    lr_schedule: object = None                         # dict(kind="constant" | "inverse_sqrt" | "cosine" | "linear",
+                                                       # warmup_steps=, total_steps=, min_lr_ratio=) on the optimizer step
+                                                       # (training.lr_at); the plateau x0.8 multiplies its base rate
     print_freq: int = 100
     checkpoint: str = ""
     zero_out_epochs_since_improvement: bool = False
@@ -268,6 +274,11 @@ def train(loader, encoder, decoder, criterion, decoder_optimizer, step, epoch, c
             if encoder_optimizer is not None:
                 encoder_optimizer.zero_grad()
             loss_t.backward()
+            if cfg.max_grad_norm is not None:
+                STATS["last_grad_norm"] = torch.nn.utils.clip_grad_norm_(
+                    [p for g in decoder_optimizer.param_groups for p in g["params"]], cfg.max_grad_norm)
+            if cfg.lr_schedule is not None:
+                _set_scheduled_lr(decoder_optimizer, cfg.lr_schedule)
             if cfg.grad_clip is not None:
                 ut.clip_gradient(decoder_optimizer, cfg.grad_clip)
                 if encoder_optimizer is not None:
@@ -286,6 +297,22 @@ def train(loader, encoder, decoder, criterion, decoder_optimizer, step, epoch, c
             break
     STATS["last_epoch_steps_per_s"] = n_steps / max(time.time() - t_epoch, 1e-9)
     return losses.avg
+
+
+def _optimizer_steps(opt):
+    """Steps a torch Adam has taken (every parameter of ours steps together; 0 before the first)."""
+    for st in opt.state.values():
+        if "step" in st:
+            return int(float(st["step"]))
+    return 0
+
+
+def _set_scheduled_lr(opt, schedule):
+    """Unfused path: the rate of the optimizer step about to be taken, from the group's base rate (kept beside "lr" under
+    "base_lr", which the plateau decay multiplies and a checkpoint carries) and training.lr_at."""
+    t = _optimizer_steps(opt) + 1
+    for g in opt.param_groups:
+        g["lr"] = lr_at(t, g.setdefault("base_lr", g["lr"]), schedule)
 
 
 def _train_fused_pipelined(loader, encoder, step, epoch, cfg, device, has_facts):
@@ -497,7 +524,8 @@ def main(cfg=None):
                          encoder=encoder if pipelined else None, deterministic=det,
                          # the pipelined loop lets step i's optimizer update run at the head of step i + 1's graph beside
                          # Encoder.conv1; _train_fused_pipelined() flushes the last one of an epoch
-                         lazy_update=bool(pipelined), label_smoothing=cfg.label_smoothing)
+                         lazy_update=bool(pipelined), label_smoothing=cfg.label_smoothing,
+                         max_grad_norm=cfg.max_grad_norm, lr_schedule=cfg.lr_schedule)
         if decoder_optimizer is not None:
             # resume: Adam moments, step count (bias correction + dropout stream position) and the decayed lr come
             # back from the pickled optimizer (ours or one written by the reference, geo-aware/utils.py:32-46)
@@ -508,6 +536,9 @@ def main(cfg=None):
         dp.broadcast_module_state([encoder, decoder], _bucket_range(step))
     elif decoder_optimizer is None:
         decoder_optimizer = torch.optim.Adam([p for p in decoder.parameters() if p.requires_grad], lr=cfg.decoder_lr)
+    if step is None:
+        check_max_grad_norm(cfg.max_grad_norm)
+        check_lr_schedule(cfg.lr_schedule)
     criterion, val_criterion = (c.to(device) for c in make_criteria(word_map["<pad>"], cfg.label_smoothing))
     loaders, samplers, shuffle_gen = make_loaders(cfg, rank, world, fused)
     sc = None
@@ -526,6 +557,9 @@ def main(cfg=None):
                 step.set_lr(step.lr * 0.8)
             else:
                 ut.adjust_learning_rate(decoder_optimizer, 0.8)
+                for g in decoder_optimizer.param_groups:        # (with lr_schedule: the base rate the schedule multiplies)
+                    if "base_lr" in g:
+                        g["base_lr"] *= 0.8
             if encoder_optimizer is not None:
                 ut.adjust_learning_rate(encoder_optimizer, 0.8)
         # the epoch's permutation depends on (seed, epoch) only, so a resumed run sees the batches the interrupted
@@ -538,6 +572,12 @@ def main(cfg=None):
         else:
             tr = train(loaders["TRAIN"], encoder, decoder, criterion, decoder_optimizer, step, epoch, cfg, device,
                        encoder_optimizer)
+        if cfg.max_grad_norm is not None:
+            # one read per epoch: the norm of the last update (the fused step keeps it in a device word)
+            norm = float(step.grad_norm.item() if step is not None else STATS.get("last_grad_norm", float("nan")))
+            STATS["last_grad_norm"] = norm
+            if rank == 0:
+                print("Epoch: [%d]\tgradient norm of the last step %.4f (max_grad_norm %g)" % (epoch, norm, cfg.max_grad_norm))
         last_loss = validate(loaders["VAL"], encoder, decoder, val_criterion, cfg, device)   # identical on every rank
         is_best = last_loss < best_loss
         best_loss = min(last_loss, best_loss)

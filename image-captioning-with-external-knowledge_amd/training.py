@@ -775,6 +775,67 @@ def unique_parameters(dec):
 
 
 # ----------------------------------------------------------------------------------------------
+# learning-rate schedule and global-norm clip: the definitions
+# ----------------------------------------------------------------------------------------------
+LR_KINDS = ("constant", "inverse_sqrt", "cosine", "linear")
+
+
+def check_lr_schedule(schedule):
+    """dict(kind=, warmup_steps=W, total_steps=N, min_lr_ratio=r) -> the same with every key present and checked
+    (None stays None).  W >= 0; inverse_sqrt needs W >= 1; cosine and linear need N > W; 0 <= r <= 1."""
+    if schedule is None:
+        return None
+    if not isinstance(schedule, dict) or set(schedule) - {"kind", "warmup_steps", "total_steps", "min_lr_ratio"}:
+        raise IckError("lr_schedule must be a dict of kind, warmup_steps, total_steps, min_lr_ratio; got %r" % (schedule,))
+    kind = schedule.get("kind", "constant")
+    if kind not in LR_KINDS:
+        raise IckError("unknown lr_schedule kind %r (one of %s)" % (kind, ", ".join(LR_KINDS)))
+    W, N, r = schedule.get("warmup_steps", 0), schedule.get("total_steps", 0), float(schedule.get("min_lr_ratio", 0.0))
+    if int(W) != W or int(N) != N or W < 0 or not 0 <= N < 2 ** 31 or W >= 2 ** 31:
+        raise IckError("lr_schedule: warmup_steps and total_steps must be integers >= 0, got %r, %r" % (W, N))
+    if kind == "inverse_sqrt" and W < 1:
+        raise IckError("lr_schedule inverse_sqrt needs warmup_steps >= 1")
+    if kind in ("cosine", "linear") and not N > W:
+        raise IckError("lr_schedule %s needs total_steps > warmup_steps, got %r <= %r" % (kind, N, W))
+    if not 0.0 <= r <= 1.0:           # (NaN fails both compares)
+        raise IckError("lr_schedule: min_lr_ratio must lie in [0, 1], got %r" % (r,))
+    return dict(kind=kind, warmup_steps=int(W), total_steps=int(N), min_lr_ratio=r)
+
+
+def lr_at(t, lr, schedule):
+    """The learning rate of the 1-based optimizer step t under `schedule` with base rate lr, in float64: the definition
+    the device schedule (csrc/opt_words.h) and the unfused path follow.
+      constant      lr * min(1, t / W)                    (W = 0: lr)
+      inverse_sqrt  lr * min(t / W, sqrt(W / t))
+      cosine        t < W: lr * t / W, else lr * (r + (1 - r) * 0.5 * (1 + cos(pi * (min(t, N) - W) / (N - W))))
+      linear        t < W: lr * t / W, else lr * (r + (1 - r) * (N - min(t, N)) / (N - W))"""
+    sch = check_lr_schedule(schedule)
+    t, lr = float(t), float(lr)
+    if sch is None:
+        return lr
+    kind, W, N, r = sch["kind"], float(sch["warmup_steps"]), float(sch["total_steps"]), sch["min_lr_ratio"]
+    if kind == "inverse_sqrt":
+        return lr * min(t / W, math.sqrt(W / t))
+    if t < W:
+        return lr * (t / W)
+    if kind == "constant":
+        return lr
+    tt = min(t, N)
+    if kind == "cosine":
+        return lr * (r + (1.0 - r) * 0.5 * (1.0 + math.cos(math.pi * (tt - W) / (N - W))))
+    return lr * (r + (1.0 - r) * (N - tt) / (N - W))
+
+
+def check_max_grad_norm(m):
+    if m is None:
+        return None
+    m = float(m)
+    if not m > 0.0:                   # (NaN fails the compare)
+        raise IckError("max_grad_norm must be a float > 0 (None: off), got %r" % (m,))
+    return m
+
+
+# ----------------------------------------------------------------------------------------------
 # fused data-parallel training step
 # ----------------------------------------------------------------------------------------------
 class TrainStep:
@@ -794,8 +855,21 @@ class TrainStep:
     replays advance without re-capturing."""
 
     def __init__(self, decoder, lr=4e-4, grad_clip=5.0, betas=(0.9, 0.999), eps=1e-8, process_group=None, seed=0,
-                 use_graph=True, encoder=None, deterministic=None, lazy_update=False, label_smoothing=0.0):
+                 use_graph=True, encoder=None, deterministic=None, lazy_update=False, label_smoothing=0.0,
+                 max_grad_norm=None, lr_schedule=None):
         self.dec = decoder
+        # max_grad_norm (float > 0; None: off; DESIGN.md 3.1h): torch.nn.utils.clip_grad_norm_(params, m, norm_type=2) on the
+        # token-mean gradient of the global batch, BEFORE the element clamp grad_clip (grad_clip=None: no clamp).
+        # lr_schedule (dict(kind=, warmup_steps=, total_steps=, min_lr_ratio=), see lr_at; None: the fixed rate lr): the
+        # rate of optimizer step t = device step counter + 1.  With either one the base rate, max_norm, the norm, the clip
+        # coefficient and the rate used live in a few device words (self._words) that the optimizer kernels read and
+        # write: set_lr() / set_max_grad_norm() / a warmup replay the captured graphs, and grad_norm, clip_coef, lr_now
+        # read the last applied update's values without a host synchronisation.  With neither, nothing changes: the same
+        # kernels, graphs and set_lr as before.  Hyper-parameters like grad_clip: not part of state_dict() -- the position
+        # in the schedule follows from the step count.
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self.lr_schedule = check_lr_schedule(lr_schedule)
+        self._words = self._norm_scratch = None
         # label_smoothing (0 <= eps < 1; DESIGN.md 3.1g): the loss of torch's CrossEntropyLoss(label_smoothing=eps), and
         # the returned loss is that smoothed loss.  Exactly 0.0 launches the plain cross entropy; a non-zero value lives
         # in a one-float device word the smoothed kernel reads, so set_label_smoothing() between two non-zero values
@@ -831,7 +905,7 @@ class TrainStep:
         # reference's default fine_tune_encoder=False) then runs inside graph A straight into the memory buffer
         self.enc = encoder
         self.seed = seed  # dropout mask stream; give every rank its own seed
-        self.lr, self.clip, self.betas, self.eps = lr, grad_clip, betas, eps
+        self.lr, self.clip, self.betas, self.eps = lr, (0.0 if grad_clip is None else grad_clip), betas, eps
         self.pg = process_group
         self.use_graph = use_graph
         self.step_count = 0
@@ -864,6 +938,8 @@ class TrainStep:
                 self.grads[id(p)] = self.flat_g[off:off + k].view(p.shape)
                 off += pad(k)
         self.params = params
+        if self.max_grad_norm is not None or self.lr_schedule is not None:
+            self._make_words()
         if self.label_smoothing != 0.0:
             self._eps_word = torch.full((1,), self.label_smoothing, device=dev, dtype=torch.float32)
         self._graphs = {}
@@ -926,6 +1002,56 @@ class TrainStep:
                 self._eps_word = torch.empty(1, device=self.flat_p.device, dtype=torch.float32)
             self._eps_word.fill_(eps)
         self.label_smoothing = eps
+
+    # ---- global-norm clip and learning-rate schedule: the optimizer words --------
+    def _make_words(self):
+        """The optimizer words (include/ick_amd.h: base lr, max_norm, norm, coef, lr used, sum of squares) and the norm
+        pass's scratch.  From here on _adam() launches ick_adam_opt[_derive], which read the rate from the words."""
+        dev = self.flat_p.device
+        if self._words is None:
+            w = [0.0] * 8
+            w[0], w[1], w[3] = float(self.lr), self.max_grad_norm or 0.0, 1.0
+            self._words = torch.tensor(w, device=dev, dtype=torch.float32)
+            self._sched = ops.lr_schedule_struct(self.lr_schedule)
+        if self.max_grad_norm is not None and self._norm_scratch is None:
+            self._norm_scratch = torch.empty(ops.grad_sqnorm_plan(self.n)[2], device=dev, dtype=torch.float32)
+
+    def _word(self, i, what):
+        if self._words is None:
+            raise IckError("%s needs a TrainStep built with max_grad_norm= or lr_schedule=" % what)
+        return self._words[i:i + 1]
+
+    @property
+    def grad_norm(self):
+        """1-element device tensor: the L2 norm of the token-mean gradient of the last applied update, before any clip
+        (a view of the optimizer words: clone() to keep a value; 0 until max_grad_norm is on and an update ran)."""
+        return self._word(2, "grad_norm")
+
+    @property
+    def clip_coef(self):
+        """1-element device tensor: min(1, max_grad_norm / (grad_norm + 1e-6)) of the last applied update."""
+        return self._word(3, "clip_coef")
+
+    @property
+    def lr_now(self):
+        """1-element device tensor: the learning rate the last applied update used (base rate times the schedule)."""
+        return self._word(4, "lr_now")
+
+    def set_max_grad_norm(self, m):
+        """A new bound of the global-norm clip.  Between two positive values only the device word is written and the
+        captured graphs replay; switching the clip on or off (None) adds or removes the norm pass, so the next step
+        captures again.  A pending (lazy_update) update is applied first, under the old bound."""
+        m = check_max_grad_norm(m)
+        self.flush()
+        if (m is None) != (self.max_grad_norm is None):
+            self._graphs.clear()
+        self.max_grad_norm = m
+        if m is None and self._words is None:
+            return
+        self._make_words()
+        self._words[1:2].fill_(m or 0.0)
+        if m is None:
+            self._words[3:4].fill_(1.0)       # nothing recomputes the coefficient any more
 
     def _loss(self, scores, captions, decode_len, weights, pack=None):
         """Packed cross entropy into the tail of the gradient bucket (it was zeroed by the side tail; nothing else touches
@@ -1008,6 +1134,24 @@ class TrainStep:
     def _adam(self):
         # divide by the global token count (device-resident), clamp, Adam with the device step counter -- and, with
         # self.derived, the re-laid-out copies of the updated weights in the same pass (ick_adam_clamp_derive)
+        den = self.flat_g[self.n + 1:]
+        if self._words is not None:
+            # The norm is taken here, behind the all-reduce, so every rank gets the same value.  It runs over [0, n): the
+            # alignment pads between the parameters lie inside, and they are zero -- _side_tail zeroes the whole bucket,
+            # the backward pass writes through self.grads (views of the parameters' own extents), the all-reduce adds
+            # zeros, and the optimizer kernels write back clamp(0 * scale) = 0.  The trailing [loss sum, token count] at
+            # n, n + 1 are outside.
+            if self.max_grad_norm is not None:
+                ops.grad_sqnorm(self.flat_g[:self.n], self._words, self._norm_scratch, gscale=1.0, gscale_den=den)
+            kw = dict(schedule=self._sched, clip=self.clip, gscale=1.0, beta1=self.betas[0], beta2=self.betas[1],
+                      eps=self.eps, step_tensor=self.counter, gscale_den=den)
+            if self.derived is not None:
+                ops.adam_opt_derive(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.derived.items_dev,
+                                    self.derived.blocks_dev, self.derived.n_blocks, 1, self._words,
+                                    nbytes=self.derived.nbytes, **kw)
+            else:
+                ops.adam_opt(self.flat_p[:self.n], self.flat_g[:self.n], self.flat_m, self.flat_v, 1, self._words, **kw)
+            return
         hyper = (1, self.lr, self.clip, 1.0, self.betas[0], self.betas[1], self.eps)
         if self.derived is not None:
             ops.adam_clamp_derive(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.derived.items_dev,
@@ -1136,10 +1280,14 @@ class TrainStep:
             if len(steps) > 1:
                 raise IckError("per-parameter Adam step counts differ (%s): not representable in the fused step" % steps)
             self.counter.fill_(steps.pop() if steps else 0)
-        self.lr = float(groups[0]["lr"])
-        self.betas = tuple(groups[0].get("betas", self.betas))
-        self.eps = float(groups[0].get("eps", self.eps))
-        self._graphs.clear()          # lr / betas / eps are baked into the captured optimizer graph
+        # (base_lr: the unfused path of train.py keeps the schedule's base rate there, "lr" then is the scheduled one)
+        lr = float(groups[0].get("base_lr", groups[0]["lr"]))
+        betas, eps = tuple(groups[0].get("betas", self.betas)), float(groups[0].get("eps", self.eps))
+        if self._words is None or betas != tuple(self.betas) or eps != self.eps:
+            self._graphs.clear()      # betas / eps (and, without the optimizer words, lr) are baked into the captured graph
+        self.lr, self.betas, self.eps = lr, betas, eps
+        if self._words is not None:
+            self._words[0:1].fill_(lr)
         self.dec.invalidate_caches()
         self.parameters_changed()
 
@@ -1172,7 +1320,10 @@ class TrainStep:
     def set_lr(self, lr):
         self.flush()                  # a pending update was computed under the old rate
         self.lr = float(lr)
-        self._graphs.clear()          # baked into the captured optimizer graph
+        if self._words is not None:
+            self._words[0:1].fill_(self.lr)       # the base rate word: the captured graphs replay, the schedule multiplies it
+        else:
+            self._graphs.clear()      # baked into the captured optimizer graph
 
     def _check_views(self):
         """The decoder's parameters must still be views of the flat bucket: decoder.to() / .cuda() /

@@ -687,6 +687,55 @@ int ick_adam_clamp_derive(float* p, float* g, float* m, float* v, const ick_adam
                           const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
                           float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
                           const float* gscale_den, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Global-norm gradient clipping and a learning-rate schedule on the device.
+ *
+ * The optimizer words: ICK_OPT_WORDS floats of device memory, 16-byte aligned, that the kernels below read and write
+ * so that a captured optimizer graph follows new values without being captured again:
+ *   [0] base learning rate                               (written by the host)
+ *   [1] max_norm of the global-norm clip, <= 0: off      (written by the host)
+ *   [2] norm: the L2 norm of the token-mean gradient g * gscale / *gscale_den over the whole bucket, before any clip
+ *   [3] coef = min(1, max_norm / (norm + 1e-6)), 1 while max_norm <= 0 (torch.nn.utils.clip_grad_norm_, norm_type 2,
+ *       error_if_nonfinite=False: a NaN norm gives a NaN coef)           ([2], [3], [5]: written by ick_grad_sqnorm)
+ *   [4] the learning rate the last applied update used   (written by ick_adam_opt[_derive])
+ *   [5] the sum of squares of the raw bucket g[0, n) that [2] was made from
+ *   [6], [7] unused.
+ * The schedule's shape is an argument (baked into a captured graph), defined on the 1-based step count t that the
+ * Adam entries already take (step + *step_ptr), with W = warmup, N = total, r = min_ratio, base = words[0]:
+ *   ICK_LR_CONSTANT      base * min(1, t / W)                                   (W = 0: base)
+ *   ICK_LR_INVERSE_SQRT  base * min(t / W, sqrt(W / t))                         (W >= 1)
+ *   ICK_LR_COSINE        t < W: base * t / W, else base * (r + (1 - r) * 0.5 * (1 + cos(pi * (min(t, N) - W) / (N - W))))
+ *   ICK_LR_LINEAR        t < W: base * t / W, else base * (r + (1 - r) * (N - min(t, N)) / (N - W))       (both: N > W) */
+#define ICK_OPT_WORDS 8
+enum { ICK_LR_CONSTANT = 0, ICK_LR_INVERSE_SQRT = 1, ICK_LR_COSINE = 2, ICK_LR_LINEAR = 3 };
+typedef struct ick_lr_schedule {
+    int32_t kind, warmup, total;
+    float min_ratio;
+} ick_lr_schedule;
+/* The launch plan of ick_grad_sqnorm for n floats: plan[0] = workgroups of the partial pass, plan[1] = floats one
+ * workgroup takes per trip of its grid-stride loop, plan[2] = the most workgroups any n gets = the floats of scratch the
+ * entry needs. */
+int ick_grad_sqnorm_plan(int64_t n, int32_t* plan);
+/* words[5] = sum of g[i]^2 over [0, n), words[2] and words[3] from it as above.  Two launches: plan[0] workgroups each
+ * leave the partial sum of their float4 stream (plus, in workgroup 0, the n % 4 tail) in scratch, one workgroup then adds
+ * the partials in a fixed order.  No atomics: the same input gives the same bits on every run, in and out of
+ * deterministic mode.  With gscale_den (may be NULL) both launches do nothing while *gscale_den is not > 0, as the Adam
+ * entries.  g 16-byte aligned; scratch_floats >= plan[2]. */
+int ick_grad_sqnorm(const float* g, int64_t n, float gscale, const float* gscale_den, float* scratch,
+                    int64_t scratch_floats, float* words, void* stream);
+/* ick_adam_clamp / ick_adam_clamp_derive with the learning rate of the step taken from words[0] and the schedule, and
+ * the gradient multiplied by words[3] between the scale and the clamp:
+ *   x = g * gscale [/ *gscale_den];  x = x * coef;  clamp;  m, v, p as ick_adam_clamp with lr = schedule(words[0], t).
+ * words[4] receives that lr.  With coef == 1 and ICK_LR_CONSTANT, warmup 0, the results are ick_adam_clamp[_derive]'s
+ * bit for bit.  The gradient written back is the clipped one. */
+int ick_adam_opt(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float* words,
+                 ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
+                 const float* gscale_den, void* stream);
+int ick_adam_opt_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items, const ick_adam_block* blocks,
+                        int32_t n_blocks, float gscale, float clip, float* words, ick_lr_schedule sched, float beta1,
+                        float beta2, float eps, int32_t step, const uint32_t* step_ptr, const float* gscale_den,
+                        void* stream);
 /* *counter += inc on the stream (step / dropout-epoch counter of captured training graphs). */
 int ick_counter_add(uint32_t* counter, uint32_t inc, void* stream);
 /* ... only if *flag > 0 (device scalar): the step counter of a training step whose optimizer update is deferred into the
