@@ -9,6 +9,8 @@ Import as `ick_amd` (see /ick_amd.py).  Sub-modules:
   training   TrainStep: the fused cross-entropy training step
   scst       SelfCriticalStep: self-critical sequence training on sampled captions (also `ick_amd.SelfCriticalStep`)
   cider      CiderD: CIDEr-D on token ids, on the device (also `ick_amd.CiderD`)
+  metrics    CaptionMetrics: BLEU-1..4, ROUGE-L and pointer precision / recall on token ids, on the device, and
+             MetricReward, their mix with CIDEr-D as an SCST reward (also `ick_amd.CaptionMetrics`)
   geo_aware/models.py, knowledge_aware/models.py, news_knowledge_aware/models.py
              drop-in replacements for the reference's per-variant `models` module
 """
@@ -30,4 +32,7 @@ def __getattr__(name):
     if name == "CiderD":
         from .cider import CiderD
         return CiderD
+    if name == "CaptionMetrics":
+        from .metrics import CaptionMetrics
+        return CaptionMetrics
     raise AttributeError("module 'ick_amd' has no attribute %r" % name)

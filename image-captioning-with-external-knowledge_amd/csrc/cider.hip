@@ -12,13 +12,10 @@
 //      length sequence depends on U only), the four searches of a lane interleaved.
 //   4. SCST layout: after a barrier, the image's n sample rewards and its baseline give the advantages.
 // Every float sum runs in a fixed order (wave_sum's DPP pattern, references in index order): bit-reproducible.
-#include "common.h"
+#include "caption_words.h"
 
 namespace ick {
 namespace {
-
-constexpr uint32_t kNone = 0xFFFFFFFFu;     // an unused key slot / a position past a row's last word
-constexpr int kMaxRefs = 16, kMaxLen = 64, kMaxIgnore = 16, kMaxWaves = 8;
 
 struct CiderArgs {
     const int64_t* cand;
@@ -30,8 +27,7 @@ struct CiderArgs {
     float* adv;
     int N, T, B, M, Lr, U, mode, n, rows_per_img;
     float log_ref_len, inv_two_sigma2;
-    int start, end, pad, n_ignore;
-    int ignore[kMaxIgnore];
+    WordRule words;
 };
 
 struct RowVec {
@@ -41,10 +37,6 @@ struct RowVec {
     float norm[4];
     int W;              // words in the row (wave-uniform)
 };
-
-__device__ __forceinline__ uint32_t lane_u32(uint32_t v, int lane) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
-}
 
 __device__ __forceinline__ bool key_greater(const uint4& k, const uint32_t* q) {     // k > q, lexicographic, unsigned
     if (k.x != q[0]) return k.x > q[0];
@@ -57,40 +49,13 @@ __device__ __forceinline__ bool key_greater(const uint4& k, const uint32_t* q) {
 __device__ RowVec row_vector(const CiderArgs& a, const int64_t* row, int len) {
     const int lane = threadIdx.x & 63;
     RowVec v;
-    const int64_t t = lane < len ? row[lane] : (int64_t)a.end;
-    const unsigned long long ends = __ballot(lane < len && t == a.end);
-    const int e = ends ? __builtin_ctzll(ends) : len;
-    bool keep = lane < e && t != a.start && t != a.pad;
-    for (int k = 0; k < a.n_ignore; ++k) keep = keep && t != a.ignore[k];
-    const unsigned long long km = __ballot(keep);
-    const int W = __popcll(km);
-    const int pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0));
-    // compaction: kept lane -> its rank among kept lanes; the others after them in lane order (a permutation)
-    const int target = keep ? pos : W + (lane - pos);
-    uint32_t cw = (uint32_t)__builtin_amdgcn_ds_permute(target * 4, (int)(uint32_t)t);
-    if (lane >= W) cw = kNone;
+    int W;
+    v.w[0] = compact_words(a.words, row, len, W);       // caption_words.h: shared with ick_caption_metrics
     v.W = W;
-    v.w[0] = cw;
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-        const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + k) & 63) * 4, (int)cw);
-        v.w[k] = lane + k < W ? o : kNone;
-    }
-    // term frequencies and first occurrences
-    int tf[4] = {0, 0, 0, 0};
-    bool first[4] = {true, true, true, true};
-    for (int j = 0; j < W; ++j) {
-        const bool e1 = v.w[0] == lane_u32(v.w[0], j);
-        const bool e2 = e1 && v.w[1] == lane_u32(v.w[1], j);
-        const bool e3 = e2 && v.w[2] == lane_u32(v.w[2], j);
-        const bool e4 = e3 && v.w[3] == lane_u32(v.w[3], j);
-        const bool eq[4] = {e1, e2, e3, e4};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            tf[s] += eq[s];
-            if (j < lane && eq[s]) first[s] = false;
-        }
-    }
+    following_words(v.w, W);
+    int tf[4];
+    bool first[4];
+    row_ngram_counts(v.w, W, tf, first);
     // document frequencies: branch-free binary search, the four n-grams of the lane interleaved
     uint32_t q[4][4];
 #pragma unroll
@@ -226,8 +191,8 @@ extern "C" int ick_cider_d(const int64_t* cand, int32_t N, int32_t T, const int6
     a.N = N; a.T = T; a.B = B; a.M = M; a.Lr = Lr; a.U = U; a.mode = mode; a.n = num_samples;
     a.log_ref_len = log_ref_len;
     a.inv_two_sigma2 = 1.f / (2.f * sigma * sigma);
-    a.start = start_token; a.end = end_token; a.pad = pad_token; a.n_ignore = n_ignore;
-    for (int k = 0; k < n_ignore; ++k) a.ignore[k] = ignore[k];
+    a.words.start = start_token; a.words.end = end_token; a.words.pad = pad_token; a.words.n_ignore = n_ignore;
+    for (int k = 0; k < n_ignore; ++k) a.words.ignore[k] = ignore[k];
     int grid, rows;
     if (mode == 0) {
         ICK_CHECK_ARG(image_index);

@@ -1,8 +1,10 @@
 """Greedy caption generation over a test split, mirroring evaluate() of the reference's eval.py
 (geo-aware/eval.py:46-125; knowledge-aware/eval.py:46-200 for the fact tokens): encoder -> decoder.predict ->
 token ids -> text (vocabulary words, entity names and fact objects decoded from their integer encodings) ->
-generated_captions.csv.  The domain metrics that follow in the reference (Jensen-Shannon, fact accuracy, BLEU...)
-are CPU text statistics outside this path."""
+generated_captions.csv.  With metrics= / refs= the written rows are also scored on the device (metrics.CaptionMetrics:
+BLEU-1..4, ROUGE-L, pointer precision / recall on token ids -- the reference's compute_eval_metrics.py without METEOR
+and spaCy's entities).  The other domain metrics of the reference (Jensen-Shannon, fact accuracy...) are CPU text
+statistics outside this path."""
 import os
 
 import numpy as np
@@ -39,7 +41,7 @@ def detokenize(seq, word_map, rev_word_map, entity_names, fact_names=None):
 
 @torch.no_grad()
 def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="generated_captions.csv", device="cuda",
-             sample=None, attention_out=None, beam=None):
+             sample=None, attention_out=None, beam=None, metrics=None, refs=None):
     """sample=None: greedy decode (predict), one CSV row per image.  sample = a dict of predict_sample keyword arguments
     (num_samples, temperature, top_k, top_p, seed, and the decoding rules no_repeat_ngram_size, min_len): sampled
     decode, one CSV row per (image, sample) with the columns image (running index over the loader), sample,
@@ -53,9 +55,18 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
     attention_out: a path for one .npz of the decoder's cross-attention (return_attention of predict / predict_sample):
     "attention" float16 (N, max_len, S), the last decoder layer's weights averaged over its heads, one row per CSV row;
     "tokens" int64 (N, max_len); "P", "K", "F": how the S memory rows split into image, entity and fact rows.  With
-    beam, the weights are those of the best hypothesis (of each group with return_groups)."""
+    beam, the weights are those of the best hypothesis (of each group with return_groups).
+    metrics: a metrics.CaptionMetrics, with refs = fn(batch_index, batch) -> the (B, M, Lr) (or (B, L)) int64 reference
+    captions of that batch: every written row is scored on the device against its image's references (sampled rows and
+    group rows through image_index), the batches' totals are added on the device and read once at the end.  Returns
+    (captions, sequences, result) with result = CaptionMetrics.result()'s dict, and writes
+    metric_scores_for_generated_captions.csv next to out_csv: the CSV's own columns plus Bleu_1..Bleu_4, ROUGE_L
+    (sentence scores), pointer_hits, pointer_generated, pointer_reference.  Without the two arguments: (captions,
+    sequences) as before."""
     if beam is not None and sample is not None:
         raise ValueError("evaluate: beam and sample are two different decoders; pass one of them")
+    if (metrics is None) != (refs is None) or (refs is not None and not callable(refs)):
+        raise ValueError("evaluate: metrics= (a CaptionMetrics) and refs= (fn(batch_index, batch) -> references) go together")
     decoder.eval()
     encoder.eval()
     rev = {v: k for k, v in word_map.items()}
@@ -70,6 +81,7 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
     img_buf = None
     attn_rows, attn_split = [], None
     want_attn = attention_out is not None
+    totals, metric_rows = None, []
     for bi, batch in enumerate(loader):                       # any batch size: captions decode independently
         ent, names = batch[4], batch[5]
         has_facts = len(batch) > 6
@@ -108,6 +120,14 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
                 raise ValueError("evaluate(attention_out=...): batches with different memory sizes %s / %s"
                                  % (attn_split, split))
             attn_split = split
+        if metrics is not None:
+            # rows b of seq: image b // n of this batch; everything stays on the device until the loop ends
+            cand = seq.t().contiguous()
+            idx = torch.arange(cand.shape[0], device=cand.device, dtype=torch.int32) // n
+            mr = metrics(cand, idx, refs(bi, batch))
+            t = metrics.totals(mr)
+            totals = t if totals is None else totals + t
+            metric_rows.append(mr)
         bufs = decoder.input_buffers() if feature_map else None
         img_buf = bufs[0] if bufs is not None and bufs[0] is not None and bufs[0].dim() == 4 else None
         for b in range(seq.shape[1]):
@@ -120,13 +140,25 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
         P, K, F = attn_split if attn_split is not None else (0, 0, 0)
         np.savez(attention_out, attention=torch.cat(attn_rows).numpy() if attn_rows else np.zeros((0, max_caption_len, 0),
                  np.float16), tokens=np.asarray(sequences, dtype=np.int64).reshape(-1, max_caption_len), P=P, K=K, F=F)
+    if groups:
+        columns = {"image": [r[0] for r in rows], "group": [r[1] for r in rows], "generated_caption": captions}
+    elif sample is None:
+        columns = {"generated_caption": captions}
+    else:
+        columns = {"image": [r[0] for r in rows], "sample": [r[1] for r in rows], "generated_caption": captions}
     if out_csv:
-        if groups:
-            pd.DataFrame({"image": [r[0] for r in rows], "group": [r[1] for r in rows],
-                          "generated_caption": captions}).to_csv(out_csv, index=False)
-        elif sample is None:
-            pd.DataFrame({"generated_caption": captions}).to_csv(out_csv, index=False)
-        else:
-            pd.DataFrame({"image": [r[0] for r in rows], "sample": [r[1] for r in rows],
-                          "generated_caption": captions}).to_csv(out_csv, index=False)
-    return captions, sequences
+        pd.DataFrame(columns).to_csv(out_csv, index=False)
+    if metrics is None:
+        return captions, sequences
+    result = metrics.result(totals) if totals is not None else {}
+    if out_csv and metric_rows:
+        bleu = torch.cat([m.bleu for m in metric_rows]).cpu().numpy()
+        ptr = torch.cat([m.pointers for m in metric_rows]).cpu().numpy()
+        for k in range(4):
+            columns["Bleu_%d" % (k + 1)] = bleu[:, k]
+        columns["ROUGE_L"] = torch.cat([m.rouge_l for m in metric_rows]).cpu().numpy()
+        for k, name in enumerate(("pointer_hits", "pointer_generated", "pointer_reference")):
+            columns[name] = ptr[:, k]
+        pd.DataFrame(columns).to_csv(os.path.join(os.path.dirname(out_csv), "metric_scores_for_generated_captions.csv"),
+                                     index=False)
+    return captions, sequences, result

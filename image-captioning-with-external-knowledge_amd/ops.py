@@ -938,6 +938,80 @@ def cider_d(tokens, refs, keys, counts, log_ref_len, sigma, start, end, pad, ign
     return rewards, adv
 
 
+def caption_metrics(tokens, refs, start, end, pad, ignore=(), pointer_base=-1, beta=1.2, image_index=None,
+                    num_samples=0, baseline=None, base_rewards=None, weights=None):
+    """BLEU components and sentence scores, ROUGE-L and pointer counts of candidate rows tokens (N, T) against refs
+    (B, M, Lr) (ick_caption_metrics; the definitions: metrics.py), all int64 device tensors.  Returns (counts (N, 10)
+    i32, bleu (N, 4) f32, rouge_l (N,) f32, pointers (N, 3) i32, rewards (N,) f32 or None, advantages (B * num_samples,)
+    f32 or None).  baseline / image_index / num_samples: cider_d's modes.  weights: six floats w_base, w_b1..w_b4, w_rouge
+    -> rewards (and, in the SCST layout, advantages); base_rewards (N,) f32: cider_d's rewards of the same rows."""
+    if baseline not in CIDER_MODES:
+        raise L.IckError('baseline must be None, "greedy" or "mean"')
+    for t, name in ((tokens, "tokens"), (refs, "refs")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
+            raise L.IckError("caption_metrics: %s must be a contiguous int64 device tensor" % name)
+    if tokens.dim() != 2 or refs.dim() != 3:
+        raise L.IckError("caption_metrics needs tokens (N, T) and refs (B, M, Lr)")
+    ignore = [int(i) for i in ignore]
+    if len(ignore) > 16:
+        raise L.IckError("caption_metrics takes at most 16 ignore ids")
+    N, T = tokens.shape
+    B, M, Lr = refs.shape
+    dev = tokens.device
+    mode = CIDER_MODES[baseline]
+    idx = None
+    if mode == 0:
+        if image_index is None or image_index.shape != (N,):
+            raise L.IckError("caption_metrics: general mode needs an (N,) image_index")
+        idx = image_index.to(device=dev, dtype=torch.int32).contiguous()
+    w = rewards = adv = None
+    if weights is not None:
+        weights = [float(x) for x in weights]
+        if len(weights) != 6 or not all(math.isfinite(x) for x in weights):
+            raise L.IckError("caption_metrics: weights are six finite floats (w_base, w_b1..w_b4, w_rouge)")
+        w = (C.c_float * 6)(*weights)
+        rewards = torch.empty(N, device=dev, dtype=torch.float32)
+        adv = torch.empty(B * num_samples, device=dev, dtype=torch.float32) if mode else None
+    if base_rewards is not None:
+        if weights is None:
+            raise L.IckError("caption_metrics: base_rewards need weights")
+        if base_rewards.shape != (N,) or base_rewards.dtype != torch.float32 or not base_rewards.is_cuda or \
+                not base_rewards.is_contiguous():
+            raise L.IckError("caption_metrics: base_rewards must be a contiguous (N,) float32 device tensor")
+    counts = torch.empty(N, 10, device=dev, dtype=torch.int32)
+    bleu = torch.empty(N, 4, device=dev, dtype=torch.float32)
+    rouge = torch.empty(N, device=dev, dtype=torch.float32)
+    pointers = torch.empty(N, 3, device=dev, dtype=torch.int32)
+    ign = (C.c_int32 * 16)(*ignore)
+    L.check(L.load().ick_caption_metrics(_p(tokens), N, T, _p(refs), B, M, Lr, start, end, pad, ign, len(ignore),
+                                         int(pointer_base), float(beta), mode, _p(idx), int(num_samples),
+                                         _p(base_rewards), w, _p(counts), _p(bleu), _p(rouge), _p(pointers),
+                                         _p(rewards), _p(adv), _stream()), "ick_caption_metrics")
+    return counts, bleu, rouge, pointers, rewards, adv
+
+
+def caption_metric_sums(counts, rouge_l, pointers, out=None):
+    """Totals of caption_metrics' rows (ick_caption_metric_sums) -> (sums (14,) int64: the ten BLEU components, the three
+    pointer counts and the number of rows counted; rouge_sum (1,) float64), on the device.  Rows with a NaN rouge_l are
+    skipped.  out: the two tensors to write."""
+    for t, dt, name in ((counts, torch.int32, "counts"), (rouge_l, torch.float32, "rouge_l"),
+                        (pointers, torch.int32, "pointers")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise L.IckError("caption_metric_sums: %s must be a contiguous %s device tensor" % (name, dt))
+    N = rouge_l.shape[0] if rouge_l.dim() == 1 else -1
+    if N < 1 or tuple(counts.shape) != (N, 10) or tuple(pointers.shape) != (N, 3):
+        raise L.IckError("caption_metric_sums needs counts (N, 10), rouge_l (N,) and pointers (N, 3), N >= 1")
+    dev = counts.device
+    if out is None:
+        out = (torch.empty(14, device=dev, dtype=torch.int64), torch.empty(1, device=dev, dtype=torch.float64))
+    sums, rouge_sum = out
+    assert sums.shape == (14,) and sums.dtype == torch.int64 and sums.is_contiguous()
+    assert rouge_sum.shape == (1,) and rouge_sum.dtype == torch.float64
+    L.check(L.load().ick_caption_metric_sums(_p(counts), _p(rouge_l), _p(pointers), N, _p(sums), _p(rouge_sum),
+                                             _p(sums[13:14]), _stream()), "ick_caption_metric_sums")
+    return sums, rouge_sum
+
+
 # ------------------------------------------------------------------------------------------------
 # Backward / training-step wrappers
 # ------------------------------------------------------------------------------------------------

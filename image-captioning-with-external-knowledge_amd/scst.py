@@ -12,7 +12,8 @@ step drops): each opens with one launch that re-derives every weight copy the de
 
 Device reward: with a cider.CiderD as reward_fn, step(..., refs=) scores every caption on the device in one launch
 (ick_cider_d, SCST layout) that writes the rewards and the advantages the training step takes as caption weights --
-nothing is copied to the host.
+nothing is copied to the host.  A metrics.MetricReward (CIDEr-D mixed with BLEU-n / ROUGE-L) is a device reward too:
+the CiderD launch, then ick_caption_metrics on its rewards, which writes the mixed rewards and their advantages.
 
 Dropout: sampling and the greedy decode never apply it; the teacher-forced pass uses the decoder's own mode, as TrainStep
 does.  In train() mode the gradient is therefore taken at the dropout-perturbed model, not at the model that drew the
@@ -27,6 +28,7 @@ from . import ops
 from .cider import CiderD
 from .decoder import _GraphedCall
 from .lib import IckError
+from .metrics import MetricReward
 
 SCSTOutput = collections.namedtuple("SCSTOutput", "loss samples rewards advantages greedy greedy_rewards sample_seed")
 
@@ -42,8 +44,9 @@ class SelfCriticalStep:
     Returns SCSTOutput: loss (device scalar, the weighted token-mean loss), samples (B * n, max_len) and rewards (B * n,),
     advantages (B * n,), greedy (B, max_len) and greedy_rewards (B,) (None with baseline="mean"), and the sampler seed
     of this step (predict_sample(..., seed=sample_seed) reproduces the samples from the same parameters).
-    reward_fn may instead be a cider.CiderD: each call then needs refs, the batch's reference captions (B, M, Lr) or
-    (B, L) int64, and the rewards and advantages come from one device launch.  SCSTOutput then holds DEVICE tensors
+    reward_fn may instead be a cider.CiderD or a metrics.MetricReward: each call then needs refs, the batch's reference
+    captions (B, M, Lr) or (B, L) int64, and the rewards and advantages come from the device (one launch for a CiderD,
+    one more for a MetricReward's mix).  SCSTOutput then holds DEVICE tensors
     (samples, rewards, advantages, greedy, greedy_rewards) and the step never synchronises with the host.
     Advantages: "greedy" a_bj = r_bj - r_greedy_b; "mean" the leave-one-out mean a_bj = r_bj - (sum_k r_bk - r_bj)/(n-1).
     encoder_out: (B, d, P) encoder output, or the (B, 2048, 14, 14) feature map with an encoder attached to the decoder or
@@ -116,11 +119,11 @@ class SelfCriticalStep:
 
     def __call__(self, encoder_out, entities, facts=None, refs=None):
         ts, dec, n, T = self.ts, self.dec, self.n, self.max_len
-        on_device = isinstance(self.reward_fn, CiderD)
+        on_device = isinstance(self.reward_fn, (CiderD, MetricReward))
         if on_device and refs is None:
-            raise IckError("a CiderD reward needs refs= (the batch's reference captions)")
+            raise IckError("a CiderD or MetricReward reward needs refs= (the batch's reference captions)")
         if refs is not None and not on_device:
-            raise IckError("refs= belongs to a CiderD reward; a host reward_fn takes the tokens only")
+            raise IckError("refs= belongs to a device reward (CiderD, MetricReward); a host reward_fn takes the tokens only")
         ts.flush()                  # the decode reads the parameters: apply a pending lazy update first
         encoder_out, entities, facts = dec._prepare_inputs(encoder_out, entities, facts)
         entities = entities.contiguous()

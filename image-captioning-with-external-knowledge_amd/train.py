@@ -14,7 +14,11 @@ SCST fine-tuning (`scst=True`, fused single-process runs only; usually from an X
 TRAIN batch runs one scst.SelfCriticalStep with a CIDEr-D reward on the device (cider.CiderD, df from the TRAIN split's
 captions), the batch's own captions as the references (one per image in this dataset format), in place of the
 cross-entropy step.  It uses the plain fused loop, not the prefetch pipeline; validation (the cross-entropy loss) and
-checkpointing are unchanged."""
+checkpointing are unchanged.  `scst_reward` mixes BLEU-n / ROUGE-L into that reward (metrics.MetricReward).
+
+`val_caption_metrics=True`: validate() also decodes every validation batch greedily and scores the captions against the
+batch's caption rows on the device (metrics.CaptionMetrics: BLEU-1..4, ROUGE-L, pointer precision / recall, and CIDEr-D
+when a CiderD exists); the totals stay on the device until the pass ends."""
 import json
 import math
 import os
@@ -30,6 +34,7 @@ from . import dp, load_models, ops
 from . import utils as ut
 from .cider import CiderD
 from .datasets import CaptionDataset
+from .metrics import CaptionMetrics
 from .scst import SelfCriticalStep
 from .training import TrainStep, check_lr_schedule, check_max_grad_norm, lr_at
 
@@ -84,6 +89,13 @@ class Config:
     scst_baseline: str = "greedy"                      # "greedy" | "mean" (leave-one-out)
     val_token_metrics: bool = False                    # validate() through decoder.score_captions: also perplexity and
                                                        # top-1 / top-5 token accuracy (STATS["val_perplexity"], ...)
+    val_caption_metrics: bool = False                  # validate() also decodes every batch (predict(), max_len = the
+                                                       # caption row length) and returns (loss, CaptionMetrics.result()
+                                                       # dict): BLEU-1..4, ROUGE-L, pointer precision / recall on token
+                                                       # ids, plus CIDEr-D under scst (STATS["caption_metrics"])
+    scst_reward: object = None                         # dict of CaptionMetrics.reward()'s keyword arguments without
+                                                       # `cider` (cider_weight=, bleu=, rouge_l=): the SCST reward is that
+                                                       # mix around the script's CiderD; None: CIDEr-D alone
 
 
 def _batch_to_device(batch, device, has_facts):
@@ -364,37 +376,80 @@ def _train_scst(loader, encoder, sc, epoch, cfg, device, has_facts):
             r_s = out.rewards.mean().item()
             r_g = out.greedy_rewards.mean().item() if out.greedy_rewards is not None else float("nan")
             STATS.setdefault("scst_rewards", []).append((epoch, i, r_s, r_g))
-            print("Epoch: [%d][%d/%d]\tSCST loss %.4f\tCIDEr-D sample %.4f greedy %.4f" %
-                  (epoch, i, len(loader), out.loss.item(), r_s, r_g))
+            print("Epoch: [%d][%d/%d]\tSCST loss %.4f\t%s sample %.4f greedy %.4f" %
+                  (epoch, i, len(loader), out.loss.item(), "CIDEr-D" if cfg.scst_reward is None else "reward", r_s, r_g))
         if cfg.max_batches and i + 1 >= cfg.max_batches:
             break
     STATS["last_epoch_steps_per_s"] = n / max(time.time() - t_epoch, 1e-9)
     return loss_sum.item() / max(n, 1)
 
 
-def validate(loader, encoder, decoder, criterion, cfg, device):
+class _ValCaptionMetrics:
+    """Config.val_caption_metrics: the greedy captions of every validation batch, scored against the batch's caption rows
+    (one reference per image in this dataset format).  Per batch one decode, one ick_caption_metrics launch, one totals
+    launch and a device add; finish() reads the totals -- the pass's one extra synchronisation."""
+
+    def __init__(self, decoder, device, cider=None):
+        self.dec, self.cider = decoder, cider
+        self.metrics = CaptionMetrics(decoder.word_map, pointer_base=decoder.vocab_size, device=device)
+        self.totals = None
+        self.cider_sum = torch.zeros(1, device=device, dtype=torch.float64) if cider is not None else None
+
+    def add(self, enc, caps, ent, facts):
+        seq = self.dec.predict(enc, caps.shape[1], ent, *((facts,) if facts is not None else ()))
+        rows = seq.t().contiguous()
+        idx = torch.arange(rows.shape[0], device=rows.device, dtype=torch.int32)
+        t = self.metrics.totals(self.metrics(rows, idx, caps))
+        self.totals = t if self.totals is None else self.totals + t
+        if self.cider is not None:
+            self.cider_sum += self.cider(rows, idx, caps).double().sum()
+
+    def finish(self):
+        if self.totals is None:
+            return {}
+        tensors = list(self.totals) + ([self.cider_sum] if self.cider is not None else [])
+        if dp.world_size() > 1:                                 # every rank scored its own shard
+            for t in tensors:
+                torch.distributed.all_reduce(t)
+        res = CaptionMetrics.result(self.totals)
+        if self.cider is not None:
+            res["CIDEr-D"] = float(self.cider_sum.item()) / max(res["captions"], 1)
+        STATS["caption_metrics"] = res
+        print("Validation: " + "\t".join("%s %.4f" % (k, v) for k, v in res.items() if k != "captions")
+              + " (%d captions)" % res["captions"])
+        return res
+
+
+def validate(loader, encoder, decoder, criterion, cfg, device, cider=None):
     """Token-weighted mean loss over the validation split (geo-aware/train.py:317-386).  Under torchrun every rank
     scores its own shard and the (sum, count) pair is all-reduced, so all ranks return the same number and take the
-    same best-checkpoint / lr-decay / early-stop decisions."""
+    same best-checkpoint / lr-decay / early-stop decisions.  With Config.val_caption_metrics it returns (loss, the
+    caption metrics of the greedy captions as a dict); cider: a CiderD whose corpus score joins that dict."""
     decoder.eval()
     encoder.eval()
+    cm = _ValCaptionMetrics(decoder, device, cider) if cfg.val_caption_metrics else None
     if cfg.val_token_metrics:
-        return _validate_token_metrics(loader, encoder, decoder, cfg, device)
+        loss = _validate_token_metrics(loader, encoder, decoder, cfg, device, cm)
+        return (loss, cm.finish()) if cm is not None else loss
     losses = ut.AverageMeter()
     has_facts = decoder.has_facts
     with torch.no_grad():
         for i, batch in enumerate(loader):
             imgs, caps, caplens, capmasks, ent, facts = _batch_to_device(batch, device, has_facts)
             extra = (facts,) if has_facts else ()
-            scores, caps_sorted, dl = decoder(caps, encoder(imgs), capmasks, caplens, ent, *extra)
+            enc = encoder(imgs)
+            scores, caps_sorted, dl = decoder(caps, enc, capmasks, caplens, ent, *extra)
             losses.update(packed_loss(criterion, scores, caps_sorted, dl).item(), sum(dl))
+            if cm is not None:
+                cm.add(enc, caps, ent, facts)
             if cfg.max_batches and i + 1 >= cfg.max_batches:
                 break
     total, count = dp.reduce_sum_count(losses.sum, losses.count, device=device)
-    return total / max(count, 1.0)
+    loss = total / max(count, 1.0)
+    return (loss, cm.finish()) if cm is not None else loss
 
 
-def _validate_token_metrics(loader, encoder, decoder, cfg, device):
+def _validate_token_metrics(loader, encoder, decoder, cfg, device, cm=None):
     """validate() with Config.val_token_metrics: every batch goes through decoder.score_captions (the score head over the
     valid positions only, no (B, L, V+K+F) matrix, no per-batch .item()); the four totals are accumulated on the device
     and read once at the end.  Same token-weighted loss; also prints and records perplexity and top-1 / top-5 accuracy."""
@@ -402,8 +457,11 @@ def _validate_token_metrics(loader, encoder, decoder, cfg, device):
     with torch.no_grad():
         for i, batch in enumerate(loader):
             imgs, caps, caplens, capmasks, ent, facts = _batch_to_device(batch, device, decoder.has_facts)
-            s = decoder.score_captions(caps, encoder(imgs), capmasks, caplens, ent, facts, top_k=5)
+            enc = encoder(imgs)
+            s = decoder.score_captions(caps, enc, capmasks, caplens, ent, facts, top_k=5)
             acc += torch.cat([s.loss_sum, s.count, s.top1_hits, s.topk_hits]).double()
+            if cm is not None:
+                cm.add(enc, caps, ent, facts)
             if cfg.max_batches and i + 1 >= cfg.max_batches:
                 break
     loss_sum, count, top1, top5 = acc.tolist()                  # the one synchronisation
@@ -478,6 +536,10 @@ def main(cfg=None):
     if cfg.scst and (not fused or world > 1 or cfg.scst_baseline not in ("greedy", "mean")):
         raise ValueError('scst=True needs a fused single-process run (fused=True, fine_tune_encoder=False, no torchrun) '
                          'and scst_baseline "greedy" or "mean"')
+    if cfg.scst_reward is not None and not (cfg.scst and isinstance(cfg.scst_reward, dict) and
+                                            "cider" not in cfg.scst_reward):
+        raise ValueError("scst_reward is a dict of CaptionMetrics.reward()'s keyword arguments without `cider`, and "
+                         "needs scst=True")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
     torch.cuda.set_device(device)
     models = load_models(cfg.variant)
@@ -541,12 +603,15 @@ def main(cfg=None):
         check_lr_schedule(cfg.lr_schedule)
     criterion, val_criterion = (c.to(device) for c in make_criteria(word_map["<pad>"], cfg.label_smoothing))
     loaders, samplers, shuffle_gen = make_loaders(cfg, rank, world, fused)
-    sc = None
+    sc = cider = None
     if cfg.scst:
         captions = torch.as_tensor(np.asarray(loaders["TRAIN"].dataset.captions), dtype=torch.long)
-        cider = CiderD(captions, word_map, device=device)
+        cider = reward = CiderD(captions, word_map, device=device)
+        if cfg.scst_reward is not None:
+            reward = CaptionMetrics(word_map, pointer_base=len(word_map), device=device).reward(cider=cider,
+                                                                                                **cfg.scst_reward)
         # sampled rows one shorter than the dataset's captions: the training rows ([<start>] + samples) keep its width
-        sc = SelfCriticalStep(step, cider, num_samples=cfg.scst_samples, baseline=cfg.scst_baseline,
+        sc = SelfCriticalStep(step, reward, num_samples=cfg.scst_samples, baseline=cfg.scst_baseline,
                               max_len=captions.shape[1] - 1, seed=cfg.seed)
     history = []
     for epoch in range(start_epoch, cfg.epochs):
@@ -578,7 +643,9 @@ def main(cfg=None):
             STATS["last_grad_norm"] = norm
             if rank == 0:
                 print("Epoch: [%d]\tgradient norm of the last step %.4f (max_grad_norm %g)" % (epoch, norm, cfg.max_grad_norm))
-        last_loss = validate(loaders["VAL"], encoder, decoder, val_criterion, cfg, device)   # identical on every rank
+        last_loss = validate(loaders["VAL"], encoder, decoder, val_criterion, cfg, device, cider=cider)   # identical on every rank
+        if cfg.val_caption_metrics:
+            last_loss = last_loss[0]                    # (the metrics dict is printed and kept in STATS)
         is_best = last_loss < best_loss
         best_loss = min(last_loss, best_loss)
         epochs_since_improvement = 0 if is_best else epochs_since_improvement + 1

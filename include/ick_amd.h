@@ -573,6 +573,48 @@ int ick_cider_d(const int64_t* cand, int32_t N, int32_t T, const int64_t* refs, 
                 int32_t mode, const int32_t* image_index, int32_t num_samples, float* rewards, float* advantages,
                 void* stream);
 
+/* BLEU-1..4, ROUGE-L and pointer precision / recall on token ids (metrics.py: CaptionMetrics; csrc/metrics.hip).  The
+ * definitions are coco-caption's, applied to token ids:
+ *   words of a row: ick_cider_d's words exactly (the same device code); c = the candidate's word count, l_m the word
+ *     count of its reference m.
+ *   BLEU components per candidate, n = 1..4 (bleu_scorer with option="closest"):
+ *     guess_n = max(0, c - n + 1);
+ *     correct_n = sum over the distinct candidate n-grams g of min(count_c(g), max_m count_m(g));
+ *     testlen = c;  reflen = the l_m that minimises (|l_m - c|, l_m).
+ *   sentence BLEU-n = (prod_{k<=n} (correct_k + 1e-15) / (guess_k + 1e-9)) ** (1/n), times exp(1 - 1/ratio) if
+ *     ratio = (testlen + 1e-15) / (reflen + 1e-9) < 1.  Corpus BLEU-n: the same formula on the components' sums.
+ *   ROUGE-L (Rouge, beta = 1.2): P = max_m LCS(c, r_m) / c, R = max_m LCS(c, r_m) / l_m (an empty reference gives 0),
+ *     score (1 + beta^2) P R / (R + beta^2 P), 0 when P or R is 0 or c = 0.  Corpus: the mean over captions.
+ *   pointers (pointer_base = V): generated = the distinct ids >= V among the candidate's words, reference = the
+ *     distinct ids >= V in the union of its references' words, hits = the size of the intersection.  Corpus precision
+ *     = sum hits / sum generated, recall = sum hits / sum reference, each 0 when its denominator is 0.  This is the
+ *     id-level counterpart of the news variant's named-entity precision / recall in its "exact" mode.
+ * Like ick_cider_d the scores equal coco-caption's on the space-joined id strings, not on detokenised text.
+ *
+ * cand (N, T) int64, refs (B, M, Lr) int64, ignore: a HOST array of n_ignore <= 16 ids; modes, image_index and
+ * num_samples as for ick_cider_d (mode 0 general, 1 / 2 the SCST layout with / without the B greedy rows).
+ * Outputs per row: counts (N, 10) int32 = guess1..4, correct1..4, testlen, reflen; bleu (N, 4) f32 sentence scores;
+ * rouge_l (N,) f32; pointers (N, 3) int32 = hits, generated, reference (all zero when pointer_base < 0).  A row whose
+ * image_index lies outside [0, B) gets NaN floats and zero counts.
+ * Rewards (optional): weights, a HOST array of six floats w_base, w_b1..w_b4, w_rouge, and rewards (N,) f32 go together;
+ * rewards = w_base * base_rewards + w_b1 * bleu1 + .. + w_b4 * bleu4 + w_rouge * rouge_l, evaluated in fp32 in this
+ * order; base_rewards (N,) f32 (the rewards of a preceding ick_cider_d launch) may be null, then the first term is
+ * absent.  In modes 1 / 2 rewards and advantages (B * n,) f32 go together, the advantages by ick_cider_d's formulas.
+ * The sentence scores are evaluated in float64 and rounded once.  Limits: T, Lr <= 64, M <= 16, rows per image <= 64.
+ * No atomics, fixed order: bit-reproducible. */
+int ick_caption_metrics(const int64_t* cand, int32_t N, int32_t T, const int64_t* refs, int32_t B, int32_t M, int32_t Lr,
+                        int32_t start_token, int32_t end_token, int32_t pad_token, const int32_t* ignore,
+                        int32_t n_ignore, int32_t pointer_base, double beta, int32_t mode, const int32_t* image_index,
+                        int32_t num_samples, const float* base_rewards, const float* weights, int32_t* counts,
+                        float* bleu, float* rouge_l, int32_t* pointers, float* rewards, float* advantages, void* stream);
+
+/* Totals of ick_caption_metrics' per-row outputs over N rows, written to the device: sums (13,) int64 = the ten BLEU
+ * components and the three pointer counts, rouge_sum (1,) float64, captions (1,) int64 = the rows counted.  Rows whose
+ * rouge_l is NaN (an image_index out of range) are skipped.  One workgroup, fixed order: bit-reproducible.  A validation
+ * loop adds the totals of its batches on the device and reads them once. */
+int ick_caption_metric_sums(const int32_t* counts, const float* rouge_l, const int32_t* pointers, int32_t N,
+                            int64_t* sums, double* rouge_sum, int64_t* captions, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Training step (row a14): backward kernels behind loss.backward() of geo-aware/train.py:282-292,
