@@ -282,10 +282,8 @@ __global__ __launch_bounds__(256) void fact_encode_bwd_det_kernel(const float* _
     const int p = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
     for (int row = 0; row < B * F; ++row) {
         const int b = row / F;
-        int subj = (int)facts[(int64_t)row * 3 + 1];
-        int pred = (int)facts[(int64_t)row * 3 + 2];
-        subj = subj < 0 ? 0 : (subj >= K ? K - 1 : subj);
-        pred = pred < 0 ? 0 : (pred >= num_pred ? num_pred - 1 : pred);
+        const int subj = clamp_row(facts[(int64_t)row * 3 + 1], K);
+        const int pred = clamp_row(facts[(int64_t)row * 3 + 2], num_pred);
         const bool e_mine = (b * K + subj) % kDetParts == p, p_mine = pred % kDetParts == p;
         if ((!e_mine && !p_mine) || c >= d) continue;
         const float g = dfe[(int64_t)row * d + c];
@@ -454,10 +452,8 @@ __global__ __launch_bounds__(256) void fact_encode_bwd_kernel(const float* __res
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= B * F) return;
     const int b = row / F;
-    int subj = (int)facts[(int64_t)row * 3 + 1];
-    int pred = (int)facts[(int64_t)row * 3 + 2];
-    subj = subj < 0 ? 0 : (subj >= K ? K - 1 : subj);
-    pred = pred < 0 ? 0 : (pred >= num_pred ? num_pred - 1 : pred);
+    const int subj = clamp_row(facts[(int64_t)row * 3 + 1], K);
+    const int pred = clamp_row(facts[(int64_t)row * 3 + 2], num_pred);
     for (int c = lane; c < d; c += 64) {
         const float g = dfe[(int64_t)row * d + c];
         atomicAdd(dee + ((int64_t)b * K + subj) * d + c, g);
@@ -711,11 +707,12 @@ extern "C" int ick_pointer_scores_bwd_packed(const float* ds, int64_t ds_ld, int
                                              const int32_t* rowmap, const int32_t* rowstart, void* stream) {
     ICK_CHECK_ARG(ds && h && ctx && w && dh && dctx && dw && dbias && B > 0 && B <= 65535 && T > 0 && Kc > 0 && d > 0);
     ICK_CHECK_ARG((rowmap == nullptr) == (rowstart == nullptr) && (int64_t)B * T <= INT32_MAX);
+    // every argument check comes before the first launch: a rejected call leaves dh untouched as well
+    const size_t smem = ((size_t)T * Kc + 4 + 256) * sizeof(float);
+    ICK_CHECK_ARG(smem <= 64 * 1024);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(pointer_bwd_dh_kernel, dim3(T, B), dim3(256), 0, s, ds, ds_ld, col0, ctx, w, ind, dh, T, Kc, d, rowmap,
                        rowstart ? rowstart + B : nullptr);
-    const size_t smem = ((size_t)T * Kc + 4 + 256) * sizeof(float);
-    ICK_CHECK_ARG(smem <= 64 * 1024);
     if (deterministic())
         hipLaunchKernelGGL(pointer_bwd_dctx_kernel<true>, dim3(1, ceil_div(d, 64)), dim3(256), smem, s, ds, ds_ld, col0, h,
                            ctx, w, ind, dctx, dw, dbias, B, T, Kc, d, rowstart);

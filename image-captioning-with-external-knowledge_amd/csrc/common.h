@@ -183,6 +183,11 @@ __device__ __forceinline__ int device_bound(int host, const int32_t* dev) {
     return host;                            // (the host pass only parses device code)
 #endif
 }
+// An int64 row index clamped to [0, n - 1] (DESIGN.md §4 deviation 2).  The clamp runs in int64 and only then narrows: an
+// index such as 2^32 + 1 is out of range, not row 1.
+__device__ __forceinline__ int clamp_row(int64_t v, int n) {
+    return (int)(v < 0 ? 0 : (v >= (int64_t)n ? (int64_t)n - 1 : v));
+}
 // Decoding rules of beam search and sampling (ick_decode_rules).  The four rule words
 // {no_repeat_ngram_size, min_len, length penalty on, 0} are device memory written by the host before a (replayed)
 // decode; the first three are read through the scalar cache like epoch_seed()'s counter.  words == nullptr: every

@@ -94,10 +94,8 @@ __global__ __launch_bounds__(256) void fact_encode_kernel(const int64_t* __restr
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= B * F) return;
     const int b = row / F;
-    int subj = (int)facts[(int64_t)row * 3 + 1];
-    int pred = (int)facts[(int64_t)row * 3 + 2];
-    subj = subj < 0 ? 0 : (subj >= K ? K - 1 : subj);
-    pred = pred < 0 ? 0 : (pred >= num_pred ? num_pred - 1 : pred);
+    const int subj = clamp_row(facts[(int64_t)row * 3 + 1], K);
+    const int pred = clamp_row(facts[(int64_t)row * 3 + 2], num_pred);
     const float* s = ee + ((int64_t)b * K + subj) * d;
     const float* p = pred_emb + (int64_t)pred * d;
     float* o = out + (int64_t)row * d;
