@@ -1,6 +1,6 @@
 // One KV-cached decode step of DecoderTransformer.predict() (geo-aware/models.py:389-443,
 // knowledge-aware/models.py:545-608) for R independent rows (R = captions, or captions x beams) in
-// 3 launches per decoder layer + 3 for the score head, instead of ~37 dependent launches:
+// 3 launches per decoder layer + 3 for the score head and the selection, instead of ~37 dependent launches:
 //
 //   dec_self_kernel   (row, head)   LN-on-load -> q|k|v rows of the head (GEMV) -> cache write -> causal
 //                                   self-attention over the cached positions -> this head's slice of out_proj
@@ -11,8 +11,8 @@
 //   dec_head_kernel   (row)         final LayerNorm -> h (x predicate gate) -> pointer scores over entities / facts
 //   dec_vocab_kernel  (16 words x 32 rows)  vocabulary logits on the fp32 MFMA, K split over the 4 waves,
 //                                   per-tile top-2 candidates
-//   dec_select_kernel (row)         top-2 over candidates + pointer scores, predict()'s bookkeeping (n-gram
-//                                   clean-up, <end>), embedding + position code of the next token
+// The kernels that choose tokens from a finished step's outputs (greedy, beam) are decode_select.hip, sampling is
+// sample.hip; the greedy choice of step i - 1 can also run inside dec_self_kernel of step i (fused_select below).
 //
 // "LN-on-load": a block does not apply its closing residual + LayerNorm itself (that would need all heads /
 // chunks of the row in one workgroup, i.e. too few workgroups to stream K/V at HBM rate).  It leaves its
@@ -26,7 +26,7 @@
 // 53 MB at B=32, S=216 -> HBM-bound) plus ~16 MB of weights that stay L2 / Infinity-Cache
 // resident.  Every workgroup's weight loads are issued before the data they multiply is ready (they do not
 // depend on it), so a kernel is ~3 memory round trips long.
-#include "common.h"
+#include "decode_select.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -110,22 +110,12 @@ __device__ __forceinline__ float4 ld4o_stream(const float* base, uint32_t byteof
 __device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ void f4add(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 
-// Lane exchanges inside a row of 16 lanes as DPP operands (one VALU instruction each) instead of ds_bpermute round
-// trips through the LDS crossbar (~100 cycles each, four in a row per dot product): quad_perm [1,0,3,2] / [2,3,0,1]
-// pair lanes inside a quad, row_half_mirror / row_mirror then pair quads and halves (every lane of a quad / half
-// already holds the same partial result), row_ror:8 swaps the halves of a row.  Full waves only (common.h).
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-template <int CTRL>
-__device__ __forceinline__ int dppi(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
-constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppMirror = 0x140, kDppRor8 = 0x128;
+// lane exchanges inside a row of 16 lanes: DPP operands (decode_select.h)
 __device__ __forceinline__ float sum8(float v) {      // over aligned groups of 8 lanes, result in every lane
-    v += dppf<kDppXor1>(v); v += dppf<kDppXor2>(v); v += dppf<kDppHalfMirror>(v);
+    v += dpp_f32<kDppXor1>(v); v += dpp_f32<kDppXor2>(v); v += dpp_f32<kDppHalfMirror>(v);
     return v;
 }
-__device__ __forceinline__ float sum16(float v) { v = sum8(v); v += dppf<kDppMirror>(v); return v; }
+__device__ __forceinline__ float sum16(float v) { v = sum8(v); v += dpp_f32<kDppMirror>(v); return v; }
 
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
     return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w)));
@@ -470,8 +460,8 @@ __device__ __forceinline__ void attend_chunk(KVRegs<NPC>& kv, const float4 (&q4)
 // columns 4c .. 4c+3.  A position's weight sits in its 8 column lanes, hence the exact factor 1/8.
 __device__ __forceinline__ void attend_reduce(AttnState& st) {
     st.l = wave_sum(st.l) * 0.125f;
-    st.acc.x += dppf<kDppRor8>(st.acc.x); st.acc.y += dppf<kDppRor8>(st.acc.y);
-    st.acc.z += dppf<kDppRor8>(st.acc.z); st.acc.w += dppf<kDppRor8>(st.acc.w);
+    st.acc.x += dpp_f32<kDppRor8>(st.acc.x); st.acc.y += dpp_f32<kDppRor8>(st.acc.y);
+    st.acc.z += dpp_f32<kDppRor8>(st.acc.z); st.acc.w += dpp_f32<kDppRor8>(st.acc.w);
 #pragma unroll
     for (int off = 16; off < 64; off <<= 1) {
         st.acc.x += __shfl_xor(st.acc.x, off, 64); st.acc.y += __shfl_xor(st.acc.y, off, 64);
@@ -496,14 +486,8 @@ struct LayerW {
 // in two alternating buffers, so that the one workgroup that records the decision (head 0: output / history / flags /
 // counter / caption buffer / next window) never writes what the others read.
 // ---------------------------------------------------------------------------------------------------------
-struct SelFuse {
-    const float4* cand; int ntiles; const float* ptr;
-    int64_t* output; int32_t* hist; int32_t* finished; int32_t* n_done; int64_t* next_token; int64_t* next_mask;
-    int64_t* cap_buf;
+struct SelFuse : GreedySel {
     const int32_t* st_in; int32_t* st_out;           // (R, 12)
-    const float *word_emb, *ee, *fe, *pe;
-    int rows_per_sample, V, K, F, step, max_len, has_facts, end_token, pad_token;
-    float emb_scale;
 };
 
 __device__ __forceinline__ uint64_t top_key(float v, int idx) {      // larger value first, then smaller index
@@ -530,7 +514,8 @@ __device__ __forceinline__ void fused_select(const SelFuse& f, int64_t r0, int R
     const int g = min(wave / WPR, G - 1), wr = wave - g * WPR;
     const bool mine = wave < G * WPR;
     const int64_t row = min(r0 + g, (int64_t)R - 1);
-    const int np = f.K + f.F, i = f.step;
+    const TokenEmbed& e = f.emb;
+    const int np = e.K + e.F, i = f.step;
     // this wave's share of the row's candidates: vocabulary tiles, then pointer scores
     float v1 = -INFINITY, v2 = -INFINITY;
     int i1 = 0x7fffffff, i2 = 0x7fffffff;
@@ -540,7 +525,7 @@ __device__ __forceinline__ void fused_select(const SelFuse& f, int64_t r0, int R
             const float4 c = f.cand[row * f.ntiles + t];
             a1 = c.x; j1 = __float_as_int(c.y); a2 = c.z; j2 = __float_as_int(c.w);
         } else {
-            a1 = f.ptr[row * np + (t - f.ntiles)]; j1 = f.V + (t - f.ntiles); a2 = -INFINITY; j2 = 0x7fffffff;
+            a1 = f.ptr[row * np + (t - f.ntiles)]; j1 = e.V + (t - f.ntiles); a2 = -INFINITY; j2 = 0x7fffffff;
         }
         // merge (a1, j1) >= (a2, j2) into the lane's running pair
         const bool b1 = top_key(a1, j1) > top_key(v1, i1);
@@ -573,61 +558,41 @@ __device__ __forceinline__ void fused_select(const SelFuse& f, int64_t r0, int R
 #pragma unroll
     for (int q = 0; q < 3; ++q) ph[q] = st[5 + q];
     const int fin = st[8];
-    int tok = 0, msk = 0, cur = 0, nfin = fin;
-    int rw1 = po[0], rw2 = po[1], rw3 = po[2];      // output[i-1 .. i-3] after the clean-up
-    int nrw = 0;
-    if (!fin) {
-        if (best == f.end_token) {
-            cur = best; nfin = 1;
-        } else {
-            cur = best;
-            // repeated n-gram clean-up (geo-aware/models.py:421-435)
-            if (i > 0 && cur == po[0]) {
-                cur = second;
-            } else if (i > 2 && cur == po[1] && po[0] == po[2]) {
-                cur = second; rw1 = ph[0]; nrw = 1;
-            } else if (i > 4 && cur == po[2] && po[0] == po[3] && po[1] == po[4]) {
-                cur = second; rw1 = ph[0]; rw2 = ph[1]; rw3 = ph[2]; nrw = 3;
-            }
-            tok = cur;
-            msk = token_kind(cur, f.V, f.K, f.has_facts);
-        }
-    }
+    const GreedyStep s = greedy_step(best, second, i, po, ph, fin, f.end_token, e.V, e.K, e.has_facts);
     if (recorder && r0 + g < R && lane == 0) {
         int64_t* o = f.output + row * f.max_len;
         if (!fin) {
-            o[i] = cur;
-            if (nfin) { f.finished[row] = 1; atomicAdd(f.n_done, 1); }
+            o[i] = s.cur;
+            if (s.ended) { f.finished[row] = 1; atomicAdd(f.n_done, 1); }
             else {
                 f.hist[row * f.max_len + i] = second;
-                if (nrw >= 1) o[i - 1] = rw1;
-                if (nrw >= 3) { o[i - 2] = rw2; o[i - 3] = rw3; }
+                if (s.nrw >= 1) o[i - 1] = s.rw[0];
+                if (s.nrw >= 3) { o[i - 2] = s.rw[1]; o[i - 3] = s.rw[2]; }
             }
         }
-        f.next_token[row] = tok;
-        f.next_mask[row] = msk;
-        if (f.cap_buf != nullptr && i + 1 < f.max_len) f.cap_buf[row * f.max_len + i + 1] = tok;
+        e.next_token[row] = s.tok;
+        e.next_mask[row] = s.msk;
+        if (f.cap_buf != nullptr && i + 1 < f.max_len) f.cap_buf[row * f.max_len + i + 1] = s.tok;
         int32_t* so = f.st_out + row * 12;
-        so[0] = fin ? po[0] : cur; so[1] = rw1; so[2] = rw2; so[3] = rw3; so[4] = po[3];
-        so[5] = (fin || nfin) ? ph[0] : second; so[6] = ph[0]; so[7] = ph[1];
-        so[8] = nfin;
+        so[0] = fin ? po[0] : s.cur; so[1] = s.rw[0]; so[2] = s.rw[1]; so[3] = s.rw[2]; so[4] = po[3];
+        so[5] = s.ended ? ph[0] : second; so[6] = ph[0]; so[7] = ph[1];
+        so[8] = s.ended;
     }
     // CaptionEmbedder + sqrt(d) scale + PositionEncoder of the token (geo-aware/models.py:155-181,355-357)
-    const float* src = token_row(tok, msk, row / f.rows_per_sample, f.word_emb, f.ee, f.fe, f.V, f.K, f.F, d,
-                                 f.pad_token);
-    const float* pe = f.pe + (int64_t)pos * d;
+    const float* src = e.row(s.tok, s.msk, row, d);
+    const float* pe = e.pe + (int64_t)pos * d;
     const int d4 = d >> 2;
     const bool ok0 = lane < d4, ok1 = 64 + lane < d4;
     float4 z0 = f4zero(), z1 = f4zero();
     if (ok0) {
         const float4 e4 = ld4(src + 4 * lane), p4 = ld4(pe + 4 * lane);
-        z0 = make_float4(fmaf(e4.x, f.emb_scale, p4.x), fmaf(e4.y, f.emb_scale, p4.y), fmaf(e4.z, f.emb_scale, p4.z),
-                         fmaf(e4.w, f.emb_scale, p4.w));
+        z0 = make_float4(fmaf(e4.x, e.emb_scale, p4.x), fmaf(e4.y, e.emb_scale, p4.y), fmaf(e4.z, e.emb_scale, p4.z),
+                         fmaf(e4.w, e.emb_scale, p4.w));
     }
     if (ok1) {
         const float4 e4 = ld4(src + 4 * (64 + lane)), p4 = ld4(pe + 4 * (64 + lane));
-        z1 = make_float4(fmaf(e4.x, f.emb_scale, p4.x), fmaf(e4.y, f.emb_scale, p4.y), fmaf(e4.z, f.emb_scale, p4.z),
-                         fmaf(e4.w, f.emb_scale, p4.w));
+        z1 = make_float4(fmaf(e4.x, e.emb_scale, p4.x), fmaf(e4.y, e.emb_scale, p4.y), fmaf(e4.z, e.emb_scale, p4.z),
+                         fmaf(e4.w, e.emb_scale, p4.w));
     }
     float* x = xs + g * kDMax;
     reinterpret_cast<float4*>(x)[lane] = z0;
@@ -1052,83 +1017,49 @@ struct VocabArgs {
     const int32_t* n_done; int n_total;
 };
 
-struct Top2 {
-    float v1, v2;
-    int i1, i2;
-};
-// branch-free: the merges run in every lane of a wave (nested ifs compile to exec-mask branches, ~20 per merge)
-__device__ __forceinline__ void top2_push(Top2& s, float v, int i) {
-    const bool b1 = v > s.v1 || (v == s.v1 && i < s.i1);
-    const bool b2 = v > s.v2 || (v == s.v2 && i < s.i2);
-    const float nv2 = b1 ? s.v1 : (b2 ? v : s.v2);
-    const int ni2 = b1 ? s.i1 : (b2 ? i : s.i2);
-    s.v1 = b1 ? v : s.v1;
-    s.i1 = b1 ? i : s.i1;
-    s.v2 = nv2;
-    s.i2 = ni2;
-}
-constexpr int kNone = 0x7fffffff;
-template <int CTRL>
-__device__ __forceinline__ Top2 top2_merge_dpp(Top2 t) {
-    const float v1 = dppf<CTRL>(t.v1), v2 = dppf<CTRL>(t.v2);
-    const int i1 = dppi<CTRL>(t.i1), i2 = dppi<CTRL>(t.i2);
-    top2_push(t, v1, i1);
-    top2_push(t, v2, i2);
-    return t;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // vocabulary logits: workgroup = kVocabTile words x all rows (blocks of 32), the eight waves split K; fp32 MFMA
 // 16x16x4.  One workgroup per CU at V = 10 000 (209 of them): its 58 KB weight slice is fetched once and stays in
 // registers for every block of 32 rows (beam search decodes captions x beams rows).
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kVocabTile = 48;
 constexpr int kVocabCT = kVocabTile / 16;     // 16-word column tiles per workgroup
 constexpr int kVocabKC = 3;                   // 16-wide k chunks per wave: 8 x 3 x 16 = 384 >= kDMax
-__global__ __launch_bounds__(kNT) void dec_vocab_kernel(VocabArgs a) {
-    __shared__ __attribute__((aligned(16))) float red[kNW][2][kVocabCT][16][17];
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
-    const int fi = lane & 15, fq = lane >> 4;
-    const int n0 = blockIdx.x * kVocabTile;
-    const int d = a.d;
-    const int done = a.n_done != nullptr ? *a.n_done : 0;
-    ICK_STAMP(3, 0);
-    // this wave's K slice of the 48 weight rows
+using VocabRed = float[kNW][2][kVocabCT][16][17];     // LDS: the waves' partial 32 x 48 products
+
+// The tile of one workgroup, the part dec_vocab_kernel and dec_headvocab_kernel share: the wave's K slice of the 48
+// weight rows in registers, the products of a block of 32 rows (the kernels differ in where the rows come from: global
+// memory, or the LN-on-load rows in LDS), and the epilogue that reduces the eight slices.
+struct VocabTile {
     float4 bw[kVocabCT][kVocabKC];
-    uint32_t koff[kVocabKC];
-    bool kok[kVocabKC];
-#pragma unroll
-    for (int t = 0; t < kVocabKC; ++t) {
-        const int k = 16 * (kVocabKC * wave + t) + 4 * fq;
-        kok[t] = k < d;                              // d % 4 == 0: a float4 is entirely inside or outside
-        koff[t] = kok[t] ? 4u * (uint32_t)k : 0u;
-    }
-#pragma unroll
-    for (int ct = 0; ct < kVocabCT; ++ct) {
-        const uint32_t rb = (uint32_t)min(n0 + 16 * ct + fi, a.V - 1) * (uint32_t)d * 4u;
+    uint32_t koff[kVocabKC];                     // byte offset of this lane's float4 of k chunk t in a row of d floats
+    bool kok[kVocabKC];                          // d % 4 == 0: a float4 is entirely inside or outside
+    float biasv[kVocabCT];
+    // (The pieces take plain values, not the kernel's VocabArgs by reference: a kernel argument whose address is taken
+    // is copied to private memory first, and the loads through its pointers stop being scalar loads.)
+    // issues the loads only: the weights first (HBM, the longest wait of either kernel), then the bias
+    __device__ __forceinline__ void load(const float* wv, const float* bv, int V, int d, int n0) {
+        const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), fi = lane & 15, fq = lane >> 4, cp = tid & 15;
 #pragma unroll
         for (int t = 0; t < kVocabKC; ++t) {
-            bw[ct][t] = ld4o(a.wv, rb + koff[t]);
-            if (!kok[t]) bw[ct][t] = f4zero();
+            const int k = 16 * (kVocabKC * wave + t) + 4 * fq;
+            kok[t] = k < d;
+            koff[t] = kok[t] ? 4u * (uint32_t)k : 0u;
         }
+#pragma unroll
+        for (int ct = 0; ct < kVocabCT; ++ct) {
+            const uint32_t rb = (uint32_t)min(n0 + 16 * ct + fi, V - 1) * (uint32_t)d * 4u;
+#pragma unroll
+            for (int t = 0; t < kVocabKC; ++t) {
+                bw[ct][t] = ld4o(wv, rb + koff[t]);
+                if (!kok[t]) bw[ct][t] = f4zero();
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < kVocabCT; ++e) biasv[e] = bv[min(n0 + kVocabCT * cp + e, V - 1)];
     }
-    const int row = tid >> 4, cp = tid & 15;         // epilogue role: one row, three columns
-    constexpr int kCols = kVocabTile / 16;
-    float biasv[kCols];
-#pragma unroll
-    for (int e = 0; e < kCols; ++e) biasv[e] = a.bv[min(n0 + kCols * cp + e, a.V - 1)];
-    if (done >= a.n_total) return;
-    for (int m0 = 0; m0 < a.R; m0 += 32) {
-        const uint32_t ra0 = (uint32_t)min(m0 + fi, a.R - 1) * (uint32_t)d * 4u,
-                       ra1 = (uint32_t)min(m0 + 16 + fi, a.R - 1) * (uint32_t)d * 4u;
-        float4 av0[kVocabKC], av1[kVocabKC];
-#pragma unroll
-        for (int t = 0; t < kVocabKC; ++t) {
-            av0[t] = ld4o(a.hv, ra0 + koff[t]);
-            av1[t] = ld4o(a.hv, ra1 + koff[t]);
-            if (!kok[t]) av0[t] = av1[t] = f4zero();
-        }
-        ICK_STAMP(3, 1);
+    // av0 / av1: rows fi and 16 + fi of the block; follow with a barrier
+    __device__ __forceinline__ void mma(const float4 (&av0)[kVocabKC], const float4 (&av1)[kVocabKC], VocabRed& red) const {
+        const int lane = threadIdx.x & 63, wave = wave_id(), fi = lane & 15, fq = lane >> 4;
 #pragma unroll
         for (int ct = 0; ct < kVocabCT; ++ct) {
             f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -1150,31 +1081,58 @@ __global__ __launch_bounds__(kNT) void dec_vocab_kernel(VocabArgs a) {
                 red[wave][1][ct][fq * 4 + rg][fi] = acc1[rg];
             }
         }
-        ICK_STAMP(3, 2);
-        __syncthreads();
-        ICK_STAMP(3, 3);
-        // thread (row = tid >> 4, three columns): sum the eight K slices in a fixed order, add the bias
-        const int gr = m0 + row;
+    }
+    // thread (row = tid >> 4 of the block, three columns): sum the eight K slices in a fixed order, add the bias, store
+    // the logits (optional) and the tile's top-2 candidates of the row; gr: the row's global index
+    __device__ __forceinline__ void epilogue(float* scores, int64_t ld, float4* cand, int ntiles, int R, int V, int n0,
+                                             int gr, const VocabRed& red) const {
+        const int row = threadIdx.x >> 4, cp = threadIdx.x & 15;
         Top2 t2{-INFINITY, -INFINITY, kNone, kNone};
 #pragma unroll
-        for (int e = 0; e < kCols; ++e) {
-            const int col = kCols * cp + e, n = n0 + col, ct = col >> 4, cc = col & 15;
+        for (int e = 0; e < kVocabCT; ++e) {
+            const int col = kVocabCT * cp + e, n = n0 + col, ct = col >> 4, cc = col & 15;
             float v = red[0][row >> 4][ct][row & 15][cc];
 #pragma unroll
             for (int w = 1; w < kNW; ++w) v += red[w][row >> 4][ct][row & 15][cc];
-            if (n < a.V) {
+            if (n < V) {
                 v += biasv[e];
-                if (a.scores != nullptr && gr < a.R) a.scores[(int64_t)gr * a.ld + n] = v;
+                if (scores != nullptr && gr < R) scores[(int64_t)gr * ld + n] = v;
                 top2_push(t2, v, n);
             }
         }
-        t2 = top2_merge_dpp<kDppXor1>(t2);      // empty slots carry (-inf, kNone): they never displace anything
-        t2 = top2_merge_dpp<kDppXor2>(t2);
-        t2 = top2_merge_dpp<kDppHalfMirror>(t2);
-        t2 = top2_merge_dpp<kDppMirror>(t2);
-        if (cp == 0 && gr < a.R)
-            a.cand[(int64_t)gr * a.ntiles + blockIdx.x] =
+        t2 = top2_merge_row(t2);                // empty slots carry (-inf, kNone): they never displace anything
+        if (cp == 0 && gr < R)
+            cand[(int64_t)gr * ntiles + blockIdx.x] =
                 make_float4(t2.v1, __int_as_float(t2.i1), t2.v2, __int_as_float(t2.i2));
+    }
+};
+
+__global__ __launch_bounds__(kNT) void dec_vocab_kernel(VocabArgs a) {
+    __shared__ __attribute__((aligned(16))) VocabRed red;
+    const int tid = threadIdx.x, fi = tid & 15;
+    const int n0 = blockIdx.x * kVocabTile;
+    const int d = a.d;
+    const int done = a.n_done != nullptr ? *a.n_done : 0;
+    ICK_STAMP(3, 0);
+    VocabTile vt;
+    vt.load(a.wv, a.bv, a.V, a.d, n0);
+    if (done >= a.n_total) return;
+    for (int m0 = 0; m0 < a.R; m0 += 32) {
+        const uint32_t ra0 = (uint32_t)min(m0 + fi, a.R - 1) * (uint32_t)d * 4u,
+                       ra1 = (uint32_t)min(m0 + 16 + fi, a.R - 1) * (uint32_t)d * 4u;
+        float4 av0[kVocabKC], av1[kVocabKC];
+#pragma unroll
+        for (int t = 0; t < kVocabKC; ++t) {
+            av0[t] = ld4o(a.hv, ra0 + vt.koff[t]);
+            av1[t] = ld4o(a.hv, ra1 + vt.koff[t]);
+            if (!vt.kok[t]) av0[t] = av1[t] = f4zero();
+        }
+        ICK_STAMP(3, 1);
+        vt.mma(av0, av1, red);
+        ICK_STAMP(3, 2);
+        __syncthreads();
+        ICK_STAMP(3, 3);
+        vt.epilogue(a.scores, a.ld, a.cand, a.ntiles, a.R, a.V, n0, m0 + (tid >> 4), red);
         ICK_STAMP(3, 4);
         if (m0 + 32 < a.R) __syncthreads();       // the exchange buffer is reused by the next block of rows
     }
@@ -1193,42 +1151,20 @@ constexpr int kHvSrc = 12;                    // residual + bias + up to 10 part
 constexpr int kHvChunk = 4;                   // source rows in flight per lane (x 5 float4)
 constexpr int kHvLd = kDMax + 4;              // LDS row stride of the normalised rows
 __global__ __launch_bounds__(kNT) void dec_headvocab_kernel(HeadArgs ha, VocabArgs a) {
-    __shared__ __attribute__((aligned(16))) float red[kNW][2][kVocabCT][16][17];
+    __shared__ __attribute__((aligned(16))) VocabRed red;
     __shared__ __attribute__((aligned(16))) float xa[32 * kHvLd];
     __shared__ __attribute__((aligned(16))) float4 psum[4 * kD4Max];
     if ((int)blockIdx.x >= a.ntiles) {          // head role (uniform per workgroup)
         head_row(ha, (int64_t)blockIdx.x - a.ntiles, xa, psum);
         return;
     }
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
-    const int fi = lane & 15, fq = lane >> 4;
+    const int tid = threadIdx.x, fi = tid & 15;
     const int n0 = blockIdx.x * kVocabTile;
     const int d = a.d, d4 = d >> 2;
     const int done = a.n_done != nullptr ? *a.n_done : 0;
-    // this wave's K slice of the 48 weight rows (HBM: the longest wait of the kernel, requested first)
-    float4 bw[kVocabCT][kVocabKC];
-    uint32_t koff[kVocabKC];
-    bool kok[kVocabKC];
-#pragma unroll
-    for (int t = 0; t < kVocabKC; ++t) {
-        const int k = 16 * (kVocabKC * wave + t) + 4 * fq;
-        kok[t] = k < d;
-        koff[t] = kok[t] ? 4u * (uint32_t)k : 0u;
-    }
-#pragma unroll
-    for (int ct = 0; ct < kVocabCT; ++ct) {
-        const uint32_t rb = (uint32_t)min(n0 + 16 * ct + fi, a.V - 1) * (uint32_t)d * 4u;
-#pragma unroll
-        for (int t = 0; t < kVocabKC; ++t) {
-            bw[ct][t] = ld4o(a.wv, rb + koff[t]);
-            if (!kok[t]) bw[ct][t] = f4zero();
-        }
-    }
-    const int row = tid >> 4, cp = tid & 15;         // LN role and epilogue role: one row per 16 lanes
-    constexpr int kCols = kVocabTile / 16;
-    float biasv[kCols];
-#pragma unroll
-    for (int e = 0; e < kCols; ++e) biasv[e] = a.bv[min(n0 + kCols * cp + e, a.V - 1)];
+    VocabTile vt;
+    vt.load(a.wv, a.bv, a.V, a.d, n0);
+    const int row = tid >> 4, cp = tid & 15;         // LN role: one row per 16 lanes
     if (done >= a.n_total) return;
     // ---- x[row] = LayerNorm(res + bias + sum of the partial rows) (x gate): lane cp holds float4 columns cp + 16 it
     {
@@ -1305,636 +1241,12 @@ __global__ __launch_bounds__(kNT) void dec_headvocab_kernel(HeadArgs ha, VocabAr
     float4 av0[kVocabKC], av1[kVocabKC];
 #pragma unroll
     for (int t = 0; t < kVocabKC; ++t) {
-        av0[t] = kok[t] ? *reinterpret_cast<const float4*>(xa + fi * kHvLd + (koff[t] >> 2)) : f4zero();
-        av1[t] = kok[t] ? *reinterpret_cast<const float4*>(xa + (16 + fi) * kHvLd + (koff[t] >> 2)) : f4zero();
+        av0[t] = vt.kok[t] ? *reinterpret_cast<const float4*>(xa + fi * kHvLd + (vt.koff[t] >> 2)) : f4zero();
+        av1[t] = vt.kok[t] ? *reinterpret_cast<const float4*>(xa + (16 + fi) * kHvLd + (vt.koff[t] >> 2)) : f4zero();
     }
-#pragma unroll
-    for (int ct = 0; ct < kVocabCT; ++ct) {
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < kVocabKC; ++t) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[t].x, bw[ct][t].x, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[t].x, bw[ct][t].x, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[t].y, bw[ct][t].y, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[t].y, bw[ct][t].y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[t].z, bw[ct][t].z, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[t].z, bw[ct][t].z, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[t].w, bw[ct][t].w, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[t].w, bw[ct][t].w, acc1, 0, 0, 0);
-        }
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-            red[wave][0][ct][fq * 4 + rg][fi] = acc0[rg];
-            red[wave][1][ct][fq * 4 + rg][fi] = acc1[rg];
-        }
-    }
+    vt.mma(av0, av1, red);
     __syncthreads();
-    // thread (row = tid >> 4, three columns): sum the eight K slices in a fixed order, add the bias
-    Top2 t2{-INFINITY, -INFINITY, kNone, kNone};
-#pragma unroll
-    for (int e = 0; e < kCols; ++e) {
-        const int colv = kCols * cp + e, n = n0 + colv, ct = colv >> 4, cc = colv & 15;
-        float v = red[0][row >> 4][ct][row & 15][cc];
-#pragma unroll
-        for (int w = 1; w < kNW; ++w) v += red[w][row >> 4][ct][row & 15][cc];
-        if (n < a.V) {
-            v += biasv[e];
-            if (a.scores != nullptr && row < a.R) a.scores[(int64_t)row * a.ld + n] = v;
-            top2_push(t2, v, n);
-        }
-    }
-    t2 = top2_merge_dpp<kDppXor1>(t2);
-    t2 = top2_merge_dpp<kDppXor2>(t2);
-    t2 = top2_merge_dpp<kDppHalfMirror>(t2);
-    t2 = top2_merge_dpp<kDppMirror>(t2);
-    if (cp == 0 && row < a.R)
-        a.cand[(int64_t)row * a.ntiles + blockIdx.x] =
-            make_float4(t2.v1, __int_as_float(t2.i1), t2.v2, __int_as_float(t2.i2));
-}
-
-struct SelectArgs {
-    const float4* cand; int ntiles;
-    const float* ptr;              // (R, K + F)
-    int64_t* output;               // (R, max_len)
-    int32_t* hist;                 // (R, max_len) runner-up of every step
-    int32_t* finished;             // (R)
-    int32_t* n_done;               // number of finished rows (early exit of the following steps)
-    int64_t* next_token; int64_t* next_mask;   // (R)
-    int64_t* cap_buf;              // optional (R, max_len): the caption buffer get_context_indicators reads
-    // embedding of the next token
-    const float *word_emb, *ee, *fe, *pe;
-    float* x0;                     // (R, d)
-    int R, rows_per_sample, d, V, K, F, step, max_len, has_facts, end_token, pad_token;
-    float emb_scale;
-    int n_total;
-};
-
-__device__ __forceinline__ Top2 top2_merge_wave(Top2 t) {
-    t = top2_merge_dpp<kDppXor1>(t);
-    t = top2_merge_dpp<kDppXor2>(t);
-    t = top2_merge_dpp<kDppHalfMirror>(t);
-    t = top2_merge_dpp<kDppMirror>(t);
-#pragma unroll
-    for (int off = 16; off < 64; off <<= 1) {
-        Top2 o;
-        o.v1 = __shfl_xor(t.v1, off, 64); o.i1 = __shfl_xor(t.i1, off, 64);
-        o.v2 = __shfl_xor(t.v2, off, 64); o.i2 = __shfl_xor(t.i2, off, 64);
-        top2_push(t, o.v1, o.i1);
-        top2_push(t, o.v2, o.i2);
-    }
-    return t;
-}
-
-// Selection + predict()'s per-step bookkeeping for one caption (geo-aware/models.py:410-441) + embedding of the
-// next input token.  Thread 0 fetches the caption's recent history while the workgroup scans the candidates, so the
-// n-gram clean-up runs on registers: the kernel is two memory round trips long (candidates, embedding row).
-__global__ __launch_bounds__(256) void dec_select_kernel(SelectArgs a) {
-    if (*a.n_done >= a.n_total) return;
-    __shared__ Top2 sh[4];
-    __shared__ int64_t tok_sh[2];
-    const int tid = threadIdx.x, i = a.step;
-    const int64_t r = blockIdx.x;
-    int64_t* o = a.output + r * a.max_len;
-    int32_t* hs = a.hist + r * a.max_len;
-    int64_t po[5] = {-1, -1, -1, -1, -1};     // output[i-1 .. i-5]
-    int ph[3] = {0, 0, 0};                    // runner-ups of steps i-1 .. i-3
-    int fin = 0;
-    if (tid == 0) {
-        fin = a.finished[r];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) po[q] = o[max(i - 1 - q, 0)];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) ph[q] = hs[max(i - 1 - q, 0)];
-    }
-    Top2 s{-INFINITY, -INFINITY, kNone, kNone};
-    constexpr int NC = 4;                      // 1024 candidate tiles (49 152 words) per sweep
-    for (int t0 = 0; t0 < a.ntiles; t0 += 256 * NC) {
-        float4 cd[NC];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) cd[q] = a.cand[r * a.ntiles + min(t0 + tid + 256 * q, a.ntiles - 1)];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) {
-            if (t0 + tid + 256 * q >= a.ntiles) continue;
-            const int i1 = __float_as_int(cd[q].y), i2 = __float_as_int(cd[q].w);
-            top2_push(s, cd[q].x, i1);
-            top2_push(s, cd[q].z, i2);
-        }
-    }
-    const int np = a.K + a.F;
-    for (int k = tid; k < np; k += 256) top2_push(s, a.ptr[r * np + k], a.V + k);
-    s = top2_merge_wave(s);
-    if ((tid & 63) == 0) sh[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-        Top2 t = sh[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            top2_push(t, sh[w].v1, sh[w].i1);
-            top2_push(t, sh[w].v2, sh[w].i2);
-        }
-        const int best = t.i1, second = t.i2 == kNone ? t.i1 : t.i2;
-        int64_t tok = 0, msk = 0;
-        if (!fin) {
-            if (best == a.end_token) {
-                o[i] = best;
-                a.finished[r] = 1;
-                atomicAdd(a.n_done, 1);
-            } else {
-                hs[i] = second;
-                int64_t cur = best;
-                // repeated n-gram clean-up (geo-aware/models.py:421-435) on the registers
-                if (i > 0 && cur == po[0]) {
-                    cur = second;
-                } else if (i > 2 && cur == po[1] && po[0] == po[2]) {
-                    cur = second;
-                    o[i - 1] = ph[0];
-                } else if (i > 4 && cur == po[2] && po[0] == po[3] && po[1] == po[4]) {
-                    cur = second;
-                    o[i - 1] = ph[0]; o[i - 2] = ph[1]; o[i - 3] = ph[2];
-                }
-                o[i] = cur;
-                tok = cur;
-                msk = token_kind(cur, a.V, a.K, a.has_facts);
-            }
-        }
-        a.next_token[r] = tok;
-        a.next_mask[r] = msk;
-        tok_sh[0] = tok;
-        tok_sh[1] = msk;
-        if (a.cap_buf != nullptr && i + 1 < a.max_len) a.cap_buf[r * a.max_len + i + 1] = tok;
-    }
-    __syncthreads();
-    if (i + 1 >= a.max_len) return;
-    // CaptionEmbedder + sqrt(d) scale + PositionEncoder of the next input token (geo-aware/models.py:155-181,355-357)
-    const int64_t tok = tok_sh[0], msk = tok_sh[1];
-    const float* src = token_row(tok, (int)msk, r / a.rows_per_sample, a.word_emb, a.ee, a.fe, a.V, a.K, a.F, a.d,
-                                 a.pad_token);
-    const float* pe = a.pe + (int64_t)(i + 1) * a.d;
-    for (int c = tid; c < a.d; c += 256) a.x0[r * a.d + c] = fmaf(src[c], a.emb_scale, pe[c]);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// beam selection: one workgroup per caption; its k hypotheses are rows b*k .. b*k+k-1
-// ---------------------------------------------------------------------------------------------------------
-constexpr int kBeamMax = 8;
-struct BeamArgs {
-    const float* rec;                   // (R, nchunk, kBeamRec) chunk records of dec_beam_partial_kernel
-    float* cum;                         // (R) cumulative log-probability of every hypothesis
-    int32_t* fin;                       // (R) hypothesis has produced <end>
-    const int64_t* seq_in; int64_t* seq_out;     // (R, max_len) tokens so far
-    const int32_t* anc_in; int32_t* anc_out;     // (R, max_len) cache row of every position
-    const int64_t* cap_in; int64_t* cap_out;     // optional (R, max_len) caption buffers (<start> + tokens)
-    int32_t* n_done;
-    int64_t* next_token; int64_t* next_mask;
-    const float *word_emb, *ee, *fe, *pe;
-    float* x0;
-    int R, k, d, V, K, F, step, max_len, has_facts, end_token, pad_token, start_token;
-    float emb_scale;
-    int n_total;
-    // decoding rules (the RULES variant): rule words (length penalty: words[2] != 0), lp[0..max_len], and the tokens
-    // of every hypothesis, <end> included
-    const int32_t* words; const float* lp; int32_t* len;
-    // diverse beam search (the DIVERSE variant): `groups` groups of k / groups hypotheses, and the penalty lambda (one
-    // fp32 in device memory)
-    int groups; const float* penalty;
-    // constrained beam search (the FORCED variant): the forced columns (B, kForceMax), -1 = empty slot, the met-slot
-    // mask of every hypothesis (R), and the step's score rows (the unmet forced columns are read from them)
-    const int32_t* force; int32_t* met;
-    const float* scores; int64_t ld; const float* ptr;
-};
-constexpr int kForceMax = 8;            // forced-column slots per caption (ick_decode_constraints)
-
-// The diversity penalty lambda of ick_decode_diversity, read through the scalar cache like rule_words(): a device input
-// the host writes before a (replayed) decode.
-__device__ __forceinline__ float diversity_penalty(const float* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t v;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
-    return __uint_as_float(v);
-#else
-    return *p;                              // (the host pass only parses device code)
-#endif
-}
-
-// Block-wide arg-best of (value, code) pairs: larger value wins, ties go to the smaller code.  Result in every thread.
-__device__ __forceinline__ void block_best(float& v, int& c, float* shv, int* shc) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float ov = __shfl_xor(v, off, 64);
-        const int oc = __shfl_xor(c, off, 64);
-        const bool take = ov > v || (ov == v && oc < c);
-        v = take ? ov : v;
-        c = take ? oc : c;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = v; shc[threadIdx.x >> 6] = c; }
-    __syncthreads();
-    v = shv[0]; c = shc[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        const bool take = shv[w] > v || (shv[w] == v && shc[w] < c);
-        v = take ? shv[w] : v;
-        c = take ? shc[w] : c;
-    }
-}
-
-// block_best() with a leading integer rank: the larger rank wins, then the larger value, then the smaller code.
-__device__ __forceinline__ bool ranked_before(int p, float v, int c, int op, float ov, int oc) {
-    return op > p || (op == p && (ov > v || (ov == v && oc < c)));
-}
-__device__ __forceinline__ void block_best_ranked(int& p, float& v, int& c, int* shp, float* shv, int* shc) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int op = __shfl_xor(p, off, 64);
-        const float ov = __shfl_xor(v, off, 64);
-        const int oc = __shfl_xor(c, off, 64);
-        const bool take = ranked_before(p, v, c, op, ov, oc);
-        p = take ? op : p;
-        v = take ? ov : v;
-        c = take ? oc : c;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { shp[threadIdx.x >> 6] = p; shv[threadIdx.x >> 6] = v; shc[threadIdx.x >> 6] = c; }
-    __syncthreads();
-    p = shp[0]; v = shv[0]; c = shc[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        const bool take = ranked_before(p, v, c, shp[w], shv[w], shc[w]);
-        p = take ? shp[w] : p;
-        v = take ? shv[w] : v;
-        c = take ? shc[w] : c;
-    }
-}
-
-constexpr int kBeamChunk = 1024;      // scores per stage-1 workgroup
-constexpr int kBeamCandPerThread = 16; // stage 2 holds beam^2 x chunks candidates in the registers of 256 threads
-constexpr int kBeamRec = 2 + 2 * kBeamMax;   // floats per (row, chunk) record: max, sum of exp, kBeamMax x (value, index)
-
-// Stage 1 of the beam selection, one workgroup per (chunk of 1024 scores, row): the chunk's maximum, its sum of
-// exp(score - maximum), and its k best (value, index) pairs -- 5 x 10 k scores per caption are reduced by 50
-// workgroups instead of one.
-struct BeamPartArgs {
-    const float* scores; int64_t ld; const float* ptr;
-    const float* cum; const int32_t* fin;
-    float* rec;                         // (R, nchunk, kBeamRec)
-    int R, k, V, np, nchunk;
-    const int32_t* n_done; int n_total;
-    // decoding rules (nullptr: off): the row's tokens so far seq (R, max_len), the rule words
-    const int64_t* seq; const int32_t* words;
-    int step, max_len, end_token;
-};
-// Constrained beam search (the FORCED variant) appends the forced columns (R / k, kForceMax) and the met-slot masks (R).
-// They extend the struct for that variant alone: the hidden launch arguments the other instantiations read follow the
-// explicit ones, and would move with them.
-struct BeamPartForcedArgs : BeamPartArgs {
-    const int32_t* force; const int32_t* met;
-};
-// RULES: the decoding-rules variant (ick_decode_select_beam_rules); FORCED: constrained beam search
-// (ick_decode_select_beam_forced)
-template <bool RULES, bool FORCED = false>
-__global__ __launch_bounds__(256)
-void dec_beam_partial_kernel(std::conditional_t<FORCED, BeamPartForcedArgs, BeamPartArgs> a) {
-    if (*a.n_done >= a.n_total) return;
-    __shared__ float shv[4];
-    __shared__ int shc[4];
-    __shared__ float red[8];
-    __shared__ uint32_t ban[kBeamChunk / 32];
-    __shared__ int hs[kRuleHistMax];
-    const int tid = threadIdx.x, ch = blockIdx.x;
-    const int64_t r = blockIdx.y;
-    if (a.fin[r] || a.cum[r] == -INFINITY) return;         // ended / unused hypothesis: nothing to expand (uniform)
-    const uint4 rw = RULES ? rule_words(a.words) : make_uint4(0u, 0u, 0u, 0u);
-    const int nrep = (int)rw.x, mlen = (int)rw.y;
-    const int Vx = a.V + a.np;
-    const float* row = a.scores + r * a.ld;
-    const float* pr = a.ptr + r * a.np;
-    float x[4];
-    int idx[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        idx[q] = ch * kBeamChunk + tid + 256 * q;
-        const int v = min(idx[q], Vx - 1);
-        x[q] = v < a.V ? row[v] : pr[v - a.V];
-        if (idx[q] >= Vx) { x[q] = -INFINITY; idx[q] = kNone; }
-    }
-    float m = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
-    m = block_max<4>(m, red);
-    float e = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) e += x[q] == -INFINITY ? 0.f : __expf(x[q] - m);
-    e = block_sum<4>(e, red);
-    float* rec = a.rec + (r * a.nchunk + ch) * kBeamRec;
-    if (tid == 0) { rec[0] = m; rec[1] = e; }
-    if (RULES && (nrep > 0 || a.step < mlen)) {             // uniform: the banned columns leave the pool (not the sums)
-        mark_bans(a.seq + r * a.max_len, a.step, nrep, mlen, a.end_token, ban, ch * kBeamChunk, kBeamChunk / 32, hs);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c = tid + 256 * q;
-            if ((ban[c >> 5] >> (c & 31)) & 1u) { x[q] = -INFINITY; idx[q] = kNone; }
-        }
-    }
-    if constexpr (FORCED) {
-        // The row's unmet forced columns, and <end> while one is unmet, leave the pool as bans do (not the sums):
-        // stage 2 ranks the former as candidates of their own, in a higher bank.  Every column left has the row's bank.
-        const int32_t* fr = a.force + (r / a.k) * kForceMax;
-        const int met = a.met[r];
-        bool unmet_any = false;
-#pragma unroll
-        for (int s = 0; s < kForceMax; ++s) {
-            const int w = fr[s];
-            const bool unmet = w >= 0 && !((met >> s) & 1);
-            unmet_any = unmet_any || unmet;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (unmet && idx[q] == w) { x[q] = -INFINITY; idx[q] = kNone; }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (unmet_any && idx[q] == a.end_token) { x[q] = -INFINITY; idx[q] = kNone; }
-    }
-    for (int round = 0; round < a.k; ++round) {
-        float bv = -INFINITY; int bc = kNone;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool take = x[q] > bv || (x[q] == bv && idx[q] < bc);
-            bv = take ? x[q] : bv;
-            bc = take ? idx[q] : bc;
-        }
-        block_best(bv, bc, shv, shc);
-        if (tid == 0) { rec[2 + 2 * round] = bv; rec[3 + 2 * round] = __int_as_float(bc); }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (idx[q] == bc) { x[q] = -INFINITY; idx[q] = kNone; }      // the winner leaves the pool
-    }
-}
-
-// The LDS tables of one caption's selection step, by hypothesis (force: by forced slot).  met, force, nmet belong to the
-// FORCED variant and xtok to the DIVERSE one.
-struct BeamRows {
-    float *cum, *lse;
-    int *fin, *len, *parent, *tok, *nfin, *met, *force, *nmet, *xtok;
-};
-
-// One selection round: the block-wide arg-best (bv, bc) of every thread's candidates; the winner leaves the pool.
-template <int N>
-__device__ __forceinline__ void beam_round(float (&v)[N], int (&c)[N], float& bv, int& bc, float* shv, int* shc) {
-    bv = -INFINITY; bc = kNone;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        const bool take = v[q] > bv || (v[q] == bv && c[q] < bc);
-        bv = take ? v[q] : bv;
-        bc = take ? c[q] : bc;
-    }
-    block_best(bv, bc, shv, shc);
-#pragma unroll
-    for (int q = 0; q < N; ++q)
-        if (c[q] == bc) { v[q] = -INFINITY; c[q] = kNone; }
-}
-
-// The winner of a round (code c, key `key`) becomes hypothesis h: thread 0 decides parent, token and ended-or-not and
-// stores the step's bookkeeping.  cum is the raw summed log-probability: where the key is not that (length penalty,
-// diversity penalty, banks) it is derived again from the step's score row, by the expression that made the key.
-template <bool DIVERSE, bool FORCED>
-__device__ __forceinline__ void beam_winner(const BeamArgs& a, const BeamRows& s, int64_t r0, bool lp_on, int h,
-                                            float key, int c) {
-    const int np = a.K + a.F, Vx = a.V + np;
-    const bool rederive = DIVERSE || FORCED || lp_on;
-    float v = rederive || c == kNone ? -INFINITY : key;         // fewer candidates than beams: a dead slot
-    int parent = 0, tok = a.pad_token, nf = 1, len = 0, met = 0;
-    if (c != kNone) {
-        parent = c / Vx;
-        if constexpr (FORCED) met = s.met[parent];
-        if (s.fin[parent]) {                                    // an ended hypothesis is carried as it is
-            if (rederive) v = s.cum[parent];
-            if (lp_on) len = s.len[parent];
-        } else {
-            tok = c - parent * Vx; nf = tok == a.end_token;
-            if (rederive) {
-                const float x = tok < a.V ? a.scores[(r0 + parent) * a.ld + tok]
-                                          : a.ptr[(r0 + parent) * np + (tok - a.V)];
-                v = s.cum[parent] - s.lse[parent] + x;
-            }
-            len = a.step + 1;
-            if constexpr (FORCED)
-                for (int f = 0; f < kForceMax; ++f) met |= s.force[f] == tok ? 1 << f : 0;
-        }
-    }
-    s.parent[h] = parent; s.tok[h] = tok; s.nfin[h] = nf;
-    if constexpr (FORCED) s.nmet[h] = met;
-    if constexpr (DIVERSE) s.xtok[h] = c != kNone && !s.fin[parent] ? tok : -1;
-    if (lp_on) a.len[r0 + h] = len;
-    a.cum[r0 + h] = v;
-    a.fin[r0 + h] = nf;
-    const bool live = c != kNone && !nf;
-    a.next_token[r0 + h] = live ? tok : 0;
-    a.next_mask[r0 + h] = live ? token_kind(tok, a.V, a.K, a.has_facts) : 0;
-}
-
-// DIVERSE: diverse beam search (ick_decode_select_beam_diverse); FORCED: constrained beam search
-// (ick_decode_select_beam_forced)
-template <bool RULES, bool DIVERSE = false, bool FORCED = false>
-__global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
-    // No exit on *n_done here: other workgroups of this very launch add to it, and the hypothesis tables are
-    // ping-pong buffers -- a step that skipped its carry-copy would leave the previous step's rows (in another
-    // order) in the buffer the caller reads.  The decision below only looks at this caption's own state, which no
-    // other workgroup writes.
-    __shared__ float shv[4];
-    __shared__ int shc[4];
-    __shared__ float cum_s[kBeamMax], lse_s[kBeamMax];
-    __shared__ int fin_s[kBeamMax], parent_s[kBeamMax], tok_s[kBeamMax], nfin_s[kBeamMax];
-    __shared__ int len_s[kBeamMax];
-    __shared__ float lpf_s[kBeamMax];
-    __shared__ int met_s[FORCED ? kBeamMax : 1], force_s[FORCED ? kForceMax : 1], nmet_s[FORCED ? kBeamMax : 1];
-    __shared__ int shp[FORCED ? 4 : 1];
-    __shared__ int xtok_s[DIVERSE ? kBeamMax : 1];          // column expanded into slot j at this step, or -1
-    const BeamRows rows{cum_s, lse_s, fin_s, len_s, parent_s, tok_s, nfin_s, met_s, force_s, nmet_s, xtok_s};
-    const int tid = threadIdx.x, k = a.k;
-    const int64_t r0 = (int64_t)blockIdx.x * k;
-    const int np = a.K + a.F, Vx = a.V + np;
-    const int nchunk = (Vx + kBeamChunk - 1) / kBeamChunk;
-    // length penalty (uniform): candidates are ranked by cum / lp[L], L = step + 1 for a live expansion and the length
-    // it ended at for an ended hypothesis; cum itself stays the raw summed log-probability
-    const bool lp_on = RULES && rule_words(a.words).z != 0u;
-    if (tid < k) {
-        cum_s[tid] = a.cum[r0 + tid]; fin_s[tid] = a.fin[r0 + tid];
-        if (lp_on) { len_s[tid] = a.len[r0 + tid]; lpf_s[tid] = a.lp[len_s[tid]]; }
-    }
-    if constexpr (FORCED) {
-        if (tid < k) met_s[tid] = a.met[r0 + tid];
-        if (tid >= 64 && tid < 64 + kForceMax) force_s[tid - 64] = a.force[blockIdx.x * kForceMax + tid - 64];
-    }
-    __syncthreads();
-    bool live_any = false;
-    for (int j = 0; j < k; ++j) live_any = live_any || !(fin_s[j] || cum_s[j] == -INFINITY);
-    if (!live_any) {
-        // every hypothesis of this caption has ended: the tables move to the other buffer as they are
-        for (int idx = tid; idx < k * a.max_len; idx += 256) {
-            const int64_t e = r0 * a.max_len + idx;
-            a.seq_out[e] = a.seq_in[e];
-            a.anc_out[e] = a.anc_in[e];
-            if (a.cap_out != nullptr) a.cap_out[e] = a.cap_in[e];
-        }
-        if (tid < k) { a.next_token[r0 + tid] = 0; a.next_mask[r0 + tid] = 0; }
-        return;
-    }
-    // log-sum-exp of every live row from its chunk records (wave j handles row j, j + 4)
-    for (int j = tid >> 6; j < k; j += 4) {
-        if (fin_s[j] || cum_s[j] == -INFINITY) continue;
-        const int lane = tid & 63;
-        float m = -INFINITY;
-        for (int c = lane; c < nchunk; c += 64) m = fmaxf(m, a.rec[((r0 + j) * nchunk + c) * kBeamRec]);
-        m = wave_max(m);
-        float e = 0.f;
-        for (int c = lane; c < nchunk; c += 64) {
-            const float* rc = a.rec + ((r0 + j) * nchunk + c) * kBeamRec;
-            e += rc[1] * __expf(rc[0] - m);
-        }
-        e = wave_sum(e);
-        if (lane == 0) lse_s[j] = m + __logf(e);
-    }
-    __syncthreads();
-    // candidates: k per (live row, chunk), one per ended row; every thread keeps up to NC of them
-    constexpr int NC = kBeamCandPerThread;
-    const float lp_live = lp_on ? a.lp[a.step + 1] : 1.f;
-    float cv[NC]; int cc[NC];
-    const int per_row = nchunk * k, total = k * per_row;
-#pragma unroll
-    for (int q = 0; q < NC; ++q) {
-        cv[q] = -INFINITY; cc[q] = kNone;
-        const int id = tid + 256 * q;
-        if (id < total) {
-            const int j = id / per_row, rem = id - j * per_row, c = rem / k, slot = rem - c * k;
-            if (cum_s[j] != -INFINITY) {
-                if (fin_s[j]) {
-                    if (rem == 0) {                                      // an ended hypothesis competes as it is
-                        cv[q] = lp_on ? cum_s[j] / lpf_s[j] : cum_s[j]; cc[q] = j * Vx;
-                    }
-                } else {
-                    const float* rc = a.rec + ((r0 + j) * nchunk + c) * kBeamRec;
-                    const int idx = __float_as_int(rc[3 + 2 * slot]);
-                    if (idx != kNone) {
-                        const float v = cum_s[j] - lse_s[j] + rc[2 + 2 * slot];
-                        cv[q] = lp_on ? v / lp_live : v; cc[q] = j * Vx + idx;
-                    }
-                }
-            }
-        }
-    }
-    if constexpr (FORCED) {
-        // Constrained beam search (dynamic beam allocation): every candidate carries its bank, the number of met slots
-        // of the hypothesis it would make.  A pool candidate has its row's bank (stage 1 took the unmet forced columns
-        // and a closed <end> out of the pool); thread j * kForceMax + s adds row j's unmet forced column of slot s,
-        // scored from the row like the pool's.  The k rounds visit the banks from the highest down and round again,
-        // skipping empty ones: the rank below puts the non-empty bank whose turn it is first, so one ranked arg-best
-        // per round takes that bank's best candidate.
-        constexpr int NF = NC + 1;
-        float fv[NF]; int fc[NF], fb[NF];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) {
-            fv[q] = cv[q]; fc[q] = cc[q];
-            fb[q] = cc[q] == kNone ? -32 : __popc(met_s[cc[q] / Vx]);
-        }
-        fv[NC] = -INFINITY; fc[NC] = kNone; fb[NC] = -32;
-        if (tid < k * kForceMax) {
-            const int j = tid / kForceMax, s = tid - j * kForceMax, w = force_s[s];
-            bool cand = w >= 0 && !((met_s[j] >> s) & 1) && !fin_s[j] && cum_s[j] != -INFINITY;
-            int add = 0;
-#pragma unroll
-            for (int s2 = 0; s2 < kForceMax; ++s2) {
-                const bool same = force_s[s2] == w;
-                cand = cand && !(same && s2 < s);               // slots holding one id: one candidate, the first slot's
-                add |= same ? 1 << s2 : 0;
-            }
-            if (cand) {
-                const float x = w < a.V ? a.scores[(r0 + j) * a.ld + w] : a.ptr[(r0 + j) * np + (w - a.V)];
-                const float v = cum_s[j] - lse_s[j] + x;
-                fv[NC] = lp_on ? v / lp_live : v; fc[NC] = j * Vx + w;
-                fb[NC] = __popc(met_s[j] | add);
-            }
-        }
-        int turn = kForceMax + 1;                               // the bank visited last
-        for (int round = 0; round < k; ++round) {
-            int bp = -64; float bv = -INFINITY; int bc = kNone;
-#pragma unroll
-            for (int q = 0; q < NF; ++q) {
-                const int p = fb[q] < turn ? fb[q] + 16 : fb[q];
-                const bool take = ranked_before(bp, bv, bc, p, fv[q], fc[q]);
-                bp = take ? p : bp;
-                bv = take ? fv[q] : bv;
-                bc = take ? fc[q] : bc;
-            }
-            block_best_ranked(bp, bv, bc, shp, shv, shc);
-#pragma unroll
-            for (int q = 0; q < NF; ++q)
-                if (fc[q] == bc) { fv[q] = -INFINITY; fc[q] = kNone; fb[q] = -32; }
-            if (bc != kNone) turn = bp >= 16 ? bp - 16 : bp;
-            if (tid == 0) beam_winner<false, true>(a, rows, r0, lp_on, round, bv, bc);
-        }
-        __syncthreads();
-        if (tid < k) a.met[r0 + tid] = nmet_s[tid];
-    } else if constexpr (!DIVERSE) {
-        for (int round = 0; round < k; ++round) {
-            float bv; int bc;
-            beam_round(cv, cc, bv, bc, shv, shc);
-            if (tid == 0) beam_winner<false, false>(a, rows, r0, lp_on, round, bv, bc);
-        }
-    } else {
-        // Diverse beam search: the groups choose in order.  Group g ranks the candidates of its own rows g*kg ..
-        // (g+1)*kg - 1 by key - lambda * n, n = the number of hypotheses of groups 0 .. g-1 expanded with the
-        // candidate's column at this step (an ended hypothesis competes with its key as it is), and its kg rounds fill
-        // slots g*kg + round: k rounds in all, as without groups.
-        const int kg = k / a.groups;
-        const float lam = diversity_penalty(a.penalty);
-        for (int g = 0; g < a.groups; ++g) {
-            const int lo = g * kg * Vx, hi = lo + kg * Vx;
-            float gv[NC]; int gc[NC];
-#pragma unroll
-            for (int q = 0; q < NC; ++q) {
-                gv[q] = -INFINITY; gc[q] = kNone;
-                if (cc[q] >= lo && cc[q] < hi) {            // (kNone is above every code)
-                    const int j = cc[q] / Vx, col = cc[q] - j * Vx;
-                    int n = 0;
-                    if (!fin_s[j])
-                        for (int i = 0; i < g * kg; ++i) n += xtok_s[i] == col;
-                    gv[q] = cv[q] - lam * (float)n; gc[q] = cc[q];
-                }
-            }
-            for (int round = 0; round < kg; ++round) {
-                float bv; int bc;
-                beam_round(gv, gc, bv, bc, shv, shc);
-                if (tid == 0) beam_winner<true, false>(a, rows, r0, lp_on, g * kg + round, bv, bc);
-            }
-            __syncthreads();                                // xtok_s of this group before the next group reads it
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int before = 0, after = 0;
-        for (int j = 0; j < k; ++j) { before += fin_s[j] || cum_s[j] == -INFINITY; after += nfin_s[j]; }
-        if (after != before) atomicAdd(a.n_done, after - before);
-    }
-    // histories of the chosen parents move to their new rows
-    for (int idx = tid; idx < k * a.max_len; idx += 256) {
-        const int j = idx / a.max_len, p = idx - j * a.max_len;
-        const int64_t src = (r0 + parent_s[j]) * a.max_len + p, dst = (r0 + j) * a.max_len + p;
-        const bool carried = fin_s[parent_s[j]] != 0;
-        a.seq_out[dst] = p < a.step ? a.seq_in[src] : (p == a.step && !carried ? (int64_t)tok_s[j]
-                                                       : (carried ? a.seq_in[src] : (int64_t)a.pad_token));
-        a.anc_out[dst] = p < a.step ? a.anc_in[src] : (p == a.step ? (int32_t)(r0 + parent_s[j]) : 0);
-        if (a.cap_out != nullptr)
-            a.cap_out[dst] = p <= a.step ? a.cap_in[src]
-                                         : (p == a.step + 1 && !nfin_s[j] ? (int64_t)tok_s[j] : (int64_t)a.start_token);
-    }
-    if (a.step + 1 >= a.max_len) return;
-    const float* pe = a.pe + (int64_t)(a.step + 1) * a.d;
-    for (int idx = tid; idx < k * a.d; idx += 256) {
-        const int j = idx / a.d, c = idx - j * a.d;
-        const int tok = nfin_s[j] ? 0 : tok_s[j];
-        // (tok is in [0, Vx), has_facts is F > 0 and fe is non-null exactly then: no clamp of token_row() acts here)
-        const float* src = token_row(tok, token_kind(tok, a.V, a.K, a.has_facts), (int64_t)blockIdx.x, a.word_emb, a.ee,
-                                     a.fe, a.V, a.K, a.F, a.d, a.pad_token);
-        a.x0[(r0 + j) * a.d + c] = fmaf(src[c], a.emb_scale, pe[c]);
-    }
+    vt.epilogue(a.scores, a.ld, a.cand, a.ntiles, a.R, a.V, n0, row, red);
 }
 
 }  // namespace
@@ -2062,11 +1374,6 @@ extern "C" int ick_decode_supported(int32_t d, int32_t H, int32_t FF, int32_t S,
            S > 0 && S <= kSMax && max_len > 0 && max_len <= kMLMax;
 }
 
-extern "C" int ick_decode_beam_supported(int32_t Vx, int32_t beam) {
-    if (Vx <= 0 || beam < 1 || beam > kBeamMax) return 0;
-    return (int64_t)beam * beam * ceil_div(Vx, kBeamChunk) <= 256 * kBeamCandPerThread;   // candidates the selection holds
-}
-
 extern "C" int ick_decode_plan(int32_t R, int32_t rows_per_sample, int32_t d, int32_t H, int32_t FF, int32_t* out) {
     ICK_CHECK_ARG(out && R > 0 && R <= 65535 && rows_per_sample > 0 && R % rows_per_sample == 0);
     ICK_CHECK_ARG(d > 0 && d % 4 == 0 && d <= kDMax && H > 0 && H <= kPartsMax && d % H == 0 && FF > 0 &&
@@ -2107,15 +1414,10 @@ static int decode_layers_impl(const ick_decode_ctx* c, int32_t pos, void* stream
             // the token of step pos - 1 is chosen inside this launch (fused_select)
             ICK_CHECK_ARG(c->rows_per_sample == 1 && c->output && c->hist && c->finished && c->n_done && c->next_token &&
                           c->next_mask && c->word_emb && c->pe && c->cand && c->ptr && c->ee);
-            SelFuse& f = sa.sel;
-            f.cand = reinterpret_cast<const float4*>(c->cand); f.ntiles = ceil_div(c->V, kVocabTile); f.ptr = c->ptr;
-            f.output = c->output; f.hist = c->hist; f.finished = c->finished; f.n_done = c->n_done;
-            f.next_token = c->next_token; f.next_mask = c->next_mask; f.cap_buf = c->cap_buf;
             const int i = pos - 1;
-            f.st_in = c->sel_state + (size_t)(i & 1) * R * 12; f.st_out = c->sel_state + (size_t)((i + 1) & 1) * R * 12;
-            f.word_emb = c->word_emb; f.ee = c->ee; f.fe = c->F > 0 ? c->fe : nullptr; f.pe = c->pe;
-            f.rows_per_sample = c->rows_per_sample; f.V = c->V; f.K = c->K; f.F = c->F; f.step = i; f.max_len = c->max_len;
-            f.has_facts = c->F > 0; f.end_token = c->end_token; f.pad_token = c->pad_token; f.emb_scale = c->emb_scale;
+            fill_greedy_sel(sa.sel, c, i);
+            sa.sel.st_in = c->sel_state + (size_t)(i & 1) * R * 12;
+            sa.sel.st_out = c->sel_state + (size_t)((i + 1) & 1) * R * 12;
         }
         const bool first_self = l == 0;
         if ((which & 1u) && !(part == 2 && first_self))
@@ -2212,93 +1514,3 @@ extern "C" int ick_debug_decode_subset(const ick_decode_ctx* c, int32_t pos, uns
     return 0;
 }
 #endif
-
-extern "C" int ick_decode_select_greedy(const ick_decode_ctx* c, int32_t pos, void* stream) {
-    ICK_CHECK_ARG(c && c->R > 0 && pos >= 0 && pos < c->max_len);
-    ICK_CHECK_ARG(c->output && c->hist && c->finished && c->n_done && c->next_token && c->next_mask && c->word_emb &&
-                  c->pe && c->x0 && c->cand && c->ptr && c->ee);
-    SelectArgs a;
-    a.cand = reinterpret_cast<const float4*>(c->cand); a.ntiles = ceil_div(c->V, kVocabTile); a.ptr = c->ptr;
-    a.output = c->output; a.hist = c->hist; a.finished = c->finished; a.n_done = c->n_done;
-    a.next_token = c->next_token; a.next_mask = c->next_mask; a.cap_buf = c->cap_buf;
-    a.word_emb = c->word_emb; a.ee = c->ee; a.fe = c->F > 0 ? c->fe : nullptr; a.pe = c->pe; a.x0 = c->x0;
-    a.R = c->R; a.rows_per_sample = c->rows_per_sample; a.d = c->d; a.V = c->V; a.K = c->K; a.F = c->F; a.step = pos;
-    a.max_len = c->max_len; a.has_facts = c->F > 0; a.end_token = c->end_token; a.pad_token = c->pad_token;
-    a.emb_scale = c->emb_scale; a.n_total = c->R;
-    hipLaunchKernelGGL(dec_select_kernel, dim3(c->R), dim3(256), 0, (hipStream_t)stream, a);
-    ICK_LAUNCH_RET();
-}
-
-static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, const ick_decode_rules* rules,
-                            const ick_decode_diversity* div, const ick_decode_constraints* fc, int32_t pos,
-                            void* stream) {
-    ICK_CHECK_ARG(c && bs && c->R > 0 && pos >= 0 && pos < c->max_len);
-    ICK_CHECK_ARG(c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax && c->R % c->rows_per_sample == 0);
-    ICK_CHECK_ARG(c->scores && c->scores_ld >= c->V && c->ptr && c->n_done && c->next_token && c->next_mask &&
-                  c->word_emb && c->pe && c->x0 && c->ee);
-    ICK_CHECK_ARG(bs->cum && bs->fin && bs->seq_in && bs->seq_out && bs->anc_in && bs->anc_out);
-    ICK_CHECK_ARG((bs->cap_in == nullptr) == (bs->cap_out == nullptr));
-    ICK_CHECK_ARG(bs->rec != nullptr);
-    const int Vx = c->V + c->K + c->F, nchunk = ceil_div(Vx, kBeamChunk);
-    ICK_CHECK_ARG(ick_decode_beam_supported(Vx, c->rows_per_sample));
-    BeamPartForcedArgs pa;
-    pa.scores = c->scores; pa.ld = c->scores_ld; pa.ptr = c->ptr; pa.cum = bs->cum; pa.fin = bs->fin; pa.rec = bs->rec;
-    pa.R = c->R; pa.k = c->rows_per_sample; pa.V = c->V; pa.np = c->K + c->F; pa.nchunk = nchunk;
-    pa.n_done = c->n_done; pa.n_total = c->R;
-    pa.seq = bs->seq_in; pa.words = rules ? rules->words : nullptr;
-    pa.step = pos; pa.max_len = c->max_len; pa.end_token = c->end_token;
-    if (fc != nullptr) {
-        pa.force = fc->force; pa.met = fc->met;
-        void (*part)(BeamPartForcedArgs) = rules ? dec_beam_partial_kernel<true, true> : dec_beam_partial_kernel<false, true>;
-        hipLaunchKernelGGL(part, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, pa);
-    } else {
-        void (*part)(BeamPartArgs) = rules ? dec_beam_partial_kernel<true> : dec_beam_partial_kernel<false>;
-        hipLaunchKernelGGL(part, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, (const BeamPartArgs&)pa);
-    }
-    BeamArgs a;
-    a.rec = bs->rec; a.cum = bs->cum; a.fin = bs->fin;
-    a.seq_in = bs->seq_in; a.seq_out = bs->seq_out; a.anc_in = bs->anc_in; a.anc_out = bs->anc_out;
-    a.cap_in = bs->cap_in; a.cap_out = bs->cap_out; a.n_done = c->n_done;
-    a.next_token = c->next_token; a.next_mask = c->next_mask;
-    a.word_emb = c->word_emb; a.ee = c->ee; a.fe = c->F > 0 ? c->fe : nullptr; a.pe = c->pe; a.x0 = c->x0;
-    a.R = c->R; a.k = c->rows_per_sample; a.d = c->d; a.V = c->V; a.K = c->K; a.F = c->F; a.step = pos;
-    a.max_len = c->max_len; a.has_facts = c->F > 0; a.end_token = c->end_token; a.pad_token = c->pad_token;
-    a.start_token = bs->start_token; a.emb_scale = c->emb_scale; a.n_total = c->R;
-    a.words = rules ? rules->words : nullptr; a.lp = rules ? rules->lp : nullptr; a.len = rules ? rules->len : nullptr;
-    a.groups = div ? div->groups : 1; a.penalty = div ? div->penalty : nullptr;
-    a.force = fc ? fc->force : nullptr; a.met = fc ? fc->met : nullptr;
-    a.scores = c->scores; a.ld = c->scores_ld; a.ptr = c->ptr;
-    void (*sel)(BeamArgs) = fc ? (rules ? dec_select_beam_kernel<true, false, true>
-                                        : dec_select_beam_kernel<false, false, true>) :
-                            div ? (rules ? dec_select_beam_kernel<true, true> : dec_select_beam_kernel<false, true>)
-                                : (rules ? dec_select_beam_kernel<true, false> : dec_select_beam_kernel<false, false>);
-    hipLaunchKernelGGL(sel, dim3(c->R / c->rows_per_sample), dim3(256), 0, (hipStream_t)stream, a);
-    ICK_LAUNCH_RET();
-}
-
-extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_state* bs, int32_t pos, void* stream) {
-    return select_beam_impl(c, bs, nullptr, nullptr, nullptr, pos, stream);
-}
-
-extern "C" int ick_decode_select_beam_rules(const ick_decode_ctx* c, const ick_beam_state* bs,
-                                            const ick_decode_rules* rules, int32_t pos, void* stream) {
-    ICK_CHECK_ARG(rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, nullptr, nullptr, pos, stream);
-}
-
-extern "C" int ick_decode_select_beam_diverse(const ick_decode_ctx* c, const ick_beam_state* bs,
-                                              const ick_decode_rules* rules, const ick_decode_diversity* div,
-                                              int32_t pos, void* stream) {
-    ICK_CHECK_ARG(c && div && div->penalty && div->groups >= 1 && c->rows_per_sample >= 1 &&
-                  c->rows_per_sample % div->groups == 0);
-    ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, div, nullptr, pos, stream);
-}
-
-extern "C" int ick_decode_select_beam_forced(const ick_decode_ctx* c, const ick_beam_state* bs,
-                                             const ick_decode_rules* rules, const ick_decode_constraints* fc,
-                                             int32_t pos, void* stream) {
-    ICK_CHECK_ARG(c && fc && fc->force && fc->met && c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax);
-    ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, nullptr, fc, pos, stream);
-}

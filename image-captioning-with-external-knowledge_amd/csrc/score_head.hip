@@ -6,7 +6,7 @@
 // The vocabulary logits themselves are ick_gemm writing straight into the concatenated
 // (B, L, V+K+F) rows; the pointer kernel fills columns [V, V+K) and [V+K, V+K+F) of the same
 // rows, so the reference's (L,B,K,d) broadcast products and the torch.cat never exist.
-#include "common.h"
+#include "decode_select.h"
 
 namespace ick {
 namespace {
@@ -77,17 +77,6 @@ __global__ __launch_bounds__(256) void pointer_scores_kernel(const float* __rest
     }
 }
 
-struct Top2 {
-    float v1, v2;
-    int i1, i2;
-};
-__device__ __forceinline__ void top2_push(Top2& s, float v, int i) {
-    if (v > s.v1 || (v == s.v1 && i < s.i1)) {
-        s.v2 = s.v1; s.i2 = s.i1; s.v1 = v; s.i1 = i;
-    } else if (v > s.v2 || (v == s.v2 && i < s.i2)) {
-        s.v2 = v; s.i2 = i;
-    }
-}
 // Top-2 of one score row by a 256-thread workgroup; the result is valid in thread 0 (sh[0]).  The row is read
 // eight elements per thread at a time (loads first, comparisons after: one memory round trip per batch instead of
 // one per element).
@@ -138,40 +127,28 @@ __device__ __forceinline__ void greedy_update_one(int b, int best_b, int second_
                                                   int32_t* __restrict__ hist, int32_t* __restrict__ finished,
                                                   int64_t* __restrict__ next_token, int64_t* __restrict__ next_mask,
                                                   int step, int max_len, int V, int K, int has_facts, int end_token) {
-    if (finished[b]) {
-        next_token[b] = 0;
-        next_mask[b] = 0;
-        return;
-    }
     int64_t* o = output + (int64_t)b * max_len;
     int32_t* hs = hist + (int64_t)b * max_len;
-    const int i = step;
-    int64_t out = best_b;
-    o[i] = out;
-    if (out == end_token) {
-        finished[b] = 1;
-        next_token[b] = 0;
-        next_mask[b] = 0;
-        return;
-    }
-    hs[i] = second_b;
-    // repeated n-gram clean-up (geo-aware/models.py:421-435)
-    for (int dupl = 0; dupl <= 4; dupl += 2) {
-        if (i > dupl) {
-            const int half = (dupl + 2) / 2;
-            bool same = true;
-            for (int j = 0; j < half; ++j) same = same && (o[i - j] == o[i - half - j]);
-            if (same) {
-                const int top = dupl == 0 ? 1 : dupl;
-                for (int r = 0; r < top; ++r) o[i - r] = hs[i - r];
-                break;
-            }
+    const int i = step, fin = finished[b];
+    int po[5], ph[3];                       // output[i-1 .. i-5], runner-ups of steps i-1 .. i-3
+#pragma unroll
+    for (int q = 0; q < 5; ++q) po[q] = (int)o[max(i - 1 - q, 0)];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) ph[q] = hs[max(i - 1 - q, 0)];
+    const GreedyStep g = greedy_step(best_b, second_b, i, po, ph, fin, end_token, V, K, has_facts);
+    if (!fin) {
+        o[i] = g.cur;
+        if (g.ended) {
+            finished[b] = 1;
+        } else {
+            hs[i] = second_b;
+            if (g.nrw >= 1) o[i - 1] = g.rw[0];
+            if (g.nrw >= 3) { o[i - 2] = g.rw[1]; o[i - 3] = g.rw[2]; }
         }
     }
-    out = o[i];
-    if (i < max_len - 1) {
-        next_token[b] = out;
-        next_mask[b] = token_kind(out, V, K, has_facts);
+    if (g.ended || i < max_len - 1) {       // a live caption's last step has no next token: left as it is
+        next_token[b] = g.tok;
+        next_mask[b] = g.msk;
     }
 }
 

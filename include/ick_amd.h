@@ -354,8 +354,9 @@ int ick_greedy_select(const float* scores, int64_t ld, int32_t B, int32_t Vx, in
  * for R independent rows (R = captions x rows_per_sample; rows_per_sample > 1 = beams sharing their caption's
  * memory) in 3 launches per decoder layer + 2 (ick_decode_layers) + 1 (ick_decode_select_*), KV-cached.
  * A block's closing residual + LayerNorm is applied by the NEXT kernel while it loads its input row (see
- * csrc/decode.hip); partial out-projection rows travel through p1 / p2 / p3.  out_wt / w2t are the TRANSPOSED
- * out_proj / linear2 weights ((in_features, d) row-major).  All buffers are caller-owned device memory. */
+ * csrc/decode.hip; the selection kernels are csrc/decode_select.hip); partial out-projection rows travel through
+ * p1 / p2 / p3.  out_wt / w2t are the TRANSPOSED out_proj / linear2 weights ((in_features, d) row-major).  All buffers
+ * are caller-owned device memory. */
 typedef struct {
     const float *sa_in_w, *sa_in_b, *sa_out_wt, *sa_out_b, *n1_g, *n1_b;   /* self_attn, norm1 */
     const float *ca_in_w, *ca_in_b, *ca_out_wt, *ca_out_b, *n2_g, *n2_b;   /* multihead_attn (q rows used), norm2 */

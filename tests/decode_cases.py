@@ -115,7 +115,8 @@ def shape_params(case, P):
     return P
 
 
-VOCAB_TILE, SELECT_SWEEP_TILES = 48, 1024          # csrc/decode.hip: kVocabTile, tiles per sweep of dec_select_kernel
+# csrc/decode_select.h: kVocabTile; csrc/decode_select.hip: tiles per sweep of dec_select_kernel
+VOCAB_TILE, SELECT_SWEEP_TILES = 48, 1024
 
 
 def kernels_of(case, plan):

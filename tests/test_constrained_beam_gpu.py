@@ -1,5 +1,5 @@
 """Constrained beam search on the device: the FORCED instantiations of dec_beam_partial_kernel and
-dec_select_beam_kernel (csrc/decode.hip) behind predict_beam(force_tokens), held slot by slot to the CPU search of
+dec_select_beam_kernel (csrc/decode_select.hip) behind predict_beam(force_tokens), held slot by slot to the CPU search of
 tests/constrained_beam_ref.py on the oracle's scores, with the decoding rules of §3.2e composed."""
 import pytest
 import torch

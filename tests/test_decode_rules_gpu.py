@@ -1,5 +1,5 @@
 """Decoding rules on the device: GNMT length penalty, no-repeat n-gram blocking and minimum length in
-the beam selection kernels (csrc/decode.hip) and the sampled selection (csrc/sample.hip).  Beam search is held to the
+the beam selection kernels (csrc/decode_select.hip) and the sampled selection (csrc/sample.hip).  Beam search is held to the
 rules beam search of tests/beam_rules_ref.py; sampling is restated token for token with the oracle's teacher-forced
 scores, the bans, the kept set and the Philox-Gumbel draw (tests/sample_ref.py)."""
 import numpy as np

@@ -1,5 +1,5 @@
 """Diverse beam search on the device: the DIVERSE instantiations of dec_select_beam_kernel
-(csrc/decode.hip) behind predict_beam(num_beam_groups, diversity_penalty, return_groups), held group by group to the
+(csrc/decode_select.hip) behind predict_beam(num_beam_groups, diversity_penalty, return_groups), held group by group to the
 CPU search of tests/diverse_beam_ref.py on the oracle's scores, with the decoding rules of §3.2e composed."""
 import numpy as np
 import pytest
