@@ -11,6 +11,8 @@ Import as `ick_amd` (see /ick_amd.py).  Sub-modules:
   cider      CiderD: CIDEr-D on token ids, on the device (also `ick_amd.CiderD`)
   metrics    CaptionMetrics: BLEU-1..4, ROUGE-L and pointer precision / recall on token ids, on the device, and
              MetricReward, their mix with CIDEr-D as an SCST reward (also `ick_amd.CaptionMetrics`)
+  geo_metric GeoReferenceMetric: the geo variant's Jensen-Shannon geo-reference metric, counted on the device (also
+             `ick_amd.GeoReferenceMetric`)
   geo_aware/models.py, knowledge_aware/models.py, news_knowledge_aware/models.py
              drop-in replacements for the reference's per-variant `models` module
 """
@@ -35,4 +37,7 @@ def __getattr__(name):
     if name == "CaptionMetrics":
         from .metrics import CaptionMetrics
         return CaptionMetrics
+    if name == "GeoReferenceMetric":
+        from .geo_metric import GeoReferenceMetric
+        return GeoReferenceMetric
     raise AttributeError("module 'ick_amd' has no attribute %r" % name)

@@ -26,6 +26,7 @@
 // (W_fix = the sum of the kept tokens' fixed-point weights, compared in double, exact below 2^53), so a token whose
 // strictly-greater mass lies within ~Vx * 2^-33 of p * W can go either way relative to an exact-real restatement.
 #include "common.h"
+#include "philox.h"
 
 #include <climits>
 
@@ -56,18 +57,6 @@ struct SampleArgs {
     int n_total;
     const int32_t* words;                  // optional rule words (no-repeat n-gram size, min length)
 };
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-        const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 
 // order-preserving key of a float (larger float -> larger key); -0 is folded onto +0 first (x + 0 = +0 for x = -0)
 __device__ __forceinline__ uint32_t okey(float f) {

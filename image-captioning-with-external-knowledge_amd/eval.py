@@ -3,8 +3,9 @@
 token ids -> text (vocabulary words, entity names and fact objects decoded from their integer encodings) ->
 generated_captions.csv.  With metrics= / refs= the written rows are also scored on the device (metrics.CaptionMetrics:
 BLEU-1..4, ROUGE-L, pointer precision / recall on token ids -- the reference's compute_eval_metrics.py without METEOR
-and spaCy's entities).  The other domain metrics of the reference (Jensen-Shannon, fact accuracy...) are CPU text
-statistics outside this path."""
+and spaCy's entities).  With geo_metric= the geo variant's Jensen-Shannon geo-reference metric (its
+jensen_shannon_metric.py, eval.py:116,125) is counted on the device as well (geo_metric.GeoReferenceMetric).  The other
+domain metrics of the reference (fact accuracy...) are CPU text statistics outside this path."""
 import os
 
 import numpy as np
@@ -41,7 +42,7 @@ def detokenize(seq, word_map, rev_word_map, entity_names, fact_names=None):
 
 @torch.no_grad()
 def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="generated_captions.csv", device="cuda",
-             sample=None, attention_out=None, beam=None, metrics=None, refs=None):
+             sample=None, attention_out=None, beam=None, metrics=None, refs=None, geo_metric=None):
     """sample=None: greedy decode (predict), one CSV row per image.  sample = a dict of predict_sample keyword arguments
     (num_samples, temperature, top_k, top_p, seed, and the decoding rules no_repeat_ngram_size, min_len): sampled
     decode, one CSV row per (image, sample) with the columns image (running index over the loader), sample,
@@ -61,8 +62,12 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
     group rows through image_index), the batches' totals are added on the device and read once at the end.  Returns
     (captions, sequences, result) with result = CaptionMetrics.result()'s dict, and writes
     metric_scores_for_generated_captions.csv next to out_csv: the CSV's own columns plus Bleu_1..Bleu_4, ROUGE_L
-    (sentence scores), pointer_hits, pointer_generated, pointer_reference.  Without the two arguments: (captions,
-    sequences) as before."""
+    (sentence scores), pointer_hits, pointer_generated, pointer_reference.
+    geo_metric: a geo_metric.GeoReferenceMetric: every written row's geo references are counted on the device against
+    its image's entity features and names (batch[4], batch[5]; sampled rows and group rows through image_index, row_offset
+    = the number of rows written before the batch), the batches' histograms are added on the device and read once at the
+    end; result gains "geo_js" = GeoReferenceMetric.result()'s dict.  Returns (captions, sequences, result) when either
+    metrics or geo_metric is given; without them: (captions, sequences) as before."""
     if beam is not None and sample is not None:
         raise ValueError("evaluate: beam and sample are two different decoders; pass one of them")
     if (metrics is None) != (refs is None) or (refs is not None and not callable(refs)):
@@ -82,6 +87,7 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
     attn_rows, attn_split = [], None
     want_attn = attention_out is not None
     totals, metric_rows = None, []
+    geo_counts = None
     for bi, batch in enumerate(loader):                       # any batch size: captions decode independently
         ent, names = batch[4], batch[5]
         has_facts = len(batch) > 6
@@ -128,6 +134,11 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
             t = metrics.totals(mr)
             totals = t if totals is None else totals + t
             metric_rows.append(mr)
+        if geo_metric is not None:
+            cand = seq.t().contiguous()
+            idx = torch.arange(cand.shape[0], device=cand.device, dtype=torch.int32) // n
+            gc = geo_metric(cand, idx, ent, names, row_offset=len(sequences))
+            geo_counts = gc if geo_counts is None else geo_counts + gc
         bufs = decoder.input_buffers() if feature_map else None
         img_buf = bufs[0] if bufs is not None and bufs[0] is not None and bufs[0].dim() == 4 else None
         for b in range(seq.shape[1]):
@@ -148,10 +159,12 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
         columns = {"image": [r[0] for r in rows], "sample": [r[1] for r in rows], "generated_caption": captions}
     if out_csv:
         pd.DataFrame(columns).to_csv(out_csv, index=False)
-    if metrics is None:
+    if metrics is None and geo_metric is None:
         return captions, sequences
     result = metrics.result(totals) if totals is not None else {}
-    if out_csv and metric_rows:
+    if geo_metric is not None:
+        result["geo_js"] = geo_metric.result(geo_counts) if geo_counts is not None else None
+    if metrics is not None and out_csv and metric_rows:
         bleu = torch.cat([m.bleu for m in metric_rows]).cpu().numpy()
         ptr = torch.cat([m.pointers for m in metric_rows]).cpu().numpy()
         for k in range(4):

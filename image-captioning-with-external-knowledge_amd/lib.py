@@ -256,6 +256,8 @@ SIGNATURES = {
     "ick_caption_metrics": [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, C.c_double, i32, vp, i32, vp,
                             vp, vp, vp, vp, vp, vp, vp, vp],
     "ick_caption_metric_sums": [vp, vp, vp, i32, vp, vp, vp, vp],
+    "ick_geo_reference_counts": [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, i32, i32, vp, i32, vp,
+                                 i32, i32, i64, i64, i64, vp, vp, vp, vp],
 }
 
 _lib = None

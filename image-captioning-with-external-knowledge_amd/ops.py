@@ -1012,6 +1012,59 @@ def caption_metric_sums(counts, rouge_l, pointers, out=None):
     return sums, rouge_sum
 
 
+GEO_TERMS, GEO_NAME_CHARS, GEO_MAX_T, GEO_MAX_K, GEO_MAX_BINS, GEO_MAX_TYPES = 8, 50, 128, 4095, 64, 4096
+
+
+def geo_reference_counts(tokens, image_index, entities, entity_names, V, trigger_ids, of_id, the_id, a_id,
+                         bins_distance, bins_azimuth, n_types, seed=0, row_offset=0):
+    """The geo-reference histograms of caption rows tokens (N, T) int64 (ick_geo_reference_counts; the definition:
+    geo_metric.py).  image_index (N,) row -> image; entities (B, K, C) float32; entity_names (B, K, 52) int64;
+    trigger_ids: the 8 terms' word ids (-1: absent); bins_distance / bins_azimuth: (n, 2) float64 device tables.
+    Returns (generated, random, marks): two (8, 1 + 64 + 64 + n_types rounded up to 64) int32 histograms and the
+    (N, T) int32 marks.  Everything is checked before the launch; nothing is read back."""
+    for t, name, dt, nd in ((tokens, "tokens (N, T)", torch.int64, 2), (entities, "entities (B, K, C)", torch.float32, 3),
+                            (entity_names, "entity_names (B, K, 52)", torch.int64, 3),
+                            (bins_distance, "bins_distance (n, 2)", torch.float64, 2),
+                            (bins_azimuth, "bins_azimuth (n, 2)", torch.float64, 2)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != nd or not t.is_cuda or not t.is_contiguous():
+            raise L.IckError("geo_reference_counts: %s must be a contiguous %s device tensor" % (name, dt))
+    N, T = tokens.shape
+    B, K, Cf = entities.shape
+    if N < 1 or not 1 <= T <= GEO_MAX_T:
+        raise L.IckError("geo_reference_counts: N >= 1 and 1 <= T <= %d (got %d, %d)" % (GEO_MAX_T, N, T))
+    if B < 1 or not 1 <= K <= GEO_MAX_K or Cf < 5:
+        raise L.IckError("geo_reference_counts: entities need B >= 1, 1 <= K <= %d and C >= 5" % GEO_MAX_K)
+    if tuple(entity_names.shape) != (B, K, 2 + GEO_NAME_CHARS):
+        raise L.IckError("geo_reference_counts: entity_names must be (%d, %d, %d)" % (B, K, 2 + GEO_NAME_CHARS))
+    for t, name in ((bins_distance, "bins_distance"), (bins_azimuth, "bins_azimuth")):
+        if t.shape[1] != 2 or not 1 <= t.shape[0] <= GEO_MAX_BINS:
+            raise L.IckError("geo_reference_counts: %s holds 1..%d [lo, hi] rows" % (name, GEO_MAX_BINS))
+    if isinstance(n_types, bool) or not isinstance(n_types, int) or not 1 <= n_types <= GEO_MAX_TYPES:
+        raise L.IckError("geo_reference_counts: 1 <= n_types <= %d" % GEO_MAX_TYPES)
+    trigger_ids = [int(i) for i in trigger_ids]
+    ids = trigger_ids + [int(of_id), int(the_id), int(a_id)]
+    if len(trigger_ids) != GEO_TERMS or not isinstance(V, int) or V < 1 or not all(-1 <= i < V for i in ids):
+        raise L.IckError("geo_reference_counts: 8 trigger ids and the ids of of / the / a, each -1 or in [0, V)")
+    if not isinstance(image_index, torch.Tensor) or image_index.shape != (N,):
+        raise L.IckError("geo_reference_counts needs an (N,) image_index")
+    if not 0 <= int(row_offset) <= 2 ** 62 or not -2 ** 63 <= int(seed) < 2 ** 64:
+        raise L.IckError("geo_reference_counts: row_offset >= 0 and a 64-bit seed")
+    dev = tokens.device
+    idx = image_index.to(device=dev, dtype=torch.int32).contiguous()
+    seed = int(seed) & (2 ** 64 - 1)
+    seed -= 2 ** 64 if seed >= 2 ** 63 else 0
+    ld = 1 + 2 * GEO_MAX_BINS + (n_types + 63) // 64 * 64
+    hist = torch.zeros(2, GEO_TERMS, ld, device=dev, dtype=torch.int32)
+    marks = torch.empty(N, T, device=dev, dtype=torch.int32)
+    trig = (C.c_int32 * GEO_TERMS)(*trigger_ids)
+    L.check(L.load().ick_geo_reference_counts(_p(tokens), N, T, _p(idx), _p(entities), _p(entity_names), B, K, Cf, V, trig,
+                                              int(of_id), int(the_id), int(a_id), _p(bins_distance),
+                                              bins_distance.shape[0], _p(bins_azimuth), bins_azimuth.shape[0], n_types,
+                                              ld, seed, int(row_offset), _p(marks), _p(hist[0]), _p(hist[1]), _stream()),
+            "ick_geo_reference_counts")
+    return hist[0], hist[1], marks
+
+
 # ------------------------------------------------------------------------------------------------
 # Backward / training-step wrappers
 # ------------------------------------------------------------------------------------------------

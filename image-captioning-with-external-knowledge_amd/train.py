@@ -18,7 +18,9 @@ checkpointing are unchanged.  `scst_reward` mixes BLEU-n / ROUGE-L into that rew
 
 `val_caption_metrics=True`: validate() also decodes every validation batch greedily and scores the captions against the
 batch's caption rows on the device (metrics.CaptionMetrics: BLEU-1..4, ROUGE-L, pointer precision / recall, and CIDEr-D
-when a CiderD exists); the totals stay on the device until the pass ends."""
+when a CiderD exists); the totals stay on the device until the pass ends.  `val_geo_metric=<dict>` (with it): the same
+captions' geo references are counted on the device (geo_metric.GeoReferenceMetric) and their Jensen-Shannon distances
+join the dict as "geo_js"."""
 import json
 import math
 import os
@@ -34,6 +36,7 @@ from . import dp, load_models, ops
 from . import utils as ut
 from .cider import CiderD
 from .datasets import CaptionDataset
+from .geo_metric import GeoReferenceMetric
 from .metrics import CaptionMetrics
 from .scst import SelfCriticalStep
 from .training import TrainStep, check_lr_schedule, check_max_grad_norm, lr_at
@@ -96,6 +99,11 @@ class Config:
     scst_reward: object = None                         # dict of CaptionMetrics.reward()'s keyword arguments without
                                                        # `cider` (cider_weight=, bleu=, rouge_l=): the SCST reward is that
                                                        # mix around the script's CiderD; None: CIDEr-D alone
+    val_geo_metric: object = None                      # dict of GeoReferenceMetric's arguments after the word map
+                                                       # (bins_distance=, bins_azimuth=, n_types=, train_distribution=,
+                                                       # seed=; GeoReferenceMetric.constructor_data() makes one): with
+                                                       # val_caption_metrics the decoded captions' geo references are
+                                                       # counted too, "geo_js" in that dict; None: off
 
 
 def _batch_to_device(batch, device, has_facts):
@@ -389,13 +397,15 @@ class _ValCaptionMetrics:
     (one reference per image in this dataset format).  Per batch one decode, one ick_caption_metrics launch, one totals
     launch and a device add; finish() reads the totals -- the pass's one extra synchronisation."""
 
-    def __init__(self, decoder, device, cider=None):
+    def __init__(self, decoder, device, cider=None, geo=None):
         self.dec, self.cider = decoder, cider
+        self.geo = GeoReferenceMetric(decoder.word_map, device=device, **geo) if geo is not None else None
+        self.geo_counts, self.rows = None, 0
         self.metrics = CaptionMetrics(decoder.word_map, pointer_base=decoder.vocab_size, device=device)
         self.totals = None
         self.cider_sum = torch.zeros(1, device=device, dtype=torch.float64) if cider is not None else None
 
-    def add(self, enc, caps, ent, facts):
+    def add(self, enc, caps, ent, facts, names=None):
         seq = self.dec.predict(enc, caps.shape[1], ent, *((facts,) if facts is not None else ()))
         rows = seq.t().contiguous()
         idx = torch.arange(rows.shape[0], device=rows.device, dtype=torch.int32)
@@ -403,11 +413,17 @@ class _ValCaptionMetrics:
         self.totals = t if self.totals is None else self.totals + t
         if self.cider is not None:
             self.cider_sum += self.cider(rows, idx, caps).double().sum()
+        if self.geo is not None:
+            c = self.geo(rows, idx, ent, names, row_offset=self.rows)
+            self.geo_counts = c if self.geo_counts is None else self.geo_counts + c
+            self.rows += rows.shape[0]
 
     def finish(self):
         if self.totals is None:
             return {}
         tensors = list(self.totals) + ([self.cider_sum] if self.cider is not None else [])
+        if self.geo is not None:
+            tensors += [self.geo_counts.generated, self.geo_counts.random]
         if dp.world_size() > 1:                                 # every rank scored its own shard
             for t in tensors:
                 torch.distributed.all_reduce(t)
@@ -417,6 +433,13 @@ class _ValCaptionMetrics:
         STATS["caption_metrics"] = res
         print("Validation: " + "\t".join("%s %.4f" % (k, v) for k, v in res.items() if k != "captions")
               + " (%d captions)" % res["captions"])
+        if self.geo is not None:
+            res["geo_js"] = self.geo.result(self.geo_counts)
+            for name, terms in res["geo_js"].items():
+                print("Validation: geo references, %s: " % name + "\t".join(
+                    "%s %d" % (t, v["n_occurrences"]) + "".join(" %s %.4f" % (f, x) for f, x in v.items()
+                                                                if f != "n_occurrences" and x is not None)
+                    for t, v in terms.items()))
         return res
 
 
@@ -427,7 +450,7 @@ def validate(loader, encoder, decoder, criterion, cfg, device, cider=None):
     caption metrics of the greedy captions as a dict); cider: a CiderD whose corpus score joins that dict."""
     decoder.eval()
     encoder.eval()
-    cm = _ValCaptionMetrics(decoder, device, cider) if cfg.val_caption_metrics else None
+    cm = _ValCaptionMetrics(decoder, device, cider, cfg.val_geo_metric) if cfg.val_caption_metrics else None
     if cfg.val_token_metrics:
         loss = _validate_token_metrics(loader, encoder, decoder, cfg, device, cm)
         return (loss, cm.finish()) if cm is not None else loss
@@ -441,7 +464,7 @@ def validate(loader, encoder, decoder, criterion, cfg, device, cider=None):
             scores, caps_sorted, dl = decoder(caps, enc, capmasks, caplens, ent, *extra)
             losses.update(packed_loss(criterion, scores, caps_sorted, dl).item(), sum(dl))
             if cm is not None:
-                cm.add(enc, caps, ent, facts)
+                cm.add(enc, caps, ent, facts, batch[5])
             if cfg.max_batches and i + 1 >= cfg.max_batches:
                 break
     total, count = dp.reduce_sum_count(losses.sum, losses.count, device=device)
@@ -461,7 +484,7 @@ def _validate_token_metrics(loader, encoder, decoder, cfg, device, cm=None):
             s = decoder.score_captions(caps, enc, capmasks, caplens, ent, facts, top_k=5)
             acc += torch.cat([s.loss_sum, s.count, s.top1_hits, s.topk_hits]).double()
             if cm is not None:
-                cm.add(enc, caps, ent, facts)
+                cm.add(enc, caps, ent, facts, batch[5])
             if cfg.max_batches and i + 1 >= cfg.max_batches:
                 break
     loss_sum, count, top1, top5 = acc.tolist()                  # the one synchronisation
@@ -536,6 +559,9 @@ def main(cfg=None):
     if cfg.scst and (not fused or world > 1 or cfg.scst_baseline not in ("greedy", "mean")):
         raise ValueError('scst=True needs a fused single-process run (fused=True, fine_tune_encoder=False, no torchrun) '
                          'and scst_baseline "greedy" or "mean"')
+    if cfg.val_geo_metric is not None and not (cfg.val_caption_metrics and isinstance(cfg.val_geo_metric, dict)):
+        raise ValueError("val_geo_metric is a dict of GeoReferenceMetric's arguments and rides on val_caption_metrics=True "
+                         "(the pass that decodes the validation batches)")
     if cfg.scst_reward is not None and not (cfg.scst and isinstance(cfg.scst_reward, dict) and
                                             "cider" not in cfg.scst_reward):
         raise ValueError("scst_reward is a dict of CaptionMetrics.reward()'s keyword arguments without `cider`, and "

@@ -864,6 +864,48 @@ int ick_caption_score_sums(const int32_t* rowstart, int32_t R, int32_t L, int32_
                            int32_t* rank, int32_t* best, float* log_prob, int32_t* tokens, float* loss_sum, float* count,
                            float* top1_hits, float* topk_hits, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Geo-reference counts: the histograms of the geo variant's Jensen-Shannon metric (the reference's
+ * JSGeoMetric.run / store_data_for_idx), on token ids.  One launch, one wave per caption row.
+ *
+ * Inputs: tokens (N, T) int64 caption rows, scanned whole (tokens after <end> are <pad> and never match); image_index
+ *   (N) int32, row -> image; entities (B, K, C) float32, C >= 5, column 1 = distance, 2 = azimuth, 4 = type;
+ *   entity_names (B, K, 2 + ICK_GEO_NAME_CHARS) int64 = [idx, length, chars...].
+ * Terms: 0 near, 1 along, 2 across, 3 in, 4 north, 5 south, 6 east, 7 west.  trigger_ids: 8 HOST ints, the word id of
+ *   each term's trigger (the azimuth words are north_of.. where the word map has north_of, else north..), -1 where the
+ *   word map lacks it; of_id, the_id, a_id: the ids of "of", "the", "a", -1 when absent.  V = the word map's size.
+ * Position i >= 1 with token t >= V counts when the previous token p0 < V and one of the windows holds:
+ *     p0 is a trigger;  i >= 2, p1 is a trigger and p0 in {of, the, a};  i >= 3, p2 is a trigger, p1 == of and p0 in
+ *     {the, a}  (the term is the trigger that matched),
+ *   and k = t - V < K, and the effective name of entity k of the row's image does not contain the seven character codes
+ *   of "unk_ent".  The effective name is the first min(length, 50) chars; a negative length gives all 50, 0 none.
+ * A counted reference adds, in row `term` of `generated` (8, hist_ld) int32: +1 to column 0 (n_occurrences); terms 0-3:
+ *   +1 to column 1 + b for the first distance bin b with lo_b <= (double)x < hi_b (nothing when no bin matches);
+ *   terms 4-7: +1 to column 1 + 64 + b for the azimuth bin found the same way; terms 1-3: +1 to column 1 + 64 + 64 + x
+ *   when the type x is an exact integer in [0, n_types).  bins_distance (n_distance, 2) / bins_azimuth (n_azimuth, 2):
+ *   float64 [lo, hi] tables in DEVICE memory, at most ICK_GEO_MAX_BINS rows each.
+ * `random` receives the same three increments for the random-entity baseline: entity s[j] where s = the slots of the
+ *   image's non-unk_ent entities in slot order and j = x mod |s|, x = the .x word of Philox-4x32-10 of counter
+ *   (i, lo32(r), hi32(r), 0), r = row_offset + n (n = the row's index in this launch), under key (lo32(seed), hi32(seed)).
+ * marks (N, T) int32 is written whole by every launch: -1 where no reference is counted, else
+ *   term << 24 | random entity << 12 | entity.  The histograms are ADDED to (integer atomics: the caller clears them; the
+ *   totals do not depend on the order of the adds, so they are the same bits on every run and in deterministic mode).
+ * A row whose image_index is outside [0, B) gets marks of -1 and no counts.
+ * ICK_EINVAL: a null pointer, N, B, K, V, n_* < 1, T > ICK_GEO_MAX_T, K > ICK_GEO_MAX_K, C < 5, more than ICK_GEO_MAX_BINS
+ *   bins, n_types > ICK_GEO_MAX_TYPES, hist_ld < 1 + 64 + 64 + n_types, an id >= V, row_offset < 0, generated == random. */
+#define ICK_GEO_TERMS 8
+#define ICK_GEO_NAME_CHARS 50
+#define ICK_GEO_MAX_T 128
+#define ICK_GEO_MAX_K 4095
+#define ICK_GEO_MAX_BINS 64
+#define ICK_GEO_MAX_TYPES 4096
+int ick_geo_reference_counts(const int64_t* tokens, int32_t N, int32_t T, const int32_t* image_index,
+                             const float* entities, const int64_t* entity_names, int32_t B, int32_t K, int32_t C,
+                             int32_t V, const int32_t* trigger_ids, int32_t of_id, int32_t the_id, int32_t a_id,
+                             const double* bins_distance, int32_t n_distance, const double* bins_azimuth,
+                             int32_t n_azimuth, int32_t n_types, int64_t hist_ld, int64_t seed, int64_t row_offset,
+                             int32_t* marks, int32_t* generated, int32_t* random, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
