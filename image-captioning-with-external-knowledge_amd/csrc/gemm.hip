@@ -669,6 +669,8 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
     ICK_CHECK_ARG((a.a_rs == 1) || (a.a_ks == 1));
     ICK_CHECK_ARG((a.b_rs == 1) || (a.b_ks == 1));
     if (a.split_k > 1) ICK_CHECK_ARG(a.flags & ICK_GEMM_ATOMIC);
+    // the epilogue runs once per K slice: a ReLU there would give sum_z relu(partial_z), not relu(sum) (as for the gate below)
+    if (a.split_k > 1) ICK_CHECK_ARG(!(a.flags & ICK_GEMM_RELU));
     if (a.colsum_a) ICK_CHECK_ARG(akm);       // column sums come from the k-major A tile
     // k-line maps: k-major operands only (a k-contiguous operand has no k lines to gather), and not beside a pre-split B,
     // whose copy was gathered when it was made (ick_presplit_item.k_map)

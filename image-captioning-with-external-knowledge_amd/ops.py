@@ -55,6 +55,8 @@ def gemm_args(A, B, Cout, M, N, K, a_rs, a_ks, b_rs, b_ks, c_rs, bias=None, a_gr
               a_kmap=None, b_kmap=None):
     """ick_gemm_args for C[m,n] = act(alpha * sum_k A(m,k) B(n,k) + bias[n]) with explicit element strides; A/B/Cout
     are tensors (only their data pointers are used -- the caller guarantees the strides stay in bounds).
+    split_k > 1 needs atomic=True and excludes relu and gate: the epilogue runs once per K slice, so either would be
+    applied to the partial sums (the library answers ICK_EINVAL).
     colsum_a (k-major A only): colsum_a[m] += sum_k A(m,k).  b_ps: the pre-split copy of the (N, K) matrix B
     (presplit_weights): large problems then run on the LDS-DMA kernel of csrc/gemm_ps.hip.
     m_bound / k_bound: one-element int32 device tensors that bound the rows / the reduction length below M / K (the

@@ -53,6 +53,8 @@ int ick_device_info(int* num_cu, int* wave_size, char* arch_name, int arch_name_
  *   C + (c_gmap ? c_gmap[m / c_grp] : m / c_grp) * c_gs + (m % c_grp) * c_rs.
  * Exactly one of (a_rs, a_ks) and one of (b_rs, b_ks) must be 1.
  * flags: bit0 = ReLU, bit1 = accumulate into C (C += ...), bit2 = atomic accumulate (split-K).
+ * ReLU is rejected (ICK_EINVAL) with split_k > 1: the epilogue runs once per K slice, so it would
+ * compute sum_z relu(partial_z) instead of relu(sum) -- like the gate, which is rejected there too.
  * Head-split epilogue (hs_dh > 0): the N columns are [segment][head][hs_dh] (packed q|k|v or
  * k|v-per-layer projections) and are scattered into the attention kernel's head-major layout
  *   C[ goff(m) + seg*(hs_H*hs_S*hs_dhp) + head*(hs_S*hs_dhp) + (hs_s0 + m % c_grp)*hs_dhp + j ]
