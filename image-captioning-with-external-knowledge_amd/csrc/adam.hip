@@ -6,14 +6,21 @@
 // spent 3 ick_pack_weights + 3 ick_presplit_weights launches per step on it (126 us of kernel time at cfg2, 30 MB per
 // launch at 0.18 of the HBM rate; skipping them took 105 us off the 1.73 ms step, profiles/r05_x_ceilings_train.txt).
 //
-// One workgroup = one block of the caller's cover of the bucket (include/ick_amd.h, ick_adam_clamp_derive):
-//   flat run   <= 1024 float4, the seven 16-byte streams of adam_clamp_vec4_kernel (+ an optional plain copy);
-//   tile       64 rows x 64 columns of a 2-D parameter (row segments of 256 contiguous bytes): updated in registers,
-//              written back, the new values staged in LDS and read out once per image in that image's own order, so that
-//              every image is written in runs of >= 1 KiB (pack, pack_t: [64 rows][4 k] granules; ps, ps_t: 64-byte
-//              rows of one plane and K slice).
-// The arithmetic is adam_clamp_kernel's, operation for operation (tests/test_adam_derive_gpu.py: bit-identical
-// parameters and moments; images bit-identical to ick_pack_weights / ick_presplit_weights of the updated weights).
+//   g = clamp(g * gscale [/ *gscale_den], -clip, clip);  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
+//   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// (default betas / eps, no weight decay, no amsgrad.)  The update is written once: adam_hyper() is the prologue, adam1()
+// the arithmetic of one element.  Three kernels address the bucket differently around them:
+//   adam_clamp_kernel       one float per lane and trip: tails, short and unaligned buckets;
+//   adam_clamp_vec4_kernel  one float4 per lane and trip, seven 16-byte streams: the aligned bulk of a flat bucket;
+//   adam_derive_kernel      one workgroup = one block of the caller's cover of the bucket (include/ick_amd.h,
+//                           ick_adam_clamp_derive):
+//     flat run   <= 1024 float4, the seven 16-byte streams of adam_clamp_vec4_kernel (+ an optional plain copy);
+//     tile       64 rows x 64 columns of a 2-D parameter (row segments of 256 contiguous bytes): updated in registers,
+//                written back, the new values staged in LDS and read out once per image in that image's own order, so
+//                that every image is written in runs of >= 1 KiB (pack, pack_t: [64 rows][4 k] granules; ps, ps_t:
+//                64-byte rows of one plane and K slice).
+// tests/test_adam_derive_gpu.py and tests/test_grad_norm_gpu.py hold the three to the same bits, and the images to
+// ick_pack_weights / ick_presplit_weights of the updated weights.
 #include "gemm_common.h"
 #include "opt_words.h"
 
@@ -24,26 +31,89 @@ struct AdamHyper {
     float gscale, clip, b1, b2, c1, c2, eps, step, bc2_sqrt, coef;
 };
 
-// kOpt (ick_adam_opt_derive): the gradient times the global-norm clip's coefficient between the scale and
-// the clamp, as an operation of its own (coef == 1: the plain instantiation's bits)
+// The prologue of every Adam kernel.  false: no token contributed to the (global) batch, which then has no mean loss --
+// the kernel leaves parameters, moments, images and the rate word alone instead of spreading 0 * inf = NaN over every
+// weight.  kOpt (ick_adam_opt[_derive]): the step's rate comes from the base rate word and the schedule
+// instead of the literal, h.coef is the global-norm clip's coefficient, and workgroup 0 leaves the rate it used in
+// words[4].
+template <bool kOpt>
+__device__ __forceinline__ bool adam_hyper(AdamHyper& h, float gscale, float clip, float lr, float b1, float b2, float eps,
+                                           int step0, const uint32_t* step_ptr, const float* __restrict__ gscale_den,
+                                           float* words, const ick_lr_schedule& sched) {
+    if (gscale_den) {
+        if (!(gscale_den[0] > 0.f)) return false;
+        gscale = gscale / gscale_den[0];
+    }
+    const float t = (float)(step0 + (step_ptr ? (int)*step_ptr : 0));
+    const float bc1 = 1.f - powf(b1, t);
+    h.bc2_sqrt = sqrtf(1.f - powf(b2, t));
+    h.coef = 1.f;
+    if (kOpt) {
+        lr = lr_schedule(words[kWordBaseLr], sched, t);
+        h.coef = words[kWordCoef];
+        if (blockIdx.x == 0 && threadIdx.x == 0) words[kWordLrNow] = lr;
+    }
+    h.step = lr / bc1;
+    h.gscale = gscale; h.clip = clip; h.b1 = b1; h.b2 = b2; h.c1 = 1.f - b1; h.c2 = 1.f - b2; h.eps = eps;
+    return true;
+}
+
+// The update of one element, the only place its arithmetic is written (-ffp-contract=off keeps the operations apart).
+// kOpt: the gradient times the clip coefficient between the scale and the clamp, as an operation of its own -- with
+// coef == 1 and a constant schedule the bits are the plain instantiation's.
+template <bool kOpt>
+__device__ __forceinline__ void adam1(const AdamHyper& h, float& p, float& g, float& m, float& v) {
+    float x = g * h.gscale;
+    if (kOpt) x = x * h.coef;
+    if (h.clip > 0.f) x = fminf(fmaxf(x, -h.clip), h.clip);
+    g = x;
+    m = h.b1 * m + h.c1 * x;
+    v = h.b2 * v + h.c2 * x * x;
+    p -= h.step * m / (sqrtf(v) / h.bc2_sqrt + h.eps);
+}
+
 template <bool kOpt>
 __device__ __forceinline__ void adam4(const AdamHyper& h, float4& p, float4& g, float4& m, float4& v) {
-    float ga[4] = {g.x, g.y, g.z, g.w}, ma[4] = {m.x, m.y, m.z, m.w}, va[4] = {v.x, v.y, v.z, v.w};
-    float pa[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {      // the arithmetic of adam_clamp_kernel (csrc/backward.hip), operation for operation
-        float x = ga[k] * h.gscale;
-        if (kOpt) x = x * h.coef;
-        if (h.clip > 0.f) x = fminf(fmaxf(x, -h.clip), h.clip);
-        ga[k] = x;
-        ma[k] = h.b1 * ma[k] + h.c1 * x;
-        va[k] = h.b2 * va[k] + h.c2 * x * x;
-        pa[k] -= h.step * ma[k] / (sqrtf(va[k]) / h.bc2_sqrt + h.eps);
+    adam1<kOpt>(h, p.x, g.x, m.x, v.x);
+    adam1<kOpt>(h, p.y, g.y, m.y, v.y);
+    adam1<kOpt>(h, p.z, g.z, m.z, v.z);
+    adam1<kOpt>(h, p.w, g.w, m.w, v.w);
+}
+
+template <bool kOpt>
+__global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                         float gscale, float clip, float lr, float b1, float b2,
+                                                         float eps, int step0, const uint32_t* step_ptr,
+                                                         const float* __restrict__ gscale_den, float* words,
+                                                         ick_lr_schedule sched) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    AdamHyper h;
+    if (!adam_hyper<kOpt>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched)) return;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        float gi = g[i], mi = m[i], vi = v[i], pi = p[i];
+        adam1<kOpt>(h, pi, gi, mi, vi);
+        g[i] = gi; m[i] = mi; v[i] = vi; p[i] = pi;
     }
-    g = make_float4(ga[0], ga[1], ga[2], ga[3]);
-    m = make_float4(ma[0], ma[1], ma[2], ma[3]);
-    v = make_float4(va[0], va[1], va[2], va[3]);
-    p = make_float4(pa[0], pa[1], pa[2], pa[3]);
+}
+
+// The same update on float4: seven 16-byte streams per lane (the scalar form reaches 0.66 of the HBM rate, 320 MB per
+// cfg2 step).  n4 = n / 4 elements of float4; the launcher sends a tail of n % 4 to the scalar kernel.
+template <bool kOpt>
+__global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict__ p, float4* __restrict__ g,
+                                                              float4* __restrict__ m, float4* __restrict__ v, int64_t n4,
+                                                              float gscale, float clip, float lr, float b1, float b2,
+                                                              float eps, int step0, const uint32_t* step_ptr,
+                                                              const float* __restrict__ gscale_den, float* words,
+                                                              ick_lr_schedule sched) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    AdamHyper h;
+    if (!adam_hyper<kOpt>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched)) return;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        float4 gi = g[i], mi = m[i], vi = v[i], pi = p[i];
+        adam4<kOpt>(h, pi, gi, mi, vi);
+        g[i] = gi; m[i] = mi; v[i] = vi; p[i] = pi;
+    }
 }
 
 constexpr int kT = 64;        // tile edge
@@ -59,25 +129,8 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
                                                           float* words, ick_lr_schedule sched) {
     __shared__ __attribute__((aligned(16))) float tile[kT * kLd];
     const ick_adam_block blk = blocks[blockIdx.x];
-    if (gscale_den) {
-        // a (global) batch without a single contributing token has no mean loss: parameters, moments and every image stay
-        if (!(gscale_den[0] > 0.f)) return;
-        gscale = gscale / gscale_den[0];
-    }
     AdamHyper h;
-    {
-        const float t = (float)(step0 + (step_ptr ? (int)*step_ptr : 0));
-        const float bc1 = 1.f - powf(b1, t);
-        h.bc2_sqrt = sqrtf(1.f - powf(b2, t));
-        h.coef = 1.f;
-        if (kOpt) {        // the step's rate from the base rate word and the schedule; workgroup 0 reports it
-            lr = lr_schedule(words[kWordBaseLr], sched, t);
-            h.coef = words[kWordCoef];
-            if (blockIdx.x == 0 && threadIdx.x == 0) words[kWordLrNow] = lr;
-        }
-        h.step = lr / bc1;
-        h.gscale = gscale; h.clip = clip; h.b1 = b1; h.b2 = b2; h.c1 = 1.f - b1; h.c2 = 1.f - b2; h.eps = eps;
-    }
+    if (!adam_hyper<kOpt>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched)) return;
     const int tid = threadIdx.x;
 
     if (blk.item < 0) {
@@ -231,18 +284,67 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
 }  // namespace
 }  // namespace ick
 
+using namespace ick;
+
+// What every entry asks of its arguments (count: the floats of a flat bucket, the blocks of a cover); al16: whether all
+// four arrays lie on 16 bytes, which the float4 kernels need.
+static int adam_args(const float* p, const float* g, const float* m, const float* v, int64_t count, int32_t step,
+                     const uint32_t* step_ptr, bool& al16) {
+    ICK_CHECK_ARG(p && g && m && v && count > 0 && (step >= 1 || step_ptr != nullptr));
+    al16 = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+             reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    return ICK_OK;
+}
+
+// ick_adam_clamp and ick_adam_opt: the float4 kernel over the aligned bulk, the scalar kernel over the rest
+template <bool kOpt>
+static int launch_adam(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr, float* words,
+                       ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
+                       const float* gscale_den, void* stream) {
+    bool al16;
+    if (int rc = adam_args(p, g, m, v, n, step, step_ptr, al16)) return rc;
+    int64_t done = 0;
+    if (n >= 4096 && al16) {
+        const int64_t n4 = n / 4;
+        hipLaunchKernelGGL(adam_clamp_vec4_kernel<kOpt>, dim3((int)std::min<int64_t>(ceil_div(n4, 256), 4096)), dim3(256),
+                           0, (hipStream_t)stream, reinterpret_cast<float4*>(p), reinterpret_cast<float4*>(g),
+                           reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), n4, gscale, clip, lr, beta1, beta2,
+                           eps, step, step_ptr, gscale_den, words, sched);
+        done = 4 * n4;
+        if (done == n) ICK_LAUNCH_RET();
+    }
+    hipLaunchKernelGGL(adam_clamp_kernel<kOpt>, dim3((int)std::min<int64_t>(ceil_div(n - done, 256), 4096)), dim3(256), 0,
+                       (hipStream_t)stream, p + done, g + done, m + done, v + done, n - done, gscale, clip, lr, beta1,
+                       beta2, eps, step, step_ptr, gscale_den, words, sched);
+    ICK_LAUNCH_RET();
+}
+
 template <bool kOpt>
 static int launch_adam_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
                               const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
                               float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
                               const uint32_t* step_ptr, const float* gscale_den, void* stream) {
-    using namespace ick;
-    ICK_CHECK_ARG(p && g && m && v && blocks && n_blocks > 0 && (step >= 1 || step_ptr != nullptr));
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (!(al16(p) && al16(g) && al16(m) && al16(v))) return ICK_EALIGN;
+    bool al16;
+    if (int rc = adam_args(p, g, m, v, blocks ? n_blocks : 0, step, step_ptr, al16)) return rc;
+    if (!al16) return ICK_EALIGN;
     hipLaunchKernelGGL(adam_derive_kernel<kOpt>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, items,
                        blocks, gscale, clip, lr, beta1, beta2, eps, step, step_ptr, gscale_den, words, sched);
     ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_adam_clamp(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr,
+                              float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
+                              const float* gscale_den, void* stream) {
+    return launch_adam<false>(p, g, m, v, n, gscale, clip, lr, nullptr, ick_lr_schedule{}, beta1, beta2, eps, step,
+                              step_ptr, gscale_den, stream);
+}
+
+extern "C" int ick_adam_opt(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float* words,
+                            ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                            const uint32_t* step_ptr, const float* gscale_den, void* stream) {
+    ICK_CHECK_ARG(words != nullptr && lr_schedule_ok(sched));
+    return launch_adam<true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step, step_ptr,
+                             gscale_den, stream);
 }
 
 extern "C" int ick_adam_clamp_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
@@ -257,7 +359,7 @@ extern "C" int ick_adam_opt_derive(float* p, float* g, float* m, float* v, const
                                    const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float* words,
                                    ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
                                    const uint32_t* step_ptr, const float* gscale_den, void* stream) {
-    ICK_CHECK_ARG(words != nullptr && ick::lr_schedule_ok(sched));
+    ICK_CHECK_ARG(words != nullptr && lr_schedule_ok(sched));
     return launch_adam_derive<true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words, sched, beta1, beta2,
                                     eps, step, step_ptr, gscale_den, stream);
 }

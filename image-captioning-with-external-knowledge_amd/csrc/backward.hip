@@ -1,11 +1,10 @@
 // Backward kernels of the training step (loss.backward() through the
-// decoder of geo-aware/train.py:282-292, then clip_gradient + Adam.step).  The GEMM-shaped
+// decoder of geo-aware/train.py:282-292; clip_gradient + Adam.step are csrc/adam.hip).  The GEMM-shaped
 // gradients (data / weight gradients of every Linear) reuse ick_gemm with k-major operands; this
 // file holds the rest: LayerNorm, ReLU mask, bias column sums, the gather/scatter backward of the
-// embedding and encoder stages, the pointer-score head, the predicate gate, and the fused
-// clamp + Adam update.
+// embedding and encoder stages, the pointer-score head, the predicate gate, and the step counter
+// and token-mean scale of the training graphs.
 #include "common.h"
-#include "opt_words.h"
 
 namespace ick {
 namespace {
@@ -523,101 +522,6 @@ __global__ __launch_bounds__(256) void context_gate_bwd_kernel(const int64_t* __
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// clip_gradient (geo-aware/utils.py:75-85) + torch.optim.Adam.step (default betas/eps, no weight
-// decay, no amsgrad) over one flat fp32 parameter bucket:
-//   g = clamp(g * gscale [/ *gscale_den], -clip, clip);  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
-//   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-// ---------------------------------------------------------------------------------------------
-// kOpt (ick_adam_opt): lr = schedule(words[0], t) instead of the literal, the gradient times words[3]
-// (the global-norm clip's coefficient) between the scale and the clamp, as an operation of its own -- with coef == 1 and a
-// constant schedule the bits are the plain instantiation's; workgroup 0 leaves the rate it used in words[4].
-template <bool kOpt>
-__global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                         float gscale, float clip, float lr, float b1, float b2,
-                                                         float eps, int step0, const uint32_t* step_ptr,
-                                                         const float* __restrict__ gscale_den, float* words,
-                                                         ick_lr_schedule sched) {
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    if (gscale_den) {
-        // a (global) batch without a single contributing token has no mean loss: leave parameters and moments alone
-        // instead of spreading 0 * inf = NaN over every weight
-        if (!(gscale_den[0] > 0.f)) return;
-        gscale = gscale / gscale_den[0];
-    }
-    const float t = (float)(step0 + (step_ptr ? (int)*step_ptr : 0));
-    const float bc1 = 1.f - powf(b1, t);
-    const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
-    float coef = 1.f;
-    if (kOpt) {
-        lr = lr_schedule(words[kWordBaseLr], sched, t);
-        coef = words[kWordCoef];
-        if (blockIdx.x == 0 && threadIdx.x == 0) words[kWordLrNow] = lr;
-    }
-    const float step = lr / bc1;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        float gi = g[i] * gscale;
-        if (kOpt) gi = gi * coef;
-        if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
-        g[i] = gi;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] -= step * mi / (sqrtf(vi) / bc2_sqrt + eps);
-    }
-}
-
-// The same update on float4: seven 16-byte streams per lane (the scalar form reaches 0.66 of the HBM rate, 320 MB per
-// cfg2 step).  n4 = n / 4 elements of float4; the launcher sends a tail of n % 4 to the scalar kernel.
-template <bool kOpt>
-__global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict__ p, float4* __restrict__ g,
-                                                              float4* __restrict__ m, float4* __restrict__ v, int64_t n4,
-                                                              float gscale, float clip, float lr, float b1, float b2,
-                                                              float eps, int step0, const uint32_t* step_ptr,
-                                                              const float* __restrict__ gscale_den, float* words,
-                                                              ick_lr_schedule sched) {
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    if (gscale_den) {
-        if (!(gscale_den[0] > 0.f)) return;
-        gscale = gscale / gscale_den[0];
-    }
-    const float t = (float)(step0 + (step_ptr ? (int)*step_ptr : 0));
-    const float bc1 = 1.f - powf(b1, t);
-    const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
-    float coef = 1.f;
-    if (kOpt) {
-        lr = lr_schedule(words[kWordBaseLr], sched, t);
-        coef = words[kWordCoef];
-        if (blockIdx.x == 0 && threadIdx.x == 0) words[kWordLrNow] = lr;
-    }
-    const float step = lr / bc1;
-    const float c1 = 1.f - b1, c2 = 1.f - b2;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        float4 gi = g[i];
-        const float4 mo = m[i], vo = v[i];
-        float4 pi = p[i];
-        float ga[4] = {gi.x, gi.y, gi.z, gi.w};
-        const float ma[4] = {mo.x, mo.y, mo.z, mo.w}, va[4] = {vo.x, vo.y, vo.z, vo.w};
-        float pa[4] = {pi.x, pi.y, pi.z, pi.w}, mn[4], vn[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {      // the arithmetic of adam_clamp_kernel, operation for operation
-            float x = ga[k] * gscale;
-            if (kOpt) x = x * coef;
-            if (clip > 0.f) x = fminf(fmaxf(x, -clip), clip);
-            ga[k] = x;
-            mn[k] = b1 * ma[k] + c1 * x;
-            vn[k] = b2 * va[k] + c2 * x * x;
-            pa[k] -= step * mn[k] / (sqrtf(vn[k]) / bc2_sqrt + eps);
-        }
-        g[i] = make_float4(ga[0], ga[1], ga[2], ga[3]);
-        m[i] = make_float4(mn[0], mn[1], mn[2], mn[3]);
-        v[i] = make_float4(vn[0], vn[1], vn[2], vn[3]);
-        p[i] = make_float4(pa[0], pa[1], pa[2], pa[3]);
-    }
-}
-
 __global__ void counter_add_kernel(uint32_t* c, uint32_t inc, const float* flag) {
     if (flag == nullptr || flag[0] > 0.f) *c += inc;
 }
@@ -763,44 +667,6 @@ extern "C" int ick_context_gate_bwd(const int64_t* captions, const int64_t* fact
         hipLaunchKernelGGL(context_gate_bwd_kernel<false>, dim3(B, ceil_div(d, 256)), dim3(256), smem, (hipStream_t)stream,
                            captions, facts, dgate, dw, dbias, B, L, T, K, F, V, num_pred, d, mode);
     ICK_LAUNCH_RET();
-}
-
-// ick_adam_clamp and ick_adam_opt: the float4 kernel over the aligned bulk, the scalar kernel over the rest
-template <bool kOpt>
-static int launch_adam(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr, float* words,
-                       ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                       const float* gscale_den, void* stream) {
-    ICK_CHECK_ARG(p && g && m && v && n > 0 && (step >= 1 || step_ptr != nullptr));
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    int64_t done = 0;
-    if (n >= 4096 && al16(p) && al16(g) && al16(m) && al16(v)) {
-        const int64_t n4 = n / 4;
-        hipLaunchKernelGGL(adam_clamp_vec4_kernel<kOpt>, dim3((int)std::min<int64_t>(ceil_div(n4, 256), 4096)), dim3(256),
-                           0, (hipStream_t)stream, reinterpret_cast<float4*>(p), reinterpret_cast<float4*>(g),
-                           reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), n4, gscale, clip, lr, beta1, beta2,
-                           eps, step, step_ptr, gscale_den, words, sched);
-        done = 4 * n4;
-        if (done == n) ICK_LAUNCH_RET();
-    }
-    hipLaunchKernelGGL(adam_clamp_kernel<kOpt>, dim3((int)std::min<int64_t>(ceil_div(n - done, 256), 4096)), dim3(256), 0,
-                       (hipStream_t)stream, p + done, g + done, m + done, v + done, n - done, gscale, clip, lr, beta1,
-                       beta2, eps, step, step_ptr, gscale_den, words, sched);
-    ICK_LAUNCH_RET();
-}
-
-extern "C" int ick_adam_clamp(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr,
-                              float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                              const float* gscale_den, void* stream) {
-    return launch_adam<false>(p, g, m, v, n, gscale, clip, lr, nullptr, ick_lr_schedule{}, beta1, beta2, eps, step,
-                              step_ptr, gscale_den, stream);
-}
-
-extern "C" int ick_adam_opt(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float* words,
-                            ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                            const uint32_t* step_ptr, const float* gscale_den, void* stream) {
-    ICK_CHECK_ARG(words != nullptr && lr_schedule_ok(sched));
-    return launch_adam<true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step, step_ptr,
-                             gscale_den, stream);
 }
 
 extern "C" int ick_scale_by_ratio(float* x, int64_t n, const float* num, const float* den, void* stream) {

@@ -1496,25 +1496,6 @@ def context_gate_bwd(captions, facts, dgate, dw, dbias, K, V, mode=0):
                                           dw.shape[1], d, mode, _stream()), "ick_context_gate_bwd")
 
 
-def adam_clamp(p, g, m, v, step, lr, clip=5.0, gscale=1.0, beta1=0.9, beta2=0.999, eps=1e-8, step_tensor=None,
-               gscale_den=None):
-    """step (+ the uint32 device counter step_tensor, if given) is Adam's 1-based step count; the gradient is
-    scaled by gscale (/ the device scalar gscale_den, if given) before the clamp."""
-    L.check(L.load().ick_adam_clamp(_p(p), _p(g), _p(m), _p(v), p.numel(), gscale, clip, lr, beta1, beta2, eps, step,
-                                    _p(step_tensor), _p(gscale_den), _stream()), "ick_adam_clamp")
-
-
-def adam_clamp_derive(p, g, m, v, items_dev, blocks_dev, n_blocks, step, lr, clip=5.0, gscale=1.0, beta1=0.9, beta2=0.999,
-                      eps=1e-8, step_tensor=None, gscale_den=None, nbytes=0):
-    """adam_clamp over the whole bucket + the re-laid-out copies of the updated weights in the same pass
-    (ick_adam_clamp_derive; items_dev / blocks_dev: device arrays of ick_adam_item / ick_adam_block built by
-    weights.DerivedWeights).  nbytes: the launch's algorithmic bytes, for profiling.py."""
-    L.ADAM_DERIVE_BYTES = nbytes
-    L.check(L.load().ick_adam_clamp_derive(_p(p), _p(g), _p(m), _p(v), _p(items_dev), _p(blocks_dev), n_blocks, gscale,
-                                           clip, lr, beta1, beta2, eps, step, _p(step_tensor), _p(gscale_den), _stream()),
-            "ick_adam_clamp_derive")
-
-
 def _opt_words(words, who):
     if not isinstance(words, torch.Tensor) or words.dtype != torch.float32 or not words.is_cuda or \
             words.numel() < L.OPT_WORDS or not words.is_contiguous() or words.data_ptr() % 16:
@@ -1558,25 +1539,36 @@ def grad_sqnorm(g, words, scratch=None, gscale=1.0, gscale_den=None):
     return words
 
 
-def adam_opt(p, g, m, v, step, words, schedule=None, clip=5.0, gscale=1.0, beta1=0.9, beta2=0.999, eps=1e-8,
-             step_tensor=None, gscale_den=None):
-    """adam_clamp with the base rate in words[0] shaped by `schedule` on the step count, and the gradient multiplied by
-    words[3] (the global-norm clip's coefficient) between the scale and the clamp (ick_adam_opt); words[4] receives the
-    rate used.  words: the optimizer words on the device -- a host scalar is refused."""
-    _opt_words(words, "adam_opt")
-    L.check(L.load().ick_adam_opt(_p(p), _p(g), _p(m), _p(v), p.numel(), gscale, clip, _p(words),
-                                  lr_schedule_struct(schedule), beta1, beta2, eps, step, _p(step_tensor), _p(gscale_den),
-                                  _stream()), "ick_adam_opt")
+_ADAM_ENTRIES = ("ick_adam_clamp", "ick_adam_opt", "ick_adam_clamp_derive", "ick_adam_opt_derive")
 
 
-def adam_opt_derive(p, g, m, v, items_dev, blocks_dev, n_blocks, step, words, schedule=None, clip=5.0, gscale=1.0,
-                    beta1=0.9, beta2=0.999, eps=1e-8, step_tensor=None, gscale_den=None, nbytes=0):
-    """adam_clamp_derive in the form of adam_opt (ick_adam_opt_derive)."""
-    _opt_words(words, "adam_opt_derive")
-    L.ADAM_DERIVE_BYTES = nbytes
-    L.check(L.load().ick_adam_opt_derive(_p(p), _p(g), _p(m), _p(v), _p(items_dev), _p(blocks_dev), n_blocks, gscale, clip,
-                                         _p(words), lr_schedule_struct(schedule), beta1, beta2, eps, step,
-                                         _p(step_tensor), _p(gscale_den), _stream()), "ick_adam_opt_derive")
+def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=None, clip=5.0, gscale=1.0, beta1=0.9,
+                beta2=0.999, eps=1e-8, step_tensor=None, gscale_den=None):
+    """g = clamp(g * gscale (/ the device scalar gscale_den, if given), +-clip), then Adam's update of p, m, v; step (+ the
+    uint32 device counter step_tensor, if given) is Adam's 1-based step count.  Nothing is written while gscale_den is
+    given and not > 0.
+    The rate is exactly one of
+      lr     a host float (ick_adam_clamp[_derive]);
+      words  the optimizer words ON THE DEVICE -- a host scalar is refused (ick_adam_opt[_derive]): the base rate in
+             words[0] shaped by `schedule` (lr_schedule_struct) on the step count, the gradient multiplied by words[3] (the
+             global-norm clip's coefficient) between the scale and the clamp; words[4] receives the rate used.
+    cover: None for the p.numel() floats of a flat bucket; otherwise the owner of a cover of the WHOLE bucket
+    (weights.DerivedWeights: items_dev / blocks_dev, device arrays of ick_adam_item / ick_adam_block, n_blocks, and nbytes,
+    the launch's algorithmic bytes for profiling.py), read at call time: the same pass then also writes the re-laid-out
+    copies of the updated weights (the *_derive entries)."""
+    if (lr is None) == (words is None):
+        raise L.IckError("adam_update needs exactly one of lr (a host float) and words (the optimizer words)")
+    if words is None and schedule is not None:
+        raise L.IckError("adam_update: a schedule shapes the rate in the optimizer words; give words, not lr")
+    name = _ADAM_ENTRIES[(words is not None) + 2 * (cover is not None)]
+    rate = (lr,) if words is None else (_p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule))
+    if cover is None:
+        over = (p.numel(),)
+    else:
+        L.ADAM_DERIVE_BYTES = cover.nbytes
+        over = (_p(cover.items_dev), _p(cover.blocks_dev), cover.n_blocks)
+    L.check(getattr(L.load(), name)(_p(p), _p(g), _p(m), _p(v), *over, gscale, clip, *rate, beta1, beta2, eps, step,
+                                    _p(step_tensor), _p(gscale_den), _stream()), name)
 
 
 def counter_add(counter, inc=1):

@@ -129,14 +129,10 @@ def classify(name, args):
         B, Lc, Vx = args[8], args[9], args[10]
         return (("weighted " if args[6] else "") + "packed cross entropy, label smoothing (+ gradient)",
                 4.0 * B * Lc * Vx * (2 if args[15] else 1), "byte")
-    if name == "ick_adam_clamp":
+    if name in ("ick_adam_clamp", "ick_adam_opt"):
         return "clamp + Adam", 4.0 * args[4] * 7, "byte"
-    if name == "ick_adam_clamp_derive":
+    if name in ("ick_adam_clamp_derive", "ick_adam_opt_derive"):
         # the seven streams of the update + every image of the updated weights (packed, transposed, bf16 planes)
-        return "clamp + Adam + re-laid-out weight copies", float(getattr(L, "ADAM_DERIVE_BYTES", 0)), "byte"
-    if name == "ick_adam_opt":
-        return "clamp + Adam", 4.0 * args[4] * 7, "byte"
-    if name == "ick_adam_opt_derive":
         return "clamp + Adam + re-laid-out weight copies", float(getattr(L, "ADAM_DERIVE_BYTES", 0)), "byte"
     if name == "ick_grad_sqnorm":
         # one read of the gradient bucket (the partials and the words are a few KiB)

@@ -1133,33 +1133,21 @@ class TrainStep:
 
     def _adam(self):
         # divide by the global token count (device-resident), clamp, Adam with the device step counter -- and, with
-        # self.derived, the re-laid-out copies of the updated weights in the same pass (ick_adam_clamp_derive)
+        # self.derived, the re-laid-out copies of the updated weights in the same pass (the cover runs over the whole
+        # bucket).  With the optimizer words the rate comes from them and the schedule, else from self.lr.
         den = self.flat_g[self.n + 1:]
-        if self._words is not None:
+        if self._words is not None and self.max_grad_norm is not None:
             # The norm is taken here, behind the all-reduce, so every rank gets the same value.  It runs over [0, n): the
             # alignment pads between the parameters lie inside, and they are zero -- _side_tail zeroes the whole bucket,
             # the backward pass writes through self.grads (views of the parameters' own extents), the all-reduce adds
             # zeros, and the optimizer kernels write back clamp(0 * scale) = 0.  The trailing [loss sum, token count] at
             # n, n + 1 are outside.
-            if self.max_grad_norm is not None:
-                ops.grad_sqnorm(self.flat_g[:self.n], self._words, self._norm_scratch, gscale=1.0, gscale_den=den)
-            kw = dict(schedule=self._sched, clip=self.clip, gscale=1.0, beta1=self.betas[0], beta2=self.betas[1],
-                      eps=self.eps, step_tensor=self.counter, gscale_den=den)
-            if self.derived is not None:
-                ops.adam_opt_derive(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.derived.items_dev,
-                                    self.derived.blocks_dev, self.derived.n_blocks, 1, self._words,
-                                    nbytes=self.derived.nbytes, **kw)
-            else:
-                ops.adam_opt(self.flat_p[:self.n], self.flat_g[:self.n], self.flat_m, self.flat_v, 1, self._words, **kw)
-            return
-        hyper = (1, self.lr, self.clip, 1.0, self.betas[0], self.betas[1], self.eps)
-        if self.derived is not None:
-            ops.adam_clamp_derive(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.derived.items_dev,
-                                  self.derived.blocks_dev, self.derived.n_blocks, *hyper, step_tensor=self.counter,
-                                  gscale_den=self.flat_g[self.n + 1:], nbytes=self.derived.nbytes)
-        else:
-            ops.adam_clamp(self.flat_p[:self.n], self.flat_g[:self.n], self.flat_m, self.flat_v, *hyper,
-                           step_tensor=self.counter, gscale_den=self.flat_g[self.n + 1:])
+            ops.grad_sqnorm(self.flat_g[:self.n], self._words, self._norm_scratch, gscale=1.0, gscale_den=den)
+        rate = dict(lr=self.lr) if self._words is None else dict(words=self._words, schedule=self._sched)
+        # (the update runs over flat_p's n floats or the cover: flat_g's two trailing words stay outside without a view)
+        ops.adam_update(self.flat_p, self.flat_g, self.flat_m, self.flat_v, 1, cover=self.derived,
+                        clip=self.clip, gscale=1.0, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                        step_tensor=self.counter, gscale_den=den, **rate)
 
     # ---- the same step in two halves (several ranks: the early half's all-reduce overlaps the late half) ----
     def _part_a1(self, captions, caption_masks, entities, facts, enc_in, gmap, lengths, weights=None):

@@ -711,7 +711,7 @@ int ick_adam_clamp(float* p, float* g, float* m, float* v, int64_t n, float gsca
  *     Constraints: K % 4 == 0, off % 4 == 0; pack_t needs drow0 % 4 == 0 and rows % 4 == 0; ps_t needs drow0 % 8 == 0
  *     and rows % 8 == 0; copy_ld % 4 == 0.
  * Every float of [0, n) must lie in exactly one block (the caller builds the cover).  items / blocks are DEVICE arrays.
- * Arithmetic: the operations of ick_adam_clamp in the same order (bit-identical parameters, moments, clamped gradients). */
+ * Arithmetic: ick_adam_clamp's own (one function, csrc/adam.hip: bit-identical parameters, moments, clamped gradients). */
 typedef struct ick_adam_item {
     int64_t off;
     int32_t rows, K, drow0, Nd;

@@ -1,8 +1,8 @@
-"""The optimizer kernel that keeps the re-laid-out weight copies current (ick_adam_clamp_derive, csrc/adam_derive.hip;
+"""The optimizer kernel that keeps the re-laid-out weight copies current (ick_adam_clamp_derive, csrc/adam.hip;
 VERDICT r4 item 6): the reference's optimizer.step() (geo-aware/train.py:292, clip at :287-288) is the only writer of the
 parameters, so the packed / transposed / bf16-plane images the next step's kernels read are written in the same pass.
   * the update itself is ick_adam_clamp's, bit for bit (parameters, moments, clamped gradients), on the real bucket of all
-    three variants;
+    three variants: the kernels share one adam1 and differ in how they address the bucket;
   * every image equals what the stand-alone packing kernels (ick_pack_weights, ick_presplit_weights) make of the updated
     weights, bit for bit, padding included;
   * a captured TrainStep with the images maintained this way computes what the per-step packing launches of rounds 2-4
@@ -46,8 +46,8 @@ def test_update_and_images_are_bit_identical_to_the_separate_kernels(variant, V)
     ts.counter.fill_(4)
     ref = [t.clone() for t in (ts.flat_p, ts.flat_g, ts.flat_m, ts.flat_v)]
     ts._adam()
-    ops.adam_clamp(ref[0], ref[1][:n], ref[2], ref[3], 1, 4e-4, 5.0, 1.0, 0.9, 0.999, 1e-8, step_tensor=ts.counter,
-                   gscale_den=ts.flat_g[n + 1:])
+    ops.adam_update(ref[0], ref[1][:n], ref[2], ref[3], 1, 4e-4, clip=5.0, gscale=1.0, beta1=0.9, beta2=0.999, eps=1e-8,
+                    step_tensor=ts.counter, gscale_den=ts.flat_g[n + 1:])
     torch.cuda.synchronize()
     assert not torch.equal(ref[0], torch.zeros_like(ref[0]))
     for mine, r, what in zip((ts.flat_p, ts.flat_g, ts.flat_m, ts.flat_v), ref, "pgmv"):

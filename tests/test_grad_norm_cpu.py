@@ -8,6 +8,7 @@ import ctypes
 import math
 import os
 import subprocess
+import types
 
 import numpy as np
 import pytest
@@ -110,13 +111,19 @@ def test_bad_arguments_raise():
     with pytest.raises(IckError):
         ops.lr_schedule_struct(dict(kind="exponential"))
     # the wrappers refuse host scalars where a device word is required (no GPU needed to be refused)
+    cover = types.SimpleNamespace(items_dev=None, blocks_dev=None, n_blocks=1, nbytes=0)
     for bad in (4e-4, torch.zeros(L.OPT_WORDS), torch.zeros(L.OPT_WORDS, dtype=torch.float64)):
         with pytest.raises(IckError):
             ops.grad_sqnorm(torch.zeros(8), bad)
         with pytest.raises(IckError):
-            ops.adam_opt(*(torch.zeros(8) for _ in range(4)), 1, bad)
+            ops.adam_update(*(torch.zeros(8) for _ in range(4)), 1, words=bad)
         with pytest.raises(IckError):
-            ops.adam_opt_derive(*(torch.zeros(8) for _ in range(4)), None, None, 1, 1, bad)
+            ops.adam_update(*(torch.zeros(8) for _ in range(4)), 1, words=bad, cover=cover)
+    # exactly one of lr and words; a schedule shapes the rate in the words only
+    for kw, why in ((dict(lr=4e-4, words=torch.zeros(L.OPT_WORDS)), "exactly one"), (dict(), "exactly one"),
+                    (dict(lr=4e-4, schedule=dict(kind="constant")), "schedule")):
+        with pytest.raises(IckError, match=why):
+            ops.adam_update(*(torch.zeros(8) for _ in range(4)), 1, **kw)
 
 
 def test_struct_words_and_kinds_follow_the_header(tmp_path):

@@ -2,7 +2,8 @@
   * ick_grad_sqnorm alone: exact on buckets whose every partial sum is an fp32 number, at the sizes where a path of the
     kernel begins or ends; against float64 on normal data; the same bits twice; the token-count rule; the coefficient;
   * ick_adam_opt / ick_adam_opt_derive against ick_adam_clamp / ick_adam_clamp_derive, bit for bit, with a coefficient
-    of 1 and of 0.25;
+    of 1 and of 0.25; the scalar kernel against the float4 kernel on the same elements (csrc/adam.hip: one adam1, three
+    kernels that address differently);
   * one TrainStep(max_grad_norm=) step against the CPU oracle with torch's clip_grad_norm_ and clamp_, in every product
     mode and both head modes; with a bound that never binds, the default step's bits;
   * the schedule inside captured steps: the rate of every step, no further capture, set_lr, resume from state_dict();
@@ -135,9 +136,9 @@ def test_wrappers_refuse_host_words():
         with pytest.raises(IckError):
             ops.grad_sqnorm(t[0], bad)
         with pytest.raises(IckError):
-            ops.adam_opt(*t, 1, bad)
+            ops.adam_update(*t, 1, words=bad)
     with pytest.raises(IckError):        # the schedule's shape is checked by the library too
-        ops.adam_opt(*t, 1, make_words(4e-4), schedule=dict(kind="cosine", warmup_steps=3, total_steps=3))
+        ops.adam_update(*t, 1, words=make_words(4e-4), schedule=dict(kind="cosine", warmup_steps=3, total_steps=3))
 
 
 # ------------------------------------------------------------------------------------------------ the Adam entries
@@ -155,10 +156,11 @@ def test_adam_opt_is_adam_clamp_bit_for_bit(n, coef):
     counter = torch.full((1,), 4, device="cuda", dtype=torch.int32)
     den = torch.tensor([7.0], device="cuda")
     ref, mine = _bucket(n, n), _bucket(n, n)
-    ops.adam_clamp(*ref, 1, 4e-4, 5.0, coef, 0.9, 0.999, 1e-8, step_tensor=counter, gscale_den=den)
+    ops.adam_update(*ref, 1, 4e-4, clip=5.0, gscale=coef, beta1=0.9, beta2=0.999, eps=1e-8, step_tensor=counter,
+                    gscale_den=den)
     words = make_words(4e-4, 1.0)
     words[W_COEF] = coef
-    ops.adam_opt(*mine, 1, words, clip=5.0, gscale=1.0, step_tensor=counter, gscale_den=den)
+    ops.adam_update(*mine, 1, words=words, clip=5.0, gscale=1.0, step_tensor=counter, gscale_den=den)
     for a, b, what in zip(mine, ref, "pgmv"):
         assert same_bits(a, b), what
     assert ref[1].abs().max().item() == 5.0                         # the clamp was exercised
@@ -166,8 +168,42 @@ def test_adam_opt_is_adam_clamp_bit_for_bit(n, coef):
     # without tokens nothing moves, the rate word included
     words[W_LR] = 0.0
     before = [t.clone() for t in mine]
-    ops.adam_opt(*mine, 1, words, step_tensor=counter, gscale_den=torch.zeros(1, device="cuda"))
+    ops.adam_update(*mine, 1, words=words, step_tensor=counter, gscale_den=torch.zeros(1, device="cuda"))
     assert all(same_bits(a, b) for a, b in zip(mine, before)) and words[W_LR].item() == 0.0
+
+
+@pytest.mark.parametrize("form", ["lr", "words"])
+def test_scalar_kernel_is_float4_kernel_bit_for_bit(form):
+    """The two flat kernels on the SAME elements (the other tests compare them on disjoint ranges only): one bucket of
+    4099 floats in arrays that start one float past a 16-byte boundary, which sends all of it through adam_clamp_kernel,
+    and the same contents aligned, where adam_clamp_vec4_kernel takes 4096 and the scalar kernel the tail of 3.  Plain
+    rate, and the words form with coefficient 0.25 at step 5 of a cosine schedule."""
+    n = 4099
+    counter = torch.full((1,), 4, device="cuda", dtype=torch.int32)
+    den = torch.tensor([7.0], device="cuda")
+    vec, odd = _bucket(n, n), []
+    for t in _bucket(n, n):
+        buf = torch.empty(n + 1, device="cuda")
+        buf[1:] = t
+        odd.append(buf[1:])
+    assert all(t.data_ptr() % 16 == 0 for t in vec) and all(t.data_ptr() % 16 == 4 for t in odd)
+    assert all(same_bits(a, b) for a, b in zip(odd, vec))
+
+    def rate():
+        if form == "lr":
+            return dict(lr=4e-4)
+        words = make_words(4e-4, 1.0)
+        words[W_COEF] = 0.25
+        return dict(words=words, schedule=dict(kind="cosine", warmup_steps=3, total_steps=9))
+
+    rates = rate(), rate()
+    for arrays, r in zip((vec, odd), rates):
+        ops.adam_update(*arrays, 1, clip=5.0, gscale=1.0, step_tensor=counter, gscale_den=den, **r)
+    for a, b, what in zip(odd, vec, "pgmv"):
+        assert same_bits(a, b), what
+    assert vec[1].abs().max().item() == 5.0                         # the clamp was exercised
+    if form == "words":
+        assert same_bits(*(r["words"] for r in rates)) and 0.0 < rates[0]["words"][W_LR].item() < 4e-4
 
 
 def _images(dw):
@@ -199,16 +235,16 @@ def test_adam_opt_derive_is_adam_clamp_derive_bit_for_bit(coef):
     den = ts.flat_g[n + 1:].clone()
     images0 = {k: v.clone() for k, v in _images(dw).items()}
     start = [t.clone() for t in (ts.flat_p, ts.flat_g, ts.flat_m, ts.flat_v)]
-    cover = (dw.items_dev, dw.blocks_dev, dw.n_blocks)
     ref = [t.clone() for t in start]
-    ops.adam_clamp_derive(*ref, *cover, 1, 4e-4, 5.0, coef, 0.9, 0.999, 1e-8, step_tensor=ts.counter, gscale_den=den)
+    ops.adam_update(*ref, 1, 4e-4, cover=dw, clip=5.0, gscale=coef, beta1=0.9, beta2=0.999, eps=1e-8,
+                    step_tensor=ts.counter, gscale_den=den)
     ref_images = {k: v.clone() for k, v in _images(dw).items()}
     for k, v in _images(dw).items():                    # back to the images of the weights before the update
         v.copy_(images0[k])
     mine = [t.clone() for t in start]
     words = make_words(4e-4, 1.0)
     words[W_COEF] = coef
-    ops.adam_opt_derive(*mine, *cover, 1, words, clip=5.0, gscale=1.0, step_tensor=ts.counter, gscale_den=den)
+    ops.adam_update(*mine, 1, words=words, cover=dw, clip=5.0, gscale=1.0, step_tensor=ts.counter, gscale_den=den)
     for a, b, what in zip(mine, ref, "pgmv"):
         assert same_bits(a[:n], b[:n]), what
     assert not torch.equal(mine[0], start[0]) and words[W_LR].item() == np.float32(4e-4)
@@ -225,7 +261,7 @@ def test_adam_opt_rate_word_follows_the_schedule(kind):
     counter = torch.zeros(1, device="cuda", dtype=torch.int32)
     words = make_words(4e-4)
     for t in range(1, 13):
-        ops.adam_opt(*t4, 1, words, schedule=sch, step_tensor=counter)
+        ops.adam_update(*t4, 1, words=words, schedule=sch, step_tensor=counter)
         ops.counter_add(counter, 1)
         want = lr_at(t, float(np.float32(4e-4)), sch)
         assert abs(words[W_LR].item() - want) <= 1e-6 * want + 1e-6 * 4e-4, (kind, t)

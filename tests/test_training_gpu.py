@@ -148,7 +148,7 @@ def test_adam_clamp_matches_torch(ops):
         g = g0 * step
         pt.grad = g.clone().clamp_(-5, 5)
         opt.step()
-        ops.adam_clamp(p, dev(g), m, v, step, 4e-4, clip=5.0)
+        ops.adam_update(p, dev(g), m, v, step, 4e-4, clip=5.0)
         close(p, pt.detach(), 2e-6, "adam step %d" % step)
 
 
