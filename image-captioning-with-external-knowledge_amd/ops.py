@@ -1539,6 +1539,40 @@ def grad_sqnorm(g, words, scratch=None, gscale=1.0, gscale_den=None):
     return words
 
 
+def conv1_wgrad_plan(B, Cc, P, d):
+    """((groups, reduction indices per group, column tiles, rows per row block), floats of scratch) of ick_conv1_wgrad
+    for d_img (B, P, d) and feats (B, Cc, P)."""
+    plan, floats = (L.i32 * 4)(), L.i64()
+    L.check(L.load().ick_conv1_wgrad_plan(B, Cc, P, d, plan, C.byref(floats)), "ick_conv1_wgrad_plan")
+    return tuple(plan), floats.value
+
+
+def conv1_wgrad(d_img, feats, dw, db, scratch=None):
+    """Encoder.conv1's weight and bias gradient straight from the NCHW feature map (ick_conv1_wgrad):
+    dw[o, c] = sum_{b, p} d_img[b, p, o] * feats[b, c, p], db[o] = sum_{b, p} d_img[b, p, o].  d_img (B, P, d), feats
+    (B, C, P) or (B, C, H, W) with H * W = P, dw (d, C) or conv1's (d, C, 1, 1), db (d,): contiguous float32 device
+    tensors.  dw and db are OVERWRITTEN.  Fixed-order reduction, the same bits on every run.  scratch: float32 device
+    tensor of conv1_wgrad_plan(B, C, P, d)[1] floats (allocated when None).  Returns (dw, db)."""
+    for name, t in (("d_img", d_img), ("feats", feats), ("dw", dw), ("db", db)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise L.IckError("conv1_wgrad needs %s as a contiguous float32 device tensor" % name)
+    if d_img.dim() != 3 or feats.dim() not in (3, 4):
+        raise L.IckError("conv1_wgrad takes d_img (B, P, d) and feats (B, C, P) or (B, C, H, W)")
+    B, P, d = d_img.shape
+    Cc = feats.shape[1]
+    if feats.shape[0] != B or feats.numel() != B * Cc * P or dw.numel() != d * Cc or db.numel() != d:
+        raise L.IckError("conv1_wgrad: d_img %s, feats %s, dw %s, db %s do not fit together"
+                         % (tuple(d_img.shape), tuple(feats.shape), tuple(dw.shape), tuple(db.shape)))
+    need = conv1_wgrad_plan(B, Cc, P, d)[1]
+    if scratch is None:
+        scratch = torch.empty(need, device=d_img.device, dtype=torch.float32)
+    elif scratch.dtype != torch.float32 or not scratch.is_cuda or not scratch.is_contiguous() or scratch.numel() < need:
+        raise L.IckError("conv1_wgrad needs %d contiguous float32 device floats of scratch" % need)
+    L.check(L.load().ick_conv1_wgrad(_p(d_img), _p(feats), _p(dw), _p(db), B, Cc, P, d, _p(scratch), scratch.numel(),
+                                     _stream()), "ick_conv1_wgrad")
+    return dw, db
+
+
 _ADAM_ENTRIES = ("ick_adam_clamp", "ick_adam_opt", "ick_adam_clamp_derive", "ick_adam_opt_derive")
 
 

@@ -67,6 +67,11 @@ class SelfCriticalStep:
         if not (temperature > 0 and temperature < float("inf")) or not (isinstance(top_k, int) and top_k >= 0) or \
                 not (0 < top_p <= 1):
             raise IckError("need a finite temperature > 0, an integer top_k >= 0 and 0 < top_p <= 1")
+        if getattr(train_step, "train_conv1", False):
+            # the sampled captions travel with image_index over token-major encoder rows, from where the step cannot
+            # reach Encoder.conv1: self-critical training with a trained projection is not supported
+            raise IckError("SelfCriticalStep cannot drive a TrainStep built with train_conv1=True (its samples share "
+                           "token-major encoder rows through image_index)")
         self.ts = train_step
         self.dec = train_step.dec
         self.reward_fn = reward_fn

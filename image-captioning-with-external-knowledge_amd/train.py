@@ -61,6 +61,11 @@ class Config:
     decoder_lr: float = 4e-4
     encoder_lr: float = 1e-4                           # geo-aware/train.py:47
     fine_tune_encoder: bool = False                    # geo-aware/train.py:52; True trains conv1 (+ trunk blocks 2-4)
+    train_conv1: bool = False                          # train Encoder.conv1 INSIDE the fused step from a feature-file
+                                                       # dataset (TrainStep(train_conv1=True, encoder_lr=encoder_lr)): what
+                                                       # fine_tune_encoder=True does to a feature-file run, at the fused
+                                                       # step's speed and with data parallelism; not with fine_tune_encoder,
+                                                       # scst or raw images
     grad_clip: float = 5.0
     label_smoothing: float = 0.0                       # eps of the TRAINING loss, 0 <= eps < 1 (Szegedy et al. 2016; 0.1
                                                        # is usual): fused, TrainStep(label_smoothing=); unfused, torch's
@@ -281,12 +286,15 @@ def train(loader, encoder, decoder, criterion, decoder_optimizer, step, epoch, c
         extra = (facts,) if has_facts else ()
         if encoder_optimizer is not None:
             enc = encoder(imgs)                     # fine_tune_encoder: the loss back-propagates into the encoder
+        elif step is not None and step.train_conv1:
+            enc = None                              # the step projects the feature map itself
         else:
             with torch.no_grad():
                 enc = encoder(imgs)
         n_tok = int((caplens - 1).sum())
         if step is not None:                                             # fused HIP step
-            loss = step(caps, enc, capmasks, caplens, ent, *extra).item()
+            # (train_conv1: the step runs Encoder.conv1 itself and needs the feature map to train it)
+            loss = step(caps, imgs if step.train_conv1 else enc, capmasks, caplens, ent, *extra).item()
         else:                                                            # the reference's statement sequence
             scores, caps_sorted, dl = decoder(caps, enc, capmasks, caplens, ent, *extra)
             loss_t = packed_loss(criterion, scores, caps_sorted, dl)
@@ -554,6 +562,10 @@ def main(cfg=None):
     if world > 1 and (not cfg.fused or cfg.fine_tune_encoder):
         raise ValueError("data-parallel training needs fused=True and fine_tune_encoder=False (TrainStep owns the "
                          "gradient all-reduce; the encoder's gradients are not part of its bucket)")
+    if cfg.train_conv1 and (cfg.fine_tune_encoder or cfg.scst or not cfg.fused):
+        raise ValueError("train_conv1=True trains Encoder.conv1 inside the fused step: it needs fused=True and excludes "
+                         "fine_tune_encoder=True (the unfused way to train the encoder) and scst=True (its samples reach "
+                         "the step as token-major encoder rows)")
     fused = cfg.fused and not cfg.fine_tune_encoder     # fine-tuning the encoder takes the reference's statement
                                                         # sequence: loss.backward() through the HIP autograd bridge
     if cfg.scst and (not fused or world > 1 or cfg.scst_baseline not in ("greedy", "mean")):
@@ -597,6 +609,7 @@ def main(cfg=None):
     encoder.fine_tune(cfg.fine_tune_encoder)
     if cfg.fine_tune_encoder and encoder_optimizer is None:
         encoder_optimizer = torch.optim.Adam([p for p in encoder.parameters() if p.requires_grad], lr=cfg.encoder_lr)
+    encoder_optimizer_ck = encoder_optimizer            # train_conv1: the step takes its state over below
     if not cfg.fine_tune_encoder:
         encoder_optimizer = None
     step = None
@@ -609,7 +622,8 @@ def main(cfg=None):
             det = os.environ["ICK_DETERMINISTIC"] not in ("", "0")      # the script's switch, read when main() runs
         pipelined = cfg.prefetch and not cfg.scst
         step = TrainStep(decoder, lr=cfg.decoder_lr, grad_clip=cfg.grad_clip, seed=cfg.seed * 1000 + rank,
-                         encoder=encoder if pipelined else None, deterministic=det,
+                         encoder=encoder if pipelined or cfg.train_conv1 else None, deterministic=det,
+                         train_conv1=cfg.train_conv1, encoder_lr=cfg.encoder_lr,
                          # the pipelined loop lets step i's optimizer update run at the head of step i + 1's graph beside
                          # Encoder.conv1; _train_fused_pipelined() flushes the last one of an epoch
                          lazy_update=bool(pipelined), label_smoothing=cfg.label_smoothing,
@@ -619,6 +633,8 @@ def main(cfg=None):
             # back from the pickled optimizer (ours or one written by the reference, geo-aware/utils.py:32-46)
             step.load_state_dict(decoder_optimizer.state_dict())
             decoder_optimizer = None
+        if cfg.train_conv1 and encoder_optimizer_ck is not None:
+            step.load_encoder_state_dict(encoder_optimizer_ck.state_dict())     # (after the decoder's: it sets the step count)
         # what the bucket does not cover (frozen Encoder.conv1 and trunk, frozen decoder parameters, buffers) also
         # starts from rank 0's copy: every process initialised its own
         dp.broadcast_module_state([encoder, decoder], _bucket_range(step))
@@ -629,6 +645,9 @@ def main(cfg=None):
         check_lr_schedule(cfg.lr_schedule)
     criterion, val_criterion = (c.to(device) for c in make_criteria(word_map["<pad>"], cfg.label_smoothing))
     loaders, samplers, shuffle_gen = make_loaders(cfg, rank, world, fused)
+    if cfg.train_conv1 and not loaders["TRAIN"].dataset.precomputed:
+        raise ValueError("train_conv1=True needs a dataset of precomputed feature maps: with raw images the ResNet trunk "
+                         "runs outside the step (fine_tune_encoder=True trains the encoder there)")
     sc = cider = None
     if cfg.scst:
         captions = torch.as_tensor(np.asarray(loaders["TRAIN"].dataset.captions), dtype=torch.long)
@@ -653,6 +672,8 @@ def main(cfg=None):
                         g["base_lr"] *= 0.8
             if encoder_optimizer is not None:
                 ut.adjust_learning_rate(encoder_optimizer, 0.8)
+            if step is not None and step.train_conv1:
+                step.set_encoder_lr(step.encoder_lr * 0.8)
         # the epoch's permutation depends on (seed, epoch) only, so a resumed run sees the batches the interrupted
         # one would have seen
         shuffle_gen.manual_seed(cfg.seed * 100003 + epoch)
@@ -681,7 +702,8 @@ def main(cfg=None):
             raise RuntimeError("data-parallel replicas diverged (epoch %d): parameters differ between ranks" % epoch)
         if rank == 0:
             opt = step.as_torch_optimizer() if step is not None else decoder_optimizer
-            ut.save_checkpoint(cfg.data_name, epoch, epochs_since_improvement, encoder, decoder, encoder_optimizer,
+            enc_opt = step.as_torch_encoder_optimizer() if step is not None and step.train_conv1 else encoder_optimizer
+            ut.save_checkpoint(cfg.data_name, epoch, epochs_since_improvement, encoder, decoder, enc_opt,
                                opt, last_loss, is_best, out_dir=cfg.out_dir)
     return history
 

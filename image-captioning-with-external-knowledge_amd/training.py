@@ -47,7 +47,7 @@ def _p(x):
 # ----------------------------------------------------------------------------------------------
 def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gmap, seed=0, epoch=None,
                       fresh_pack=False, overlap=False, feats=None, conv1=None, side_tail=None, derived=None, pre_side=None,
-                      head_rows=None):
+                      head_rows=None, pre_main=None):
     """Teacher-forced forward on already length-sorted inputs; returns (scores, tape).  Dropout is
     active iff the module is in train() mode (masks derive from `seed` + the device counter `epoch`).
     fresh_pack: rebuild the packed cross-K/V / transposed predicate weights from the live parameters
@@ -66,10 +66,14 @@ def forward_with_tape(dec, captions, caption_masks, entities, facts, enc_tok, gm
     -- TrainStep's deferred optimizer update of the previous step.  It opens the side stream, beside Encoder.conv1 on the
     main stream (frozen weights, input features: the one large kernel of the step that reads no trainable parameter);
     the entity / fact encoders follow it there and the main stream waits for that point behind conv1.
+    pre_main: work of the caller that must run on the MAIN stream before Encoder.conv1 and before the side stream opens --
+    TrainStep's deferred update of a trained conv1 (it reads the step counter the side stream's update then advances).
     head_rows: callable -> ops.HeadRows or None, asked when the score head is reached (TrainStep makes the row list in its
     side tail): the head then runs over the packed list of valid rows only and `scores` holds packed rows."""
     tape = Tape()
     m = tape.misc
+    if pre_main is not None:
+        pre_main()
     ds = DropSites(seed, dec.training, epoch)
     d, V, H = dec.emb_dim, dec.vocab_size, dec.num_heads
     B, L = captions.shape
@@ -547,14 +551,17 @@ def _rows_t_presplit(x2, pack=None):
     return buf
 
 
-def backward_from_tape(dec, tape, dscores, grads, overlap=True, want_image_grad=False):
+def backward_from_tape(dec, tape, dscores, grads, overlap=True, want_image_grad=False, image_grad_sink=None):
     """Accumulate parameter gradients of `dec` into `grads` (dict id(param) -> zero-initialised
     tensor shaped like the parameter; frozen parameters are simply absent).  With `overlap` the weight /
     bias gradients of the Linear layers run on a second HIP stream beside the data-gradient chain.
     want_image_grad: also return the gradient of the (length-sorted) image memory rows (B, P, d) -- what
     fine_tune_encoder=True back-propagates into Encoder.conv1; the default step skips that 13.5 GFLOP GEMM because
-    the reference never uses the result (geo-aware/train.py:93-100,283-284)."""
-    bp = BackwardPass(dec, tape, dscores, grads, overlap, want_image_grad)
+    the reference never uses the result (geo-aware/train.py:93-100,283-284).
+    image_grad_sink: callable(d_img) that consumes that gradient for the optimizer alone (TrainStep's conv1 weight
+    gradient): with `overlap` the image-row gradient and the sink both run on the side stream, beside the context
+    encoders' backward."""
+    bp = BackwardPass(dec, tape, dscores, grads, overlap, want_image_grad, image_grad_sink)
     bp.early(join=False)     # one pass: the side stream is only joined at the very end
     bp.late()
     return tape.misc.get("d_img")
@@ -582,9 +589,9 @@ class BackwardPass:
     early() = score head + decoder stack, with the side stream joined at its end; late() = context encoders and
     embeddings.  The two phases may be captured into two hipGraphs."""
 
-    def __init__(self, dec, tape, dscores, grads, overlap=True, want_image_grad=False):
+    def __init__(self, dec, tape, dscores, grads, overlap=True, want_image_grad=False, image_grad_sink=None):
         self.side = ops.SideStream() if overlap else None
-        self.gen = _backward_phases(dec, tape, dscores, grads, want_image_grad)
+        self.gen = _backward_phases(dec, tape, dscores, grads, want_image_grad, image_grad_sink)
 
     def _run(self, join):
         ops.SIDE = self.side
@@ -608,7 +615,7 @@ class BackwardPass:
         self._run(True)
 
 
-def _backward_phases(dec, tape, dscores, grads, want_image_grad=False):
+def _backward_phases(dec, tape, dscores, grads, want_image_grad=False, image_grad_sink=None):
     m = tape.misc
     d, V, H = dec.emb_dim, dec.vocab_size, dec.num_heads
     h, ee, fe = m["h"], m["ee"], m["fe"]
@@ -712,7 +719,18 @@ def _backward_phases(dec, tape, dscores, grads, want_image_grad=False):
     if want_image_grad:
         # image rows: d mem[:, :P] = dK/dV rows @ packed K/V weight (the data gradient of the all-layer projection)
         d_img = torch.empty(B, P, d, device=dev, dtype=torch.float32)
-        ops.gemm_raw(dkv_rows, m["wkv"], d_img, B * P, d, nseg * d, nseg * d, 1, 1, d, d, a_grp=P, a_gs=S * nseg * d)
+
+        def image_grad():
+            ops.gemm_raw(dkv_rows, m["wkv"], d_img, B * P, d, nseg * d, nseg * d, 1, 1, d, d, a_grp=P, a_gs=S * nseg * d)
+            if image_grad_sink is not None:
+                image_grad_sink(d_img)
+
+        # with a sink nothing on the main stream reads d_img: both launches go to the side stream (enqueued at the next
+        # flush, behind the context encoders' first launch); ICK_CONV1_BWD_MAIN=1 keeps them on the main stream (A/B runs)
+        if image_grad_sink is not None and ops.SIDE is not None and not os.environ.get("ICK_CONV1_BWD_MAIN"):
+            ops.SIDE.submit(image_grad, dkv_rows, m["wkv"], d_img)
+        else:
+            image_grad()
         m["d_img"] = d_img
     # ---- context encoders.  With the row chains the data gradient of the K/V projection for the context rows rides on
     # the first launch of each context encoder's backward (its rows are read straight out of the K/V gradient buffer)
@@ -856,8 +874,18 @@ class TrainStep:
 
     def __init__(self, decoder, lr=4e-4, grad_clip=5.0, betas=(0.9, 0.999), eps=1e-8, process_group=None, seed=0,
                  use_graph=True, encoder=None, deterministic=None, lazy_update=False, label_smoothing=0.0,
-                 max_grad_norm=None, lr_schedule=None):
+                 max_grad_norm=None, lr_schedule=None, train_conv1=False, encoder_lr=1e-4):
         self.dec = decoder
+        # train_conv1 (needs encoder= and the 4-D feature map as encoder_out): Encoder.conv1 is trained
+        # inside the step as the reference's fine_tune_encoder=True trains it (geo-aware/train.py:93-100,283-294): the
+        # backward pass also produces the image rows' gradient and ick_conv1_wgrad reduces it against the feature map;
+        # conv1's gradient travels behind the decoder's in the same bucket (one all-reduce), is divided by the same token
+        # count, clamped by grad_clip and fed to an Adam of its own (encoder_lr, this step's betas / eps and step counter).
+        # max_grad_norm and lr_schedule keep covering the decoder's parameters only.  False: nothing changes.
+        self.train_conv1 = bool(train_conv1)
+        self.encoder_lr = float(encoder_lr)
+        if self.train_conv1 and encoder is None:
+            raise IckError("train_conv1=True needs encoder=: the step cannot reach Encoder.conv1 without it")
         # max_grad_norm (float > 0; None: off): torch.nn.utils.clip_grad_norm_(params, m, norm_type=2) on the
         # token-mean gradient of the global batch, BEFORE the element clamp grad_clip (grad_clip=None: no clamp).
         # lr_schedule (dict(kind=, warmup_steps=, total_steps=, min_lr_ratio=), see lr_at; None: the fixed rate lr): the
@@ -923,7 +951,16 @@ class TrainStep:
         self.n_early = sum(pad(p.numel()) for p in params if id(p) in early_ids)
         # +2 trailing floats travel with the gradient bucket: [sum of token losses, token count]
         self.flat_p = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.flat_g = torch.zeros(n + 2, device=dev, dtype=torch.float32)
+        # train_conv1: conv1's extent (weight, bias, each padded like every parameter) lies between the decoder's n floats
+        # and the trailing words, so the one all-reduce carries it; self.n stays the decoder's size
+        self.ne = 0
+        if self.train_conv1:
+            c1 = encoder.conv1
+            if c1.weight.device != dev:
+                raise IckError("train_conv1=True: the encoder must be on the decoder's device (%s)" % dev)
+            self.ne = pad(c1.weight.numel()) + pad(c1.bias.numel())
+        self._t = n + self.ne                   # where [sum of token losses, token count] start in flat_g
+        self.flat_g = torch.zeros(self._t + 2, device=dev, dtype=torch.float32)
         self.flat_m = torch.zeros(n, device=dev, dtype=torch.float32)
         self.flat_v = torch.zeros(n, device=dev, dtype=torch.float32)
         self.counter = torch.zeros(1, device=dev, dtype=torch.int32)   # steps done (read as uint32 by the kernels)
@@ -938,6 +975,19 @@ class TrainStep:
                 self.grads[id(p)] = self.flat_g[off:off + k].view(p.shape)
                 off += pad(k)
         self.params = params
+        if self.train_conv1:
+            c1 = encoder.conv1
+            wn, bn = c1.weight.numel(), c1.bias.numel()
+            self.enc_p, self.enc_m, self.enc_v = (torch.zeros(self.ne, device=dev, dtype=torch.float32) for _ in range(3))
+            self.enc_g = self.flat_g[n:n + self.ne]
+            with torch.no_grad():
+                for p, o in ((c1.weight, 0), (c1.bias, pad(wn))):
+                    self.enc_p[o:o + p.numel()].copy_(p.reshape(-1))
+                    p.data = self.enc_p[o:o + p.numel()].view(p.shape)     # conv1 becomes a view of step-owned storage
+            self.enc_params = [c1.weight, c1.bias]
+            self._c1_gw = self.enc_g[:wn].view(c1.weight.shape[0], -1)
+            self._c1_gb = self.enc_g[pad(wn):pad(wn) + bn]
+            encoder.invalidate_caches()          # the weight moved: its pre-split copy is made again on first use
         if self.max_grad_norm is not None or self.lr_schedule is not None:
             self._make_words()
         if self.label_smoothing != 0.0:
@@ -951,6 +1001,8 @@ class TrainStep:
         # several ranks: every replica starts from rank 0's weights (a freshly built decoder is randomly initialised
         # per process; the reference has a single process, geo-aware/train.py:16-18).  One broadcast of the bucket.
         dp.broadcast_bucket(self.flat_p, self.pg)
+        if self.train_conv1:
+            dp.broadcast_bucket(self.enc_p, self.pg)
         # Several ranks, ICK_SPLIT_ALLREDUCE=1: the step runs as two graphs around two all-reduces -- the early half of
         # the bucket (score head, decoder stack: gradients complete first) travels while the late half (cross K/V
         # projection, context encoders, embeddings) is computed, and only the late half's all-reduce is exposed.  Measured
@@ -1058,7 +1110,7 @@ class TrainStep:
         those two floats); with per-caption weights (SelfCriticalStep's advantages) the weighted form.  pack: the scores
         are the packed rows of the valid positions, and so are the score gradients.  With label smoothing on, the
         smoothed entry in the same layout."""
-        tail = dict(want_grad=True, out_sum=self.flat_g[self.n:self.n + 1], out_count=self.flat_g[self.n + 1:])
+        tail = dict(want_grad=True, out_sum=self.flat_g[self._t:self._t + 1], out_count=self.flat_g[self._t + 1:])
         pad = self.dec.word_map["<pad>"]
         if self.label_smoothing != 0.0:
             return ops.packed_ce_smooth(scores, captions, pack if pack is not None else decode_len, pad, self._eps_word,
@@ -1096,13 +1148,16 @@ class TrainStep:
                                          overlap=self._overlap("ICK_NO_FWD_OVERLAP"),
                                          side_tail=tail, derived=self.derived,
                                          pre_side=self._deferred_update if self._lazy_active(enc_in) else None,
+                                         pre_main=self._adam_conv1 if self.train_conv1 and self._lazy_active(enc_in)
+                                         else None,
                                          head_rows=lambda: box.get("pack"), **self._enc_kwargs(enc_in))
         decode_len = box["decode_len"]
         tape.misc["prezero"] = box.get("prezero")
         ops.stamp("fwd: scores done")
         _, _, dscores = self._loss(scores, captions, decode_len, weights, box.get("pack"))
         ops.stamp("CE done")
-        backward_from_tape(dec, tape, dscores, self.grads, overlap=self._overlap("ICK_NO_BWD_OVERLAP"))
+        backward_from_tape(dec, tape, dscores, self.grads, overlap=self._overlap("ICK_NO_BWD_OVERLAP"),
+                           **self._conv1_bwd_kwargs(enc_in))
         ops.stamp("A: end (after join)")
         return self.flat_g
 
@@ -1110,11 +1165,41 @@ class TrainStep:
         return bool(self.lazy and self.use_graph and self.derived is not None and not self.split and not self.deterministic
                     and enc_in is not None and enc_in.dim() == 4 and self._overlap("ICK_NO_FWD_OVERLAP"))
 
+    def _conv1_bwd_kwargs(self, enc_in):
+        """train_conv1: the backward pass also makes the image rows' gradient and hands it to ick_conv1_wgrad, which writes
+        conv1's extent of the bucket (overwriting what the side tail zeroed)."""
+        if not self.train_conv1:
+            return {}
+
+        def sink(d_img):
+            ops.stamp("conv1 weight gradient starts")
+            ops.conv1_wgrad(d_img, enc_in, self._c1_gw, self._c1_gb)
+            ops.stamp("conv1 weight gradient done")
+
+        return dict(want_image_grad=True, image_grad_sink=sink)
+
+    def _adam_conv1(self):
+        """conv1's own update: the same division by the global token count, the element clamp, Adam with encoder_lr and
+        the step counter the decoder's update of the same step reads (so it runs before the counter advances) -- then the
+        pre-split copy of the new weight, into the buffer Encoder.conv1_presplit() hands out and captured graphs read in
+        place.  A no-op on the parameters while the token count is zero, as the decoder's update."""
+        ops.adam_update(self.enc_p, self.enc_g, self.enc_m, self.enc_v, 1, lr=self.encoder_lr, clip=self.clip, gscale=1.0,
+                        beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step_tensor=self.counter,
+                        gscale_den=self.flat_g[self._t + 1:])
+        self._conv1_resplit()
+
+    def _conv1_resplit(self):
+        ps = self.enc.conv1_presplit()            # (current by its key: no launch of its own)
+        if ps is not None:
+            w = self.enc.conv1.weight.detach()
+            ops.presplit_weights([(w.view(w.shape[0], -1), ps)])
+
     def _deferred_update(self):
         """The previous step's clamp + Adam and step counter, at the head of this step's graph.  Both are no-ops while the
-        token count in the gradient bucket's tail is zero: the very first step, and the step after a flush()."""
+        token count in the gradient bucket's tail is zero: the very first step, and the step after a flush().  (A trained
+        conv1's update has run on the main stream by now: forward_with_tape's pre_main.)"""
         self._adam()
-        ops.counter_add_if(self.counter, 1, self.flat_g[self.n + 1:])
+        ops.counter_add_if(self.counter, 1, self.flat_g[self._t + 1:])
 
     def flush(self):
         """Apply a pending (lazy_update) optimizer update now; afterwards the parameters, moments, step counter and weight
@@ -1125,7 +1210,7 @@ class TrainStep:
             self._gb.replay()
         else:
             self._part_b()
-        self.flat_g[self.n + 1:].zero_()      # the next step's leading update finds nothing to apply
+        self.flat_g[self._t + 1:].zero_()      # the next step's leading update finds nothing to apply
         self._pending = False
         self.dec.invalidate_caches()
         if self.derived is not None:
@@ -1135,7 +1220,7 @@ class TrainStep:
         # divide by the global token count (device-resident), clamp, Adam with the device step counter -- and, with
         # self.derived, the re-laid-out copies of the updated weights in the same pass (the cover runs over the whole
         # bucket).  With the optimizer words the rate comes from them and the schedule, else from self.lr.
-        den = self.flat_g[self.n + 1:]
+        den = self.flat_g[self._t + 1:]
         if self._words is not None and self.max_grad_norm is not None:
             # The norm is taken here, behind the all-reduce, so every rank gets the same value.  It runs over [0, n): the
             # alignment pads between the parameters lie inside, and they are zero -- _side_tail zeroes the whole bucket,
@@ -1164,7 +1249,7 @@ class TrainStep:
         tape.misc["prezero"] = box.get("prezero")
         self._ce = self._loss(scores, captions, decode_len, weights, box.get("pack"))
         self._bp = BackwardPass(dec, tape, self._ce[2], self.grads,
-                                overlap=self._overlap("ICK_NO_BWD_OVERLAP"))
+                                overlap=self._overlap("ICK_NO_BWD_OVERLAP"), **self._conv1_bwd_kwargs(enc_in))
         self._bp.early(join=True)
         return self.flat_g
 
@@ -1176,6 +1261,8 @@ class TrainStep:
         # divide by the global token count (device-resident), clamp, Adam with the device step counter
         ops.stamp("B: start")
         self._adam()
+        if self.train_conv1:
+            self._adam_conv1()
         ops.counter_add(self.counter, 1)
         ops.stamp("B: end")
         return self.flat_g
@@ -1294,6 +1381,69 @@ class TrainStep:
         opt.load_state_dict(self.state_dict())
         return opt
 
+    # ---- conv1's optimizer state (train_conv1), torch.optim.Adam's layout over [conv1.weight, conv1.bias] ----
+    def _enc_slot(self, flat, p):
+        off = (p.data_ptr() - self.enc_p.data_ptr()) // 4
+        return flat[off:off + p.numel()].view(p.shape)
+
+    def _need_conv1(self, what):
+        if not self.train_conv1:
+            raise IckError("%s needs a TrainStep built with train_conv1=True" % what)
+        self.flush()
+        self._check_views()
+
+    def encoder_state_dict(self):
+        """conv1's Adam state as torch.optim.Adam.state_dict() reports it for the reference's `encoder_optimizer` over a
+        feature-file encoder's trainable parameters [conv1.weight, conv1.bias] (geo-aware/train.py:93-100).  Both optimizers
+        step together: the step count is the decoder's.  Tensors are copies; state_dict() is unchanged."""
+        self._need_conv1("encoder_state_dict")
+        step = float(int(self.counter.item()) & 0xFFFFFFFF)
+        state = {}
+        if step > 0:
+            for i, p in enumerate(self.enc_params):
+                state[i] = {"step": torch.tensor(step), "exp_avg": self._enc_slot(self.enc_m, p).clone(),
+                            "exp_avg_sq": self._enc_slot(self.enc_v, p).clone()}
+        group = {"lr": self.encoder_lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": False, "params": [0, 1]}
+        return {"state": state, "param_groups": [group]}
+
+    def load_encoder_state_dict(self, sd):
+        """Restore conv1's moments and rate from a torch.optim.Adam-layout state dict over [conv1.weight, conv1.bias].  The
+        step count is the decoder's (load_state_dict sets it): a state whose step differs from it is refused."""
+        self._need_conv1("load_encoder_state_dict")
+        groups = sd["param_groups"]
+        ids = [i for g in groups for i in g["params"]]
+        if len(ids) != 2:
+            raise IckError("encoder optimizer state holds %d parameters, the step trains conv1.weight and conv1.bias (a "
+                           "state that also covers trunk blocks belongs to fine_tune_encoder=True)" % len(ids))
+        mine = int(self.counter.item()) & 0xFFFFFFFF
+        with torch.no_grad():
+            self.enc_m.zero_()
+            self.enc_v.zero_()
+            for p, i in zip(self.enc_params, ids):
+                st = sd["state"].get(i)
+                if not st:
+                    continue
+                if tuple(st["exp_avg"].shape) != tuple(p.shape):
+                    raise IckError("encoder optimizer state %d has shape %s, parameter has %s" %
+                                   (i, tuple(st["exp_avg"].shape), tuple(p.shape)))
+                if int(float(st["step"])) != mine:
+                    raise IckError("encoder optimizer state is at step %d, the decoder's at %d: both step together (load "
+                                   "the decoder's state first)" % (int(float(st["step"])), mine))
+                self._enc_slot(self.enc_m, p).copy_(st["exp_avg"])
+                self._enc_slot(self.enc_v, p).copy_(st["exp_avg_sq"])
+        self.encoder_lr = float(groups[0]["lr"])
+        self._graphs.clear()              # the rate is baked into the captured optimizer launches
+
+    def as_torch_encoder_optimizer(self):
+        """A live torch.optim.Adam over [conv1.weight, conv1.bias] carrying conv1's state: what goes into the checkpoint
+        under 'encoder_optimizer', the kind of object the reference pickles there."""
+        sd = self.encoder_state_dict()
+        opt = torch.optim.Adam(self.enc_params, lr=self.encoder_lr, betas=tuple(self.betas), eps=self.eps)
+        opt.load_state_dict(sd)
+        return opt
+
     def input_buffers(self):
         """The static input tensors of the most recently captured graphs, in __call__'s argument order
         (captions, encoder_out-or-features, caption_masks, caption_lengths, entities[, facts]).  A loader that writes
@@ -1313,6 +1463,16 @@ class TrainStep:
         else:
             self._graphs.clear()      # baked into the captured optimizer graph
 
+    def set_encoder_lr(self, lr):
+        """A new rate for conv1's Adam (train_conv1), applied from the next update on.  As set_lr without the optimizer
+        words: a pending update is applied first, under the old rate, and the rate is baked into the captured optimizer
+        launches, so the next step captures again."""
+        if not self.train_conv1:
+            raise IckError("set_encoder_lr needs a TrainStep built with train_conv1=True")
+        self.flush()
+        self.encoder_lr = float(lr)
+        self._graphs.clear()
+
     def _check_views(self):
         """The decoder's parameters must still be views of the flat bucket: decoder.to() / .cuda() /
         load_pretrained_embeddings() re-allocate them and the step would then update memory the module no longer
@@ -1322,6 +1482,12 @@ class TrainStep:
         if first.data_ptr() != lo or not (lo <= last.data_ptr() and last.data_ptr() + 4 * last.numel() <= hi):
             raise IckError("the decoder's parameters no longer live in TrainStep's bucket (module moved or a "
                            "Parameter was replaced after TrainStep was built): build a new TrainStep")
+        if self.train_conv1:
+            c1, lo = self.enc.conv1, self.enc_p.data_ptr()
+            if c1.weight is not self.enc_params[0] or c1.bias is not self.enc_params[1] or c1.weight.data_ptr() != lo or \
+                    c1.bias.data_ptr() != lo + 4 * (self.ne - (c1.bias.numel() + 63) // 64 * 64):
+                raise IckError("Encoder.conv1 no longer lives in TrainStep's storage (encoder moved or a Parameter was "
+                               "replaced after TrainStep was built): build a new TrainStep")
 
     def _row_inputs(self, caption_weights, image_index, R, n_img, dev):
         """Validated device copies of the optional per-caption inputs (None stays None).  The image index is checked
@@ -1357,6 +1523,9 @@ class TrainStep:
         dev = encoder_out.device
         if image_index is not None and encoder_out.dim() == 4:
             raise IckError("image_index needs a token-major encoder_out (B, d, P), not a 4-D feature map")
+        if self.train_conv1 and (encoder_out.dim() != 4 or image_index is not None):
+            raise IckError("train_conv1=True needs the 4-D feature map as encoder_out and no image_index: from a token-major "
+                           "encoder_out the step cannot reach Encoder.conv1")
         weights, gmap = self._row_inputs(caption_weights, image_index, captions.shape[0], encoder_out.shape[0], dev)
         # No length sort and no host round trip here: the loss is a sum over tokens, so the batch order does
         # not matter, and the lengths are only read on the device (packed cross entropy).  The reference sorts
@@ -1395,6 +1564,8 @@ class TrainStep:
                 self._graphs.clear()
             # the eager warm-up run of part B is a real optimizer step: snapshot and rewind its state
             state = (self.flat_p, self.flat_m, self.flat_v, self.counter)
+            if self.train_conv1:
+                state += (self.enc_p, self.enc_m, self.enc_v)
             snap = [t.clone() for t in state]
             try:
                 if self.split:
@@ -1416,13 +1587,15 @@ class TrainStep:
             if self.derived is not None:      # the warm-up's optimizer step wrote the images of weights that were just rewound
                 self.derived.stale = True
                 self.derived.ensure_current()
-            self.flat_g[self.n + 1:].zero_()  # (lazy_update: the warm-up's gradients are not a pending update)
+            if self.train_conv1:              # ... and the pre-split copy of conv1's
+                self._conv1_resplit()
+            self.flat_g[self._t + 1:].zero_()  # (lazy_update: the warm-up's gradients are not a pending update)
         if self.use_graph:
             ga, static, gb, ga2 = self._graphs[key]
             if self._lazy_active(enc_in) and not self._pending:
                 # nothing is waiting to be applied (first step, or the update was flushed / applied eagerly): the leading
                 # update of the graph must find a zero token count
-                self.flat_g[self.n + 1:].zero_()
+                self.flat_g[self._t + 1:].zero_()
             from .decoder import copy_inputs
             copy_inputs(static, inputs)
             ga.replay()
@@ -1458,4 +1631,4 @@ class TrainStep:
         if self.derived is not None:
             self.derived.mark_current()
         # token-mean loss of the global batch, still on the device
-        return self.flat_g[self.n:self.n + 1] / self.flat_g[self.n + 1:]
+        return self.flat_g[self._t:self._t + 1] / self.flat_g[self._t + 1:]

@@ -781,6 +781,20 @@ int ick_adam_opt_derive(float* p, float* g, float* m, float* v, const ick_adam_i
                         int32_t n_blocks, float gscale, float clip, float* words, ick_lr_schedule sched, float beta1,
                         float beta2, float eps, int32_t step, const uint32_t* step_ptr, const float* gscale_den,
                         void* stream);
+/* The weight and bias gradient of Encoder.conv1 (1x1 convolution) straight from the NCHW feature map:
+ *     dw[o, c] = sum over b, p of d_img[b, p, o] * feats[b, c, p],     db[o] = sum over b, p of d_img[b, p, o].
+ * d_img (B, P, d): the gradient of the image memory rows; feats (B, C, P): the feature map as it lies; dw (d, C): conv1's
+ * weight layout; db (d); all float32, contiguous.  Any B, C, P, d >= 1 with B * P < 2^31 - 64; 16-byte loads where
+ * d % 4 == 0 / P % 4 == 0 and the pointers allow, scalar loads otherwise.  Exact fp32 matrix products in every product mode.
+ * Two launches: workgroups per (64 columns, group of reduction chunks, block of up to 304 rows) leave their partial
+ * result in scratch, a second pass adds the groups in a fixed order.  No atomics: the same input gives the same bits on
+ * every run, in and out of deterministic mode.  dw and db are OVERWRITTEN (they need not be zeroed; nothing is
+ * accumulated into them).  ICK_EINVAL without a launch: a null pointer, a size < 1, scratch_floats too small.
+ * ick_conv1_wgrad_plan: plan[0] = groups the reduction is split into, plan[1] = reduction indices per group, plan[2] =
+ * column tiles, plan[3] = rows per row block; *scratch_floats = plan[0] * (d * C + d), the scratch the entry needs. */
+int ick_conv1_wgrad_plan(int32_t B, int32_t C, int32_t P, int32_t d, int32_t* plan, int64_t* scratch_floats);
+int ick_conv1_wgrad(const float* d_img, const float* feats, float* dw, float* db, int32_t B, int32_t C, int32_t P,
+                    int32_t d, float* scratch, int64_t scratch_floats, void* stream);
 /* *counter += inc on the stream (step / dropout-epoch counter of captured training graphs). */
 int ick_counter_add(uint32_t* counter, uint32_t inc, void* stream);
 /* ... only if *flag > 0 (device scalar): the step counter of a training step whose optimizer update is deferred into the
