@@ -179,8 +179,33 @@ def caption_embed(cfg, P, captions, masks, entities_encoded, facts_encoded=None)
 # torch.nn.MultiheadAttention / Transformer{En,De}coderLayer (post-LN) restated.
 # Call sites: geo-aware/models.py:241-244,348,358; knowledge-aware/models.py:319-324,495-496,508
 # Batch-major here: x is (B, T, d) (the reference is (T, B, d); samples are independent).
+#
+# Dropout (training; the reference builds the model with dropout_dec=0.5, dropout_enc=0.5, dropout_pos=0.1,
+# geo-aware/models.py:219,240-243): every function below takes an optional drop(name, x) -> x * mask[name], called at
+# the places torch calls dropout; drop=None is the eval-mode arithmetic, unchanged.  The site names:
+#   "pos"                       PositionEncoder.forward, after x + pe            geo-aware/models.py:208-209
+#   (stack, li, "att")          encoder self-attention weights: on the softmax output, before @ v
+#   ("d", li, "sa" | "ca")      decoder self- / cross-attention weights, likewise
+#                                 (F.multi_head_attention_forward: attn_output_weights = softmax(...), then
+#                                  dropout(attn_output_weights, p=dropout_p), then bmm(attn_output_weights, v))
+#   (stack, li, "1"|"2"|"3")    the sublayer's output, before the residual add
+#                                 (TransformerEncoderLayer._sa_block / _ff_block: return self.dropout1(x) /
+#                                  self.dropout2(x), added in norm1(x + ...) / norm2(x + ...);
+#                                  TransformerDecoderLayer._sa_block / _mha_block / _ff_block: dropout1 / 2 / 3;
+#                                  torch 1.9: tgt = tgt + self.dropout1(tgt2) and so on)
+#   (stack, li, "ff")           after the ReLU of linear1
+#                                 (_ff_block: self.linear2(self.dropout(self.activation(self.linear1(x)))))
+# stack is "e" (transformer_encoder_entities), "f" (transformer_encoder_facts) or "d" (transformer_decoder).
 # ----------------------------------------------------------------------------------------
-def mha(xq, xkv, in_w, in_b, out_w, out_b, H, causal):
+STACK_TAG = {"transformer_encoder_entities": "e", "transformer_encoder_facts": "f", "transformer_decoder": "d"}
+
+
+def _dropped(drop, name, x):
+    return x if drop is None else drop(name, x)
+
+
+def mha(xq, xkv, in_w, in_b, out_w, out_b, H, causal, drop=None, site=None):
+    """drop / site: the attention-weight dropout, drop(site, att) on the (B, H, T, S) softmax output."""
     B, T, d = xq.shape
     S = xkv.shape[1]
     dh = d // H
@@ -194,7 +219,7 @@ def mha(xq, xkv, in_w, in_b, out_w, out_b, H, causal):
     if causal:
         neg = torch.full((T, S), float("-inf")).triu(1)  # geo-aware/models.py:256-262
         att = att + neg
-    att = att.softmax(dim=-1)
+    att = _dropped(drop, site, att.softmax(dim=-1))
     ctx = (att @ v).transpose(1, 2).reshape(B, T, d)
     return F.linear(ctx, out_w, out_b)
 
@@ -203,46 +228,58 @@ def _ln(x, P, name):
     return F.layer_norm(x, (x.shape[-1],), P[name + ".weight"], P[name + ".bias"], LN_EPS)
 
 
-def encoder_layer(P, pre, x, H):
-    a = mha(x, x, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"],
-            P[pre + "self_attn.out_proj.weight"], P[pre + "self_attn.out_proj.bias"], H, False)
-    x = _ln(x + a, P, pre + "norm1")
-    f = F.linear(F.relu(F.linear(x, P[pre + "linear1.weight"], P[pre + "linear1.bias"])),
-                 P[pre + "linear2.weight"], P[pre + "linear2.bias"])
-    return _ln(x + f, P, pre + "norm2")
+def _attend(drop, site, *args):
+    # without dropout mha() is called exactly as before drop= existed (tests substitute it with that signature)
+    return mha(*args) if drop is None else mha(*args, drop=drop, site=site)
 
 
-def decoder_layer(P, pre, x, mem, H):
-    a = mha(x, x, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"],
-            P[pre + "self_attn.out_proj.weight"], P[pre + "self_attn.out_proj.bias"], H, True)
-    x = _ln(x + a, P, pre + "norm1")
-    c = mha(x, mem, P[pre + "multihead_attn.in_proj_weight"], P[pre + "multihead_attn.in_proj_bias"],
-            P[pre + "multihead_attn.out_proj.weight"], P[pre + "multihead_attn.out_proj.bias"], H, False)
-    x = _ln(x + c, P, pre + "norm2")
-    f = F.linear(F.relu(F.linear(x, P[pre + "linear1.weight"], P[pre + "linear1.bias"])),
-                 P[pre + "linear2.weight"], P[pre + "linear2.bias"])
-    return _ln(x + f, P, pre + "norm3")
+def _ffn(P, pre, x, drop, key):
+    f = _dropped(drop, key + ("ff",), F.relu(F.linear(x, P[pre + "linear1.weight"], P[pre + "linear1.bias"])))
+    return F.linear(f, P[pre + "linear2.weight"], P[pre + "linear2.bias"])
 
 
-def context_encoder(cfg, P, stack, x):
+def encoder_layer(P, pre, x, H, drop=None, key=None):
+    """key = (stack tag, layer index): the first two elements of the layer's dropout site names."""
+    key = key or ()
+    a = _attend(drop, key + ("att",), x, x, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"],
+                P[pre + "self_attn.out_proj.weight"], P[pre + "self_attn.out_proj.bias"], H, False)
+    x = _ln(x + _dropped(drop, key + ("1",), a), P, pre + "norm1")
+    f = _ffn(P, pre, x, drop, key)
+    return _ln(x + _dropped(drop, key + ("2",), f), P, pre + "norm2")
+
+
+def decoder_layer(P, pre, x, mem, H, drop=None, key=None):
+    key = key or ()
+    a = _attend(drop, key + ("sa",), x, x, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"],
+                P[pre + "self_attn.out_proj.weight"], P[pre + "self_attn.out_proj.bias"], H, True)
+    x = _ln(x + _dropped(drop, key + ("1",), a), P, pre + "norm1")
+    c = _attend(drop, key + ("ca",), x, mem, P[pre + "multihead_attn.in_proj_weight"],
+                P[pre + "multihead_attn.in_proj_bias"], P[pre + "multihead_attn.out_proj.weight"],
+                P[pre + "multihead_attn.out_proj.bias"], H, False)
+    x = _ln(x + _dropped(drop, key + ("2",), c), P, pre + "norm2")
+    f = _ffn(P, pre, x, drop, key)
+    return _ln(x + _dropped(drop, key + ("3",), f), P, pre + "norm3")
+
+
+def context_encoder(cfg, P, stack, x, drop=None):
     """stack = 'transformer_encoder_entities' | 'transformer_encoder_facts' (a8)."""
     for i in range(cfg.num_layers):
-        x = encoder_layer(P, f"{stack}.layers.{i}.", x, cfg.num_heads)
+        x = encoder_layer(P, f"{stack}.layers.{i}.", x, cfg.num_heads, drop, (STACK_TAG[stack], i))
     return x
 
 
-def build_memory(cfg, P, enc_out, entities_encoded, facts_encoded=None):
+def build_memory(cfg, P, enc_out, entities_encoded, facts_encoded=None, drop=None):
     """mem (B, S, d) = [196 image rows ; encoded entity rows ; encoded fact rows].
     geo-aware/models.py:347-349, knowledge-aware/models.py:494-499.  enc_out is (B, d, P)."""
-    parts = [enc_out.permute(0, 2, 1), context_encoder(cfg, P, "transformer_encoder_entities", entities_encoded)]
+    parts = [enc_out.permute(0, 2, 1), context_encoder(cfg, P, "transformer_encoder_entities", entities_encoded, drop)]
     if facts_encoded is not None:
-        parts.append(context_encoder(cfg, P, "transformer_encoder_facts", facts_encoded))
+        parts.append(context_encoder(cfg, P, "transformer_encoder_facts", facts_encoded, drop))
     return torch.cat(parts, dim=1)
 
 
-def decoder_stack(cfg, P, x, mem):
+def decoder_stack(cfg, P, x, mem, drop=None):
     for i in range(cfg.num_layers):
-        x = decoder_layer(P, f"transformer_decoder.layers.{i}.", x, mem, cfg.num_heads)
+        x = decoder_layer(P, f"transformer_decoder.layers.{i}.", x, mem, cfg.num_heads, drop, ("d", i))
     return x
 
 
@@ -304,8 +341,10 @@ def get_scores(cfg, P, h, entities_encoded, facts_encoded=None, eib=None, pi=Non
 # ----------------------------------------------------------------------------------------
 # a12 DecoderTransformer.forward  geo-aware/models.py:315-361, knowledge-aware/models.py:457-514
 # ----------------------------------------------------------------------------------------
-def forward(cfg, P, captions, enc_out, caption_masks, caption_lengths, entities, facts=None, stages=None):
-    """Returns (scores (B,L,Vx) in length-sorted order, captions_sorted, decode_lengths)."""
+def forward(cfg, P, captions, enc_out, caption_masks, caption_lengths, entities, facts=None, stages=None, drop=None):
+    """Returns (scores (B,L,Vx) in length-sorted order, captions_sorted, decode_lengths).
+    drop: the training-mode dropout as a callable drop(name, x) (see the site names above mha); its masks are in the
+    length-sorted order, like everything past the sort."""
     lengths, sort_ind = caption_lengths.squeeze(1).sort(dim=0, descending=True)
     enc_out = enc_out[sort_ind]
     captions = captions[sort_ind]
@@ -317,10 +356,10 @@ def forward(cfg, P, captions, enc_out, caption_masks, caption_lengths, entities,
     ee = entity_encode(cfg, P, entities, facts)
     fe = fact_encode(P, facts, ee) if cfg.has_facts else None
     emb = caption_embed(cfg, P, captions, caption_masks, ee, fe)
-    mem = build_memory(cfg, P, enc_out, ee, fe)
+    mem = build_memory(cfg, P, enc_out, ee, fe, drop)
     L = captions.shape[1]
-    x = emb * math.sqrt(cfg.emb_dim) + pe_table(L, cfg.emb_dim).unsqueeze(0)
-    h = decoder_stack(cfg, P, x, mem)
+    x = _dropped(drop, "pos", emb * math.sqrt(cfg.emb_dim) + pe_table(L, cfg.emb_dim).unsqueeze(0))
+    h = decoder_stack(cfg, P, x, mem, drop)
     if cfg.has_facts:
         eib, pi = context_indicators(cfg, captions, facts, entities.shape[1], L)
         scores = get_scores(cfg, P, h, ee, fe, eib, pi)

@@ -20,8 +20,10 @@ from . import restatement as R
 
 class StockDecoder(nn.Module):
     def __init__(self, variant, word_map, emb_dim=300, decoder_dim=512, encoder_dim=512, num_heads=10,
-                 num_layers=3, dropout=0.0):
+                 num_layers=3, dropout=0.0, dropout_pos=0.0):
         super().__init__()
+        # PositionEncoder's own dropout (geo-aware/models.py:198,209); without dropout_pos it is not called at all
+        self.pos_dropout = nn.Dropout(dropout_pos) if dropout_pos > 0.0 else None
         self.cfg = R.config_from_word_map(variant, word_map, emb_dim, num_heads, num_layers)
         d = emb_dim
         self.transformer_decoder = nn.TransformerDecoder(
@@ -80,6 +82,8 @@ class StockDecoder(nn.Module):
         mem = torch.cat(parts)
         L = captions.shape[1]
         x = emb.permute(1, 0, 2) * math.sqrt(cfg.emb_dim) + self.pe[:L].unsqueeze(1)
+        if self.pos_dropout is not None:
+            x = self.pos_dropout(x)
         mask = torch.full((L, L), float("-inf")).triu(1)
         h = self.transformer_decoder(x, mem, mask)  # (L,B,d)
         if cfg.has_facts:
