@@ -770,43 +770,58 @@ class DecoderTransformer(nn.Module):
             if qkv is None:
                 qkv = ops.project_heads(x, layer.self_attn.in_proj_weight.detach(), layer.self_attn.in_proj_bias.detach(),
                                         3, H, T)
-            t["qkv"], qkv = qkv, None
+            t["qkv"] = qkv
             t["sa"] = torch.empty_like(x)
             t["lse"] = torch.empty(B * H * T, device=x.device, dtype=torch.float32) if save else None
             ops.attention_heads(t["qkv"], t["qkv"], t["sa"], H, d // H, T, T, 0, 1, 2, lse=t["lse"], drop=t["d_att"])
             last = li == n - 1
-            if pk is not None:
-                t["x1"] = torch.empty_like(x)
-                t["o1"], t["o2"] = (torch.empty_like(x), torch.empty_like(x)) if save else (None, None)
-                t["f"] = torch.empty(B, T, layer.linear1.out_features, device=x.device, dtype=torch.float32)
-                t["m1"], t["r1"] = ops.rowchain_fwd(
-                    t["sa"], pk[(tag, li, "so")], layer.self_attn.out_proj.bias.detach(), x, *_ln(layer.norm1), t["x1"],
-                    drop1=t["d1"], o_out=t["o1"], save_stats=save, w2p=pk[(tag, li, "l1")],
-                    b2=layer.linear1.bias.detach(), y2=t["f"], relu=True, drop2=t["d_ff"], slim=slim)
-                x2 = out if (last and out is not None) else torch.empty_like(x)
-                nxt = None if last else stack.layers[li + 1]
-                if nxt is not None:
-                    qkv = torch.empty(B, 3, H, T, ops.DHP, device=x.device, dtype=torch.float32)
-                t["m2"], t["r2"] = ops.rowchain_fwd(
-                    t["f"], pk[(tag, li, "l2")], layer.linear2.bias.detach(), t["x1"], *_ln(layer.norm2), x2,
-                    drop1=t["d2"], o_out=t["o2"], save_stats=save, w2p=None if nxt is None else pk[(tag, li + 1, "si")],
-                    b2=None if nxt is None else nxt.self_attn.in_proj_bias.detach(), y2=qkv,
-                    heads=None if nxt is None else (3, H, T, 0, T), slim=slim)
-            else:
-                t["o1"] = ops.linear(t["sa"], *_wb(layer.self_attn.out_proj))
-                t["x1"], t["m1"], t["r1"] = _with_stats(ops.add_layernorm(
-                    t["o1"], x, *_ln(layer.norm1), save_stats=save, drop=t["d1"]), save)
-                t["f"] = ops.linear(t["x1"], *_wb(layer.linear1), relu=True, drop=t["d_ff"])
-                t["o2"] = ops.linear(t["f"], *_wb(layer.linear2))
-                x2, t["m2"], t["r2"] = _with_stats(ops.add_layernorm(
-                    t["o2"], t["x1"], *_ln(layer.norm2), save_stats=save, drop=t["d2"]), save)
-                if last and out is not None:
-                    out.copy_(x2)
-                    x2 = out
-            x = x2
+            x, qkv = self._layer_tail(layer, t, "sa", layer.self_attn.out_proj, "so", 1, pk, (tag, li),
+                                      None if last else stack.layers[li + 1], save, slim=slim, out=out if last else None)
             if save:
                 tape.append(t)
         return x
+
+    def _layer_tail(self, layer, t, att, out_proj, oname, i, pk, at, nxt, save, slim=False, out=None):
+        """What follows an attention in a post-LN layer of either kind of stack: out-projection of t[att] + add & norm
+        number i + linear1 (ReLU, dropout), then linear2 + add & norm number i + 1.  i fixes the keys of t: the residual
+        going in is t["x"] (i = 1) or t["x%d" % (i - 1)]; o, x, m, r, d of i and o, m, r, d of i + 1 are read / written.
+        With pk, two row-chain launches (at = (tag, li) names the layer's packed images, oname the out-projection's), the
+        second also projecting the rows into the head-major q|k|v of nxt, the next layer if any; without pk, the separate
+        kernels.  out: a (B, T, d) view that receives the output.  Returns (x, that q|k|v or None)."""
+        H = self.num_heads
+        res = t["x%d" % (i - 1)] if i > 1 else t["x"]
+        B, T, _ = res.shape
+        norm_a, norm_b = getattr(layer, "norm%d" % i), getattr(layer, "norm%d" % (i + 1))
+        o_a, x_a, m_a, r_a, d_a = ("%s%d" % (k, i) for k in "oxmrd")
+        o_b, m_b, r_b, d_b = ("%s%d" % (k, i + 1) for k in "omrd")
+        if pk is None:
+            t[o_a] = ops.linear(t[att], *_wb(out_proj))
+            t[x_a], t[m_a], t[r_a] = _with_stats(ops.add_layernorm(
+                t[o_a], res, *_ln(norm_a), save_stats=save, drop=t[d_a]), save)
+            t["f"] = ops.linear(t[x_a], *_wb(layer.linear1), relu=True, drop=t["d_ff"])
+            t[o_b] = ops.linear(t["f"], *_wb(layer.linear2))
+            x, t[m_b], t[r_b] = _with_stats(ops.add_layernorm(
+                t[o_b], t[x_a], *_ln(norm_b), save_stats=save, drop=t[d_b]), save)
+            if out is not None:
+                out.copy_(x)
+                x = out
+            return x, None
+        tag, li = at
+        t[x_a] = torch.empty_like(res)
+        t[o_a], t[o_b] = (torch.empty_like(res), torch.empty_like(res)) if save else (None, None)
+        t["f"] = torch.empty(B, T, layer.linear1.out_features, device=res.device, dtype=torch.float32)
+        t[m_a], t[r_a] = ops.rowchain_fwd(
+            t[att], pk[(tag, li, oname)], out_proj.bias.detach(), res, *_ln(norm_a), t[x_a], drop1=t[d_a], o_out=t[o_a],
+            save_stats=save, w2p=pk[(tag, li, "l1")], b2=layer.linear1.bias.detach(), y2=t["f"], relu=True,
+            drop2=t["d_ff"], slim=slim)
+        x = out if out is not None else torch.empty_like(res)
+        qkv = None if nxt is None else torch.empty(B, 3, H, T, ops.DHP, device=res.device, dtype=torch.float32)
+        t[m_b], t[r_b] = ops.rowchain_fwd(
+            t["f"], pk[(tag, li, "l2")], layer.linear2.bias.detach(), t[x_a], *_ln(norm_b), x, drop1=t[d_b],
+            o_out=t[o_b], save_stats=save, w2p=None if nxt is None else pk[(tag, li + 1, "si")],
+            b2=None if nxt is None else nxt.self_attn.in_proj_bias.detach(), y2=qkv,
+            heads=None if nxt is None else (3, H, T, 0, T), slim=slim)
+        return x, qkv
 
     def _decoder_self_block(self, li, layer, x, pk, qkv=None, ds=_NO_DROPOUT, save=False, qkv_buf=None, pos=None):
         """Self-attention block of decoder layer li on x (B, T, d), up to the cross-attention query: in_proj (unless
@@ -858,32 +873,9 @@ class DecoderTransformer(nn.Module):
         t["ca"] = torch.empty_like(x)
         t["lse_c"] = torch.empty(B * H * T, device=x.device, dtype=torch.float32) if save else None
         ops.attention_heads(t["qc"], kv, t["ca"], H, dh, T, S, 0, 2 * li, 2 * li + 1, lse=t["lse_c"], drop=t["d_ca"])
-        if pk is None:
-            t["o2"] = ops.linear(t["ca"], *_wb(layer.multihead_attn.out_proj))
-            t["x2"], t["m2"], t["r2"] = _with_stats(ops.add_layernorm(
-                t["o2"], t["x1"], *_ln(layer.norm2), save_stats=save, drop=t["d2"]), save)
-            t["f"] = ops.linear(t["x2"], *_wb(layer.linear1), relu=True, drop=t["d_ff"])
-            t["o3"] = ops.linear(t["f"], *_wb(layer.linear2))
-            x3, t["m3"], t["r3"] = _with_stats(ops.add_layernorm(
-                t["o3"], t["x2"], *_ln(layer.norm3), save_stats=save, drop=t["d3"]), save)
-            return x3, None
-        t["x2"] = torch.empty_like(x)
-        t["o2"], t["o3"] = (torch.empty_like(x), torch.empty_like(x)) if save else (None, None)
-        t["f"] = torch.empty(B, T, layer.linear1.out_features, device=x.device, dtype=torch.float32)
-        t["m2"], t["r2"] = ops.rowchain_fwd(
-            t["ca"], pk[("d", li, "co")], layer.multihead_attn.out_proj.bias.detach(), t["x1"], *_ln(layer.norm2),
-            t["x2"], drop1=t["d2"], o_out=t["o2"], save_stats=save, w2p=pk[("d", li, "l1")],
-            b2=layer.linear1.bias.detach(), y2=t["f"], relu=True, drop2=t["d_ff"])
         layers = self.transformer_decoder.layers
-        nxt = layers[li + 1] if li + 1 < len(layers) else None
-        x3 = torch.empty_like(x)
-        qkv_n = None if nxt is None else torch.empty(B, 3, H, T, ops.DHP, device=x.device, dtype=torch.float32)
-        t["m3"], t["r3"] = ops.rowchain_fwd(
-            t["f"], pk[("d", li, "l2")], layer.linear2.bias.detach(), t["x2"], *_ln(layer.norm3), x3, drop1=t["d3"],
-            o_out=t["o3"], save_stats=save, w2p=None if nxt is None else pk[("d", li + 1, "si")],
-            b2=None if nxt is None else nxt.self_attn.in_proj_bias.detach(), y2=qkv_n,
-            heads=None if nxt is None else (3, H, T, 0, T))
-        return x3, qkv_n
+        return self._layer_tail(layer, t, "ca", layer.multihead_attn.out_proj, "co", 2, pk, ("d", li),
+                                layers[li + 1] if li + 1 < len(layers) else None, save)
 
     def _score_head(self, h, ee, fe, eib, hv, out, vocab_ps=None, pack=None):
         """get_scores into `out`, a (B, T, V+K[+F]) view with any row stride: the vocabulary logits of hv (facts

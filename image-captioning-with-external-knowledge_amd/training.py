@@ -16,6 +16,7 @@ Dropout: the reference constructs the decoder with dropout 0.5/0.5/0.1; the mask
 counter-based generator (see ick_dropout) and cannot be bit-identical to torch's CPU stream, so
 parity of the training math is pinned with dropout disabled (p = 0 / eval-mode fixtures).
 """
+import collections
 import functools
 import math
 import os
@@ -275,121 +276,164 @@ def _prezeroed(dec, captions, entities, facts):
     return pre
 
 
-def _norm_args(t, i, res, layer_norm, grads, M, d, dev):
-    """The saved forward tensors of add & norm number i of a layer + fresh outputs, as ops.rowchain_bwd wants them."""
-    return dict(o=t["o%d" % i], res=res, mean=t["m%d" % i], rstd=t["r%d" % i], gamma=_p(layer_norm.weight),
-                drop=t["d%d" % i], do=torch.empty(M, d, device=dev, dtype=torch.float32),
-                part=ops.ln_partials(M, d, dev))
+# A post-LN layer's backward, written once for the context-encoder stacks and the decoder stack and for both kernel
+# paths.  What differs between the layers arrives as data: an add & norm site = (LayerNorm module, its index in the
+# layer's tape dict, the key of its residual operand), the attention's module and tape keys, the packed images' names.
+# When the side stream's queued work goes out is each stack's own choreography: the stacks below call ops.SIDE's flushes
+# between the pieces, no piece calls one (ops.layernorm_bwd flushes behind its own kernel, whoever calls it).
+Dims = collections.namedtuple("Dims", "B T M d H dh dev")       # of a stack whose activations are (B, T, d); M = B * T
 
 
-def _context_encoder_bwd(dec, stack, tapes, dx, grads, pkb=None, tag="e", g_first=None):
-    """pkb: packed transposed weights (dec.weight_images().chain_t) -> one ops.rowchain_bwd launch per layer for
-    [in_proj data gradient of the layer above] + norm2' + linear2' + ReLU' + linear1' + norm1' + out_proj' instead
-    of six kernels.  g_first = (g0 rows view, packed W0^T): the incoming gradient is g0 @ W0 (no dx tensor)."""
-    H, d = dec.num_heads, dec.emb_dim
+def _dims(dec, x):
+    B, T, d = x.shape
+    return Dims(B, T, B * T, d, dec.num_heads, d // dec.num_heads, x.device)
+
+
+def _norm_args(t, site, D):
+    """The saved forward tensors of an add & norm site + fresh outputs, as ops.rowchain_bwd wants them."""
+    norm, i, res = site
+    return dict(o=t["o%d" % i], res=t[res], mean=t["m%d" % i], rstd=t["r%d" % i], gamma=_p(norm.weight),
+                drop=t["d%d" % i], do=torch.empty(D.M, D.d, device=D.dev, dtype=torch.float32),
+                part=ops.ln_partials(D.M, D.d, D.dev), norm=norm)
+
+
+def _norm_param_grads(grads, n):
+    ops.ln_partials_reduce(n["part"], _g(grads, n["norm"].weight), _g(grads, n["norm"].bias))
+
+
+def _ffn_chain_launch(layer, t, hi, lo, out_img, pkb, at, state, D):
+    """One ops.rowchain_bwd launch: [the hand-down g0 @ W0 + dzin] + norm' (site hi) + linear2' + ReLU' + linear1' +
+    norm' (site lo) + the out-projection' below it.  state = (dz, g0, w0p): the residual-path gradient of the layer's
+    output and the gradient whose data gradient rides on this launch.  at = (tag, li) names the layer's packed transposed
+    images, out_img the out-projection's.  Returns (n_hi, n_lo, dpre, datt, dz_out): the norms' argument dicts, the
+    gradients of linear1's and of the attention's output, the residual-path gradient below site lo."""
+    dz, g0, w0p = state
+    n_hi, n_lo = _norm_args(t, hi, D), _norm_args(t, lo, D)
+    dpre = torch.empty(D.M, layer.linear1.out_features, device=D.dev, dtype=torch.float32)
+    datt = torch.empty(D.M, D.d, device=D.dev, dtype=torch.float32)
+    dz_out = torch.empty(D.M, D.d, device=D.dev, dtype=torch.float32)
+    ops.rowchain_bwd(D.M, D.d, n_hi, pkb[at + (out_img,)], datt, dz_out, g0=g0, w0p=w0p, dzin=dz,
+                     ffn=dict(w1p=pkb[at + ("l2T",)], w2p=pkb[at + ("l1T",)], act=t["f"],
+                              gate_scale=_keep_scale(t["d_ff"]), t_out=dpre), norm2=n_lo)
+    return n_hi, n_lo, dpre, datt, dz_out
+
+
+def _ffn_chain_param_grads(grads, layer, t, n_hi, n_lo, dpre, out_proj, att, valid, D):
+    """What goes with _ffn_chain_launch: the parameter gradients of the two norms, linear2, linear1 and the out-projection
+    fed by t[att].  valid (ops.HeadRows, below a packed score head): the weight gradients reduce over the valid caption
+    rows only -- every other row of their dy operands is exactly zero."""
+    _norm_param_grads(grads, n_hi)
+    _norm_param_grads(grads, n_lo)
+    _lin_bwd(grads, n_hi["do"], t["f"].view(D.M, -1), layer.linear2.weight, layer.linear2.bias, need_dx=False, valid=valid)
+    _lin_bwd(grads, dpre, n_hi["res"].view(D.M, D.d), layer.linear1.weight, layer.linear1.bias, need_dx=False, valid=valid)
+    _lin_bwd(grads, n_lo["do"], t[att].view(D.M, D.d), out_proj.weight, out_proj.bias, need_dx=False, valid=valid)
+
+
+def _norm_bwd(grads, t, site, dx):
+    norm, i, res = site
+    return ops.layernorm_bwd(dx, t["o%d" % i], t[res], _p(norm.weight), t["m%d" % i], t["r%d" % i],
+                             _g(grads, norm.weight), _g(grads, norm.bias), drop=t["d%d" % i])
+
+
+def _ffn_plain_bwd(grads, layer, t, dx, hi, valid, D):
+    """The feed-forward sublayer with the add & norm above it (site hi) on separate kernels -> gradient of its input."""
+    dz, do = _norm_bwd(grads, t, hi, dx)
+    dpre = _lin_bwd(grads, do.view(D.M, D.d), t["f"].view(D.M, -1), layer.linear2.weight, layer.linear2.bias,
+                    gate=t["f"].view(D.M, -1), gate_scale=_keep_scale(t["d_ff"]),       # ReLU' (+ dropout) fused
+                    valid=valid)
+    return _lin_bwd(grads, dpre, t[hi[2]].view(D.M, D.d), layer.linear1.weight, layer.linear1.bias, dx=dz.view(D.M, D.d),
+                    acc=True, valid=valid)
+
+
+def _out_proj_plain_bwd(grads, t, dx, site, out_proj, att, valid, D):
+    """An attention's out-projection with its add & norm on separate kernels -> (residual-path gradient, that of t[att])."""
+    dz, do = _norm_bwd(grads, t, site, dx)
+    return dz, _lin_bwd(grads, do.view(D.M, D.d), t[att].view(D.M, D.d), out_proj.weight, out_proj.bias, valid=valid)
+
+
+def _self_attn_bwd(t, datt, lse, drop, causal, D):
+    """Backward of a layer's self-attention over its head-major q|k|v -> the (M, 3 d) gradient of in_proj's output."""
+    B, T, d = D.B, D.T, D.d
+    dqkv = ops.attention_bwd_buffer((B, T, 3 * d), T, T, D.dh, D.dev)
+    ops.attention_heads_bwd(t["qkv"], t["qkv"], t["sa"], datt.view(B, T, d), t[lse], dqkv[:, :, :d],
+                            dqkv[:, :, d:2 * d], dqkv[:, :, 2 * d:], D.H, D.dh, T, T, 0, 1, 2, causal=causal, drop=t[drop])
+    return dqkv.view(D.M, 3 * d)
+
+
+def _in_proj_bwd(grads, attn, t, dqkv, dz, valid, D, hand_down=None):
+    """Backward of a self-attention's in_proj -> the state (dz, g0, w0p) for what comes next.  hand_down (the packed
+    in_proj_weight.T; chain path, a layer below exists): parameter gradients only, the data gradient dqkv @ W rides on
+    that layer's first launch.  Else it is accumulated into dz."""
+    args = (grads, dqkv, t["x"].view(D.M, D.d), attn.in_proj_weight, attn.in_proj_bias)
+    if hand_down is not None:
+        _lin_bwd(*args, need_dx=False, valid=valid)
+        return dz, dqkv, hand_down
+    return _lin_bwd(*args, dx=dz.view(D.M, D.d), acc=True, valid=valid), None, None
+
+
+def _context_encoder_bwd_chain(dec, stack, tapes, grads, pkb, tag, g0, w0p):
+    """A context encoder on the row chains (pkb: dec.weight_images().chain_t): one ops.rowchain_bwd launch per layer
+    instead of six kernels.  The incoming gradient is g0 @ W0 (g0: a rows view, w0p: packed W0^T), no dx tensor."""
     layers = list(stack.layers)
-    if pkb is not None:
-        dev = tapes[0]["x"].device
-        dz, g0, w0p = dx, None, None
-        if g_first is not None:
-            dz, (g0, w0p) = None, g_first
-        for li in reversed(range(len(layers))):
-            layer, t = layers[li], tapes[li]
-            B, T, _ = t["x"].shape
-            M = B * T
-            n2 = _norm_args(t, 2, t["x1"], layer.norm2, grads, M, d, dev)
-            n1 = _norm_args(t, 1, t["x"], layer.norm1, grads, M, d, dev)
-            dpre = torch.empty(M, layer.linear1.out_features, device=dev, dtype=torch.float32)
-            dsa = torch.empty(M, d, device=dev, dtype=torch.float32)
-            dz_out = torch.empty(M, d, device=dev, dtype=torch.float32)
-            ops.rowchain_bwd(M, d, n2, pkb[(tag, li, "soT")], dsa, dz_out, g0=g0, w0p=w0p, dzin=dz,
-                             ffn=dict(w1p=pkb[(tag, li, "l2T")], w2p=pkb[(tag, li, "l1T")], act=t["f"],
-                                      gate_scale=_keep_scale(t["d_ff"]), t_out=dpre), norm2=n1)
-            if ops.SIDE is not None:
-                ops.SIDE.flush()
-            ops.ln_partials_reduce(n2["part"], _g(grads, layer.norm2.weight), _g(grads, layer.norm2.bias))
-            ops.ln_partials_reduce(n1["part"], _g(grads, layer.norm1.weight), _g(grads, layer.norm1.bias))
-            _lin_bwd(grads, n2["do"], t["f"].view(M, -1), layer.linear2.weight, layer.linear2.bias, need_dx=False)
-            _lin_bwd(grads, dpre, t["x1"].view(M, d), layer.linear1.weight, layer.linear1.bias, need_dx=False)
-            _lin_bwd(grads, n1["do"], t["sa"].view(M, d), layer.self_attn.out_proj.weight, layer.self_attn.out_proj.bias,
-                     need_dx=False)
-            if ops.SIDE is not None and li > 0:
-                # everything queued so far only needs the chain launch above: it goes out now, beside the attention
-                # backward (the in_proj weight gradient follows with the next group) -- the side stream's last group,
-                # which nothing on the main stream overlaps any more, shrinks to one problem
-                ops.SIDE.flush_group()
-            dqkv = ops.attention_bwd_buffer((B, T, 3 * d), T, T, d // H, dev)
-            ops.attention_heads_bwd(t["qkv"], t["qkv"], t["sa"], dsa.view(B, T, d), t["lse"], dqkv[:, :, :d],
-                                    dqkv[:, :, d:2 * d], dqkv[:, :, 2 * d:], H, d // H, T, T, 0, 1, 2, drop=t["d_att"])
-            if ops.SIDE is not None:
-                ops.SIDE.flush()
-            if li > 0:
-                # the in_proj data gradient rides on the next launch (the layer below); only its weight gradient here
-                _lin_bwd(grads, dqkv.view(M, 3 * d), t["x"].view(M, d), layer.self_attn.in_proj_weight,
-                         layer.self_attn.in_proj_bias, need_dx=False)
-                dz, g0, w0p = dz_out, dqkv.view(M, 3 * d), pkb[(tag, li, "siT")]
-            else:
-                dx = _lin_bwd(grads, dqkv.view(M, 3 * d), t["x"].view(M, d), layer.self_attn.in_proj_weight,
-                              layer.self_attn.in_proj_bias, dx=dz_out, acc=True).view(B, T, d)
-                if ops.SIDE is not None:
-                    # the stack's first layer is the last thing the backward pass computes: the main stream has
-                    # nothing left while the side stream still works off the layers above -- its weight gradients
-                    # run here instead of queueing behind them
-                    ops.SIDE.flush_group_here()
-        return dx
-    for layer, t in zip(reversed(layers), reversed(tapes)):
-        B, T, _ = t["x"].shape
-        M = B * T
-        dz, do2 = ops.layernorm_bwd(dx, t["o2"], t["x1"], _p(layer.norm2.weight), t["m2"], t["r2"],
-                                    _g(grads, layer.norm2.weight), _g(grads, layer.norm2.bias), drop=t["d2"])
-        dpre = _lin_bwd(grads, do2.view(M, d), t["f"].view(M, -1), layer.linear2.weight, layer.linear2.bias,
-                        gate=t["f"].view(M, -1), gate_scale=_keep_scale(t["d_ff"]))   # ReLU' (+ dropout) fused
-        dx1 = _lin_bwd(grads, dpre, t["x1"].view(M, d), layer.linear1.weight, layer.linear1.bias, dx=dz.view(M, d),
-                       acc=True)
-        dz, do1 = ops.layernorm_bwd(dx1.view(B, T, d), t["o1"], t["x"], _p(layer.norm1.weight), t["m1"], t["r1"],
-                                    _g(grads, layer.norm1.weight), _g(grads, layer.norm1.bias), drop=t["d1"])
-        dsa = _lin_bwd(grads, do1.view(M, d), t["sa"].view(M, d), layer.self_attn.out_proj.weight,
-                       layer.self_attn.out_proj.bias)
-        dqkv = ops.attention_bwd_buffer((B, T, 3 * d), T, T, d // H, dx.device)
-        ops.attention_heads_bwd(t["qkv"], t["qkv"], t["sa"], dsa.view(B, T, d), t["lse"], dqkv[:, :, :d],
-                                dqkv[:, :, d:2 * d], dqkv[:, :, 2 * d:], H, d // H, T, T, 0, 1, 2, drop=t["d_att"])
-        dx = _lin_bwd(grads, dqkv.view(M, 3 * d), t["x"].view(M, d), layer.self_attn.in_proj_weight,
-                      layer.self_attn.in_proj_bias, dx=dz.view(M, d), acc=True).view(B, T, d)
+    D = _dims(dec, tapes[0]["x"])
+    state = (None, g0, w0p)
+    for li in reversed(range(len(layers))):
+        layer, t = layers[li], tapes[li]
+        n2, n1, dpre, dsa, dz_out = _ffn_chain_launch(layer, t, (layer.norm2, 2, "x1"), (layer.norm1, 1, "x"), "soT", pkb,
+                                                      (tag, li), state, D)
+        if ops.SIDE is not None:
+            ops.SIDE.flush()
+        _ffn_chain_param_grads(grads, layer, t, n2, n1, dpre, layer.self_attn.out_proj, "sa", None, D)
+        if ops.SIDE is not None and li > 0:
+            # everything queued so far only needs the chain launch above: it goes out now, beside the attention
+            # backward (the in_proj weight gradient follows with the next group) -- the side stream's last group,
+            # which nothing on the main stream overlaps any more, shrinks to one problem
+            ops.SIDE.flush_group()
+        dqkv = _self_attn_bwd(t, dsa, "lse", "d_att", False, D)
+        if ops.SIDE is not None:
+            ops.SIDE.flush()
+        state = _in_proj_bwd(grads, layer.self_attn, t, dqkv, dz_out, None, D, pkb[(tag, li, "siT")] if li > 0 else None)
+        if ops.SIDE is not None and li == 0:
+            # the stack's first layer is the last thing the backward pass computes: the main stream has
+            # nothing left while the side stream still works off the layers above -- its weight gradients
+            # run here instead of queueing behind them
+            ops.SIDE.flush_group_here()
+    return state[0].view(D.B, D.T, D.d)
+
+
+def _context_encoder_bwd(dec, stack, tapes, dx, grads):
+    """A context encoder on the separate GEMM / LayerNorm-backward kernels; dx (B, T, d): the gradient of its output."""
+    D = _dims(dec, dx)
+    for layer, t in zip(reversed(list(stack.layers)), reversed(tapes)):
+        dx1 = _ffn_plain_bwd(grads, layer, t, dx, (layer.norm2, 2, "x1"), None, D)
+        dz, dsa = _out_proj_plain_bwd(grads, t, dx1, (layer.norm1, 1, "x"), layer.self_attn.out_proj, "sa", None, D)
+        dqkv = _self_attn_bwd(t, dsa, "lse", "d_att", False, D)
+        dx = _in_proj_bwd(grads, layer.self_attn, t, dqkv, dz, None, D)[0]
         if ops.SIDE is not None:
             ops.SIDE.flush_group()      # this layer's weight gradients: one grouped launch
-    return dx
+    return dx.view(D.B, D.T, D.d)
 
 
-def _decoder_layer_bwd_chain(dec, li, layer, t, state, dkv_rows, kv, S, grads, pkb, mem2=None, mem_t_ps=None,
-                             valid=None):
+def _cross_attn_bwd(li, t, dca, dkv_rows, kv, S, D):
+    """Backward of decoder layer li's cross-attention (K / V gradients: the layer's columns of dkv_rows) -> dq (B, T, d)."""
+    dq = torch.empty(D.B, D.T, D.d, device=D.dev, dtype=torch.float32)
+    c0 = 2 * li * D.d
+    ops.attention_heads_bwd(t["qc"], kv, t["ca"], dca.view(D.B, D.T, D.d), t["lse_c"], dq, dkv_rows[:, :, c0:c0 + D.d],
+                            dkv_rows[:, :, c0 + D.d:c0 + 2 * D.d], D.H, D.dh, D.T, S, 0, 2 * li, 2 * li + 1, drop=t["d_ca"])
+    return dq
+
+
+def _decoder_layer_bwd_chain(li, layer, t, state, dkv_rows, kv, S, grads, pkb, mem2, mem_t_ps, valid, D):
     """Backward of decoder layer li as two ops.rowchain_bwd launches around the cross-attention backward + the
     self-attention backward.  state = (dz, g0, w0p): the residual-path gradient of this layer's output, and -- from the
     layer above -- the in_proj gradient whose data gradient rides on this layer's first launch.  Returns the state
-    for the layer below.  valid (ops.HeadRows, below a packed score head): the layer's weight gradients reduce over the
-    valid caption rows only -- every other row of their dy operands is exactly zero."""
-    H, d = dec.num_heads, dec.emb_dim
-    dh = d // H
-    B, T, _ = t["x"].shape
-    M = B * T
-    dev = t["x"].device
-    dz, g0, w0p = state
-    n3 = _norm_args(t, 3, t["x2"], layer.norm3, grads, M, d, dev)
-    n2 = _norm_args(t, 2, t["x1"], layer.norm2, grads, M, d, dev)
-    dpre = torch.empty(M, layer.linear1.out_features, device=dev, dtype=torch.float32)
-    dca = torch.empty(M, d, device=dev, dtype=torch.float32)
-    dz_a = torch.empty(M, d, device=dev, dtype=torch.float32)
-    ops.rowchain_bwd(M, d, n3, pkb[("d", li, "coT")], dca, dz_a, g0=g0, w0p=w0p, dzin=dz,
-                     ffn=dict(w1p=pkb[("d", li, "l2T")], w2p=pkb[("d", li, "l1T")], act=t["f"],
-                              gate_scale=_keep_scale(t["d_ff"]), t_out=dpre), norm2=n2)
+    for the layer below.  valid: see _ffn_chain_param_grads."""
+    M, d = D.M, D.d
+    n3, n2, dpre, dca, dz_a = _ffn_chain_launch(layer, t, (layer.norm3, 3, "x2"), (layer.norm2, 2, "x1"), "coT", pkb,
+                                                ("d", li), state, D)
     if ops.SIDE is not None:
         ops.SIDE.flush()
-    ops.ln_partials_reduce(n3["part"], _g(grads, layer.norm3.weight), _g(grads, layer.norm3.bias))
-    ops.ln_partials_reduce(n2["part"], _g(grads, layer.norm2.weight), _g(grads, layer.norm2.bias))
-    _lin_bwd(grads, n3["do"], t["f"].view(M, -1), layer.linear2.weight, layer.linear2.bias, need_dx=False,
-             valid=valid)
-    _lin_bwd(grads, dpre, t["x2"].view(M, d), layer.linear1.weight, layer.linear1.bias, need_dx=False, valid=valid)
-    _lin_bwd(grads, n2["do"], t["ca"].view(M, d), layer.multihead_attn.out_proj.weight,
-             layer.multihead_attn.out_proj.bias, need_dx=False, valid=valid)
+    _ffn_chain_param_grads(grads, layer, t, n3, n2, dpre, layer.multihead_attn.out_proj, "ca", valid, D)
     # The layer's weight gradients go out in two grouped launches: linear2 / linear1 / cross out-projection + the two
     # norms' partials right behind the chain launch above, the rest at the layer's end (the side stream finishes last:
     # starting its work earlier shortens the step, 651 -> 654 k decode-steps/s; a third launch right behind the
@@ -397,78 +441,42 @@ def _decoder_layer_bwd_chain(dec, li, layer, t, state, dkv_rows, kv, S, grads, p
     # it gains: round 2 645 k, round 5 1.733 -> 1.739 ms, profiles/r05_x_ab_kv_wgrad_subgroups.txt)
     if ops.SIDE is not None:
         ops.SIDE.flush_group()
-    dq = torch.empty(B, T, d, device=dev, dtype=torch.float32)
-    c0 = 2 * li * d
-    ops.attention_heads_bwd(t["qc"], kv, t["ca"], dca.view(B, T, d), t["lse_c"], dq, dkv_rows[:, :, c0:c0 + d],
-                            dkv_rows[:, :, c0 + d:c0 + 2 * d], H, dh, T, S, 0, 2 * li, 2 * li + 1, drop=t["d_ca"])
+    dq = _cross_attn_bwd(li, t, dca, dkv_rows, kv, S, D)
     if ops.SIDE is not None:
         ops.SIDE.flush()
-    if mem2 is not None:
-        _kv_proj_param_grads(layer, li, dkv_rows, mem2, grads, d, mem_t_ps)
-    n1 = _norm_args(t, 1, t["x"], layer.norm1, grads, M, d, dev)
-    dsa = torch.empty(M, d, device=dev, dtype=torch.float32)
-    dz_b = torch.empty(M, d, device=dev, dtype=torch.float32)
+    _kv_proj_param_grads(layer, li, dkv_rows, mem2, grads, d, mem_t_ps)
+    n1 = _norm_args(t, (layer.norm1, 1, "x"), D)
+    dsa = torch.empty(M, d, device=D.dev, dtype=torch.float32)
+    dz_b = torch.empty(M, d, device=D.dev, dtype=torch.float32)
     ops.rowchain_bwd(M, d, n1, pkb[("d", li, "soT")], dsa, dz_b, g0=dq.view(M, d), w0p=pkb[("d", li, "cqT")], dzin=dz_a)
     if ops.SIDE is not None:
         ops.SIDE.flush()
-    ops.ln_partials_reduce(n1["part"], _g(grads, layer.norm1.weight), _g(grads, layer.norm1.bias))
+    _norm_param_grads(grads, n1)
     _lin_bwd(grads, dq.view(M, d), t["x1"].view(M, d), layer.multihead_attn.in_proj_weight,
              layer.multihead_attn.in_proj_bias, w_rows=slice(0, d), need_dx=False, valid=valid)
     _lin_bwd(grads, n1["do"], t["sa"].view(M, d), layer.self_attn.out_proj.weight, layer.self_attn.out_proj.bias,
              need_dx=False, valid=valid)
-    dqkv = ops.attention_bwd_buffer((B, T, 3 * d), T, T, dh, dev)
-    ops.attention_heads_bwd(t["qkv"], t["qkv"], t["sa"], dsa.view(B, T, d), t["lse_s"], dqkv[:, :, :d],
-                            dqkv[:, :, d:2 * d], dqkv[:, :, 2 * d:], H, dh, T, T, 0, 1, 2, causal=True,
-                            drop=t["d_sa"])
-    if li > 0:
-        _lin_bwd(grads, dqkv.view(M, 3 * d), t["x"].view(M, d), layer.self_attn.in_proj_weight,
-                 layer.self_attn.in_proj_bias, need_dx=False, valid=valid)
-        out = (dz_b, dqkv.view(M, 3 * d), pkb[("d", li, "siT")])
-    else:
-        dx0 = _lin_bwd(grads, dqkv.view(M, 3 * d), t["x"].view(M, d), layer.self_attn.in_proj_weight,
-                       layer.self_attn.in_proj_bias, dx=dz_b, acc=True, valid=valid).view(B, T, d)
-        out = (dx0, None, None)
+    dqkv = _self_attn_bwd(t, dsa, "lse_s", "d_sa", True, D)
+    state = _in_proj_bwd(grads, layer.self_attn, t, dqkv, dz_b, valid, D, pkb[("d", li, "siT")] if li > 0 else None)
     if ops.SIDE is not None:
         ops.SIDE.flush_group()          # this layer's weight gradients: one grouped launch
-    return out
+    return state
 
 
-def _decoder_layer_bwd(dec, li, layer, t, dx, dkv_rows, kv, S, grads, mem2=None, mem_t_ps=None, valid=None):
-    H, d = dec.num_heads, dec.emb_dim
-    dh = d // H
-    B, T, _ = t["x"].shape
-    M = B * T
-    dz, do3 = ops.layernorm_bwd(dx, t["o3"], t["x2"], _p(layer.norm3.weight), t["m3"], t["r3"],
-                                _g(grads, layer.norm3.weight), _g(grads, layer.norm3.bias), drop=t["d3"])
-    dpre = _lin_bwd(grads, do3.view(M, d), t["f"].view(M, -1), layer.linear2.weight, layer.linear2.bias,
-                    gate=t["f"].view(M, -1), gate_scale=_keep_scale(t["d_ff"]),       # ReLU' (+ dropout) fused
-                    valid=valid)
-    dx2 = _lin_bwd(grads, dpre, t["x2"].view(M, d), layer.linear1.weight, layer.linear1.bias, dx=dz.view(M, d),
-                   acc=True, valid=valid)
-    dz, do2 = ops.layernorm_bwd(dx2.view(B, T, d), t["o2"], t["x1"], _p(layer.norm2.weight), t["m2"], t["r2"],
-                                _g(grads, layer.norm2.weight), _g(grads, layer.norm2.bias), drop=t["d2"])
-    dca = _lin_bwd(grads, do2.view(M, d), t["ca"].view(M, d), layer.multihead_attn.out_proj.weight,
-                   layer.multihead_attn.out_proj.bias, valid=valid)
-    dq = torch.empty(B, T, d, device=dx.device, dtype=torch.float32)
-    c0 = 2 * li * d
-    ops.attention_heads_bwd(t["qc"], kv, t["ca"], dca.view(B, T, d), t["lse_c"], dq, dkv_rows[:, :, c0:c0 + d],
-                            dkv_rows[:, :, c0 + d:c0 + 2 * d], H, dh, T, S, 0, 2 * li, 2 * li + 1, drop=t["d_ca"])
-    if mem2 is not None:
-        # this layer's columns of the K/V-projection gradient are complete: its weight (and bias) gradient over
-        # all B * S memory rows joins this layer's group instead of waiting for the whole decoder stack
-        _kv_proj_param_grads(layer, li, dkv_rows, mem2, grads, d, mem_t_ps)
+def _decoder_layer_bwd(li, layer, t, dx, dkv_rows, kv, S, grads, mem2, mem_t_ps, valid, D):
+    """Backward of decoder layer li on the separate kernels: the gradient dx of its output -> that of its input."""
+    M, d = D.M, D.d
+    dx2 = _ffn_plain_bwd(grads, layer, t, dx, (layer.norm3, 3, "x2"), valid, D)
+    dz, dca = _out_proj_plain_bwd(grads, t, dx2, (layer.norm2, 2, "x1"), layer.multihead_attn.out_proj, "ca", valid, D)
+    dq = _cross_attn_bwd(li, t, dca, dkv_rows, kv, S, D)
+    # this layer's columns of the K/V-projection gradient are complete: its weight (and bias) gradient over
+    # all B * S memory rows joins this layer's group instead of waiting for the whole decoder stack
+    _kv_proj_param_grads(layer, li, dkv_rows, mem2, grads, d, mem_t_ps)
     dx1 = _lin_bwd(grads, dq.view(M, d), t["x1"].view(M, d), layer.multihead_attn.in_proj_weight,
                    layer.multihead_attn.in_proj_bias, w_rows=slice(0, d), dx=dz.view(M, d), acc=True, valid=valid)
-    dz, do1 = ops.layernorm_bwd(dx1.view(B, T, d), t["o1"], t["x"], _p(layer.norm1.weight), t["m1"], t["r1"],
-                                _g(grads, layer.norm1.weight), _g(grads, layer.norm1.bias), drop=t["d1"])
-    dsa = _lin_bwd(grads, do1.view(M, d), t["sa"].view(M, d), layer.self_attn.out_proj.weight,
-                   layer.self_attn.out_proj.bias, valid=valid)
-    dqkv = ops.attention_bwd_buffer((B, T, 3 * d), T, T, dh, dx.device)
-    ops.attention_heads_bwd(t["qkv"], t["qkv"], t["sa"], dsa.view(B, T, d), t["lse_s"], dqkv[:, :, :d],
-                            dqkv[:, :, d:2 * d], dqkv[:, :, 2 * d:], H, dh, T, T, 0, 1, 2, causal=True,
-                            drop=t["d_sa"])
-    dx0 = _lin_bwd(grads, dqkv.view(M, 3 * d), t["x"].view(M, d), layer.self_attn.in_proj_weight,
-                   layer.self_attn.in_proj_bias, dx=dz.view(M, d), acc=True, valid=valid).view(B, T, d)
+    dz, dsa = _out_proj_plain_bwd(grads, t, dx1, (layer.norm1, 1, "x"), layer.self_attn.out_proj, "sa", valid, D)
+    dqkv = _self_attn_bwd(t, dsa, "lse_s", "d_sa", True, D)
+    dx0 = _in_proj_bwd(grads, layer.self_attn, t, dqkv, dz, valid, D)[0]
     if ops.SIDE is not None:
         ops.SIDE.flush_group()          # this layer's weight gradients: one grouped launch
     return dx0
@@ -617,20 +625,19 @@ class BackwardPass:
 
 def _backward_phases(dec, tape, dscores, grads, want_image_grad=False, image_grad_sink=None):
     m = tape.misc
-    d, V, H = dec.emb_dim, dec.vocab_size, dec.num_heads
+    V = dec.vocab_size
     h, ee, fe = m["h"], m["ee"], m["fe"]
+    dims = _dims(dec, h)
+    B, L, M, d, H, _, dev = dims
     # frozen parameters (other than the word embedding, whose scatter is simply skipped) get a scratch
     # buffer so every kernel has somewhere to accumulate; the scratch is dropped afterwards
     grads = dict(grads)
     for prm in unique_parameters(dec):
         if id(prm) not in grads and prm is not dec.word_embedding.weight:
             grads[id(prm)] = torch.zeros_like(prm)
-    B, L, _ = h.shape
     P, K, Fn, S = m["P"], m["K"], m["Fn"], m["S"]
-    M = B * L
     Vx = dscores.shape[2]
     dsc2 = dscores.view(M, Vx)
-    dev = h.device
     pre = m.get("prezero") or {}
 
     def zeroed(name, like):
@@ -650,19 +657,15 @@ def _backward_phases(dec, tape, dscores, grads, want_image_grad=False, image_gra
     # (tests/test_packed_head_gpu.py), and packed rows fall into other 4-row MFMA groups than logical ones
     valid = pack if os.environ.get("ICK_NO_VALID_ROW_WGRAD", "0") in ("", "0") and not ops.is_deterministic() else None
     hv_t_ps = _rows_t_presplit(hv.view(M, d), pack) if _g(grads, dec.fc_vocab.weight) is not None else None
-    if pack is not None:
-        # M' rows of data gradient, scattered into the zeroed logical buffer: the padded positions stay exactly zero
-        if dhv0 is None or dhv0.shape != (M, d):
-            dhv0 = torch.zeros(M, d, device=dev, dtype=torch.float32)
-        dhv = _lin_bwd(grads, dsc2[:, :V], hv.view(M, d), dec.fc_vocab.weight, dec.fc_vocab.bias, dx=dhv0, acc=True,
-                       group_now=True, wt_ps=m.get("vocab_t_ps"), xt_ps=hv_t_ps, pack=pack).view(B, L, d)
-    elif dhv0 is not None and dhv0.shape == (M, d) and not ops.is_deterministic():
-        # split-K partial sums add into the buffer the forward pass's side stream zeroed
-        dhv = _lin_bwd(grads, dsc2[:, :V], hv.view(M, d), dec.fc_vocab.weight, dec.fc_vocab.bias, dx=dhv0, acc=True,
-                       group_now=True, wt_ps=m.get("vocab_t_ps"), xt_ps=hv_t_ps).view(B, L, d)
-    else:
-        dhv = _lin_bwd(grads, dsc2[:, :V], hv.view(M, d), dec.fc_vocab.weight, dec.fc_vocab.bias,
-                       group_now=True, wt_ps=m.get("vocab_t_ps"), xt_ps=hv_t_ps).view(B, L, d)
+    # The data gradient's target.  Packed head: M' rows of data gradient, scattered into a zeroed logical buffer (the padded
+    # positions stay exactly zero).  Else split-K partial sums add into the buffer the forward pass's side stream zeroed,
+    # where there is one (not in deterministic mode: no split-K there); without a target the GEMM makes its own output
+    if dhv0 is not None and (dhv0.shape != (M, d) or (pack is None and ops.is_deterministic())):
+        dhv0 = None
+    if dhv0 is None and pack is not None:
+        dhv0 = torch.zeros(M, d, device=dev, dtype=torch.float32)
+    dhv = _lin_bwd(grads, dsc2[:, :V], hv.view(M, d), dec.fc_vocab.weight, dec.fc_vocab.bias, dx=dhv0,
+                   acc=dhv0 is not None, group_now=True, wt_ps=m.get("vocab_t_ps"), xt_ps=hv_t_ps, pack=pack).view(B, L, d)
     if dec.has_facts:
         dh = ops.mul(dhv, m["gate"])
         dgate = ops.mul(dhv, h)
@@ -684,31 +687,29 @@ def _backward_phases(dec, tape, dscores, grads, want_image_grad=False, image_gra
     layers = list(dec.transformer_decoder.layers)
     nseg = 2 * len(layers)
     dkv_rows = ops.attention_bwd_buffer((B, S, nseg * d), L, S, d // H, dev)
-    dx = dh
     ops.stamp("bwd: head done")
+    # the packed transposed weights exist only when dec.chain_bwd_supported() holds, and that covers a hand-down of
+    # max(3, nseg) * d columns: pkb => the K/V projection's data gradient (nseg * d columns) fits the context encoders'
+    # first chain launch as well
     pkb = m.get("pkb")
     mem_t_ps = _memory_t_presplit(m, B, S, d)
-    if pkb is not None:
-        state = (dh.view(M, d), None, None)
-        for li in reversed(range(len(layers))):
-            state = _decoder_layer_bwd_chain(dec, li, layers[li], tape.dec_layers[li], state, dkv_rows, m["kv"], S,
-                                             grads, pkb, mem2=m["mem"].view(B * S, d), mem_t_ps=mem_t_ps,
-                                             valid=valid)
-            ops.stamp("bwd: decoder layer %d done" % li)
-        dx = state[0]
-    else:
-        for li in reversed(range(len(layers))):
-            dx = _decoder_layer_bwd(dec, li, layers[li], tape.dec_layers[li], dx, dkv_rows, m["kv"], S, grads,
-                                    mem2=m["mem"].view(B * S, d), mem_t_ps=mem_t_ps, valid=valid)
-            ops.stamp("bwd: decoder layer %d done" % li)
+    mem2 = m["mem"].view(B * S, d)
+    dx, state = dh, (dh.view(M, d), None, None)
+    for li in reversed(range(len(layers))):
+        if pkb is not None:
+            state = _decoder_layer_bwd_chain(li, layers[li], tape.dec_layers[li], state, dkv_rows, m["kv"], S, grads,
+                                             pkb, mem2, mem_t_ps, valid, dims)
+            dx = state[0]
+        else:
+            dx = _decoder_layer_bwd(li, layers[li], tape.dec_layers[li], dx, dkv_rows, m["kv"], S, grads, mem2,
+                                    mem_t_ps, valid, dims)
+        ops.stamp("bwd: decoder layer %d done" % li)
     yield    # ---- end of the early phase: every gradient of early_parameters() has been enqueued
     # ---- cross K/V projection: the weight gradients went out with the decoder layers; data gradient for the
     # context rows only (the image rows' gradient would be Encoder.conv1's, which the reference never uses)
     nctx = K + Fn
     dkv_ctx = dkv_rows[:, P:]                       # (B, nctx, 2 * layers * d) view of the K/V gradient rows
-    fuse_ctx = pkb is not None and ops.rowchain_bwd_supported(nseg * d, d, 0)
-    dctx = None
-    if not fuse_ctx:
+    if pkb is None:
         # K = 2 * layers * d = 1800 over only B * nctx x d outputs: split the reduction (40 -> ~15 us with the fill)
         ksplit = max(1, min(8, (nseg * d) // 450)) if B * nctx * d <= 1280 * 512 else 1
         if ops.is_deterministic():
@@ -735,16 +736,18 @@ def _backward_phases(dec, tape, dscores, grads, want_image_grad=False, image_gra
     # ---- context encoders.  With the row chains the data gradient of the K/V projection for the context rows rides on
     # the first launch of each context encoder's backward (its rows are read straight out of the K/V gradient buffer)
     ops.stamp("bwd: context gradient ready")
-    dee_enc = _context_encoder_bwd(dec, dec.transformer_encoder_entities, tape.enc_layers["entities"],
-                                   None if fuse_ctx else dctx[:, :K].contiguous(), grads, pkb=pkb, tag="e",
-                                   g_first=(dkv_ctx[:, :K], pkb[("kv", "T")]) if fuse_ctx else None)
+
+    def context_encoder_bwd(stack, name, tag, rows):
+        if pkb is not None:
+            return _context_encoder_bwd_chain(dec, stack, tape.enc_layers[name], grads, pkb, tag, dkv_ctx[:, rows],
+                                              pkb[("kv", "T")])
+        return _context_encoder_bwd(dec, stack, tape.enc_layers[name], dctx[:, rows].contiguous(), grads)
+
+    dee_enc = context_encoder_bwd(dec.transformer_encoder_entities, "entities", "e", slice(0, K))
     ops.stamp("bwd: entity context encoder done")
     dee += dee_enc
     if dec.has_facts:
-        dfe_enc = _context_encoder_bwd(dec, dec.transformer_encoder_facts, tape.enc_layers["facts"],
-                                       None if fuse_ctx else dctx[:, K:].contiguous(), grads, pkb=pkb, tag="f",
-                                       g_first=(dkv_ctx[:, K:], pkb[("kv", "T")]) if fuse_ctx else None)
-        dfe += dfe_enc
+        dfe += context_encoder_bwd(dec.transformer_encoder_facts, "facts", "f", slice(K, None))
     # ---- caption embedding, fact encoder, entity encoder
     gword = _g(grads, dec.word_embedding.weight)
     ops.caption_embed_bwd(dx, m["captions"], m["masks"], gword, dee, dfe, V, dec.word_map["<pad>"], math.sqrt(d),
