@@ -9,7 +9,9 @@
 //   g = clamp(g * gscale [/ *gscale_den], -clip, clip);  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // (default betas / eps, no weight decay, no amsgrad.)  The update is written once: adam_hyper() is the prologue, adam1()
-// the arithmetic of one element.  Three kernels address the bucket differently around them:
+// the arithmetic of one element.  kEma (ick_adam_ema[_derive]): the lane that holds the new p also keeps
+// an exponential moving average of it in a fourth array, e += (1 - d_t) (p - e) (ema1()), two more 16-byte streams in the
+// same pass; kEma = false is the code without it.  Three kernels address the bucket differently around them:
 //   adam_clamp_kernel       one float per lane and trip: tails, short and unaligned buckets;
 //   adam_clamp_vec4_kernel  one float4 per lane and trip, seven 16-byte streams: the aligned bulk of a flat bucket;
 //   adam_derive_kernel      one workgroup = one block of the caller's cover of the bucket (include/ick_amd.h,
@@ -28,18 +30,28 @@ namespace ick {
 namespace {
 
 struct AdamHyper {
-    float gscale, clip, b1, b2, c1, c2, eps, step, bc2_sqrt, coef;
+    float gscale, clip, b1, b2, c1, c2, eps, step, bc2_sqrt, coef, w;
+};
+
+// The moving average's operands (kEma): the array, the device word that holds the decay, the warmup flag.  Passed to
+// every instantiation so that the kernels keep one signature; the ones without kEma never read it (nor AdamHyper::w):
+// their instruction stream and register counts are those from before the flag, their kernarg segment is 24 bytes longer.
+struct AdamEma {
+    float* e;
+    const float* decay;
+    int warmup;
 };
 
 // The prologue of every Adam kernel.  false: no token contributed to the (global) batch, which then has no mean loss --
 // the kernel leaves parameters, moments, images and the rate word alone instead of spreading 0 * inf = NaN over every
 // weight.  kOpt (ick_adam_opt[_derive]): the step's rate comes from the base rate word and the schedule
 // instead of the literal, h.coef is the global-norm clip's coefficient, and workgroup 0 leaves the rate it used in
-// words[4].
-template <bool kOpt>
+// words[4].  kEma: h.w = 1 - d_t, the weight of the new parameter in the moving average, with d_t = *decay or, with the
+// warmup flag, min(*decay, (1 + t) / (10 + t)) on the step t of the bias correction.
+template <bool kOpt, bool kEma>
 __device__ __forceinline__ bool adam_hyper(AdamHyper& h, float gscale, float clip, float lr, float b1, float b2, float eps,
                                            int step0, const uint32_t* step_ptr, const float* __restrict__ gscale_den,
-                                           float* words, const ick_lr_schedule& sched) {
+                                           float* words, const ick_lr_schedule& sched, const AdamEma& ema) {
     if (gscale_den) {
         if (!(gscale_den[0] > 0.f)) return false;
         gscale = gscale / gscale_den[0];
@@ -54,6 +66,12 @@ __device__ __forceinline__ bool adam_hyper(AdamHyper& h, float gscale, float cli
         if (blockIdx.x == 0 && threadIdx.x == 0) words[kWordLrNow] = lr;
     }
     h.step = lr / bc1;
+    h.w = 0.f;
+    if (kEma) {
+        float d = ema.decay[0];
+        if (ema.warmup) d = fminf(d, (1.f + t) / (10.f + t));
+        h.w = 1.f - d;
+    }
     h.gscale = gscale; h.clip = clip; h.b1 = b1; h.b2 = b2; h.c1 = 1.f - b1; h.c2 = 1.f - b2; h.eps = eps;
     return true;
 }
@@ -72,6 +90,19 @@ __device__ __forceinline__ void adam1(const AdamHyper& h, float& p, float& g, fl
     p -= h.step * m / (sqrtf(v) / h.bc2_sqrt + h.eps);
 }
 
+// The moving average of one element, written once like adam1: the difference, the product and the sum stay apart.
+__device__ __forceinline__ void ema1(const AdamHyper& h, float& e, float p) {
+    const float d = p - e;
+    e = e + h.w * d;
+}
+
+__device__ __forceinline__ void ema4(const AdamHyper& h, float4& e, const float4& p) {
+    ema1(h, e.x, p.x);
+    ema1(h, e.y, p.y);
+    ema1(h, e.z, p.z);
+    ema1(h, e.w, p.w);
+}
+
 template <bool kOpt>
 __device__ __forceinline__ void adam4(const AdamHyper& h, float4& p, float4& g, float4& m, float4& v) {
     adam1<kOpt>(h, p.x, g.x, m.x, v.x);
@@ -80,57 +111,62 @@ __device__ __forceinline__ void adam4(const AdamHyper& h, float4& p, float4& g, 
     adam1<kOpt>(h, p.w, g.w, m.w, v.w);
 }
 
-template <bool kOpt>
+template <bool kOpt, bool kEma>
 __global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                          float gscale, float clip, float lr, float b1, float b2,
                                                          float eps, int step0, const uint32_t* step_ptr,
                                                          const float* __restrict__ gscale_den, float* words,
-                                                         ick_lr_schedule sched) {
+                                                         ick_lr_schedule sched, AdamEma ema) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     AdamHyper h;
-    if (!adam_hyper<kOpt>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched)) return;
+    if (!adam_hyper<kOpt, kEma>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema)) return;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        float gi = g[i], mi = m[i], vi = v[i], pi = p[i];
+        float gi = g[i], mi = m[i], vi = v[i], pi = p[i], ei = 0.f;
+        if (kEma) ei = ema.e[i];
         adam1<kOpt>(h, pi, gi, mi, vi);
         g[i] = gi; m[i] = mi; v[i] = vi; p[i] = pi;
+        if (kEma) { ema1(h, ei, pi); ema.e[i] = ei; }
     }
 }
 
 // The same update on float4: seven 16-byte streams per lane (the scalar form reaches 0.66 of the HBM rate, 320 MB per
 // cfg2 step).  n4 = n / 4 elements of float4; the launcher sends a tail of n % 4 to the scalar kernel.
-template <bool kOpt>
+template <bool kOpt, bool kEma>
 __global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict__ p, float4* __restrict__ g,
                                                               float4* __restrict__ m, float4* __restrict__ v, int64_t n4,
                                                               float gscale, float clip, float lr, float b1, float b2,
                                                               float eps, int step0, const uint32_t* step_ptr,
                                                               const float* __restrict__ gscale_den, float* words,
-                                                              ick_lr_schedule sched) {
+                                                              ick_lr_schedule sched, AdamEma ema) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     AdamHyper h;
-    if (!adam_hyper<kOpt>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched)) return;
+    if (!adam_hyper<kOpt, kEma>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema)) return;
+    float4* __restrict__ e = reinterpret_cast<float4*>(ema.e);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        float4 gi = g[i], mi = m[i], vi = v[i], pi = p[i];
+        float4 gi = g[i], mi = m[i], vi = v[i], pi = p[i], ei;
+        if (kEma) ei = e[i];
         adam4<kOpt>(h, pi, gi, mi, vi);
         g[i] = gi; m[i] = mi; v[i] = vi; p[i] = pi;
+        if (kEma) { ema4(h, ei, pi); e[i] = ei; }
     }
 }
 
 constexpr int kT = 64;        // tile edge
 constexpr int kLd = 68;       // LDS row stride of the tile (16-byte aligned rows, 4 banks of skew per row)
 
-template <bool kOpt>
+template <bool kOpt, bool kEma>
 __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p, float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v,
                                                           const ick_adam_item* __restrict__ items,
                                                           const ick_adam_block* __restrict__ blocks, float gscale,
                                                           float clip, float lr, float b1, float b2, float eps, int step0,
                                                           const uint32_t* step_ptr, const float* __restrict__ gscale_den,
-                                                          float* words, ick_lr_schedule sched) {
+                                                          float* words, ick_lr_schedule sched, AdamEma ema) {
     __shared__ __attribute__((aligned(16))) float tile[kT * kLd];
     const ick_adam_block blk = blocks[blockIdx.x];
     AdamHyper h;
-    if (!adam_hyper<kOpt>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched)) return;
+    if (!adam_hyper<kOpt, kEma>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema)) return;
     const int tid = threadIdx.x;
 
     if (blk.item < 0) {
@@ -139,11 +175,15 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
         float4* g4 = reinterpret_cast<float4*>(g) + blk.off4;
         float4* m4 = reinterpret_cast<float4*>(m) + blk.off4;
         float4* v4 = reinterpret_cast<float4*>(v) + blk.off4;
-        float4 pi[4], gi[4], mi[4], vi[4];
+        float4* e4 = reinterpret_cast<float4*>(ema.e) + blk.off4;
+        float4 pi[4], gi[4], mi[4], vi[4], ei[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int j = tid + 256 * i;
-            if (j < blk.cnt4) { gi[i] = g4[j]; mi[i] = m4[j]; vi[i] = v4[j]; pi[i] = p4[j]; }
+            if (j < blk.cnt4) {
+                gi[i] = g4[j]; mi[i] = m4[j]; vi[i] = v4[j]; pi[i] = p4[j];
+                if (kEma) ei[i] = e4[j];
+            }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -151,6 +191,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
             if (j < blk.cnt4) {
                 adam4<kOpt>(h, pi[i], gi[i], mi[i], vi[i]);
                 g4[j] = gi[i]; m4[j] = mi[i]; v4[j] = vi[i]; p4[j] = pi[i];
+                if (kEma) { ema4(h, ei[i], pi[i]); e4[j] = ei[i]; }
                 if (blk.copy) reinterpret_cast<float4*>(blk.copy)[j] = pi[i];
             }
         }
@@ -162,7 +203,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
     const int n0 = blk.tn * kT, k0 = blk.tk * kT;
     const int K = it.K;
     {
-        float4 pi[4], gi[4], mi[4], vi[4];
+        float4 pi[4], gi[4], mi[4], vi[4], ei[4];
         int64_t at[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -175,6 +216,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
                 mi[i] = *reinterpret_cast<const float4*>(m + at[i]);
                 vi[i] = *reinterpret_cast<const float4*>(v + at[i]);
                 pi[i] = *reinterpret_cast<const float4*>(p + at[i]);
+                if (kEma) ei[i] = *reinterpret_cast<const float4*>(ema.e + at[i]);
             }
         }
 #pragma unroll
@@ -188,6 +230,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
                 *reinterpret_cast<float4*>(m + at[i]) = mi[i];
                 *reinterpret_cast<float4*>(v + at[i]) = vi[i];
                 *reinterpret_cast<float4*>(p + at[i]) = pi[i];
+                if (kEma) { ema4(h, ei[i], pi[i]); *reinterpret_cast<float4*>(ema.e + at[i]) = ei[i]; }
                 out = pi[i];
                 if (it.copy) *reinterpret_cast<float4*>(it.copy + (int64_t)(n0 + row) * it.copy_ld + k0 + 4 * c4) = pi[i];
             }
@@ -287,72 +330,78 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
 using namespace ick;
 
 // What every entry asks of its arguments (count: the floats of a flat bucket, the blocks of a cover); al16: whether all
-// four arrays lie on 16 bytes, which the float4 kernels need.
+// the arrays lie on 16 bytes, which the float4 kernels need.  kEma: the moving average is one more array, and its decay
+// word must be there.
+template <bool kEma>
 static int adam_args(const float* p, const float* g, const float* m, const float* v, int64_t count, int32_t step,
-                     const uint32_t* step_ptr, bool& al16) {
+                     const uint32_t* step_ptr, const AdamEma& ema, bool& al16) {
     ICK_CHECK_ARG(p && g && m && v && count > 0 && (step >= 1 || step_ptr != nullptr));
+    if (kEma) ICK_CHECK_ARG(ema.e != nullptr && ema.decay != nullptr);
     al16 = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-             reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+             reinterpret_cast<uintptr_t>(v) | (kEma ? reinterpret_cast<uintptr_t>(ema.e) : 0)) & 15) == 0;
     return ICK_OK;
 }
 
-// ick_adam_clamp and ick_adam_opt: the float4 kernel over the aligned bulk, the scalar kernel over the rest
-template <bool kOpt>
+// ick_adam_clamp, ick_adam_opt and ick_adam_ema: the float4 kernel over the aligned bulk, the scalar kernel over the rest
+template <bool kOpt, bool kEma>
 static int launch_adam(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr, float* words,
                        ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                       const float* gscale_den, void* stream) {
+                       const float* gscale_den, AdamEma ema, void* stream) {
     bool al16;
-    if (int rc = adam_args(p, g, m, v, n, step, step_ptr, al16)) return rc;
+    if (int rc = adam_args<kEma>(p, g, m, v, n, step, step_ptr, ema, al16)) return rc;
+    if (kEma && (reinterpret_cast<uintptr_t>(ema.e) & 3)) return ICK_EALIGN;
     int64_t done = 0;
     if (n >= 4096 && al16) {
         const int64_t n4 = n / 4;
-        hipLaunchKernelGGL(adam_clamp_vec4_kernel<kOpt>, dim3((int)std::min<int64_t>(ceil_div(n4, 256), 4096)), dim3(256),
-                           0, (hipStream_t)stream, reinterpret_cast<float4*>(p), reinterpret_cast<float4*>(g),
+        hipLaunchKernelGGL((adam_clamp_vec4_kernel<kOpt, kEma>), dim3((int)std::min<int64_t>(ceil_div(n4, 256), 4096)),
+                           dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(p), reinterpret_cast<float4*>(g),
                            reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), n4, gscale, clip, lr, beta1, beta2,
-                           eps, step, step_ptr, gscale_den, words, sched);
+                           eps, step, step_ptr, gscale_den, words, sched, ema);
         done = 4 * n4;
         if (done == n) ICK_LAUNCH_RET();
     }
-    hipLaunchKernelGGL(adam_clamp_kernel<kOpt>, dim3((int)std::min<int64_t>(ceil_div(n - done, 256), 4096)), dim3(256), 0,
-                       (hipStream_t)stream, p + done, g + done, m + done, v + done, n - done, gscale, clip, lr, beta1,
-                       beta2, eps, step, step_ptr, gscale_den, words, sched);
+    if (kEma) ema.e += done;
+    hipLaunchKernelGGL((adam_clamp_kernel<kOpt, kEma>), dim3((int)std::min<int64_t>(ceil_div(n - done, 256), 4096)),
+                       dim3(256), 0, (hipStream_t)stream, p + done, g + done, m + done, v + done, n - done, gscale, clip, lr,
+                       beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema);
     ICK_LAUNCH_RET();
 }
 
-template <bool kOpt>
+template <bool kOpt, bool kEma>
 static int launch_adam_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
                               const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
                               float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                              const uint32_t* step_ptr, const float* gscale_den, void* stream) {
+                              const uint32_t* step_ptr, const float* gscale_den, AdamEma ema, void* stream) {
     bool al16;
-    if (int rc = adam_args(p, g, m, v, blocks ? n_blocks : 0, step, step_ptr, al16)) return rc;
+    if (int rc = adam_args<kEma>(p, g, m, v, blocks ? n_blocks : 0, step, step_ptr, ema, al16)) return rc;
     if (!al16) return ICK_EALIGN;
-    hipLaunchKernelGGL(adam_derive_kernel<kOpt>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, items,
-                       blocks, gscale, clip, lr, beta1, beta2, eps, step, step_ptr, gscale_den, words, sched);
+    hipLaunchKernelGGL((adam_derive_kernel<kOpt, kEma>), dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       items, blocks, gscale, clip, lr, beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema);
     ICK_LAUNCH_RET();
 }
 
 extern "C" int ick_adam_clamp(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr,
                               float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
                               const float* gscale_den, void* stream) {
-    return launch_adam<false>(p, g, m, v, n, gscale, clip, lr, nullptr, ick_lr_schedule{}, beta1, beta2, eps, step,
-                              step_ptr, gscale_den, stream);
+    return launch_adam<false, false>(p, g, m, v, n, gscale, clip, lr, nullptr, ick_lr_schedule{}, beta1, beta2, eps, step,
+                                     step_ptr, gscale_den, AdamEma{}, stream);
 }
 
 extern "C" int ick_adam_opt(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float* words,
                             ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
                             const uint32_t* step_ptr, const float* gscale_den, void* stream) {
     ICK_CHECK_ARG(words != nullptr && lr_schedule_ok(sched));
-    return launch_adam<true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step, step_ptr,
-                             gscale_den, stream);
+    return launch_adam<true, false>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step, step_ptr,
+                                    gscale_den, AdamEma{}, stream);
 }
 
 extern "C" int ick_adam_clamp_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
                                      const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
                                      float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
                                      const float* gscale_den, void* stream) {
-    return launch_adam_derive<false>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr, nullptr, ick_lr_schedule{},
-                                     beta1, beta2, eps, step, step_ptr, gscale_den, stream);
+    return launch_adam_derive<false, false>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr, nullptr,
+                                            ick_lr_schedule{}, beta1, beta2, eps, step, step_ptr, gscale_den, AdamEma{},
+                                            stream);
 }
 
 extern "C" int ick_adam_opt_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
@@ -360,6 +409,37 @@ extern "C" int ick_adam_opt_derive(float* p, float* g, float* m, float* v, const
                                    ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
                                    const uint32_t* step_ptr, const float* gscale_den, void* stream) {
     ICK_CHECK_ARG(words != nullptr && lr_schedule_ok(sched));
-    return launch_adam_derive<true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words, sched, beta1, beta2,
-                                    eps, step, step_ptr, gscale_den, stream);
+    return launch_adam_derive<true, false>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words, sched, beta1,
+                                           beta2, eps, step, step_ptr, gscale_den, AdamEma{}, stream);
 }
+
+// The entries with the moving average: words == NULL takes the plain instantiation and the host rate lr, else the
+// optimizer words' one (lr is then not read).
+extern "C" int ick_adam_ema(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip, float lr,
+                            float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                            const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
+                            void* stream) {
+    const AdamEma ema{e, ema_decay, ema_warmup != 0};
+    if (!words)
+        return launch_adam<false, true>(p, g, m, v, n, gscale, clip, lr, nullptr, ick_lr_schedule{}, beta1, beta2, eps,
+                                        step, step_ptr, gscale_den, ema, stream);
+    ICK_CHECK_ARG(lr_schedule_ok(sched));
+    return launch_adam<true, true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step, step_ptr,
+                                   gscale_den, ema, stream);
+}
+
+extern "C" int ick_adam_ema_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
+                                   const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
+                                   float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                                   const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay,
+                                   int32_t ema_warmup, void* stream) {
+    const AdamEma ema{e, ema_decay, ema_warmup != 0};
+    if (!words)
+        return launch_adam_derive<false, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr, nullptr,
+                                               ick_lr_schedule{}, beta1, beta2, eps, step, step_ptr, gscale_den, ema,
+                                               stream);
+    ICK_CHECK_ARG(lr_schedule_ok(sched));
+    return launch_adam_derive<true, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words, sched, beta1,
+                                          beta2, eps, step, step_ptr, gscale_den, ema, stream);
+}
+

@@ -1574,10 +1574,11 @@ def conv1_wgrad(d_img, feats, dw, db, scratch=None):
 
 
 _ADAM_ENTRIES = ("ick_adam_clamp", "ick_adam_opt", "ick_adam_clamp_derive", "ick_adam_opt_derive")
+_ADAM_EMA_ENTRIES = ("ick_adam_ema", "ick_adam_ema_derive")      # (both rates: words == NULL selects the host float)
 
 
 def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=None, clip=5.0, gscale=1.0, beta1=0.9,
-                beta2=0.999, eps=1e-8, step_tensor=None, gscale_den=None):
+                beta2=0.999, eps=1e-8, step_tensor=None, gscale_den=None, ema=None, ema_decay_word=None, ema_warmup=False):
     """g = clamp(g * gscale (/ the device scalar gscale_den, if given), +-clip), then Adam's update of p, m, v; step (+ the
     uint32 device counter step_tensor, if given) is Adam's 1-based step count.  Nothing is written while gscale_den is
     given and not > 0.
@@ -1589,20 +1590,40 @@ def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=N
     cover: None for the p.numel() floats of a flat bucket; otherwise the owner of a cover of the WHOLE bucket
     (weights.DerivedWeights: items_dev / blocks_dev, device arrays of ick_adam_item / ick_adam_block, n_blocks, and nbytes,
     the launch's algorithmic bytes for profiling.py), read at call time: the same pass then also writes the re-laid-out
-    copies of the updated weights (the *_derive entries)."""
+    copies of the updated weights (the *_derive entries).
+    ema: None, or the exponential moving average of p, a float32 device tensor laid out like p, updated in the same pass
+    (ick_adam_ema[_derive]): e += (1 - d) * (p_new - e) with the decay d read from ema_decay_word, a one-float tensor ON THE
+    DEVICE (a host scalar is refused: it would be baked into a captured launch); ema_warmup: d = min(d, (1 + t) / (10 + t))
+    on the step count t.  p, g, m, v get the bits they get without ema."""
     if (lr is None) == (words is None):
         raise L.IckError("adam_update needs exactly one of lr (a host float) and words (the optimizer words)")
     if words is None and schedule is not None:
         raise L.IckError("adam_update: a schedule shapes the rate in the optimizer words; give words, not lr")
-    name = _ADAM_ENTRIES[(words is not None) + 2 * (cover is not None)]
-    rate = (lr,) if words is None else (_p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule))
+    if ema is None and (ema_decay_word is not None or ema_warmup):
+        raise L.IckError("adam_update: ema_decay_word / ema_warmup shape a moving average; give ema= as well")
+    if ema is None:
+        name = _ADAM_ENTRIES[(words is not None) + 2 * (cover is not None)]
+        rate = (lr,) if words is None else (_p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule))
+        avg, tail = (), ()
+    else:
+        for what, t, least in (("ema", ema, p.numel()), ("ema_decay_word", ema_decay_word, 1)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or \
+                    t.numel() < least:
+                raise L.IckError("adam_update needs %s as a contiguous float32 device tensor of at least %d element(s)"
+                                 % (what, least))
+        if ema.data_ptr() % (4 if cover is None else 16):
+            raise L.IckError("adam_update: ema must lie on %d bytes" % (4 if cover is None else 16))
+        name = _ADAM_EMA_ENTRIES[cover is not None]
+        rate = (0.0, _p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule)) if words is not None else \
+            (lr, None, L.LrSchedule())
+        avg, tail = (_p(ema),), (_p(ema_decay_word), int(bool(ema_warmup)))
     if cover is None:
         over = (p.numel(),)
     else:
-        L.ADAM_DERIVE_BYTES = cover.nbytes
+        L.ADAM_DERIVE_BYTES, L.ADAM_DERIVE_FLOATS = cover.nbytes, p.numel()     # (profiling.py's byte model)
         over = (_p(cover.items_dev), _p(cover.blocks_dev), cover.n_blocks)
-    L.check(getattr(L.load(), name)(_p(p), _p(g), _p(m), _p(v), *over, gscale, clip, *rate, beta1, beta2, eps, step,
-                                    _p(step_tensor), _p(gscale_den), _stream()), name)
+    L.check(getattr(L.load(), name)(_p(p), _p(g), _p(m), _p(v), *avg, *over, gscale, clip, *rate, beta1, beta2, eps, step,
+                                    _p(step_tensor), _p(gscale_den), *tail, _stream()), name)
 
 
 def counter_add(counter, inc=1):

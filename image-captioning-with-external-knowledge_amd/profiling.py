@@ -134,6 +134,12 @@ def classify(name, args):
     if name in ("ick_adam_clamp_derive", "ick_adam_opt_derive"):
         # the seven streams of the update + every image of the updated weights (packed, transposed, bf16 planes)
         return "clamp + Adam + re-laid-out weight copies", float(getattr(L, "ADAM_DERIVE_BYTES", 0)), "byte"
+    if name == "ick_adam_ema":
+        # the moving average is read and written in the same pass: nine streams
+        return "clamp + Adam + EMA", 4.0 * args[5] * 9, "byte"
+    if name == "ick_adam_ema_derive":
+        return ("clamp + Adam + EMA + re-laid-out weight copies",
+                float(getattr(L, "ADAM_DERIVE_BYTES", 0)) + 8.0 * getattr(L, "ADAM_DERIVE_FLOATS", 0), "byte")
     if name == "ick_grad_sqnorm":
         # one read of the gradient bucket (the partials and the words are a few KiB)
         return "gradient norm (global-norm clip)", 4.0 * args[1], "byte"

@@ -20,7 +20,13 @@ checkpointing are unchanged.  `scst_reward` mixes BLEU-n / ROUGE-L into that rew
 batch's caption rows on the device (metrics.CaptionMetrics: BLEU-1..4, ROUGE-L, pointer precision / recall, and CIDEr-D
 when a CiderD exists); the totals stay on the device until the pass ends.  `val_geo_metric=<dict>` (with it): the same
 captions' geo references are counted on the device (geo_metric.GeoReferenceMetric) and their Jensen-Shannon distances
-join the dict as "geo_js"."""
+join the dict as "geo_js".
+
+`ema_decay=<float in [0, 1)>`: an exponential moving average of the trained parameters (fused: kept by the optimizer
+launch, TrainStep(ema_decay=); unfused: TorchEma, a lerp_ after optimizer.step()); with `ema_validate` the validation pass
+-- and so early stopping and BEST_ -- runs on the averaged weights, and the checkpoint carries the average under
+"decoder_ema" (utils.load_ema_weights copies it into a loaded checkpoint's modules)."""
+import contextlib
 import json
 import math
 import os
@@ -39,7 +45,7 @@ from .datasets import CaptionDataset
 from .geo_metric import GeoReferenceMetric
 from .metrics import CaptionMetrics
 from .scst import SelfCriticalStep
-from .training import TrainStep, check_lr_schedule, check_max_grad_norm, lr_at
+from .training import TrainStep, check_ema_decay, check_lr_schedule, check_max_grad_norm, ema_decay_at, lr_at
 
 
 @dataclass
@@ -109,6 +115,20 @@ class Config:
                                                        # seed=; GeoReferenceMetric.constructor_data() makes one): with
                                                        # val_caption_metrics the decoded captions' geo references are
                                                        # counted too, "geo_js" in that dict; None: off
+    ema_decay: object = None                           # float in [0, 1): keep an exponential moving average of the trained
+                                                       # parameters (fused: inside the optimizer launch,
+                                                       # TrainStep(ema_decay=); unfused: lerp_ after optimizer.step()); the
+                                                       # checkpoint then carries it under "decoder_ema"
+                                                       # (utils.load_ema_weights); None: off
+    ema_warmup: bool = False                           # the decay of step t is min(ema_decay, (1 + t) / (10 + t))
+    ema_validate: bool = True                          # with ema_decay: validate (early stopping, BEST_) on the averaged
+                                                       # weights instead of the raw ones
+
+    def __post_init__(self):
+        try:
+            check_ema_decay(self.ema_decay)
+        except RuntimeError as e:
+            raise ValueError(str(e))
 
 
 def _batch_to_device(batch, device, has_facts):
@@ -271,7 +291,58 @@ def packed_loss(criterion, scores, caps_sorted, decode_lengths):
     return criterion(s, t)
 
 
-def train(loader, encoder, decoder, criterion, decoder_optimizer, step, epoch, cfg, device, encoder_optimizer=None):
+class TorchEma:
+    """The unfused path's moving average of the trained parameters: the definition TrainStep(ema_decay=) follows, as a
+    plain lerp_ per parameter after optimizer.step().  The same state layout as TrainStep.ema_state_dict(): "params" for
+    the decoder optimizer's parameters in its order, "encoder_params" for the encoder optimizer's (fine_tune_encoder)."""
+
+    def __init__(self, decay, warmup, decoder_optimizer, encoder_optimizer=None):
+        self.decay, self.warmup = check_ema_decay(decay), bool(warmup)
+        groups = lambda opt: [p for g in opt.param_groups for p in g["params"]] if opt is not None else []     # noqa: E731
+        self.params, self.enc_params = groups(decoder_optimizer), groups(encoder_optimizer)
+        self.avg = [p.detach().clone() for p in self.params + self.enc_params]
+
+    def update(self, t):
+        """After the t-th (1-based) optimizer step."""
+        w = 1.0 - ema_decay_at(t, self.decay, self.warmup)
+        with torch.no_grad():
+            for e, p in zip(self.avg, self.params + self.enc_params):
+                e.lerp_(p.detach(), w)
+
+    def state_dict(self):
+        n = len(self.params)
+        sd = {"decay": self.decay, "warmup": self.warmup, "params": [e.clone() for e in self.avg[:n]]}
+        if self.enc_params:
+            sd["encoder_params"] = [e.clone() for e in self.avg[n:]]
+        return sd
+
+    def load_state_dict(self, sd):
+        theirs = list(sd["params"]) + list(sd.get("encoder_params", ()))
+        if len(sd["params"]) != len(self.params) or len(theirs) != len(self.avg) or \
+                any(tuple(t.shape) != tuple(e.shape) for t, e in zip(theirs, self.avg)):
+            raise ValueError("the checkpoint's moving average does not fit the trained parameters")
+        with torch.no_grad():
+            for e, t in zip(self.avg, theirs):
+                e.copy_(t)
+
+    @contextlib.contextmanager
+    def weights(self):
+        """Inside: the parameters hold the averages (exchanged, and exchanged back on the way out)."""
+        def exchange():
+            with torch.no_grad():
+                for e, p in zip(self.avg, self.params + self.enc_params):
+                    t = p.detach().clone()
+                    p.copy_(e)
+                    e.copy_(t)
+        exchange()
+        try:
+            yield self
+        finally:
+            exchange()
+
+
+def train(loader, encoder, decoder, criterion, decoder_optimizer, step, epoch, cfg, device, encoder_optimizer=None,
+          ema=None):
     decoder.train()
     encoder.train()
     batch_time, losses = ut.AverageMeter(), ut.AverageMeter()
@@ -314,6 +385,8 @@ def train(loader, encoder, decoder, criterion, decoder_optimizer, step, epoch, c
             decoder_optimizer.step()
             if encoder_optimizer is not None:
                 encoder_optimizer.step()
+            if ema is not None:
+                ema.update(_optimizer_steps(decoder_optimizer))
             loss = loss_t.item()
         losses.update(loss, n_tok)
         batch_time.update(time.time() - start)
@@ -627,7 +700,8 @@ def main(cfg=None):
                          # the pipelined loop lets step i's optimizer update run at the head of step i + 1's graph beside
                          # Encoder.conv1; _train_fused_pipelined() flushes the last one of an epoch
                          lazy_update=bool(pipelined), label_smoothing=cfg.label_smoothing,
-                         max_grad_norm=cfg.max_grad_norm, lr_schedule=cfg.lr_schedule)
+                         max_grad_norm=cfg.max_grad_norm, lr_schedule=cfg.lr_schedule, ema_decay=cfg.ema_decay,
+                         ema_warmup=cfg.ema_warmup)
         if decoder_optimizer is not None:
             # resume: Adam moments, step count (bias correction + dropout stream position) and the decayed lr come
             # back from the pickled optimizer (ours or one written by the reference, geo-aware/utils.py:32-46)
@@ -640,6 +714,16 @@ def main(cfg=None):
         dp.broadcast_module_state([encoder, decoder], _bucket_range(step))
     elif decoder_optimizer is None:
         decoder_optimizer = torch.optim.Adam([p for p in decoder.parameters() if p.requires_grad], lr=cfg.decoder_lr)
+    # the moving average: the fused step keeps its own; the unfused path's is a lerp_ after optimizer.step().  A resumed
+    # run takes it from the checkpoint (a checkpoint without one: the average starts at the loaded weights).
+    ema = None
+    if cfg.ema_decay is not None:
+        if step is None:
+            ema = TorchEma(cfg.ema_decay, cfg.ema_warmup, decoder_optimizer, encoder_optimizer)
+        ema_ck = ck.get("decoder_ema") if cfg.checkpoint and not cfg.zero_out_epochs_since_improvement else None
+        if ema_ck is not None:
+            (step.load_ema_state_dict if step is not None else ema.load_state_dict)(
+                dict(ema_ck, decay=cfg.ema_decay, warmup=cfg.ema_warmup))
     if step is None:
         check_max_grad_norm(cfg.max_grad_norm)
         check_lr_schedule(cfg.lr_schedule)
@@ -683,14 +767,18 @@ def main(cfg=None):
             tr = _train_scst(loaders["TRAIN"], encoder, sc, epoch, cfg, device, decoder.has_facts)
         else:
             tr = train(loaders["TRAIN"], encoder, decoder, criterion, decoder_optimizer, step, epoch, cfg, device,
-                       encoder_optimizer)
+                       encoder_optimizer, ema)
         if cfg.max_grad_norm is not None:
             # one read per epoch: the norm of the last update (the fused step keeps it in a device word)
             norm = float(step.grad_norm.item() if step is not None else STATS.get("last_grad_norm", float("nan")))
             STATS["last_grad_norm"] = norm
             if rank == 0:
                 print("Epoch: [%d]\tgradient norm of the last step %.4f (max_grad_norm %g)" % (epoch, norm, cfg.max_grad_norm))
-        last_loss = validate(loaders["VAL"], encoder, decoder, val_criterion, cfg, device, cider=cider)   # identical on every rank
+        averaged = contextlib.nullcontext()
+        if cfg.ema_decay is not None and cfg.ema_validate:      # early stopping and BEST_ then follow the averaged weights
+            averaged = step.ema_weights() if step is not None else ema.weights()
+        with averaged:
+            last_loss = validate(loaders["VAL"], encoder, decoder, val_criterion, cfg, device, cider=cider)   # identical on every rank
         if cfg.val_caption_metrics:
             last_loss = last_loss[0]                    # (the metrics dict is printed and kept in STATS)
         is_best = last_loss < best_loss
@@ -703,8 +791,11 @@ def main(cfg=None):
         if rank == 0:
             opt = step.as_torch_optimizer() if step is not None else decoder_optimizer
             enc_opt = step.as_torch_encoder_optimizer() if step is not None and step.train_conv1 else encoder_optimizer
+            extra = {}
+            if cfg.ema_decay is not None:
+                extra["decoder_ema"] = (step.ema_state_dict() if step is not None else ema.state_dict())
             ut.save_checkpoint(cfg.data_name, epoch, epochs_since_improvement, encoder, decoder, enc_opt,
-                               opt, last_loss, is_best, out_dir=cfg.out_dir)
+                               opt, last_loss, is_best, out_dir=cfg.out_dir, **extra)
     return history
 
 

@@ -17,6 +17,7 @@ counter-based generator (see ick_dropout) and cannot be bit-identical to torch's
 parity of the training math is pinned with dropout disabled (p = 0 / eval-mode fixtures).
 """
 import collections
+import contextlib
 import functools
 import math
 import os
@@ -847,6 +848,24 @@ def lr_at(t, lr, schedule):
     return lr * (r + (1.0 - r) * (N - tt) / (N - W))
 
 
+def check_ema_decay(d):
+    """None (no moving average) or a float in [0, 1)."""
+    if d is None:
+        return None
+    d = float(d)
+    if not 0.0 <= d < 1.0:            # (NaN fails both compares)
+        raise IckError("ema_decay must lie in [0, 1) (None: off), got %r" % (d,))
+    return d
+
+
+def ema_decay_at(t, decay, warmup=False):
+    """The decay d_t of the moving average at the 1-based optimizer step t, in float64: the definition the optimizer
+    kernels (csrc/adam.hip, in float32) and the unfused path follow.  Without warmup the decay itself; with it
+    min(decay, (1 + t) / (10 + t)), so the average follows the first steps' weights instead of the initial ones."""
+    decay, t = float(decay), float(t)
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+
+
 def check_max_grad_norm(m):
     if m is None:
         return None
@@ -877,8 +896,20 @@ class TrainStep:
 
     def __init__(self, decoder, lr=4e-4, grad_clip=5.0, betas=(0.9, 0.999), eps=1e-8, process_group=None, seed=0,
                  use_graph=True, encoder=None, deterministic=None, lazy_update=False, label_smoothing=0.0,
-                 max_grad_norm=None, lr_schedule=None, train_conv1=False, encoder_lr=1e-4):
+                 max_grad_norm=None, lr_schedule=None, train_conv1=False, encoder_lr=1e-4, ema_decay=None,
+                 ema_warmup=False):
         self.dec = decoder
+        # ema_decay (float in [0, 1); None: off): an exponential moving average of every trained parameter
+        # (conv1's with train_conv1), e += (1 - d_t) (p - e) after each applied update, kept by the optimizer launch itself
+        # in flat_e / enc_e, laid out like flat_p / enc_p and starting as copies of them.  d_t = ema_decay, or with
+        # ema_warmup min(ema_decay, (1 + t) / (10 + t)) on the optimizer step t.  The decay lives in a one-float device word
+        # (set_ema_decay replays the captured graphs); whether there is an average is fixed at construction.  The average
+        # is a function of parameters that are identical on every rank, so it needs no collective.  ema_state_dict() /
+        # load_ema_state_dict() carry it; state_dict() is unchanged.  None: nothing is allocated, the same launches.
+        self.ema_decay = check_ema_decay(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.flat_e = self.enc_e = self._ema_word = None
+        self._ema_swapped = False
         # train_conv1 (needs encoder= and the 4-D feature map as encoder_out): Encoder.conv1 is trained
         # inside the step as the reference's fine_tune_encoder=True trains it (geo-aware/train.py:93-100,283-294): the
         # backward pass also produces the image rows' gradient and ick_conv1_wgrad reduces it against the feature map;
@@ -995,6 +1026,8 @@ class TrainStep:
             self._make_words()
         if self.label_smoothing != 0.0:
             self._eps_word = torch.full((1,), self.label_smoothing, device=dev, dtype=torch.float32)
+        if self.ema_decay is not None:
+            self._ema_word = torch.full((1,), self.ema_decay, device=dev, dtype=torch.float32)
         self._graphs = {}
         # the re-laid-out copies of the weights (packed row-chain images, cross K/V gather, bf16 planes) that the optimizer
         # kernel keeps current itself: built on the first call (DerivedWeights); ICK_ADAM_DERIVE=0 keeps the per-step
@@ -1006,6 +1039,10 @@ class TrainStep:
         dp.broadcast_bucket(self.flat_p, self.pg)
         if self.train_conv1:
             dp.broadcast_bucket(self.enc_p, self.pg)
+        if self.ema_decay is not None:          # the averages start at the (broadcast) parameters; the pads stay zero
+            self.flat_e = self.flat_p.clone()
+            if self.train_conv1:
+                self.enc_e = self.enc_p.clone()
         # Several ranks, ICK_SPLIT_ALLREDUCE=1: the step runs as two graphs around two all-reduces -- the early half of
         # the bucket (score head, decoder stack: gradients complete first) travels while the late half (cross K/V
         # projection, context encoders, embeddings) is computed, and only the late half's all-reduce is exposed.  Measured
@@ -1181,6 +1218,11 @@ class TrainStep:
 
         return dict(want_image_grad=True, image_grad_sink=sink)
 
+    def _ema_kwargs(self, e):
+        if self.ema_decay is None:
+            return {}
+        return dict(ema=e, ema_decay_word=self._ema_word, ema_warmup=self.ema_warmup)
+
     def _adam_conv1(self):
         """conv1's own update: the same division by the global token count, the element clamp, Adam with encoder_lr and
         the step counter the decoder's update of the same step reads (so it runs before the counter advances) -- then the
@@ -1188,7 +1230,7 @@ class TrainStep:
         place.  A no-op on the parameters while the token count is zero, as the decoder's update."""
         ops.adam_update(self.enc_p, self.enc_g, self.enc_m, self.enc_v, 1, lr=self.encoder_lr, clip=self.clip, gscale=1.0,
                         beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step_tensor=self.counter,
-                        gscale_den=self.flat_g[self._t + 1:])
+                        gscale_den=self.flat_g[self._t + 1:], **self._ema_kwargs(self.enc_e))
         self._conv1_resplit()
 
     def _conv1_resplit(self):
@@ -1235,7 +1277,7 @@ class TrainStep:
         # (the update runs over flat_p's n floats or the cover: flat_g's two trailing words stay outside without a view)
         ops.adam_update(self.flat_p, self.flat_g, self.flat_m, self.flat_v, 1, cover=self.derived,
                         clip=self.clip, gscale=1.0, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                        step_tensor=self.counter, gscale_den=den, **rate)
+                        step_tensor=self.counter, gscale_den=den, **rate, **self._ema_kwargs(self.flat_e))
 
     # ---- the same step in two halves (several ranks: the early half's all-reduce overlaps the late half) ----
     def _part_a1(self, captions, caption_masks, entities, facts, enc_in, gmap, lengths, weights=None):
@@ -1447,6 +1489,105 @@ class TrainStep:
         opt.load_state_dict(sd)
         return opt
 
+    # ---- the moving average of the parameters (ema_decay=) -------------------------
+    def _need_ema(self, what):
+        if self.ema_decay is None:
+            raise IckError("%s needs a TrainStep built with ema_decay=" % what)
+        self.flush()
+        self._check_views()
+
+    def set_ema_decay(self, d):
+        """A new decay of the moving average, applied from the next update on: only the device word is written, the
+        captured graphs replay.  A pending (lazy_update) update is applied first, under the old decay.  Whether there is
+        an average at all is fixed at construction: None here, or a value for a step built without one, is refused."""
+        if (d is None) != (self.ema_decay is None):
+            raise IckError("the moving average cannot be switched %s after construction: build the TrainStep with%s "
+                           "ema_decay=" % (("off", "out") if d is None else ("on", "")))
+        if d is None:
+            return
+        d = check_ema_decay(d)
+        self.flush()
+        self.ema_decay = d
+        self._ema_word.fill_(d)
+
+    def _ema_params(self):
+        """(parameter, its slot of the average) in ema_state_dict()'s order: _adam_order(), then conv1's two."""
+        out = [(p, self._slot(self.flat_e, p)) for p in self._adam_order()]
+        if self.train_conv1:
+            out += [(p, self._enc_slot(self.enc_e, p)) for p in self.enc_params]
+        return out
+
+    def ema_state_dict(self):
+        """The moving average: {"decay", "warmup", "params": one tensor per parameter in _adam_order()'s order[,
+        "encoder_params": conv1.weight's and conv1.bias's with train_conv1]}.  Tensors are copies; a pending update is
+        applied first.  Refused inside ema_weights(), where the two buckets are exchanged and flat_e holds the training
+        weights."""
+        self._need_ema("ema_state_dict")
+        if self._ema_swapped:
+            raise IckError("ema_state_dict inside ema_weights(): the buckets are exchanged there; leave the context first")
+        n = len(self._adam_order())
+        avg = [e.clone() for _, e in self._ema_params()]
+        sd = {"decay": self.ema_decay, "warmup": self.ema_warmup, "params": avg[:n]}
+        if self.train_conv1:
+            sd["encoder_params"] = avg[n:]
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """Restore the moving average (and its decay and warmup flag) from ema_state_dict()'s layout."""
+        self._need_ema("load_ema_state_dict")
+        if self._ema_swapped:
+            raise IckError("load_ema_state_dict inside ema_weights(): leave the context first")
+        mine = self._ema_params()
+        theirs = list(sd["params"]) + list(sd.get("encoder_params", ()))
+        if len(theirs) != len(mine) or len(sd["params"]) != len(self._adam_order()):
+            raise IckError("the moving average holds %d (+ %d encoder) tensors, the step trains %d (+ %d)" %
+                           (len(sd["params"]), len(sd.get("encoder_params", ())), len(self._adam_order()),
+                            len(mine) - len(self._adam_order())))
+        for i, ((p, _), t) in enumerate(zip(mine, theirs)):
+            if tuple(t.shape) != tuple(p.shape):
+                raise IckError("moving average %d has shape %s, the parameter has %s" % (i, tuple(t.shape), tuple(p.shape)))
+        decay = check_ema_decay(sd.get("decay", self.ema_decay))
+        if decay is None:
+            raise IckError("the moving average's state carries no decay")
+        with torch.no_grad():
+            for (_, e), t in zip(mine, theirs):
+                e.copy_(t)
+        self.ema_decay = decay
+        self._ema_word.fill_(decay)
+        if bool(sd.get("warmup", self.ema_warmup)) != self.ema_warmup:
+            self.ema_warmup = not self.ema_warmup
+            self._graphs.clear()          # the flag is an argument of the captured optimizer launches
+
+    def _ema_exchange(self):
+        with torch.no_grad():
+            for a, b in ((self.flat_p, self.flat_e), (self.enc_p, self.enc_e) if self.train_conv1 else (None, None)):
+                if a is not None:
+                    t = a.clone()
+                    a.copy_(b)
+                    b.copy_(t)
+        self.dec.invalidate_caches()
+        if self.enc is not None:
+            self.enc.invalidate_caches()
+        self.parameters_changed()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the parameters hold the averaged weights: forward, predict*, score_captions, validate see
+        them through the parameters' own views of the bucket.  A pending update is applied first; the contents of flat_p
+        and flat_e (and of conv1's pair) are exchanged, every cache of re-laid-out weights is invalidated, and on the way
+        out -- also when the body raises -- they are exchanged back and invalidated again, so the next step trains the
+        very bits it left.  A training step inside the context is refused."""
+        self._need_ema("ema_weights")
+        if self._ema_swapped:
+            raise IckError("ema_weights() is already in effect")
+        self._ema_exchange()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swapped = False
+            self._ema_exchange()
+
     def input_buffers(self):
         """The static input tensors of the most recently captured graphs, in __call__'s argument order
         (captions, encoder_out-or-features, caption_masks, caption_lengths, entities[, facts]).  A loader that writes
@@ -1521,6 +1662,9 @@ class TrainStep:
         fewer rows (several captions of one image share its encoder output); not with a 4-D feature map.  Both are
         inputs of the captured graphs (new values replay, never re-capture); their presence is part of the graph key."""
         dec = self.dec
+        if self._ema_swapped:
+            raise IckError("a training step inside ema_weights(): the parameters hold the averaged weights there; leave "
+                           "the context first")
         self._check_views()
         encoder_out, entities, facts = dec._prepare_inputs(encoder_out, entities, facts)
         dev = encoder_out.device
@@ -1569,6 +1713,7 @@ class TrainStep:
             state = (self.flat_p, self.flat_m, self.flat_v, self.counter)
             if self.train_conv1:
                 state += (self.enc_p, self.enc_m, self.enc_v)
+            state += tuple(t for t in (self.flat_e, self.enc_e) if t is not None)
             snap = [t.clone() for t in state]
             try:
                 if self.split:

@@ -18,9 +18,11 @@ def checkpoint_name(data_name, epoch):
 
 
 def save_checkpoint(data_name, epoch, epochs_since_improvement, encoder, decoder, encoder_optimizer,
-                    decoder_optimizer, loss, is_best, out_dir="."):
+                    decoder_optimizer, loss, is_best, out_dir=".", decoder_ema=None):
     state = dict(epoch=epoch, epochs_since_improvement=epochs_since_improvement, loss=loss, encoder=encoder,
                  decoder=decoder, encoder_optimizer=encoder_optimizer, decoder_optimizer=decoder_optimizer)
+    if decoder_ema is not None:       # (Config.ema_decay: the moving average of the trained parameters, load_ema_weights)
+        state["decoder_ema"] = decoder_ema
     # (device-side caches -- graphs, weight images, pinned staging -- stay with the live modules: __getstate__ skips them)
     name = checkpoint_name(data_name, epoch)
     torch.save(state, os.path.join(out_dir, name))
@@ -33,6 +35,40 @@ def load_checkpoint(path, map_location=None):
     """Whole-object pickles need weights_only=False (torch >= 2.6 defaults to True); `models` must already
     resolve to a drop-in module for reference-written files."""
     return torch.load(path, map_location=map_location, weights_only=False)
+
+
+def load_ema_weights(decoder, ema, encoder=None):
+    """Copy the moving averages of a checkpoint (ck["decoder_ema"], written by a run with Config.ema_decay) into the
+    checkpoint's own modules, so that eval.evaluate decodes with the averaged weights.  ema["params"] follow the decoder's
+    trainable parameters in the optimizer's order; ema["encoder_params"] (a run that trained the encoder) go to
+    Encoder.conv1's weight and bias when there are two, else to the encoder's trainable parameters -- and need encoder=."""
+    from .lib import IckError
+
+    def fill(params, tensors, what):
+        if len(params) != len(tensors) or any(tuple(p.shape) != tuple(t.shape) for p, t in zip(params, tensors)):
+            raise IckError("the moving average does not fit the %s's trainable parameters (%d tensors for %d)"
+                           % (what, len(tensors), len(params)))
+        with torch.no_grad():
+            for p, t in zip(params, tensors):
+                p.copy_(t)
+
+    seen, mine = set(), []
+    for p in decoder.parameters():
+        if p.requires_grad and id(p) not in seen:
+            seen.add(id(p))
+            mine.append(p)
+    fill(mine, list(ema["params"]), "decoder")
+    enc_avg = list(ema.get("encoder_params", ()))
+    if enc_avg:
+        if encoder is None:
+            raise IckError("the moving average also covers the encoder: pass encoder=")
+        fill([encoder.conv1.weight, encoder.conv1.bias] if len(enc_avg) == 2 else
+             [p for p in encoder.parameters() if p.requires_grad], enc_avg, "encoder")
+        if hasattr(encoder, "invalidate_caches"):
+            encoder.invalidate_caches()
+    if hasattr(decoder, "invalidate_caches"):
+        decoder.invalidate_caches()
+    return decoder
 
 
 class AverageMeter:

@@ -781,6 +781,26 @@ int ick_adam_opt_derive(float* p, float* g, float* m, float* v, const ick_adam_i
                         int32_t n_blocks, float gscale, float clip, float* words, ick_lr_schedule sched, float beta1,
                         float beta2, float eps, int32_t step, const uint32_t* step_ptr, const float* gscale_den,
                         void* stream);
+/* The Adam entries above which ALSO keep an exponential moving average of the parameters.  e: a fourth
+ * array laid out like p (n floats, or the bucket the cover runs over).  The lane that has made the new p updates e at the
+ * same offset, in this order of float32 operations:
+ *     w = 1 - d_t;   e = e + w * (p_new - e)
+ * with d_t = *ema_decay (a DEVICE float: a captured graph follows a new value), or, with ema_warmup != 0,
+ * d_t = min(*ema_decay, (1 + t) / (10 + t)) on the step count t = step + *step_ptr of the bias correction.
+ * words == NULL: the rate is the host float lr, sched is not read, and p, g, m, v get ick_adam_clamp[_derive]'s bits;
+ * words != NULL: the optimizer words as in ick_adam_opt[_derive] (lr is not read) and their bits.  While *gscale_den is
+ * not > 0 nothing is written, e included.  The re-laid-out images of the derive form stay images of p.
+ * ICK_EINVAL without a launch: e or ema_decay NULL (and what the entries above refuse); ICK_EALIGN without a launch: e not
+ * on 4 bytes (flat form; like p, g, m, v it need not lie on 16: the scalar kernel then runs), e not on 16 bytes (derive
+ * form). */
+int ick_adam_ema(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip, float lr,
+                 float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                 const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
+                 void* stream);
+int ick_adam_ema_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
+                        const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr, float* words,
+                        ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
+                        const float* gscale_den, const float* ema_decay, int32_t ema_warmup, void* stream);
 /* The weight and bias gradient of Encoder.conv1 (1x1 convolution) straight from the NCHW feature map:
  *     dw[o, c] = sum over b, p of d_img[b, p, o] * feats[b, c, p],     db[o] = sum over b, p of d_img[b, p, o].
  * d_img (B, P, d): the gradient of the image memory rows; feats (B, C, P): the feature map as it lies; dw (d, C): conv1's
