@@ -7,6 +7,7 @@ Import as `ick_amd` (see /ick_amd.py).  Sub-modules:
   ops        per-op Python wrappers (device pointers from torch tensors)
   decoder    DecoderTransformer / Encoder engine shared by the three variants
   training   TrainStep: the fused cross-entropy training step
+  bucket     ParamBucket: trained parameters, Adam moments and their average in flat fp32 tensors (pure torch)
   scst       SelfCriticalStep: self-critical sequence training on sampled captions (also `ick_amd.SelfCriticalStep`)
   cider      CiderD: CIDEr-D on token ids, on the device (also `ick_amd.CiderD`)
   metrics    CaptionMetrics: BLEU-1..4, ROUGE-L and pointer precision / recall on token ids, on the device, and

@@ -26,6 +26,7 @@ import weakref
 import torch
 
 from . import dp, ops
+from .bucket import ParamBucket
 from .decoder import DropSites
 from .lib import IckError
 from .weights import DerivedWeights, first_stage, vocab_planes_wanted      # noqa: F401  (DerivedWeights is also imported from here)
@@ -977,51 +978,35 @@ class TrainStep:
         early_ids = {id(p) for p in early_parameters(decoder)}
         params = [p for p in params if id(p) in early_ids] + [p for p in params if id(p) not in early_ids]
         dev = params[0].device
-        # every parameter starts at a multiple of 64 floats (256 bytes): the GEMM's 16-byte vector loads need aligned
-        # weight rows, and one odd-sized parameter (fc_entity.bias has a single element) would misalign all that follow
-        pad = lambda k: (k + 63) // 64 * 64     # noqa: E731
-        n = sum(pad(p.numel()) for p in params)
-        self.n = n
-        self.n_early = sum(pad(p.numel()) for p in params if id(p) in early_ids)
-        # +2 trailing floats travel with the gradient bucket: [sum of token losses, token count]
-        self.flat_p = torch.zeros(n, device=dev, dtype=torch.float32)
-        # train_conv1: conv1's extent (weight, bias, each padded like every parameter) lies between the decoder's n floats
-        # and the trailing words, so the one all-reduce carries it; self.n stays the decoder's size
+        if self.train_conv1 and encoder.conv1.weight.device != dev:
+            raise IckError("train_conv1=True: the encoder must be on the decoder's device (%s)" % dev)
+        # The state lives in ParamBuckets (bucket.py: the layout, the parameters as views of it): the decoder's and, with
+        # train_conv1, one over [conv1.weight, conv1.bias].  The flat_* / enc_* names are those buckets' tensors.
+        self._dec_bucket = db = ParamBucket(params, IckError)
+        self._buckets = [db]
+        self.params, self.n = params, db.n
+        self.n_early = db.offsets[sum(id(p) in early_ids for p in params)]      # the early parameters come first
+        self.flat_p, self.flat_m, self.flat_v = db.p, db.m, db.v
+        # train_conv1: conv1's extent lies between the decoder's n floats and the trailing words, so the one all-reduce
+        # carries it; self.n stays the decoder's size
         self.ne = 0
         if self.train_conv1:
             c1 = encoder.conv1
-            if c1.weight.device != dev:
-                raise IckError("train_conv1=True: the encoder must be on the decoder's device (%s)" % dev)
-            self.ne = pad(c1.weight.numel()) + pad(c1.bias.numel())
-        self._t = n + self.ne                   # where [sum of token losses, token count] start in flat_g
+            self._enc_bucket = eb = ParamBucket([c1.weight, c1.bias], IckError)
+            self._buckets.append(eb)
+            self.enc_params, self.ne = eb.params, eb.n
+            self.enc_p, self.enc_m, self.enc_v = eb.p, eb.m, eb.v
+            encoder.invalidate_caches()          # the weight moved: its pre-split copy is made again on first use
+        # one gradient allocation: [decoder n | conv1 ne | sum of token losses, token count]
+        self._t = self.n + self.ne              # where [sum of token losses, token count] start in flat_g
         self.flat_g = torch.zeros(self._t + 2, device=dev, dtype=torch.float32)
-        self.flat_m = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.flat_v = torch.zeros(n, device=dev, dtype=torch.float32)
+        self.grads = db.grad_views(self.flat_g[:self.n])
+        if self.train_conv1:
+            self.enc_g = self.flat_g[self.n:self._t]
+            eg = eb.grad_views(self.enc_g)
+            self._c1_gw, self._c1_gb = eg[id(c1.weight)].view(c1.weight.shape[0], -1), eg[id(c1.bias)]
         self.counter = torch.zeros(1, device=dev, dtype=torch.int32)   # steps done (read as uint32 by the kernels)
         self.one = torch.ones(1, device=dev, dtype=torch.float32)
-        self.grads = {}
-        off = 0
-        with torch.no_grad():
-            for p in params:
-                k = p.numel()
-                self.flat_p[off:off + k].copy_(p.reshape(-1))
-                p.data = self.flat_p[off:off + k].view(p.shape)      # parameters become views of the bucket
-                self.grads[id(p)] = self.flat_g[off:off + k].view(p.shape)
-                off += pad(k)
-        self.params = params
-        if self.train_conv1:
-            c1 = encoder.conv1
-            wn, bn = c1.weight.numel(), c1.bias.numel()
-            self.enc_p, self.enc_m, self.enc_v = (torch.zeros(self.ne, device=dev, dtype=torch.float32) for _ in range(3))
-            self.enc_g = self.flat_g[n:n + self.ne]
-            with torch.no_grad():
-                for p, o in ((c1.weight, 0), (c1.bias, pad(wn))):
-                    self.enc_p[o:o + p.numel()].copy_(p.reshape(-1))
-                    p.data = self.enc_p[o:o + p.numel()].view(p.shape)     # conv1 becomes a view of step-owned storage
-            self.enc_params = [c1.weight, c1.bias]
-            self._c1_gw = self.enc_g[:wn].view(c1.weight.shape[0], -1)
-            self._c1_gb = self.enc_g[pad(wn):pad(wn) + bn]
-            encoder.invalidate_caches()          # the weight moved: its pre-split copy is made again on first use
         if self.max_grad_norm is not None or self.lr_schedule is not None:
             self._make_words()
         if self.label_smoothing != 0.0:
@@ -1036,13 +1021,14 @@ class TrainStep:
         self._derived_tried = False
         # several ranks: every replica starts from rank 0's weights (a freshly built decoder is randomly initialised
         # per process; the reference has a single process, geo-aware/train.py:16-18).  One broadcast of the bucket.
-        dp.broadcast_bucket(self.flat_p, self.pg)
+        # (the moments start at zero everywhere, and the averages start at the broadcast parameters)
+        for b in self._buckets:
+            dp.broadcast_bucket(b.p, self.pg)
+            if self.ema_decay is not None:
+                b.start_average()
+        self.flat_e = self._dec_bucket.e
         if self.train_conv1:
-            dp.broadcast_bucket(self.enc_p, self.pg)
-        if self.ema_decay is not None:          # the averages start at the (broadcast) parameters; the pads stay zero
-            self.flat_e = self.flat_p.clone()
-            if self.train_conv1:
-                self.enc_e = self.enc_p.clone()
+            self.enc_e = self._enc_bucket.e
         # Several ranks, ICK_SPLIT_ALLREDUCE=1: the step runs as two graphs around two all-reduces -- the early half of
         # the bucket (score head, decoder stack: gradients complete first) travels while the late half (cross K/V
         # projection, context encoders, embeddings) is computed, and only the late half's all-reduce is exposed.  Measured
@@ -1177,29 +1163,31 @@ class TrainStep:
 
         return tail
 
-    def _part_a(self, captions, caption_masks, entities, facts, enc_in, gmap, lengths, weights=None):
-        dec = self.dec
-        ops.stamp("A: start")
+    def _forward_and_loss(self, captions, caption_masks, entities, facts, enc_in, gmap, lengths, weights=None):
+        """Part A up to the backward pass, for the one-graph and the split step alike: the side tail, the forward pass with
+        saved activations and the loss -> the (args, kwargs) of the backward pass, which _part_a runs in one go and
+        _part_a1 / _part_a2 in two phases.  The lazy hooks are None in the split step (_lazy_active is false there)."""
         box = {}
-        tail = self._side_tail(box, captions, entities, facts, lengths)
-
-        scores, tape = forward_with_tape(dec, captions, caption_masks, entities, facts, gmap=gmap,
+        lazy = self._lazy_active(enc_in)
+        scores, tape = forward_with_tape(self.dec, captions, caption_masks, entities, facts, gmap=gmap,
                                          seed=self.seed * 2654435761 & 0xFFFFFFFF, epoch=self.counter, fresh_pack=True,
                                          overlap=self._overlap("ICK_NO_FWD_OVERLAP"),
-                                         side_tail=tail, derived=self.derived,
-                                         pre_side=self._deferred_update if self._lazy_active(enc_in) else None,
-                                         pre_main=self._adam_conv1 if self.train_conv1 and self._lazy_active(enc_in)
-                                         else None,
+                                         side_tail=self._side_tail(box, captions, entities, facts, lengths),
+                                         derived=self.derived, pre_side=self._deferred_update if lazy else None,
+                                         pre_main=self._adam_conv1 if self.train_conv1 and lazy else None,
                                          head_rows=lambda: box.get("pack"), **self._enc_kwargs(enc_in))
-        decode_len = box["decode_len"]
         tape.misc["prezero"] = box.get("prezero")
         ops.stamp("fwd: scores done")
-        _, _, dscores = self._loss(scores, captions, decode_len, weights, box.get("pack"))
+        ce = self._loss(scores, captions, box["decode_len"], weights, box.get("pack"))
         ops.stamp("CE done")
-        backward_from_tape(dec, tape, dscores, self.grads, overlap=self._overlap("ICK_NO_BWD_OVERLAP"),
-                           **self._conv1_bwd_kwargs(enc_in))
+        return (self.dec, tape, ce[2], self.grads), dict(self._conv1_bwd_kwargs(enc_in),
+                                                         overlap=self._overlap("ICK_NO_BWD_OVERLAP"))
+
+    def _part_a(self, *inputs):
+        ops.stamp("A: start")
+        args, kwargs = self._forward_and_loss(*inputs)
+        backward_from_tape(*args, **kwargs)
         ops.stamp("A: end (after join)")
-        return self.flat_g
 
     def _lazy_active(self, enc_in):
         return bool(self.lazy and self.use_graph and self.derived is not None and not self.split and not self.deterministic
@@ -1280,27 +1268,13 @@ class TrainStep:
                         step_tensor=self.counter, gscale_den=den, **rate, **self._ema_kwargs(self.flat_e))
 
     # ---- the same step in two halves (several ranks: the early half's all-reduce overlaps the late half) ----
-    def _part_a1(self, captions, caption_masks, entities, facts, enc_in, gmap, lengths, weights=None):
-        dec = self.dec
-        box = {}
-        tail = self._side_tail(box, captions, entities, facts, lengths)
-
-        scores, tape = forward_with_tape(dec, captions, caption_masks, entities, facts, gmap=gmap,
-                                         seed=self.seed * 2654435761 & 0xFFFFFFFF, epoch=self.counter, fresh_pack=True,
-                                         overlap=self._overlap("ICK_NO_FWD_OVERLAP"),
-                                         side_tail=tail, derived=self.derived, head_rows=lambda: box.get("pack"),
-                                         **self._enc_kwargs(enc_in))
-        decode_len = box["decode_len"]
-        tape.misc["prezero"] = box.get("prezero")
-        self._ce = self._loss(scores, captions, decode_len, weights, box.get("pack"))
-        self._bp = BackwardPass(dec, tape, self._ce[2], self.grads,
-                                overlap=self._overlap("ICK_NO_BWD_OVERLAP"), **self._conv1_bwd_kwargs(enc_in))
+    def _part_a1(self, *inputs):
+        args, kwargs = self._forward_and_loss(*inputs)
+        self._bp = BackwardPass(*args, **kwargs)
         self._bp.early(join=True)
-        return self.flat_g
 
     def _part_a2(self):
         self._bp.late()
-        return self.flat_g
 
     def _part_b(self):
         # divide by the global token count (device-resident), clamp, Adam with the device step counter
@@ -1310,16 +1284,21 @@ class TrainStep:
             self._adam_conv1()
         ops.counter_add(self.counter, 1)
         ops.stamp("B: end")
-        return self.flat_g
 
-    def _capture(self, fn, inputs):
+    @staticmethod
+    def _warm_static(fn, inputs):
+        """Static clones of the inputs and one run of fn on them off the capture, on a side stream (lazy kernel
+        attributes); the warm-up steps touch the gradient bucket only."""
         static = [None if t is None else t.contiguous().clone() for t in inputs]
-        # warm-up off the capture (lazy kernel attributes); the warm-up steps touch the gradient bucket only
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             fn(*static)
         torch.cuda.current_stream().wait_stream(side)
+        return static
+
+    def _capture(self, fn, inputs):
+        static = self._warm_static(fn, inputs)
         g = torch.cuda.CUDAGraph()
         with ops.capture(g):
             fn(*static)
@@ -1328,13 +1307,7 @@ class TrainStep:
     def _capture_split(self, inputs):
         """Graphs A1 (forward, CE, early backward) and A2 (late backward) over one memory pool: A2 reads what A1 left
         in the tape."""
-        static = [None if t is None else t.contiguous().clone() for t in inputs]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._part_a1(*static)
-            self._part_a2()
-        torch.cuda.current_stream().wait_stream(side)
+        static = self._warm_static(lambda *s: (self._part_a1(*s), self._part_a2()), inputs)
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with ops.capture(g1):
             self._part_a1(*static)
@@ -1350,8 +1323,11 @@ class TrainStep:
         return [p for p in unique_parameters(self.dec) if id(p) in mine]
 
     def _slot(self, flat, p):
-        off = (p.data_ptr() - self.flat_p.data_ptr()) // 4
-        return flat[off:off + p.numel()].view(p.shape)
+        """Decoder parameter p's extent of flat_m / flat_v / flat_e / flat_g (or a tensor laid out like them)."""
+        return self._dec_bucket.slot(flat, p)
+
+    def _step(self):
+        return int(self.counter.item()) & 0xFFFFFFFF
 
     def state_dict(self):
         """The optimizer state as torch.optim.Adam.state_dict() would report it (exp_avg / exp_avg_sq / step per
@@ -1359,17 +1335,7 @@ class TrainStep:
         (geo-aware/utils.py:32-46) and with the fused=False path.  Tensors are copies."""
         self.flush()
         self._check_views()
-        order = self._adam_order()
-        step = float(int(self.counter.item()) & 0xFFFFFFFF)
-        state = {}
-        if step > 0:
-            for i, p in enumerate(order):
-                state[i] = {"step": torch.tensor(step), "exp_avg": self._slot(self.flat_m, p).clone(),
-                            "exp_avg_sq": self._slot(self.flat_v, p).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
-                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "decoupled_weight_decay": False, "params": list(range(len(order)))}
-        return {"state": state, "param_groups": [group]}
+        return self._dec_bucket.adam_state(self._adam_order(), self._step(), self.lr, self.betas, self.eps)
 
     def load_state_dict(self, sd):
         """Restore Adam moments, step count (which also positions the dropout stream) and learning rate from a
@@ -1377,32 +1343,14 @@ class TrainStep:
         self.flush()
         self._check_views()
         order = self._adam_order()
-        groups = sd["param_groups"]
-        ids = [i for g in groups for i in g["params"]]
-        if len(ids) != len(order):
-            raise IckError("optimizer state holds %d parameters, the decoder has %d trainable ones" %
-                           (len(ids), len(order)))
-        steps = set()
-        with torch.no_grad():
-            self.flat_m.zero_()
-            self.flat_v.zero_()
-            for pos, i in enumerate(ids):
-                st = sd["state"].get(i)
-                if not st:
-                    continue
-                p = order[pos]
-                if tuple(st["exp_avg"].shape) != tuple(p.shape):
-                    raise IckError("optimizer state %d has shape %s, parameter has %s" %
-                                   (i, tuple(st["exp_avg"].shape), tuple(p.shape)))
-                self._slot(self.flat_m, p).copy_(st["exp_avg"])
-                self._slot(self.flat_v, p).copy_(st["exp_avg_sq"])
-                steps.add(int(float(st["step"])))
-            if len(steps) > 1:
-                raise IckError("per-parameter Adam step counts differ (%s): not representable in the fused step" % steps)
-            self.counter.fill_(steps.pop() if steps else 0)
+        steps, group = self._dec_bucket.load_adam_state(sd, order, "optimizer state",
+                                                        "the decoder has %d trainable ones" % len(order))
+        if len(steps) > 1:
+            raise IckError("per-parameter Adam step counts differ (%s): not representable in the fused step" % steps)
+        self.counter.fill_(steps.pop() if steps else 0)
         # (base_lr: the unfused path of train.py keeps the schedule's base rate there, "lr" then is the scheduled one)
-        lr = float(groups[0].get("base_lr", groups[0]["lr"]))
-        betas, eps = tuple(groups[0].get("betas", self.betas)), float(groups[0].get("eps", self.eps))
+        lr = float(group.get("base_lr", group["lr"]))
+        betas, eps = tuple(group.get("betas", self.betas)), float(group.get("eps", self.eps))
         if self._words is None or betas != tuple(self.betas) or eps != self.eps:
             self._graphs.clear()      # betas / eps (and, without the optimizer words, lr) are baked into the captured graph
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -1427,10 +1375,6 @@ class TrainStep:
         return opt
 
     # ---- conv1's optimizer state (train_conv1), torch.optim.Adam's layout over [conv1.weight, conv1.bias] ----
-    def _enc_slot(self, flat, p):
-        off = (p.data_ptr() - self.enc_p.data_ptr()) // 4
-        return flat[off:off + p.numel()].view(p.shape)
-
     def _need_conv1(self, what):
         if not self.train_conv1:
             raise IckError("%s needs a TrainStep built with train_conv1=True" % what)
@@ -1442,43 +1386,20 @@ class TrainStep:
         feature-file encoder's trainable parameters [conv1.weight, conv1.bias] (geo-aware/train.py:93-100).  Both optimizers
         step together: the step count is the decoder's.  Tensors are copies; state_dict() is unchanged."""
         self._need_conv1("encoder_state_dict")
-        step = float(int(self.counter.item()) & 0xFFFFFFFF)
-        state = {}
-        if step > 0:
-            for i, p in enumerate(self.enc_params):
-                state[i] = {"step": torch.tensor(step), "exp_avg": self._enc_slot(self.enc_m, p).clone(),
-                            "exp_avg_sq": self._enc_slot(self.enc_v, p).clone()}
-        group = {"lr": self.encoder_lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
-                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "decoupled_weight_decay": False, "params": [0, 1]}
-        return {"state": state, "param_groups": [group]}
+        return self._enc_bucket.adam_state(self.enc_params, self._step(), self.encoder_lr, self.betas, self.eps)
 
     def load_encoder_state_dict(self, sd):
         """Restore conv1's moments and rate from a torch.optim.Adam-layout state dict over [conv1.weight, conv1.bias].  The
         step count is the decoder's (load_state_dict sets it): a state whose step differs from it is refused."""
         self._need_conv1("load_encoder_state_dict")
-        groups = sd["param_groups"]
-        ids = [i for g in groups for i in g["params"]]
-        if len(ids) != 2:
-            raise IckError("encoder optimizer state holds %d parameters, the step trains conv1.weight and conv1.bias (a "
-                           "state that also covers trunk blocks belongs to fine_tune_encoder=True)" % len(ids))
-        mine = int(self.counter.item()) & 0xFFFFFFFF
-        with torch.no_grad():
-            self.enc_m.zero_()
-            self.enc_v.zero_()
-            for p, i in zip(self.enc_params, ids):
-                st = sd["state"].get(i)
-                if not st:
-                    continue
-                if tuple(st["exp_avg"].shape) != tuple(p.shape):
-                    raise IckError("encoder optimizer state %d has shape %s, parameter has %s" %
-                                   (i, tuple(st["exp_avg"].shape), tuple(p.shape)))
-                if int(float(st["step"])) != mine:
-                    raise IckError("encoder optimizer state is at step %d, the decoder's at %d: both step together (load "
-                                   "the decoder's state first)" % (int(float(st["step"])), mine))
-                self._enc_slot(self.enc_m, p).copy_(st["exp_avg"])
-                self._enc_slot(self.enc_v, p).copy_(st["exp_avg_sq"])
-        self.encoder_lr = float(groups[0]["lr"])
+        steps, group = self._enc_bucket.load_adam_state(
+            sd, self.enc_params, "encoder optimizer state", "the step trains conv1.weight and conv1.bias (a state that "
+            "also covers trunk blocks belongs to fine_tune_encoder=True)")
+        mine = self._step()
+        if steps - {mine}:
+            raise IckError("encoder optimizer state is at step %d, the decoder's at %d: both step together (load "
+                           "the decoder's state first)" % (min(steps - {mine}), mine))
+        self.encoder_lr = float(group["lr"])
         self._graphs.clear()              # the rate is baked into the captured optimizer launches
 
     def as_torch_encoder_optimizer(self):
@@ -1512,10 +1433,8 @@ class TrainStep:
 
     def _ema_params(self):
         """(parameter, its slot of the average) in ema_state_dict()'s order: _adam_order(), then conv1's two."""
-        out = [(p, self._slot(self.flat_e, p)) for p in self._adam_order()]
-        if self.train_conv1:
-            out += [(p, self._enc_slot(self.enc_e, p)) for p in self.enc_params]
-        return out
+        orders = [self._adam_order()] + ([self.enc_params] if self.train_conv1 else [])
+        return [(p, b.slot(b.e, p)) for b, order in zip(self._buckets, orders) for p in order]
 
     def ema_state_dict(self):
         """The moving average: {"decay", "warmup", "params": one tensor per parameter in _adam_order()'s order[,
@@ -1559,12 +1478,8 @@ class TrainStep:
             self._graphs.clear()          # the flag is an argument of the captured optimizer launches
 
     def _ema_exchange(self):
-        with torch.no_grad():
-            for a, b in ((self.flat_p, self.flat_e), (self.enc_p, self.enc_e) if self.train_conv1 else (None, None)):
-                if a is not None:
-                    t = a.clone()
-                    a.copy_(b)
-                    b.copy_(t)
+        for b in self._buckets:
+            b.exchange_average()
         self.dec.invalidate_caches()
         if self.enc is not None:
             self.enc.invalidate_caches()
@@ -1620,16 +1535,13 @@ class TrainStep:
     def _check_views(self):
         """The decoder's parameters must still be views of the flat bucket: decoder.to() / .cuda() /
         load_pretrained_embeddings() re-allocate them and the step would then update memory the module no longer
-        reads (silently).  Two pointer compares per call."""
-        first, last = self.params[0], self.params[-1]
-        lo, hi = self.flat_p.data_ptr(), self.flat_p.data_ptr() + 4 * self.n
-        if first.data_ptr() != lo or not (lo <= last.data_ptr() and last.data_ptr() + 4 * last.numel() <= hi):
+        reads (silently).  Two pointer compares per bucket and call (ParamBucket.resident)."""
+        if not self._dec_bucket.resident():
             raise IckError("the decoder's parameters no longer live in TrainStep's bucket (module moved or a "
                            "Parameter was replaced after TrainStep was built): build a new TrainStep")
         if self.train_conv1:
-            c1, lo = self.enc.conv1, self.enc_p.data_ptr()
-            if c1.weight is not self.enc_params[0] or c1.bias is not self.enc_params[1] or c1.weight.data_ptr() != lo or \
-                    c1.bias.data_ptr() != lo + 4 * (self.ne - (c1.bias.numel() + 63) // 64 * 64):
+            c1 = self.enc.conv1
+            if c1.weight is not self.enc_params[0] or c1.bias is not self.enc_params[1] or not self._enc_bucket.resident():
                 raise IckError("Encoder.conv1 no longer lives in TrainStep's storage (encoder moved or a Parameter was "
                                "replaced after TrainStep was built): build a new TrainStep")
 
@@ -1710,10 +1622,7 @@ class TrainStep:
             if len(self._graphs) >= 4:
                 self._graphs.clear()
             # the eager warm-up run of part B is a real optimizer step: snapshot and rewind its state
-            state = (self.flat_p, self.flat_m, self.flat_v, self.counter)
-            if self.train_conv1:
-                state += (self.enc_p, self.enc_m, self.enc_v)
-            state += tuple(t for t in (self.flat_e, self.enc_e) if t is not None)
+            state = [self.counter] + [t for b in self._buckets for t in b.tensors()]
             snap = [t.clone() for t in state]
             try:
                 if self.split:
@@ -1738,6 +1647,7 @@ class TrainStep:
             if self.train_conv1:              # ... and the pre-split copy of conv1's
                 self._conv1_resplit()
             self.flat_g[self._t + 1:].zero_()  # (lazy_update: the warm-up's gradients are not a pending update)
+        # how the parts of this step run: replays of the captured graphs, or the Python functions on the inputs
         if self.use_graph:
             ga, static, gb, ga2 = self._graphs[key]
             if self._lazy_active(enc_in) and not self._pending:
@@ -1746,34 +1656,25 @@ class TrainStep:
                 self.flat_g[self._t + 1:].zero_()
             from .decoder import copy_inputs
             copy_inputs(static, inputs)
-            ga.replay()
-            if ga2 is None:
-                dp.allreduce_bucket(self.flat_g, self.pg)
-            else:
-                # [early gradients] travel while graph A2 computes [late gradients | loss_sum, count]
-                w1 = dp.allreduce_bucket(self.flat_g[:self.n_early], self.pg, async_op=True)
-                ga2.replay()
-                w2 = dp.allreduce_bucket(self.flat_g[self.n_early:], self.pg, async_op=True)
-                for w in (w1, w2):
-                    if w is not None:
-                        w.wait()
-            if self._lazy_active(enc_in):
-                self._pending = True      # applied at the head of the next step's graph (or by flush())
-            else:
-                gb.replay()
-        elif self.split:
-            self._part_a1(*inputs)
+            part_a, part_a2, part_b = ga.replay, None if ga2 is None else ga2.replay, gb.replay
+        else:
+            part_a = functools.partial(self._part_a1 if self.split else self._part_a, *inputs)
+            part_a2, part_b = self._part_a2 if self.split else None, self._part_b
+        part_a()
+        if part_a2 is None:
+            dp.allreduce_bucket(self.flat_g, self.pg)
+        else:
+            # [early gradients] travel while part A2 computes [late gradients | loss_sum, count]
             w1 = dp.allreduce_bucket(self.flat_g[:self.n_early], self.pg, async_op=True)
-            self._part_a2()
+            part_a2()
             w2 = dp.allreduce_bucket(self.flat_g[self.n_early:], self.pg, async_op=True)
             for w in (w1, w2):
                 if w is not None:
                     w.wait()
-            self._part_b()
+        if self._lazy_active(enc_in):     # (captured steps only)
+            self._pending = True          # applied at the head of the next step's graph (or by flush())
         else:
-            self._part_a(*inputs)
-            dp.allreduce_bucket(self.flat_g, self.pg)
-            self._part_b()
+            part_b()
         self.step_count += 1
         dec.invalidate_caches()   # the update went around torch's version counters
         if self.derived is not None:
