@@ -942,6 +942,11 @@ class DecoderTransformer(nn.Module):
         dev = self.fc_vocab.weight.device
         if dev.type != "cuda":
             raise IckError("DecoderTransformer parameters must live on the GPU (decoder.to('cuda'))")
+        dh = self.emb_dim // self.num_heads
+        if dh > ops.DHP:
+            # the head-major q / k / v buffers hold ops.DHP floats per head: refused here, before anything is launched
+            raise IckError("head width %d (emb_dim %d / %d heads) is above the limit of %d the head-major attention "
+                           "buffers hold" % (dh, self.emb_dim, self.num_heads, ops.DHP))
         entities = entities.to(device=dev, dtype=torch.float32)
         if self.has_facts:
             if facts is None:

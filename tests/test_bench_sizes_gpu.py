@@ -71,8 +71,13 @@ def reference_train_step_cached(key, cfg, P, batch, enc_out):
     return _REF_STEPS[key]
 
 
-def reference_train_step(cfg, P, batch, enc_out, lr=4e-4, clip=5.0):
-    """geo-aware/train.py:275-292 on the CPU oracle: CE over packed rows, backward, clamp, Adam."""
+def reference_train_step(cfg, P, batch, enc_out, lr=4e-4, clip=5.0, float64=False):
+    """geo-aware/train.py:275-292 on the CPU oracle: CE over packed rows, backward, clamp, Adam.  float64: the whole
+    sequence in float64 (the oracle allocates with the default dtype: decode_ref.float64_default)."""
+    if float64:
+        from decode_ref import float64_default, params64
+        with float64_default():
+            return reference_train_step(cfg, params64(P), batch, enc_out.double(), lr, clip)
     Pr = {k: v.clone().requires_grad_(True) for k, v in P.items() if not k.startswith("fact_encoder.")}
     if cfg.has_facts:
         Pr["fact_encoder.predicate_embedding.weight"] = Pr["predicate_embedding.weight"]
@@ -89,15 +94,36 @@ def reference_train_step(cfg, P, batch, enc_out, lr=4e-4, clip=5.0):
     return loss.item(), grads, {k: v.detach() for k, v in Pr.items()}
 
 
-def run_train_step_vs_oracle(variant, B, L, K, V, Fn, seed, plan_log):
+def run_train_step_vs_oracle(variant, B, L, K, V, Fn, seed, plan_log, geometry=None, float64=False, reference=None):
+    """geometry: dict(d, H, decoder_dim, encoder_dim, num_layers, P) of a model other than build_decoder's (None: 300 / 10 /
+    512 / 512 / 3 layers over 196 image rows); float64: the oracle's step in float64; reference: (cfg, P, batch, enc_out)
+    -> (loss, gradients, parameters after the step) in place of reference_train_step_cached (tests/model_cases.py's cases
+    share one oracle step among their tests)."""
     from ick_amd.training import TrainStep
-    P = synth.make_params(variant, V, seed)
     wm = synth.make_word_map(V)
-    cfg = R.config_from_word_map(variant, wm)
+    if geometry is None:
+        P = synth.make_params(variant, V, seed)
+        cfg = R.config_from_word_map(variant, wm)
+        enc_out = synth.make_enc_out(B, seed)
+    else:
+        g = geometry
+        P = synth.make_params(variant, V, seed, d=g["d"], decoder_dim=g["decoder_dim"], encoder_dim=g["encoder_dim"],
+                              num_layers=g["num_layers"])
+        cfg = R.config_from_word_map(variant, wm, emb_dim=g["d"], num_heads=g["H"], num_layers=g["num_layers"])
+        enc_out = synth.make_enc_out(B, seed, emb_dim=g["d"], P=g["P"])
     batch = synth.make_batch(variant, B, L, K, V, Fn, seed)
-    enc_out = synth.make_enc_out(B, seed)
-    loss_ref, grads_ref, P_after = reference_train_step_cached((variant, B, L, K, V, Fn, seed), cfg, P, batch, enc_out)
-    dec = zero_dropout(build_decoder(variant, V, P).train())
+    if reference is not None:
+        loss_ref, grads_ref, P_after = reference(cfg, P, batch, enc_out)
+    elif geometry is None and not float64:
+        loss_ref, grads_ref, P_after = reference_train_step_cached((variant, B, L, K, V, Fn, seed), cfg, P, batch, enc_out)
+    else:
+        loss_ref, grads_ref, P_after = reference_train_step(cfg, P, batch, enc_out, float64=float64)
+    if geometry is None:
+        dec = zero_dropout(build_decoder(variant, V, P).train())
+    else:
+        from model_cases import build_model
+        dec = zero_dropout(build_model(variant, g["d"], g["H"], g["decoder_dim"], g["encoder_dim"], g["num_layers"],
+                                       P, V).train())
     ts = TrainStep(dec, lr=4e-4, grad_clip=5.0)      # use_graph=True: the captured step the bench replays
     args = [batch["captions"].cuda(), enc_out.cuda(), batch["caption_masks"].cuda(), batch["caption_lengths"].cuda(),
             batch["entities"]]
@@ -108,7 +134,7 @@ def run_train_step_vs_oracle(variant, B, L, K, V, Fn, seed, plan_log):
     assert abs(loss.item() - loss_ref) < 2e-5, (loss.item(), loss_ref)
     # after the step the bucket holds what Adam consumed: the token-mean gradient, clamped to +-5
     named = dict(dec.named_parameters())
-    flipped = {}
+    flipped, worst = {}, (0.0, None)
     for k, gr in grads_ref.items():
         mine = ts.grads[id(named[k])].detach().cpu()
         gr = gr.clamp(-5.0, 5.0)
@@ -126,8 +152,12 @@ def run_train_step_vs_oracle(variant, B, L, K, V, Fn, seed, plan_log):
             d[bad] = 0
             assert (mine - gr).double().norm().item() <= 5e-3 * gr.double().norm().item(), ("gradient norm", k)
         err = d.max().item() / scale
+        if err > worst[0]:
+            worst = (err, k)
         assert err < 2e-3, ("gradient", k, err)
     assert len(flipped) <= 2, flipped
+    print("%s train step: loss err %.3e, worst gradient error / max %.3e (%s), ReLU-flip units set aside: %s"
+          % (variant, abs(loss.item() - loss_ref), worst[0], worst[1], {k: v.tolist() for k, v in flipped.items()}))
     # The optimizer itself, on EVERY element: from the gradient the bucket held, Adam's first
     # step is w - lr * g / (|g| + eps) exactly (bias-corrected moments of a single step are g and g^2), so the post-step
     # weights are checked against that closed form with no conditioning allowance -- the comparison with the oracle's
