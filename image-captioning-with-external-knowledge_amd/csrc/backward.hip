@@ -139,9 +139,45 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a
 }
 
 // ---------------------------------------------------------------------------------------------
-// CaptionEmbedder backward: dx (B,L,d) * scale is added to the row each token was read from
-// (word embedding / encoded entity / encoded fact) -- mirrors ick_caption_embed's selection.
+// Scatter-adds of the gather stages' backward: one kernel body per stage, the walk chosen by SEQ.  The indices come
+// from the rules the forward kernels use (context_index.h).
+//   atomic (SEQ = false): one wave per source row, lanes stride the columns, terms added with float atomics -- the
+//     hardware picks the order in which a destination row receives its terms.
+//   ordered (SEQ = true; ick_set_deterministic / ICK_DETERMINISTIC=1): a (kDetParts, column blocks of 256) grid.  Every
+//     workgroup walks ALL source rows in index order and workgroup p applies only the terms whose destination key has
+//     key % kDetParts == p: one thread owns one column of a destination row for the whole launch, so its terms arrive
+//     in source order.
 // ---------------------------------------------------------------------------------------------
+constexpr int kDetParts = 32;
+
+template <bool SEQ>
+struct ScatterWalk {
+    int row, row_end;       // source rows [row, row_end)
+    int col, col_step;      // columns col, col + col_step, .. below d
+    int part;
+    __device__ __forceinline__ explicit ScatterWalk(int rows) {
+        if (SEQ) {
+            row = 0; row_end = rows;
+            col = blockIdx.y * 256 + threadIdx.x; col_step = 256 * gridDim.y;       // one column per thread
+            part = blockIdx.x;
+        } else {
+            row = blockIdx.x * 4 + (threadIdx.x >> 6); row_end = min(row + 1, rows);
+            col = threadIdx.x & 63; col_step = 64;
+            part = 0;
+        }
+    }
+    // whether this workgroup applies the terms of destination key `key` (uniform over the workgroup)
+    __device__ __forceinline__ bool owns(int64_t key) const { return !SEQ || (int)(key % kDetParts) == part; }
+    // *dst += v: a float atomic, or the plain read-modify-write of the one thread that owns dst
+    __device__ __forceinline__ void add(float* dst, int64_t key, float v) const {
+        if (!SEQ) atomicAdd(dst, v);
+        else if (owns(key)) *dst += v;
+    }
+};
+
+// CaptionEmbedder backward: dx (B,L,d) * scale is added to the row each token was read from (word embedding /
+// encoded entity / encoded fact: caption_slot()).
+template <bool SEQ>
 __global__ __launch_bounds__(256) void caption_embed_bwd_kernel(const float* __restrict__ dx,
                                                                 const int64_t* __restrict__ captions,
                                                                 const int64_t* __restrict__ masks,
@@ -149,145 +185,87 @@ __global__ __launch_bounds__(256) void caption_embed_bwd_kernel(const float* __r
                                                                 float* __restrict__ dfe, int B, int L, int K, int F,
                                                                 int V, int d, int pad_token, float scale,
                                                                 DropArg darg) {
-    chain_priority();
+    if (!SEQ) chain_priority();
     const Dropout drop = darg.get();
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= B * L) return;
-    const int b = row / L;
-    const int64_t tok = captions[row];
-    const int64_t m = masks[row];
-    float* dst;
-    if (m == 1) {
-        int64_t ei = tok - V;
-        if (ei < 0 || ei >= K) ei = K - 1;
-        dst = dee + ((int64_t)b * K + ei) * d;
-    } else if (m == 2 && dfe != nullptr) {
-        int64_t fi = tok - V - K;
-        if (fi < 0 || fi >= F) fi = F - 1;
-        dst = dfe + ((int64_t)b * F + fi) * d;
-    } else {
-        if (dword == nullptr) return;
-        int64_t w = tok >= V ? (int64_t)pad_token : tok;
-        if (w < 0) w = pad_token;
-        dst = dword + w * d;
-    }
-    const float* src = dx + (int64_t)row * d;
-    for (int c = lane; c < d; c += 64) {
-        float v = src[c] * scale;
-        if (drop.on()) v *= drop.mask((uint32_t)row * (uint32_t)d + (uint32_t)c);   // PositionEncoder dropout
-        // positions past the caption's end carry exactly zero gradient (nothing after them is in the loss) and all
-        // point at the <pad> row: skipping zero addends removes a ~400-way atomic pile-up on that row
-        if (v != 0.f) atomicAdd(dst + c, v);
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Deterministic forms of the scatter-adds above (ick_set_deterministic / ICK_DETERMINISTIC=1).  A float atomic lets the
-// hardware pick the order in which a destination row receives its terms; here the SOURCE rows are walked in index order
-// by every workgroup, and workgroup p applies only the terms whose destination row r has r % kDetParts == p: one
-// thread owns one column of a destination row for the whole launch, so its terms arrive in source order.
-// ---------------------------------------------------------------------------------------------
-constexpr int kDetParts = 32;
-
-__global__ __launch_bounds__(256) void caption_embed_bwd_det_kernel(const float* __restrict__ dx,
-                                                                    const int64_t* __restrict__ captions,
-                                                                    const int64_t* __restrict__ masks,
-                                                                    float* __restrict__ dword, float* __restrict__ dee,
-                                                                    float* __restrict__ dfe, int B, int L, int K, int F,
-                                                                    int V, int d, int pad_token, float scale,
-                                                                    DropArg darg) {
-    const Dropout drop = darg.get();
-    const int p = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
-    for (int row = 0; row < B * L; ++row) {
-        const int b = row / L;
-        const int64_t tok = captions[row];
-        const int64_t m = masks[row];
-        float* dst;
-        int64_t key;
-        if (m == 1) {
-            int64_t ei = tok - V;
-            if (ei < 0 || ei >= K) ei = K - 1;
-            key = (int64_t)b * K + ei;
-            dst = dee + key * d;
-        } else if (m == 2 && dfe != nullptr) {
-            int64_t fi = tok - V - K;
-            if (fi < 0 || fi >= F) fi = F - 1;
-            key = (int64_t)b * F + fi;
-            dst = dfe + key * d;
-            key += 11;
-        } else {
-            if (dword == nullptr) continue;
-            int64_t w = tok >= V ? (int64_t)pad_token : tok;
-            if (w < 0) w = pad_token;
-            key = w + 23;
-            dst = dword + w * d;
+    const ScatterWalk<SEQ> w(B * L);
+    for (int row = w.row; row < w.row_end; ++row) {
+        const CaptionSlot s = caption_slot(captions[row], masks[row], row / L, V, K, F, pad_token, dfe != nullptr);
+        if (s.table == kWordTable && dword == nullptr) continue;
+        // the three tables share the parts; the offsets keep their first rows out of one workgroup
+        const int64_t key = s.row + (s.table == kFactTable ? 11 : (s.table == kWordTable ? 23 : 0));
+        if (!w.owns(key)) continue;
+        float* dst = s.row_of(dword, dee, dfe, d);
+        for (int c = w.col; c < d; c += w.col_step) {
+            float v = dx[(int64_t)row * d + c] * scale;
+            if (drop.on()) v *= drop.mask((uint32_t)row * (uint32_t)d + (uint32_t)c);   // PositionEncoder dropout
+            // positions past the caption's end carry exactly zero gradient (nothing after them is in the loss) and all
+            // point at the <pad> row: skipping zero addends removes a ~400-way atomic pile-up on that row
+            if (v != 0.f) w.add(dst + c, key, v);
         }
-        if ((int)(key % kDetParts) != p || c >= d) continue;       // uniform per workgroup except the column guard
-        float v = dx[(int64_t)row * d + c] * scale;
-        if (drop.on()) v *= drop.mask((uint32_t)row * (uint32_t)d + (uint32_t)c);
-        if (v != 0.f) dst[c] += v;
     }
 }
 
-__global__ __launch_bounds__(256) void entity_encode_bwd_det_kernel(int variant, const float* __restrict__ dee,
-                                                                    const float* __restrict__ ent, int cols,
-                                                                    const float* __restrict__ ee,
-                                                                    const float* __restrict__ word_emb, int vocab,
-                                                                    float* __restrict__ dtype_emb, int ntypes,
-                                                                    float* __restrict__ dword, int B, int K, int d) {
-    const int p = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
-    const int type_off = variant == ICK_GEO ? 4 : (variant == ICK_KNOWLEDGE ? 6 : 5);
-    for (int row = 0; row < B * K; ++row) {
-        const float* e = ent + (int64_t)row * cols;
-        int ty = (int)e[4];
-        ty = ty < 0 ? 0 : (ty >= ntypes ? ntypes - 1 : ty);
-        int name[5] = {0, 0, 0, 0, 0};
-        bool mine = ty % kDetParts == p;
-        if (variant == ICK_NEWS) {
+// EntityEncoder backward: only the type embedding is trainable (feature slots are inputs).  News:
+// e = enc * avg(name words)  =>  d enc = de * avg ; d word_emb[name_w] += de * enc / 5.
+template <bool SEQ>
+__global__ __launch_bounds__(256) void entity_encode_bwd_kernel(int variant, const float* __restrict__ dee,
+                                                                const float* __restrict__ ent, int cols,
+                                                                const float* __restrict__ ee,
+                                                                const float* __restrict__ word_emb, int vocab,
+                                                                float* __restrict__ dtype_emb, int ntypes,
+                                                                float* __restrict__ dword, int B, int K, int d) {
+    if (!SEQ) chain_priority();
+    const ScatterWalk<SEQ> w(B * K);
+    for (int row = w.row; row < w.row_end; ++row) {
+        const EntityIndex ix = entity_index(variant, ent + (int64_t)row * cols, ntypes, vocab);
+        // ordered form: a row none of whose destinations this workgroup owns costs no further loads
+        bool mine = w.owns(ix.type);
+        if (variant == ICK_NEWS && dword != nullptr) {
 #pragma unroll
-            for (int w = 0; w < 5; ++w) {
-                int n = (int)e[5 + w];
-                name[w] = n < 0 ? 0 : (n >= vocab ? vocab - 1 : n);
-                mine = mine || (dword != nullptr && name[w] % kDetParts == p);
+            for (int q = 0; q < 5; ++q) mine = mine || w.owns(ix.name[q]);
+        }
+        if (!mine) continue;
+        for (int c = w.col; c < d; c += w.col_step) {
+            float g = dee[(int64_t)row * d + c];
+            if (variant == ICK_NEWS) {
+                float s = 0.f;
+#pragma unroll
+                for (int q = 0; q < 5; ++q) s += word_emb[(int64_t)ix.name[q] * d + c];
+                const float avg = s / 5.0f;
+                // enc = ee / avg is not recoverable when avg == 0; recompute enc's trainable part instead
+                const float enc_g = g * avg;                       // gradient wrt the un-scaled encoding
+                if (dword) {
+                    // d avg = g * enc ; enc = ee / avg when avg != 0, and the product ee is what we stored
+                    const float enc = avg != 0.f ? ee[(int64_t)row * d + c] / avg : 0.f;
+                    const float gw = g * enc / 5.0f;
+#pragma unroll
+                    for (int q = 0; q < 5; ++q) w.add(dword + (int64_t)ix.name[q] * d + c, ix.name[q], gw);
+                }
+                g = enc_g;
             }
+            if (c >= ix.type_off)
+                w.add(dtype_emb + (int64_t)ix.type * (d - ix.type_off) + (c - ix.type_off), ix.type, g);
         }
-        if (!mine || c >= d) continue;
-        float g = dee[(int64_t)row * d + c];
-        if (variant == ICK_NEWS) {
-            float s = 0.f;
-#pragma unroll
-            for (int w = 0; w < 5; ++w) s += word_emb[(int64_t)name[w] * d + c];
-            const float avg = s / 5.0f;
-            const float enc_g = g * avg;
-            if (dword) {
-                const float enc = avg != 0.f ? ee[(int64_t)row * d + c] / avg : 0.f;
-                const float gw = g * enc / 5.0f;
-#pragma unroll
-                for (int w = 0; w < 5; ++w)
-                    if (name[w] % kDetParts == p) dword[(int64_t)name[w] * d + c] += gw;
-            }
-            g = enc_g;
-        }
-        if (c >= type_off && ty % kDetParts == p) dtype_emb[(int64_t)ty * (d - type_off) + (c - type_off)] += g;
     }
 }
 
-__global__ __launch_bounds__(256) void fact_encode_bwd_det_kernel(const float* __restrict__ dfe,
-                                                                  const int64_t* __restrict__ facts, float* __restrict__ dee,
-                                                                  float* __restrict__ dpred, int num_pred, int B, int K,
-                                                                  int F, int d) {
-    const int p = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
-    for (int row = 0; row < B * F; ++row) {
-        const int b = row / F;
-        const int subj = clamp_row(facts[(int64_t)row * 3 + 1], K);
-        const int pred = clamp_row(facts[(int64_t)row * 3 + 2], num_pred);
-        const bool e_mine = (b * K + subj) % kDetParts == p, p_mine = pred % kDetParts == p;
-        if ((!e_mine && !p_mine) || c >= d) continue;
-        const float g = dfe[(int64_t)row * d + c];
-        if (e_mine) dee[((int64_t)b * K + subj) * d + c] += g;
-        if (p_mine) dpred[(int64_t)pred * d + c] += g;
+// FactEncoder backward: f = ee[subject] + pred_emb[predicate]
+template <bool SEQ>
+__global__ __launch_bounds__(256) void fact_encode_bwd_kernel(const float* __restrict__ dfe,
+                                                              const int64_t* __restrict__ facts, float* __restrict__ dee,
+                                                              float* __restrict__ dpred, int num_pred, int B, int K,
+                                                              int F, int d) {
+    if (!SEQ) chain_priority();
+    const ScatterWalk<SEQ> w(B * F);
+    for (int row = w.row; row < w.row_end; ++row) {
+        const FactPair f = fact_pair(facts, row, K, num_pred);
+        const int64_t erow = (int64_t)(row / F) * K + f.subj;
+        if (!w.owns(erow) && !w.owns(f.pred)) continue;
+        for (int c = w.col; c < d; c += w.col_step) {
+            const float g = dfe[(int64_t)row * d + c];
+            w.add(dee + erow * d + c, erow, g);
+            w.add(dpred + (int64_t)f.pred * d + c, f.pred, g);
+        }
     }
 }
 
@@ -395,75 +373,9 @@ __global__ __launch_bounds__(256) void pointer_bwd_dctx_kernel(const float* __re
   }
 }
 
-// EntityEncoder backward: only the type embedding is trainable (feature slots are inputs).  News:
-// e = enc * avg(name words)  =>  d enc = de * avg ; d word_emb[name_w] += de * enc / 5.
-__global__ __launch_bounds__(256) void entity_encode_bwd_kernel(int variant, const float* __restrict__ dee,
-                                                                const float* __restrict__ ent, int cols,
-                                                                const float* __restrict__ ee,
-                                                                const float* __restrict__ word_emb, int vocab,
-                                                                float* __restrict__ dtype_emb, int ntypes,
-                                                                float* __restrict__ dword, int B, int K, int d) {
-    chain_priority();
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= B * K) return;
-    const float* e = ent + (int64_t)row * cols;
-    const int type_off = variant == ICK_GEO ? 4 : (variant == ICK_KNOWLEDGE ? 6 : 5);
-    int ty = (int)e[4];
-    ty = ty < 0 ? 0 : (ty >= ntypes ? ntypes - 1 : ty);
-    int name[5] = {0, 0, 0, 0, 0};
-    if (variant == ICK_NEWS) {
-#pragma unroll
-        for (int w = 0; w < 5; ++w) {
-            int n = (int)e[5 + w];
-            name[w] = n < 0 ? 0 : (n >= vocab ? vocab - 1 : n);
-        }
-    }
-    for (int c = lane; c < d; c += 64) {
-        float g = dee[(int64_t)row * d + c];
-        if (variant == ICK_NEWS) {
-            float s = 0.f;
-#pragma unroll
-            for (int w = 0; w < 5; ++w) s += word_emb[(int64_t)name[w] * d + c];
-            const float avg = s / 5.0f;
-            // enc = ee / avg is not recoverable when avg == 0; recompute enc's trainable part instead
-            const float enc_g = g * avg;                       // gradient wrt the un-scaled encoding
-            if (dword) {
-                // d avg = g * enc ; enc = ee / avg when avg != 0, and the product ee is what we stored
-                const float enc = avg != 0.f ? ee[(int64_t)row * d + c] / avg : 0.f;
-                const float gw = g * enc / 5.0f;
-#pragma unroll
-                for (int w = 0; w < 5; ++w) atomicAdd(dword + (int64_t)name[w] * d + c, gw);
-            }
-            g = enc_g;
-        }
-        if (c >= type_off) atomicAdd(dtype_emb + (int64_t)ty * (d - type_off) + (c - type_off), g);
-    }
-}
-
-// FactEncoder backward: f = ee[subject] + pred_emb[predicate]
-__global__ __launch_bounds__(256) void fact_encode_bwd_kernel(const float* __restrict__ dfe,
-                                                              const int64_t* __restrict__ facts, float* __restrict__ dee,
-                                                              float* __restrict__ dpred, int num_pred, int B, int K,
-                                                              int F, int d) {
-    chain_priority();
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= B * F) return;
-    const int b = row / F;
-    const int subj = clamp_row(facts[(int64_t)row * 3 + 1], K);
-    const int pred = clamp_row(facts[(int64_t)row * 3 + 2], num_pred);
-    for (int c = lane; c < d; c += 64) {
-        const float g = dfe[(int64_t)row * d + c];
-        atomicAdd(dee + ((int64_t)b * K + subj) * d + c, g);
-        atomicAdd(dpred + (int64_t)pred * d + c, g);
-    }
-}
-
 // Predicate-gate backward (knowledge variants): gate[b,p,:] = bias + sum_{distinct active preds} W[:, pred]
 // => dW[:, pred] += sum over positions where pred is active of dgate[b,p,:];  dbias += sum dgate.
-// Same activation / representative logic as context_indicators_kernel (prefill.hip).
-constexpr int kInf = 0x3fffffff;
+// Activation and representatives are the gate tables context_indicators_kernel builds (context_index.h).
 template <bool SEQ>
 __global__ __launch_bounds__(256) void context_gate_bwd_kernel(const int64_t* __restrict__ captions,
                                                                const int64_t* __restrict__ facts,
@@ -471,39 +383,13 @@ __global__ __launch_bounds__(256) void context_gate_bwd_kernel(const int64_t* __
                                                                float* __restrict__ dbias, int B, int L, int T, int K, int F,
                                                                int V, int num_pred, int d, int mode) {
     extern __shared__ int smi[];
-    int* first = smi;
-    int* act = first + K;
-    int* pred = act + F;
-    int* rep = pred + F;
     const int tid = threadIdx.x;
   for (int b = SEQ ? 0 : blockIdx.x; b < (SEQ ? B : (int)blockIdx.x + 1); ++b) {
-    for (int k = tid; k < K; k += 256) first[k] = kInf;
-    __syncthreads();
-    for (int t = tid; t < L; t += 256) {
-        const int64_t n = captions[(int64_t)b * L + t] - V;
-        if (n >= 0 && n < K) atomicMin(&first[(int)n], t);
-    }
-    __syncthreads();
-    for (int j = tid; j < F; j += 256) {
-        const int64_t subj = facts[((int64_t)b * F + j) * 3 + 1];
-        const int64_t q = facts[((int64_t)b * F + j) * 3 + 2];
-        int a = kInf;
-        if (subj >= 0 && subj < K && first[(int)subj] < kInf) a = mode == 0 ? first[(int)subj] + 1 : 0;
-        act[j] = a;
-        pred[j] = (q >= 0 && q < num_pred) ? (int)q : -1;
-    }
-    __syncthreads();
-    for (int j = tid; j < F; j += 256) {
-        int r = act[j] < kInf && pred[j] >= 0;
-        if (r)
-            for (int i = 0; i < F; ++i)
-                if (i != j && pred[i] == pred[j] && (act[i] < act[j] || (act[i] == act[j] && i < j))) { r = 0; break; }
-        rep[j] = r;
-    }
-    __syncthreads();
+    const GateTables g = build_gate_tables(smi, captions, facts, b, L, K, F, V, num_pred, mode);
+    const int *act = g.act, *pred = g.pred, *rep = g.rep;
     // suffix sums of dgate over positions, once per column (registers walk p = T-1 .. 0, LDS keeps suf[p]): a predicate
     // active from position a gets suf[a] = sum_{p >= a} dgate[b,p,c]  (was: T loads per (fact, column) pair)
-    float* suf = reinterpret_cast<float*>(rep + F);     // T * 256 floats
+    float* suf = reinterpret_cast<float*>(g.end);       // T * 256 floats
     const int c = blockIdx.y * 256 + tid;
     if (c < d) {
         float run = 0.f;
@@ -588,11 +474,11 @@ extern "C" int ick_caption_embed_bwd(const float* dx, const int64_t* captions, c
                                      uint32_t drop_site, const uint32_t* drop_epoch, void* stream) {
     ICK_CHECK_ARG(dx && captions && masks && dee && B > 0 && L > 0 && K > 0 && d > 0);
     if (deterministic())
-        hipLaunchKernelGGL(caption_embed_bwd_det_kernel, dim3(kDetParts, ceil_div(d, 256)), dim3(256), 0,
+        hipLaunchKernelGGL(caption_embed_bwd_kernel<true>, dim3(kDetParts, ceil_div(d, 256)), dim3(256), 0,
                            (hipStream_t)stream, dx, captions, masks, dword, dee, dfe, B, L, K, F, V, d, pad_token, scale,
                            DropArg{drop_p, drop_seed, drop_site, drop_epoch});
     else
-        hipLaunchKernelGGL(caption_embed_bwd_kernel, dim3(ceil_div((int64_t)B * L, 4)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(caption_embed_bwd_kernel<false>, dim3(ceil_div((int64_t)B * L, 4)), dim3(256), 0, (hipStream_t)stream,
                            dx, captions, masks, dword, dee, dfe, B, L, K, F, V, d, pad_token, scale,
                            DropArg{drop_p, drop_seed, drop_site, drop_epoch});
     ICK_LAUNCH_RET();
@@ -632,11 +518,11 @@ extern "C" int ick_entity_encode_bwd(int32_t variant, const float* dee, const fl
     ICK_CHECK_ARG(dee && entities && dtype_emb && B > 0 && K > 0 && d > 6);
     if (variant == ICK_NEWS) ICK_CHECK_ARG(ee && word_emb && vocab > 0);
     if (deterministic())
-        hipLaunchKernelGGL(entity_encode_bwd_det_kernel, dim3(kDetParts, ceil_div(d, 256)), dim3(256), 0,
+        hipLaunchKernelGGL(entity_encode_bwd_kernel<true>, dim3(kDetParts, ceil_div(d, 256)), dim3(256), 0,
                            (hipStream_t)stream, variant, dee, entities, ent_cols, ee, word_emb, vocab, dtype_emb, ntypes,
                            dword, B, K, d);
     else
-        hipLaunchKernelGGL(entity_encode_bwd_kernel, dim3(ceil_div((int64_t)B * K, 4)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(entity_encode_bwd_kernel<false>, dim3(ceil_div((int64_t)B * K, 4)), dim3(256), 0, (hipStream_t)stream,
                            variant, dee, entities, ent_cols, ee, word_emb, vocab, dtype_emb, ntypes, dword, B, K, d);
     ICK_LAUNCH_RET();
 }
@@ -645,10 +531,10 @@ extern "C" int ick_fact_encode_bwd(const float* dfe, const int64_t* facts, float
                                    int32_t B, int32_t K, int32_t F, int32_t d, void* stream) {
     ICK_CHECK_ARG(dfe && facts && dee && dpred && B > 0 && K > 0 && F > 0 && d > 0);
     if (deterministic())
-        hipLaunchKernelGGL(fact_encode_bwd_det_kernel, dim3(kDetParts, ceil_div(d, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(fact_encode_bwd_kernel<true>, dim3(kDetParts, ceil_div(d, 256)), dim3(256), 0, (hipStream_t)stream,
                            dfe, facts, dee, dpred, num_pred, B, K, F, d);
     else
-        hipLaunchKernelGGL(fact_encode_bwd_kernel, dim3(ceil_div((int64_t)B * F, 4)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(fact_encode_bwd_kernel<false>, dim3(ceil_div((int64_t)B * F, 4)), dim3(256), 0, (hipStream_t)stream,
                            dfe, facts, dee, dpred, num_pred, B, K, F, d);
     ICK_LAUNCH_RET();
 }
@@ -658,7 +544,7 @@ extern "C" int ick_context_gate_bwd(const int64_t* captions, const int64_t* fact
                                     int32_t num_pred, int32_t d, int32_t mode, void* stream) {
     ICK_CHECK_ARG(captions && facts && dgate && dw && dbias && B > 0 && L > 0 && K > 0 && F > 0);
     ICK_CHECK_ARG((mode == 0 && T == L) || (mode == 1 && T == 1));
-    const size_t smem = (size_t)(K + 3 * F) * sizeof(int) + (size_t)T * 256 * sizeof(float);
+    const size_t smem = gate_table_ints(K, F) * sizeof(int) + (size_t)T * 256 * sizeof(float);    // + the suffix sums
     ICK_CHECK_ARG(smem <= 64 * 1024);
     if (deterministic())
         hipLaunchKernelGGL(context_gate_bwd_kernel<true>, dim3(1, ceil_div(d, 256)), dim3(256), smem, (hipStream_t)stream,

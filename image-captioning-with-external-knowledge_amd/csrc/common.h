@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "context_index.h"     // clamp_row, token_kind / token_row and the other context index rules
 #include "ick_amd.h"
 
 namespace ick {
@@ -183,11 +184,6 @@ __device__ __forceinline__ int device_bound(int host, const int32_t* dev) {
     return host;                            // (the host pass only parses device code)
 #endif
 }
-// An int64 row index clamped to [0, n - 1] (DESIGN.md §4 deviation 2).  The clamp runs in int64 and only then narrows: an
-// index such as 2^32 + 1 is out of range, not row 1.
-__device__ __forceinline__ int clamp_row(int64_t v, int n) {
-    return (int)(v < 0 ? 0 : (v >= (int64_t)n ? (int64_t)n - 1 : v));
-}
 // Decoding rules of beam search and sampling (ick_decode_rules).  The four rule words
 // {no_repeat_ngram_size, min_len, length penalty on, 0} are device memory written by the host before a (replayed)
 // decode; the first three are read through the scalar cache like epoch_seed()'s counter.  words == nullptr: every
@@ -239,28 +235,6 @@ __device__ __forceinline__ void mark_bans(const Tok* hist, int t, int n, int m, 
 inline bool rules_ok(const ick_decode_ctx* c, const ick_decode_rules* rules, bool beam) {
     if (!(c && rules && rules->words && ((uintptr_t)rules->words & 15) == 0 && c->max_len <= kRuleHistMax)) return false;
     return !beam || (rules->lp && rules->len && c->end_token >= 0 && c->end_token < c->V);
-}
-
-// The next input token of a decode step: its kind (0 word, 1 entity, 2 fact: the caption mask CaptionEmbedder reads) and
-// the embedding row of caption b it stands for, out-of-range indices clamped (geo-aware/models.py:155-181).
-template <typename T>
-__device__ __forceinline__ int token_kind(T tok, int V, int K, bool has_facts) {
-    return (has_facts && tok >= V + K) ? 2 : (tok >= V ? 1 : 0);
-}
-template <typename T>
-__device__ __forceinline__ const float* token_row(T tok, int kind, int64_t b, const float* word_emb, const float* ee,
-                                                  const float* fe, int V, int K, int F, int d, int pad_token) {
-    if (kind == 1) {
-        T e = tok - V;
-        if (e < 0 || e >= K) e = K - 1;
-        return ee + (b * K + e) * d;
-    }
-    if (kind == 2 && fe != nullptr) {
-        T e = tok - V - K;
-        if (e < 0 || e >= F) e = F - 1;
-        return fe + (b * F + e) * d;
-    }
-    return word_emb + (int64_t)(tok >= 0 && tok < V ? tok : (T)pad_token) * d;
 }
 
 struct DropArg {

@@ -24,7 +24,6 @@ __global__ __launch_bounds__(256) void entity_encode_kernel(int variant, const f
     const int b = row / K, k = row - b * K;
     const float* e = ent + (int64_t)row * cols;
     float* o = out + (int64_t)row * d;
-    const int type_off = variant == ICK_GEO ? 4 : (variant == ICK_KNOWLEDGE ? 6 : 5);
 
     // fact count of this entity (knowledge-aware/models.py:101-128); <unk_ent> (last row) -> 0
     float count = 0.f;
@@ -50,32 +49,22 @@ __global__ __launch_bounds__(256) void entity_encode_kernel(int variant, const f
         slot[0] = e[1]; slot[1] = (float)north; slot[2] = (float)east; slot[3] = e[3];
         if (variant == ICK_KNOWLEDGE) { slot[4] = count; slot[5] = count > 0.f ? 1.f : 0.f; }
     }
-    int ty = (int)e[4];
-    ty = ty < 0 ? 0 : (ty >= ntypes ? ntypes - 1 : ty);
-    const float* trow = type_emb + (int64_t)ty * (d - type_off);
-
-    int name[5] = {0, 0, 0, 0, 0};
-    if (variant == ICK_NEWS) {
-#pragma unroll
-        for (int w = 0; w < 5; ++w) {
-            int n = (int)e[5 + w];
-            name[w] = n < 0 ? 0 : (n >= vocab ? vocab - 1 : n);
-        }
-    }
+    const EntityIndex ix = entity_index(variant, e, ntypes, vocab);
+    const float* trow = type_emb + (int64_t)ix.type * (d - ix.type_off);
     for (int c = lane; c < d; c += 64) {
         float v;
-        if (c < type_off) {
+        if (c < ix.type_off) {
             v = slot[0];
 #pragma unroll
             for (int q = 1; q < 6; ++q) v = (c == q) ? slot[q] : v;
         } else {
-            v = trow[c - type_off];
+            v = trow[c - ix.type_off];
         }
         if (variant == ICK_NEWS) {
             // torch.mean over the 5 name-word rows: sequential sum, then divide
-            float s = word_emb[(int64_t)name[0] * d + c];
+            float s = word_emb[(int64_t)ix.name[0] * d + c];
 #pragma unroll
-            for (int w = 1; w < 5; ++w) s = __fadd_rn(s, word_emb[(int64_t)name[w] * d + c]);
+            for (int w = 1; w < 5; ++w) s = __fadd_rn(s, word_emb[(int64_t)ix.name[w] * d + c]);
             v = __fmul_rn(v, __fdiv_rn(s, 5.0f));
         }
         o[c] = v;
@@ -94,10 +83,9 @@ __global__ __launch_bounds__(256) void fact_encode_kernel(const int64_t* __restr
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= B * F) return;
     const int b = row / F;
-    const int subj = clamp_row(facts[(int64_t)row * 3 + 1], K);
-    const int pred = clamp_row(facts[(int64_t)row * 3 + 2], num_pred);
-    const float* s = ee + ((int64_t)b * K + subj) * d;
-    const float* p = pred_emb + (int64_t)pred * d;
+    const FactPair f = fact_pair(facts, row, K, num_pred);
+    const float* s = ee + ((int64_t)b * K + f.subj) * d;
+    const float* p = pred_emb + (int64_t)f.pred * d;
     float* o = out + (int64_t)row * d;
     for (int c = lane; c < d; c += 64) o[c] = __fadd_rn(s[c], p[c]);
 }
@@ -119,22 +107,7 @@ __global__ __launch_bounds__(256) void caption_embed_kernel(const int64_t* __res
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= B * L) return;
     const int b = row / L, l = row - b * L;
-    const int64_t tok = captions[row];
-    const int64_t m = masks[row];
-    const float* src;
-    if (m == 1) {
-        int64_t ei = tok - V;
-        if (ei < 0 || ei >= K) ei = K - 1;  // not an entity pointer -> <unk_ent>, the last row
-        src = ee + ((int64_t)b * K + ei) * d;
-    } else if (m == 2 && fe != nullptr) {
-        int64_t fi = tok - V - K;
-        if (fi < 0 || fi >= F) fi = F - 1;  // -> <unk_fact>
-        src = fe + ((int64_t)b * F + fi) * d;
-    } else {
-        int64_t w = tok >= V ? (int64_t)pad_token : tok;
-        if (w < 0) w = pad_token;
-        src = word_emb + w * d;
-    }
+    const float* src = caption_slot(captions[row], masks[row], b, V, K, F, pad_token, fe != nullptr).row_of(word_emb, ee, fe, d);
     const float* per = pe + (int64_t)(pos0 + l) * d;
     float* o = out + (int64_t)row * d;
     for (int c = lane; c < d; c += 64) {
@@ -148,12 +121,10 @@ __global__ __launch_bounds__(256) void caption_embed_kernel(const int64_t* __res
 
 // ---------------------------------------------------------------------------------------------
 // get_context_indicators, fused with fc_predicate: one workgroup per sample.
-//   act[j]  = first caption position at which fact j's subject counts as "already mentioned"
-//   rep[j]  = fact j is the first (by act, then index) fact carrying its predicate
+//   act / pred / rep: the gate tables of context_index.h
+//   eib[p, j] = act[j] <= p
 //   gate[p] = bias + sum over rep facts with act <= p of fc_predicate.weight[:, pred]   (W^T rows)
 // ---------------------------------------------------------------------------------------------
-constexpr int kInf = 0x3fffffff;
-
 __global__ __launch_bounds__(256) void context_indicators_kernel(const int64_t* __restrict__ captions,
                                                                  const int64_t* __restrict__ facts,
                                                                  const float* __restrict__ wt,
@@ -161,37 +132,9 @@ __global__ __launch_bounds__(256) void context_indicators_kernel(const int64_t* 
                                                                  float* __restrict__ gate, int L, int T, int K, int F,
                                                                  int V, int num_pred, int d, int mode) {
     extern __shared__ int sm[];
-    int* first = sm;        // K
-    int* act = first + K;   // F
-    int* pred = act + F;    // F
-    int* rep = pred + F;    // F
     const int b = blockIdx.x, tid = threadIdx.x;
-    for (int k = tid; k < K; k += 256) first[k] = kInf;
-    __syncthreads();
-    for (int t = tid; t < L; t += 256) {
-        const int64_t n = captions[(int64_t)b * L + t] - V;
-        if (n >= 0 && n < K) atomicMin(&first[(int)n], t);
-    }
-    __syncthreads();
-    for (int j = tid; j < F; j += 256) {
-        const int64_t subj = facts[((int64_t)b * F + j) * 3 + 1];
-        const int64_t q = facts[((int64_t)b * F + j) * 3 + 2];
-        int a = kInf;
-        if (subj >= 0 && subj < K && first[(int)subj] < kInf) a = mode == 0 ? first[(int)subj] + 1 : 0;
-        act[j] = a;
-        pred[j] = (q >= 0 && q < num_pred) ? (int)q : -1;
-    }
-    __syncthreads();
-    for (int j = tid; j < F; j += 256) {
-        int r = act[j] < kInf && pred[j] >= 0;
-        if (r) {
-            for (int i = 0; i < F; ++i) {
-                if (i != j && pred[i] == pred[j] && (act[i] < act[j] || (act[i] == act[j] && i < j))) { r = 0; break; }
-            }
-        }
-        rep[j] = r;
-    }
-    __syncthreads();
+    const GateTables g = build_gate_tables(sm, captions, facts, b, L, K, F, V, num_pred, mode);
+    const int *act = g.act, *pred = g.pred, *rep = g.rep;
     // entity_idx_before (written by the first workgroup of the sample's column split)
     for (int idx = tid; blockIdx.y == 0 && idx < T * F; idx += 256) {
         const int p = idx / F, j = idx - p * F;
@@ -201,7 +144,7 @@ __global__ __launch_bounds__(256) void context_indicators_kernel(const int64_t* 
     // fact becomes active, so the facts are ranked by (act, index) once and the running sum walks that list
     // (same summation order as a position-by-position, fact-by-fact scan, ~T + F steps instead of T * F)
     if (gate) {
-        int* ord_act = rep + F;     // F
+        int* ord_act = g.end;       // F
         int* ord_pred = ord_act + F;  // F
         int* nrep = ord_pred + F;   // 1
         if (tid == 0) *nrep = 0;
@@ -293,7 +236,7 @@ extern "C" int ick_context_indicators(const int64_t* captions, const int64_t* fa
     ICK_CHECK_ARG(captions && facts && eib && B > 0 && L > 0 && K > 0 && F > 0);
     ICK_CHECK_ARG((mode == 0 && T == L) || (mode == 1 && T == 1));
     if (gate) ICK_CHECK_ARG(num_pred > 0 && d > 0 && ((fc_pred_wt && fc_pred_b) || (!fc_pred_wt && d == num_pred)));
-    const size_t smem = (size_t)(K + 5 * F + 1) * sizeof(int);
+    const size_t smem = (gate_table_ints(K, F) + 2 * (size_t)F + 1) * sizeof(int);    // + the gate's ordering: 2 F + 1
     ICK_CHECK_ARG(smem <= 64 * 1024);
     const int csplit = gate ? std::max(1, std::min(4, ceil_div(d, 256))) : 1;   // workgroups per sample (gate columns)
     hipLaunchKernelGGL(context_indicators_kernel, dim3(B, csplit), dim3(256), smem, (hipStream_t)stream, captions, facts,

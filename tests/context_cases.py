@@ -1,6 +1,7 @@
 """Case table of the context, embedding and pointer kernels' envelope: the entity / fact encoders, the caption embedder,
 the context indicators with the predicate gate (csrc/prefill.hip), their backward kernels (csrc/backward.hip from
-caption_embed_bwd_kernel down to context_gate_bwd_kernel) and pointer_scores_kernel (csrc/score_head.hip).
+caption_embed_bwd_kernel down to context_gate_bwd_kernel), the index rules all of them decode through
+(csrc/context_index.h) and pointer_scores_kernel (csrc/score_head.hip).
 tests/test_context_envelope_gpu.py runs every case against tests/context_ref.py; tests/test_context_ref_cpu.py checks
 that the table reaches every hand-placed index it promises.
 
