@@ -43,12 +43,6 @@ extern "C" int ick_debug_read_gemm_stamps(unsigned long long* out, int n) {
 #endif
 
 namespace ick {
-
-int launch_gemm_ps(const ick_gemm_args& a, bool akm, int tile, int tiles_m, int tiles_n, int kchunk, int split, int a_nt,
-                   hipStream_t s);      // gemm_ps.hip
-void gemm_ps_tile_dims(int tile, int* bm, int* bn, int* wgs_per_cu);
-int gemm_ps_tile_count();
-
 namespace {
 
 
@@ -558,10 +552,11 @@ struct Plan {
     bool big;                    // 64 x 64 tiles (else 32 x 32)
     bool wide;                   // 128 x 64 tiles, 8 waves (single launches only)
     bool spl;                    // split-bf16 products (64 x 64 and 128 x 64 tiles of the vector path)
-    bool xl;                     // 128 x 128 tiles, 8 waves, split products only (single launches only; implies wide)
+    bool xl;                     // 128 x 128 tiles, 4 waves, split products only (single launches only; implies wide)
     bool ps;                     // B read from its pre-split copy (gemm_ps.hip) ...
-    int ps_tile, ps_nt;          // ... on tile shape ps_tile (gemm_ps_tile_dims), A loads non-temporal when ps_nt
+    PsTile ps_tile;              // ... on this tile (gemm_ps_tile)
     bool kmap;                   // an operand gathers its k lines through a map: the MAP instantiations (four-wave tiles)
+    int tile_m, tile_n, waves;   // the workgroup tile and the waves that share it, as launched
     int tiles_m, tiles_n, kchunk, split;
 };
 
@@ -745,16 +740,15 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
         if (pl.xl) pl.wide = true;
     }
     const int BMN = pl.big ? 64 : 32;
-    pl.tiles_m = ceil_div(a.M, pl.wide ? 128 : BMN); pl.tiles_n = ceil_div(a.N, pl.xl ? 128 : BMN);
+    pl.tile_m = pl.wide ? 128 : BMN; pl.tile_n = pl.xl ? 128 : BMN;
+    pl.waves = pl.wide && !pl.xl ? 8 : 4;      // (launch_plan: launch_wide; launch_xl4 and launch_one)
     pl.kchunk = ceil_div(ceil_div(a.K, split_req), 32) * 32;
     pl.split = ceil_div(a.K, pl.kchunk);
     // B pre-split by the caller (b_ps): both operands staged by LDS-DMA, only the A fragments split in the kernel
     // (gemm_ps.hip).  Needs the vector conditions on A (16-byte pieces) and a problem large enough for its tiles.
-    pl.ps = false; pl.ps_tile = 0; pl.ps_nt = 0;
+    pl.ps = false; pl.ps_tile = kPs128x128;
     if (a.b_ps != nullptr && gemm_split_mode() >= 1 && avec && aligned16(a.b_ps) && a.a_extent >= 4 &&
         a_need <= a.a_extent + 3 && a.colsum_a == nullptr && !(a.flags & ICK_GEMM_COLSUM_ONLY)) {
-        static int ps_tile_env = -2;      // ICK_PS_TILE: one tile shape for every pre-split problem (tools/gemm_ps_bench.py sweeps)
-        if (ps_tile_env == -2) { const char* e = getenv("ICK_PS_TILE"); ps_tile_env = e ? atoi(e) : -1; }
         const double flop = 2.0 * a.M * a.N * a.K;
         // a one-column-tile problem (N <= 320, no K split) needs ~180 row tiles of 128 to fill the chip with the pre-split
         // kernel's 128-row tiles (Encoder.conv1 at batch 32 -- 98 workgroups -- took as long as at batch 64).  Below that
@@ -767,7 +761,7 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
         const bool narrow_small_tile = narrow_underfilled && ceil_div(a.M, 64) * ceil_div(a.N, 160) >= 128;
         // the pre-split copy is addressed through one buffer descriptor: it must stay below 2 GiB
         const bool ps_fits = (int64_t)ceil_div(a.K, 32) * 3 * ceil_div(a.N, 64) * 64 * 64 < ((int64_t)1 << 31);
-        if (ps_fits && flop >= 1.0e9 && a.M >= 256 && a.N >= 128 && (!narrow_underfilled || narrow_small_tile || ps_tile_env >= 0)) {
+        if (ps_fits && flop >= 1.0e9 && a.M >= 256 && a.N >= 128 && (!narrow_underfilled || narrow_small_tile)) {
             // Tile choice, measured (tools/gemm_ps_bench.py, profiles/r04_e_gemm_ps_tiles.txt: every tile x every shape):
             // 128 x 128 with two workgroups per CU wins wherever the output is wider than 320 columns (cross K/V 100 us
             // against 129-143 on the other tiles, vocabulary 65 against 80-88); outputs at most 320 wide (Encoder.conv1,
@@ -780,20 +774,18 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
             // workgroups cannot share a CU with a 139 KB tile: on 128 x 80 (62 KB, two per CU; alone 2-8 % slower than
             // 128 x 160) the cfg2 train step is 1.748 -> 1.722 ms and the forward pass 0.702 -> 0.693
             // (profiles/r04_y_ab_narrow_tile.txt)
-            int best = narrow ? (narrow_small_tile ? 8 : 9) : 1;
+            pl.ps_tile = narrow ? (narrow_small_tile ? kPs64x160 : kPs128x80) : kPs128x128;
             // split-K problems at most 320 columns wide (the vocabulary's data gradient 1280 x 300 over K = 10 000, the
             // cross K/V and vocabulary weight gradients): 128 x 80 as well -- the data gradient's 40 x 12 = 480 workgroups
             // fill the chip's two slots per CU once (train step 1.770 -> 1.741 ms), the weight gradients are unchanged
-            if (a.N <= 320 && split_req > 1) best = 9;
-            if (ps_tile_env >= 0 && ps_tile_env < gemm_ps_tile_count()) best = ps_tile_env;
-            int bm, bn, wpc; gemm_ps_tile_dims(best, &bm, &bn, &wpc);
-            pl.ps = true; pl.ps_tile = best;
+            if (a.N <= 320 && split_req > 1) pl.ps_tile = kPs128x80;
+            const PsTileInfo t = gemm_ps_tile(pl.ps_tile);
+            pl.ps = true;
             pl.spl = true; pl.big = true; pl.wide = pl.xl = false;
-            pl.tiles_m = ceil_div(a.M, bm);
-            pl.tiles_n = ceil_div(a.N, bn);
-            pl.ps_nt = 0;    // non-temporal A loads: measured, no gain (same file)
+            pl.tile_m = t.bm; pl.tile_n = t.bn; pl.waves = t.waves;
         }
     }
+    pl.tiles_m = ceil_div(a.M, pl.tile_m); pl.tiles_n = ceil_div(a.N, pl.tile_n);
     return ICK_OK;
 }
 
@@ -815,7 +807,7 @@ int make_plan(const ick_gemm_args* in, Plan& pl, int force_big = 0) {
 #define ICK_COMMA_FALSE , false
 
 int launch_plan(const Plan& pl, hipStream_t s) {
-    if (pl.ps) return launch_gemm_ps(pl.a, pl.akm, pl.ps_tile, pl.tiles_m, pl.tiles_n, pl.kchunk, pl.split, pl.ps_nt, s);
+    if (pl.ps) return launch_gemm_ps(pl.a, pl.akm, pl.ps_tile, pl.tiles_m, pl.tiles_n, pl.kchunk, pl.split, s);
     if (pl.kmap) {
         if (!pl.vec) ICK_BY_LAYOUT_MAP(launch_one, 2, 2, ICK_COMMA_FALSE, pl, s);
         if (pl.big) ICK_BY_LAYOUT_MAP(launch_one, 2, 2, ICK_COMMA_TRUE, pl, s);
@@ -859,14 +851,8 @@ extern "C" int ick_gemm_plan(const ick_gemm_args* in, ick_gemm_plan_info* out) {
     if (!out) return ICK_EINVAL;
     Plan pl;
     if (int rc = make_plan(in, pl)) return rc;
-    const int bmn = pl.big ? 64 : 32;
-    out->tile_m = pl.wide ? 128 : bmn; out->tile_n = pl.xl ? 128 : bmn; out->waves = pl.wide ? 8 : 4;   // (xl: 4 or 8, ICK_GEMM_XL4)
+    out->tile_m = pl.tile_m; out->tile_n = pl.tile_n; out->waves = pl.waves;
     out->presplit = pl.ps;
-    if (pl.ps) {
-        int wpc;
-        gemm_ps_tile_dims(pl.ps_tile, &out->tile_m, &out->tile_n, &wpc);
-        out->waves = (pl.ps_tile == 7 || pl.ps_tile == 8) ? 4 : 8;      // the four-wave tiles of csrc/gemm_ps.hip
-    }
     out->tiles_m = pl.tiles_m; out->tiles_n = pl.tiles_n; out->split_k = pl.split;
     out->a_kmajor = pl.akm; out->b_kmajor = pl.bkm; out->vec = pl.vec;
     out->split_bf16 = pl.spl;

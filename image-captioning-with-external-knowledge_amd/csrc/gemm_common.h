@@ -5,6 +5,13 @@
 #include "common.h"
 
 namespace ick {
+
+// The tiles of the pre-split kernel (gemm_ps.hip): make_plan (gemm.hip) picks one by name and reads its record.
+enum PsTile { kPs128x128, kPs64x160, kPs128x80 };
+struct PsTileInfo { int bm, bn, waves, wgs_per_cu; };
+PsTileInfo gemm_ps_tile(PsTile tile);
+int launch_gemm_ps(const ick_gemm_args& a, bool akm, PsTile tile, int tiles_m, int tiles_n, int kchunk, int split, hipStream_t s);
+
 namespace {
 
 struct RowMap {  // offset of logical row r:  goff(r / grp) + (r % grp) * rs

@@ -13,20 +13,20 @@
 //   * every tile slice travels global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction): the
 //     pre-split B planes in the MFMA operand's image (64-byte rows, XOR-swizzled chunks -- the swizzle is applied to
 //     the SOURCE address, the LDS side of a DMA is lane-linear), the A tile as raw fp32;
-//   * both operands run through rings of D + 1 LDS buffers, D slices in flight ahead of the one being read; the only
-//     waits are counted s_waitcnt vmcnt(N) + one raw s_barrier per slice (with D = 2 every wave issues the same number
-//     of pieces per slice -- a zero fill into a scratch KiB where a wave has one piece less -- so N is an immediate);
+//   * both operands run through two LDS buffers, one slice in flight ahead of the one being read; the only waits are
+//     one s_waitcnt vmcnt(0) + one raw s_barrier per slice;
 //   * a wave owns TM x 16 rows x (TN x 16) columns: it requests its B fragments (PF blocks ahead, or the whole slice),
 //     reads its raw A fragment (k-major: eight ds_read_b32 from a line image rotated by 16 floats per 8 k lines;
 //     k-contiguous: two ds_read_b128 from 128-byte rows with XOR-swizzled chunks -- both conflict free: PMC
 //     SQ_LDS_BANK_CONFLICT = 0), splits it (44 VALU) and issues 6 x TM x TN v_mfma_f32_16x16x32_bf16;
-//   * tile shapes: see launch_gemm_ps below.  Measured (tools/gemm_ps_bench.py, profiles/r04_*_gemm_ps_tiles.txt, PMC
-//     profiles/r04_c_pmc_gemm_ps.txt): 128 x 128 with two workgroups per CU is the fastest wherever the output is wider
-//     than 320 columns (cross K/V 128 -> 100 us, vocabulary 76 -> 65 us against the stager-split kernel), 128 x 160 for
-//     Encoder.conv1 (121 us: level with the stager-split 128 x 64 tile).  Ring depth, fragment prefetch depth, tile
-//     size and non-temporal A loads all leave the rate at 120-135 TFLOP/s fp32-equivalent with the matrix pipe ~50 %
-//     busy on the CUs in use -- about 60 % of what bf16 MFMA loops hold on random data at the clock the chip keeps under
-//     that load (MI355X_MICROARCH.md, DVFS give-back: 1.25 PFLOP/s at 1.9 GHz, i.e. ~208 TFLOP/s fp32-equivalent).
+//   * tile shapes: the three of the table above launch_gemm_ps below, all two workgroups per CU.  Measured
+//     (profiles/r04_*_gemm_ps_tiles.txt, PMC profiles/r04_c_pmc_gemm_ps.txt): 128 x 128 is the fastest wherever the
+//     output is wider than 320 columns (cross K/V 128 -> 100 us, vocabulary 76 -> 65 us against the stager-split
+//     kernel).  Ring depth, fragment prefetch depth, tile size and non-temporal A loads all left the rate at 120-135
+//     TFLOP/s fp32-equivalent with the matrix pipe ~50 % busy on the CUs in use -- about 60 % of what bf16 MFMA loops
+//     hold on random data at the clock the chip keeps under that load (MI355X_MICROARCH.md, DVFS give-back: 1.25
+//     PFLOP/s at 1.9 GHz, i.e. ~208 TFLOP/s fp32-equivalent).  The variants of those sweeps (eight more tile shapes,
+//     ring depths 2 and 3) are no longer in the source: DESIGN.md section 3.1c.
 #include <algorithm>
 
 #include "gemm_common.h"
@@ -131,11 +131,11 @@ __global__ __launch_bounds__(256) void presplit_kernel(PsBatch b) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
-template <int WM_, int WN_, int TM_, int TN_, bool AKM_, int D_, int PF_>
+template <int WM_, int WN_, int TM_, int TN_, bool AKM_, int PF_>
 struct PsCfg {
-    static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_, D = D_;   // D: slices in flight ahead of the one being read
+    static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_;
     static constexpr int PF = PF_ < TN_ ? PF_ : TN_;   // B fragment blocks requested from LDS ahead of the MFMAs that use them
-    static constexpr int ST = D + 1;                                         // ring buffers per operand
+    static constexpr int ST = 2;                        // LDS buffers per operand: the slice being read and the next one
     static constexpr bool AKM = AKM_;
     static constexpr int BM = WM * TM * 16, BN = WN * TN * 16, NW = WM * WN, NT = NW * 64;
     static constexpr int A_STAGE = BM * 32 * 4;          // bytes: raw fp32 slice of the A tile
@@ -145,26 +145,23 @@ struct PsCfg {
     static constexpr int NPB = 3 * BN / 16;              // ... of a B slice (16 rows of one plane each)
     static constexpr int PA_W = NPA / NW;                // pieces per wave
     static constexpr int PB_W = (NPB + NW - 1) / NW;
-    // D >= 2: the waits are counted (s_waitcnt vmcnt(N) with N pieces of the younger slices still in flight), so every
-    // wave must issue the SAME number of pieces per slice: the waves that have one B piece less send a zero fill into a
-    // 1 KiB scratch area instead
-    static constexpr bool UNIFORM = D >= 2;
-    static constexpr int SCRATCH = UNIFORM && (NPB % NW != 0) ? 1024 : 0;
-    static constexpr int LDS = ST * (A_STAGE + B_STAGE) + SCRATCH;
-    static constexpr int IN_FLIGHT = (D - 1) * (PA_W + PB_W);   // pieces of the younger slices at the end of an iteration
-    static_assert(NPA % NW == 0 && PA_W >= 1, "every wave issues the same number of A pieces (counted vmcnt)");
-    static_assert(D == 1 || D == 2, "ring depth");
+    static constexpr int LDS = ST * (A_STAGE + B_STAGE);
+    static constexpr int WGS_PER_CU = 160 * 1024 / LDS;  // what the LDS footprint leaves room for
+    // waves per SIMD the register allocator may plan for: those of the workgroups that share a CU, on its 4 SIMDs (4 for
+    // the eight-wave tiles, 2 for the four-wave tile: 256 VGPRs each, enough to hold a whole slice's B fragments)
+    static constexpr int WAVES_PER_EU = WGS_PER_CU * NW / 4;
+    static_assert(NPA % NW == 0 && PA_W >= 1, "every wave issues the same number of A pieces");
     static_assert(LDS <= 160 * 1024, "tile exceeds the LDS of a CU");
 };
 
-#define ICK_WAIT_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
+#define ICK_WAIT_VMCNT0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 // every wave is done reading the slice (its LDS reads have been consumed by MFMAs; the explicit wait covers reads the
 // compiler may have left in flight) and its DMA pieces have landed: one barrier publishes both
 #define ICK_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // One slice of the B tile / of the A tile by LDS-DMA: this wave's 1 KiB pieces (see the kernel below).
 template <class C>
-__device__ __forceinline__ void ps_dma_b(const __amdgpu_buffer_rsrc_t& rsrc, char* Bs, char* scratch, int buf, int wave,
+__device__ __forceinline__ void ps_dma_b(const __amdgpu_buffer_rsrc_t& rsrc, char* Bs, int buf, int wave,
                                          uint32_t bvoff, int slice, bool valid, int n0, int np_rows) {
 #pragma unroll
     for (int j = 0; j < C::PB_W; ++j) {
@@ -175,13 +172,11 @@ __device__ __forceinline__ void ps_dma_b(const __amdgpu_buffer_rsrc_t& rsrc, cha
             const uint32_t soff = (uint32_t)((((int64_t)slice * 3 + plane) * np_rows + rblk * 16) * 64);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_ptr)(Bs + buf * C::B_STAGE + plane * C::B_PLANE + rblk * 1024),
                                                      16, in ? bvoff : kOobOffset, in ? soff : 0u, 0, 0);
-        } else if (C::UNIFORM) {        // keeps this wave's piece count equal to the others': a zero fill nobody reads
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_ptr)scratch, 16, kOobOffset, 0u, 0, 0);
         }
     }
 }
-// nt: the A operand is read once by the whole launch (one column tile): a non-temporal load keeps it from evicting the
-// weight planes, which every workgroup of the XCD re-reads, from that XCD's L2
+// nt: non-temporal loads.  Measured without gain and always false: launch_ps_cfg passes 0.  The
+// kernel argument and this arm stay because the compiler schedules the K loop differently without them.
 template <class C>
 __device__ __forceinline__ void ps_dma_a(const __amdgpu_buffer_rsrc_t& rsrc, char* As, int buf, int wave,
                                          const uint32_t* avoff, const int* akl, int k0, int kend,
@@ -201,7 +196,7 @@ __device__ __forceinline__ void ps_dma_a(const __amdgpu_buffer_rsrc_t& rsrc, cha
 // per slice: a CU's address unit takes one 1 KiB wave request per 16 cycles -- tools/debug/gemm_ps_stamps.py.)
 template <class C>
 __device__ __forceinline__ void ps_dma_piece(int idx, const __amdgpu_buffer_rsrc_t& rsrc_a, const __amdgpu_buffer_rsrc_t& rsrc_b,
-                                             char* As, char* Bs, char* scratch, int buf, int wave, uint32_t bvoff,
+                                             char* As, char* Bs, int buf, int wave, uint32_t bvoff,
                                              const uint32_t* avoff, const int* akl, int slice, bool valid,
                                              int n0, int np_rows, int k0, int kend, uint32_t soff_a) {
     if (idx < C::PB_W) {
@@ -212,8 +207,6 @@ __device__ __forceinline__ void ps_dma_piece(int idx, const __amdgpu_buffer_rsrc
             const uint32_t soff = (uint32_t)((((int64_t)slice * 3 + plane) * np_rows + rblk * 16) * 64);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_void_ptr)(Bs + buf * C::B_STAGE + plane * C::B_PLANE + rblk * 1024),
                                                      16, in ? bvoff : kOobOffset, in ? soff : 0u, 0, 0);
-        } else if (C::UNIFORM) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_void_ptr)scratch, 16, kOobOffset, 0u, 0, 0);
         }
     } else {
         const int j = idx - C::PB_W;
@@ -224,14 +217,12 @@ __device__ __forceinline__ void ps_dma_piece(int idx, const __amdgpu_buffer_rsrc
     }
 }
 
-// waves per SIMD the register allocator may plan for: 2 when the tile's LDS footprint leaves room for one workgroup per CU
-// (8 waves on 4 SIMDs: 256 VGPRs each, enough to hold a whole slice's B fragments), 4 for the two-workgroup tile
-template <int WM_, int WN_, int TM_, int TN_, bool AKM_, int D_, int PF_>
+template <int WM_, int WN_, int TM_, int TN_, bool AKM_, int PF_>
 __global__ __launch_bounds__(WM_ * WN_ * 64)
-__attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>::LDS > 80 * 1024 || WM_ * WN_ <= 4 ? 2 : 4)))) void gemm_ps_kernel(ick_gemm_args p, int np_rows, int64_t bps_bytes, int tiles_m,
-                                                                 int tiles_n, int kchunk, int a_nt) {
-    using C = PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>;
-    constexpr int BM = C::BM, BN = C::BN, TM = C::TM, TN = C::TN, NW = C::NW, D = C::D, ST = C::ST;
+__attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, PF_>::WAVES_PER_EU)))) void gemm_ps_kernel(
+    ick_gemm_args p, int np_rows, int64_t bps_bytes, int tiles_m, int tiles_n, int kchunk, int a_nt) {
+    using C = PsCfg<WM_, WN_, TM_, TN_, AKM_, PF_>;
+    constexpr int BM = C::BM, BN = C::BN, TM = C::TM, TN = C::TN, NW = C::NW, ST = C::ST;
     constexpr bool AKM = C::AKM;
     extern __shared__ __attribute__((aligned(1024))) char smem_ps[];
 #ifdef ICK_PS_STAMPS
@@ -241,7 +232,6 @@ __attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>:
 #endif
     char* const As = smem_ps;
     char* const Bs = smem_ps + ST * C::A_STAGE;
-    char* const scratch = Bs + ST * C::B_STAGE;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     constexpr int WN = C::WN;
@@ -321,7 +311,7 @@ __attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>:
         __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.b_ps), (short)0, (int)bps_bytes, 0x00020000);
     const uint32_t bvoff = (uint32_t)((n0 + (lane >> 2)) * 64 + (((lane & 3) ^ ((-(lane >> 4)) & 3)) * 16));
 
-    auto dma_b = [&](int it, int buf) { ps_dma_b<C>(rsrc_b, Bs, scratch, buf, wave, bvoff, s0 + it, it < nk, n0, np_rows); };
+    auto dma_b = [&](int it, int buf) { ps_dma_b<C>(rsrc_b, Bs, buf, wave, bvoff, s0 + it, it < nk, n0, np_rows); };
     auto dma_a = [&](int it, int buf) {
         const int k0 = kbeg + 32 * it;
         const uint32_t soff = it < nk ? (uint32_t)(AKM ? (int64_t)k0 * p.a_ks * 4 : (int64_t)k0 * 4) : 0u;
@@ -334,29 +324,30 @@ __attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>:
 #pragma unroll
         for (int b = 0; b < TN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // prologue: slices 0 .. D-1 (B then A of each); the first must have landed
+    // prologue: the slices ahead of the K loop, one per buffer but the last (B then A); they must have landed.  (A loop of
+    // one trip: with the two calls written out the compiler schedules the K loop differently, 40 instructions longer on
+    // the 64 x 160 tile.)
 #pragma unroll
-    for (int i = 0; i < D; ++i) { dma_b(i, i); dma_a(i, i); }
-    ICK_WAIT_VMCNT(C::IN_FLIGHT);
+    for (int i = 0; i < ST - 1; ++i) { dma_b(i, i); dma_a(i, i); }
+    ICK_WAIT_VMCNT0();
     ICK_LDS_BARRIER();
 
 #ifdef ICK_PS_STAMPS
     unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, ta = 0, tb = 0, tc = 0, td = 0, te = 0, tf = 0;
     ICK_PSTAMP(t_loop);
 #endif
-    int buf = 0;                             // ring buffer holding slice `it`
+    int buf = 0;                             // LDS buffer holding slice `it`
     for (int it = 0; it < nk; ++it) {
         ICK_PSTAMP(ta);
-        // slice it + D goes into the buffer that was read in iteration it - 1 (slices beyond the range are zero fills that
-        // touch no memory: the piece counts stay constant, so the waits below are immediates); its pieces are issued one
-        // by one between the MFMAs below
-        int nb = buf + D;
+        // slice it + 1 goes into the buffer that was read in iteration it - 1 (a slice beyond the range is a zero fill that
+        // touches no memory); its pieces are issued one by one between the MFMAs below
+        int nb = buf + 1;
         if (nb >= ST) nb -= ST;
-        const int k0_nx = kbeg + 32 * (it + D);
-        const uint32_t soff_nx = it + D < nk ? (uint32_t)(AKM ? (int64_t)k0_nx * p.a_ks * 4 : (int64_t)k0_nx * 4) : 0u;
+        const int k0_nx = kbeg + 32 * (it + 1);
+        const uint32_t soff_nx = it + 1 < nk ? (uint32_t)(AKM ? (int64_t)k0_nx * p.a_ks * 4 : (int64_t)k0_nx * 4) : 0u;
         auto piece = [&](int idx) {
-            ps_dma_piece<C>(idx, rsrc_a, rsrc_b, As, Bs, scratch, nb, wave, bvoff, avoff, akl, s0 + it + D, it + D < nk, n0,
-                            np_rows, k0_nx, kend, soff_nx);
+            ps_dma_piece<C>(idx, rsrc_a, rsrc_b, As, Bs, nb, wave, bvoff, avoff, akl, s0 + it + 1, it + 1 < nk, n0, np_rows,
+                            k0_nx, kend, soff_nx);
         };
         const int abuf = buf, bbuf = buf;
         ICK_PSTAMP(tb);
@@ -425,10 +416,10 @@ __attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>:
                         if (b < TN)
                             acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a][pa[q]], bf[g & 1][j][pb[q]], acc[a][b], 0, 0, 0);
                     }
-                // one DMA piece of slice it + D per slot; with D = 1 the pieces go out in the first half of the slots (they
-                // must have landed by the end of this iteration), with D >= 2 over all of them
+                // one DMA piece of slice it + 1 per slot, in the first half of the slots (they must have landed by the end of
+                // this iteration)
                 constexpr int NS = NG * 6, NP = C::PB_W + C::PA_W;
-                constexpr int SPAN = D >= 2 ? NS : (NS + 1) / 2;
+                constexpr int SPAN = (NS + 1) / 2;
                 constexpr int STRIDE = SPAN / NP > 0 ? SPAN / NP : 1;
                 const int slot = g * 6 + q;
                 if (slot % STRIDE == 0 && slot / STRIDE < NP) piece(slot / STRIDE);
@@ -439,8 +430,8 @@ __attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>:
             }
         }
         ICK_PSTAMP(td);
-        // slice it + 1 has landed (in-order completion: only the pieces of the D - 1 younger slices may remain)
-        ICK_WAIT_VMCNT(C::IN_FLIGHT);
+        // slice it + 1 has landed
+        ICK_WAIT_VMCNT0();
         ICK_PSTAMP(te);
         ICK_LDS_BARRIER();
         ICK_PSTAMP(tf);
@@ -453,7 +444,7 @@ __attribute__((amdgpu_waves_per_eu(1, (PsCfg<WM_, WN_, TM_, TN_, AKM_, D_, PF_>:
     ICK_PSTAMP(t_end);
     const unsigned long long t_loop_end = t_end;
 #endif
-    ICK_WAIT_VMCNT(0);       // the zero fills of the last iterations write LDS too: none may outlive the workgroup
+    ICK_WAIT_VMCNT0();       // the zero fill of the last iteration writes LDS too: it may not outlive the workgroup
     gemm_epilogue<TM, TN>(p, Mr, acc, m0, n0, wm, wn, fi, fq, zid);
 #ifdef ICK_PS_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stores of the epilogue have been acknowledged
@@ -473,69 +464,48 @@ namespace {
 
 template <class C>
 int launch_ps_cfg(const ick_gemm_args& a, int np_rows, int64_t bytes, int tiles_m, int tiles_n, int kchunk, int split,
-                  int a_nt, hipStream_t s) {
+                  hipStream_t s) {
     static LdsAttrOnce attr;
-    if (int e = attr.ensure(reinterpret_cast<const void*>(gemm_ps_kernel<C::WM, C::WN, C::TM, C::TN, C::AKM, C::D, C::PF>), 160 * 1024))
+    if (int e = attr.ensure(reinterpret_cast<const void*>(gemm_ps_kernel<C::WM, C::WN, C::TM, C::TN, C::AKM, C::PF>), 160 * 1024))
         return e;
-    hipLaunchKernelGGL((gemm_ps_kernel<C::WM, C::WN, C::TM, C::TN, C::AKM, C::D, C::PF>), dim3(tiles_m * tiles_n, 1, split),
-                       dim3(C::NT), C::LDS, s, a, np_rows, bytes, tiles_m, tiles_n, kchunk, a_nt);
+    hipLaunchKernelGGL((gemm_ps_kernel<C::WM, C::WN, C::TM, C::TN, C::AKM, C::PF>), dim3(tiles_m * tiles_n, 1, split),
+                       dim3(C::NT), C::LDS, s, a, np_rows, bytes, tiles_m, tiles_n, kchunk, /*a_nt=*/0);
     ICK_LAUNCH_RET();
 }
 
-template <int WM, int WN, int TM, int TN, int D, int PF>
-int launch_ps_tile(const ick_gemm_args& a, bool akm, int np, int64_t bytes, int tiles_m, int tiles_n, int kchunk, int split,
-                   int a_nt, hipStream_t s) {
-    if (akm) return launch_ps_cfg<PsCfg<WM, WN, TM, TN, true, D, PF>>(a, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-    return launch_ps_cfg<PsCfg<WM, WN, TM, TN, false, D, PF>>(a, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
+// The tiles of the pre-split kernel: waves as WM x WN, wave tile TM x TN blocks of 16 x 16, PF = B fragment blocks requested
+// ahead of their MFMAs.  Two workgroups per CU each: they are not barrier-coupled, so their fragment and MFMA phases overlap.
+//   128 x 128  8 x 1 waves of 16 x 128, PF 2, 80 KB of LDS   <- outputs wider than 320 columns
+//   64 x 160   2 x 2 waves of 32 x 80, PF 5, 76 KB           <- one column tile pair, too few rows to fill the chip by 128
+//   128 x 80   8 x 1 waves of 16 x 80, PF 2, 62 KB           <- outputs at most 320 wide: Encoder.conv1, split-K gradients
+template <bool AKM> using Ps128x128 = PsCfg<8, 1, 1, 8, AKM, 2>;
+template <bool AKM> using Ps64x160 = PsCfg<2, 2, 2, 5, AKM, 5>;
+template <bool AKM> using Ps128x80 = PsCfg<8, 1, 1, 5, AKM, 2>;
+
+// f(the PsCfg of `tile` for this A layout)
+template <class F>
+auto with_ps_tile(PsTile tile, bool akm, F f) {
+    switch (tile) {
+        case kPs128x128: return akm ? f(Ps128x128<true>{}) : f(Ps128x128<false>{});
+        case kPs64x160: return akm ? f(Ps64x160<true>{}) : f(Ps64x160<false>{});
+        case kPs128x80: return akm ? f(Ps128x80<true>{}) : f(Ps128x80<false>{});
+    }
+    __builtin_unreachable();
 }
 
 }  // namespace
 
-// Tile shapes of the pre-split kernel (ick_gemm's plan picks 1 or 2; the others stay selectable with ICK_PS_TILE so that the
-// sweep tables under profiles/r04_*_gemm_ps_* can be reproduced): bm x bn, waves as WM x WN, wave tile TM x TN blocks, D
-// slices in flight, PF = B fragment blocks requested ahead of their MFMAs.
-//   0: 64 x 320   4 x 2 waves of 16 x 160, D 1, 136 KB of LDS
-//   1: 128 x 128  8 x 1 waves of 16 x 128, D 1,  80 KB: two workgroups per CU            <- outputs wider than 320 columns, split K
-//   2: 128 x 160  8 x 1 waves of 16 x 160, D 2, 139 KB                                   <- Encoder.conv1 (N = 300, one column pair)
-//   3: 128 x 320  4 x 2 waves of 32 x 160, D 1, 152 KB
-//   4: 128 x 128  as 1 with D 2, 120 KB: one workgroup per CU
-//   5: 128 x 128  4 x 2 waves of 32 x 64 (32-row wave tiles read 1.5 x less LDS per product), D 1, two workgroups per CU
-//   6: 128 x 160  4 x 2 waves of 32 x 80, D 2
-// What was measured on them, and on variants that are no longer compiled (ring depth 3, 64 x 64 / 64 x 128 tiles at four
-// workgroups per CU, a ping-pong schedule of two wave groups half a slice apart): DESIGN.md section 3.1c.
-//   7: 128 x 128  FOUR waves (4 x 1) of 32 x 128, D 1, 80 KB: two workgroups per CU, one wave of each per SIMD -- the two
-//                 workgroups are not coupled by a barrier, so one's fragment phase can run under the other's MFMAs
-//   8: 64 x 160   four waves (2 x 2) of 32 x 80, D 1, 76 KB: two per CU
-//   9: 128 x 80   8 x 1 waves of 16 x 80, D 1, 62 KB: two workgroups per CU (Encoder.conv1 as 98 x 4 tiles: the two
-//                 workgroups of a CU are not barrier-coupled, so their fragment and MFMA phases overlap)
-//  10: 128 x 160  as 2 with D 1, 92 KB: leaves room on the CU for a 49 KB row-chain workgroup of the other stream
-constexpr int kPsTiles = 11;
-void gemm_ps_tile_dims(int tile, int* bm, int* bn, int* wgs_per_cu) {
-    static const int dims[kPsTiles][3] = {{64, 320, 1}, {128, 128, 2}, {128, 160, 1}, {128, 320, 1}, {128, 128, 1},
-                                          {128, 128, 2}, {128, 160, 1}, {128, 128, 2}, {64, 160, 2}, {128, 80, 2}, {128, 160, 1}};
-    *bm = dims[tile][0]; *bn = dims[tile][1]; *wgs_per_cu = dims[tile][2];
+PsTileInfo gemm_ps_tile(PsTile tile) {
+    return with_ps_tile(tile, false, [](auto c) { return PsTileInfo{c.BM, c.BN, c.NW, c.WGS_PER_CU}; });
 }
-int gemm_ps_tile_count() { return kPsTiles; }
 
-int launch_gemm_ps(const ick_gemm_args& a, bool akm, int tile, int tiles_m, int tiles_n, int kchunk, int split, int a_nt,
-                   hipStream_t s) {
+int launch_gemm_ps(const ick_gemm_args& a, bool akm, PsTile tile, int tiles_m, int tiles_n, int kchunk, int split, hipStream_t s) {
     const int np = (int)ps_rows(a.N);
     const int64_t bytes = ps_bytes(a.N, a.K);
     if (bytes >= ((int64_t)1 << 31)) return ICK_EINVAL;
-    switch (tile) {
-        case 0: return launch_ps_tile<4, 2, 1, 10, 1, 10>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 1: return launch_ps_tile<8, 1, 1, 8, 1, 2>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 2: return launch_ps_tile<8, 1, 1, 10, 2, 10>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 3: return launch_ps_tile<4, 2, 2, 10, 1, 3>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 4: return launch_ps_tile<8, 1, 1, 8, 2, 8>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 5: return launch_ps_tile<4, 2, 2, 4, 1, 2>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 6: return launch_ps_tile<4, 2, 2, 5, 2, 5>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 7: return launch_ps_tile<4, 1, 2, 8, 1, 2>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 8: return launch_ps_tile<2, 2, 2, 5, 1, 5>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 9: return launch_ps_tile<8, 1, 1, 5, 1, 2>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-        case 10: return launch_ps_tile<8, 1, 1, 10, 1, 10>(a, akm, np, bytes, tiles_m, tiles_n, kchunk, split, a_nt, s);
-    }
-    return ICK_EINVAL;
+    return with_ps_tile(tile, akm, [&](auto c) {
+        return launch_ps_cfg<decltype(c)>(a, np, bytes, tiles_m, tiles_n, kchunk, split, s);
+    });
 }
 
 }  // namespace ick

@@ -7,9 +7,9 @@ tests/test_gemm_envelope_gpu.py runs every case against an exact integer referen
 Every case sits at the smallest shape that selects its configuration (make_plan): element-wise staging for ragged or
 misaligned operands, 32 x 32 tiles below 512 tiles of 64 x 64, 64 x 64 from there on, 128 x 64 (eight waves) for long-K
 narrow-N problems with a k-major A, 128 x 128 for split products from 512 such tiles on, and the three tiles of the
-pre-split kernel that the planner picks itself (128 x 128, 64 x 160, 128 x 80).  The other pre-split tiles are reachable
-only through ICK_PS_TILE, a benchmark knob read once per process: they are not part of this table.  Grouped launches
-(ick_gemm_grouped) are not visible through ick_gemm_plan; GROUPED lists them by the plan each member has alone.
+pre-split kernel (128 x 128, 64 x 160, 128 x 80).  WAVES gives the waves per workgroup ick_gemm_plan must report beside
+each plan.  Grouped launches (ick_gemm_grouped) are not visible through ick_gemm_plan; GROUPED lists them by the plan
+each member has alone.
 
 Problem (below) lays a case out in memory exactly as include/ick_amd.h words the addressing, so both test modules build
 the same ick_gemm_args: the CPU test on uninitialised host tensors (the planner looks at pointers, alignment and sizes
@@ -86,6 +86,19 @@ def _wide():                 # 128 x 64, eight waves (k-major A, k-contiguous B)
 def _ps(tile, mode0, vec=1, k=1):
     p = _w(tile[0], tile[1], vec=vec, spl=1, ps=1, k=k)
     return (mode0, p, p)
+
+
+# waves per workgroup by plan family: (tile_m, tile_n, presplit) -> waves.  Element-wise staging runs on the 64 x 64 tile.
+WAVES = {
+    (32, 32, 0): 4, (64, 64, 0): 4, (64, 160, 1): 4,
+    (128, 64, 0): 8, (128, 128, 1): 8, (128, 80, 1): 8,
+    (128, 128, 0): 4,        # stager-split: four waves of 64 x 64
+}
+
+
+def waves(w):
+    """Waves per workgroup of a plan tuple (tile_m, tile_n, vec, split_bf16, presplit, split_k)."""
+    return WAVES[(w[0], w[1], w[4])]
 
 
 def C(name, shape, layout, want, **kw):

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from gemm_cases import (ACCEPTED, CASES, CC, CM, EPILOGUES, GROUPED, LAYOUTS, MC, MM, REJECTED, STAGINGS, Problem,
-                        a_group, value_bound)
+                        a_group, value_bound, waves)
 
 
 @pytest.fixture(scope="module")
@@ -187,6 +187,7 @@ def test_case_plans_are_the_launchers(ops, c):
     for mode in (0, 1, 2):
         ops.set_gemm_split(mode)
         assert p.plan() == c.want[mode], (c.name, mode, p.plan(), c.why)
+        assert ops.gemm_plan(p.args)["waves"] == waves(c.want[mode]), (c.name, mode)
     assert c.modes()[0] == 0
 
 

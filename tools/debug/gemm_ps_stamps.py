@@ -1,7 +1,8 @@
 """Where does a wave of the pre-split GEMM (csrc/gemm_ps.hip) spend a slice?  Builds a copy of the library with
--DICK_PS_STAMPS, runs one shape per tile and prints wave 0's mean shader-clock ticks per slice in each phase:
+-DICK_PS_STAMPS, runs one shape on the tile the planner picks for it and prints wave 0's mean shader-clock ticks per
+slice in each phase:
 DMA issue | B fragment requests + A fragment read + split | MFMA issue | wait for the next slice's DMA | barrier.
-usage: gemm_ps_stamps.py [shape [tile ...]]   (shapes of tools/gemm_ps_bench.py)"""
+usage: gemm_ps_stamps.py [shape]   (shapes of tools/gemm_ps_bench.py)"""
 import ctypes
 import os
 import subprocess
@@ -57,9 +58,6 @@ import ick_amd.build as b  # noqa: E402
 dbg = os.path.join(ROOT, "gpurun_out", "libick_amd_psstamps.so")
 os.makedirs(os.path.dirname(dbg), exist_ok=True)
 subprocess.check_call([b.HIPCC] + b.FLAGS + ["-DICK_PS_STAMPS", "-w", "-shared", "-o", dbg] + b.sources())
-shape = sys.argv[2] if len(sys.argv) > 2 and sys.argv[1] == "--shape" else (sys.argv[1] if len(sys.argv) > 1 else "conv1")
-tiles = sys.argv[2:] if len(sys.argv) > 2 else ["2", "0", "6"]
-for t in tiles:
-    env = dict(os.environ, ICK_PS_TILE=t)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", shape], env=env, capture_output=True, text=True)
-    sys.stdout.write(r.stdout if r.returncode == 0 else "FAILED tile %s: %s\n" % (t, r.stderr[-400:]))
+shape = sys.argv[1] if len(sys.argv) > 1 else "conv1"
+r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", shape], capture_output=True, text=True)
+sys.stdout.write(r.stdout if r.returncode == 0 else "FAILED %s: %s\n" % (shape, r.stderr[-400:]))

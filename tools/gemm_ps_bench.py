@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""The four large GEMMs of the path on the pre-split kernel (csrc/gemm_ps.hip), per tile shape and A-load policy:
-duration (events around `reps` back-to-back launches, operands as cold as a 256 MB Infinity Cache leaves them) and the
-maximum difference from the exact fp32 MFMA path.  Every (tile, nt) setting runs in a child process: the plan reads
-ICK_PS_TILE once.   python tools/gemm_ps_bench.py [shape-name-prefix]"""
+"""The large GEMMs of the path on the pre-split kernel (csrc/gemm_ps.hip), each on the tile the planner picks for it:
+duration per launch (events around it; operands hot, and as cold as a 384 MB fill between launches leaves them) and the
+maximum difference from the exact fp32 MFMA path.  Every shape runs in a child process of its own.
+python tools/gemm_ps_bench.py [shape-name-prefix]"""
 import os
 import subprocess
 import sys
@@ -87,12 +87,7 @@ if __name__ == "__main__":
     for name in SHAPES:
         if not name.startswith(want):
             continue
-        for tile in (os.environ.get("TILES", ",0,1,2,3,4,5,6,7,8,9,10").split(",")):
-            if True:
-                env = dict(os.environ)
-                if tile:
-                    env["ICK_PS_TILE"] = tile
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name], env=env, capture_output=True,
-                                   text=True, timeout=300)
-                sys.stdout.write(("auto: " if tile == "" else "      ") + (r.stdout if r.returncode == 0 else "FAILED %s %s: %s\n" % (name, tile, r.stderr[-300:])))
-                sys.stdout.flush()
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name], capture_output=True, text=True,
+                           timeout=300)
+        sys.stdout.write(r.stdout if r.returncode == 0 else "FAILED %s: %s\n" % (name, r.stderr[-300:]))
+        sys.stdout.flush()
