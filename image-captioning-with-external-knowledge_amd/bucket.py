@@ -49,14 +49,32 @@ class ParamBucket:
             self.p.copy_(self.e)
             self.e.copy_(t)
 
+    def decay_mask(self, selected):
+        """Which granules of the bucket weight decay covers: a uint8 tensor of n / ALIGN granules on the
+        bucket's device, 1 over the granules of the parameters in `selected` (parameters of this bucket, or their ids) and
+        0 over the others'.  Every parameter starts at a multiple of ALIGN, so a granule belongs to exactly one
+        parameter; the pad behind a parameter's last element lies in that parameter's last granule and stays zero under
+        either form of decay (0 * f = 0; 0 + wd * 0 = 0)."""
+        chosen = {p if isinstance(p, int) else id(p) for p in selected}
+        if chosen - set(self._off):
+            raise self.error("decay_mask: %d selected parameter(s) do not live in this bucket" % len(chosen - set(self._off)))
+        mask = torch.zeros(self.n // ALIGN, dtype=torch.uint8, device=self.p.device)
+        for p, lo, hi in zip(self.params, self.offsets, self.offsets[1:]):
+            if id(p) in chosen:
+                mask[lo // ALIGN:hi // ALIGN] = 1
+        return mask
+
     def resident(self):
         """Do the parameters still live here?  Only the first and the last are looked at (module.to() / .cuda() move every
         parameter): this runs once per training step, whose host path must not loop over the parameters."""
         base = self.p.data_ptr()
         return self.params[0].data_ptr() == base and self.params[-1].data_ptr() == base + 4 * self.offsets[-2]
 
-    def adam_state(self, order, step, lr, betas, eps):
-        """The moments as torch.optim.Adam(order).state_dict() reports them after `step` steps.  Tensors are copies."""
+    def adam_state(self, order, step, lr, betas, eps, decay=None, decoupled=True):
+        """The moments as torch.optim.Adam(order).state_dict() reports them after `step` steps.  Tensors are copies.
+        decay: None, or one weight-decay value per parameter of `order` -- the dict is then torch.optim.AdamW's
+        (decoupled) or torch.optim.Adam's over ONE PARAM GROUP PER PARAMETER, ids 0..n-1 in the same order, each with its
+        own weight_decay (load_adam_state flattens the groups in order, so both layouts load)."""
         state = {}
         if step > 0:
             for i, p in enumerate(order):
@@ -65,7 +83,14 @@ class ParamBucket:
         group = {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "decoupled_weight_decay": False, "params": list(range(len(order)))}
-        return {"state": state, "param_groups": [group]}
+        if decay is None:
+            return {"state": state, "param_groups": [group]}
+        decay = [float(wd) for wd in decay]
+        if len(decay) != len(order):
+            raise self.error("adam_state: %d decay values for %d parameters" % (len(decay), len(order)))
+        groups = [dict(group, weight_decay=wd, decoupled_weight_decay=bool(decoupled), params=[i])
+                  for i, wd in enumerate(decay)]
+        return {"state": state, "param_groups": groups}
 
     def load_adam_state(self, sd, order, what, owner):
         """Fill the moments from a torch.optim.Adam-layout state dict over `order` (a parameter without state gets zeros)

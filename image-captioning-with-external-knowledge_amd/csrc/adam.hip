@@ -8,10 +8,15 @@
 //
 //   g = clamp(g * gscale [/ *gscale_den], -clip, clip);  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-// (default betas / eps, no weight decay, no amsgrad.)  The update is written once: adam_hyper() is the prologue, adam1()
-// the arithmetic of one element.  kEma (ick_adam_ema[_derive]): the lane that holds the new p also keeps
-// an exponential moving average of it in a fourth array, e += (1 - d_t) (p - e) (ema1()), two more 16-byte streams in the
-// same pass; kEma = false is the code without it.  Three kernels address the bucket differently around them:
+// (default betas / eps, no amsgrad.)  The update is written once: adam_hyper() is the prologue, adam1() the arithmetic of
+// one element.  kDecay (ick_adam_decay[_derive]): weight decay on the elements whose 64-float granule of
+// the bucket has its byte of the caller's mask set -- decoupled (torch.optim.AdamW), p = p * (1 - lr_t * wd) ahead of
+// the unchanged update, or coupled (torch.optim.Adam(weight_decay=), L2), wd * p added to the clamped gradient that the
+// moments and the update see, while the gradient written back stays without the term; wd is read from a device word.
+// kDecay = false is the code without it.  kEma (ick_adam_ema[_derive]): the lane that holds the new p
+// also keeps an exponential moving average of it in a fourth array, e += (1 - d_t) (p - e) (ema1()), two more 16-byte
+// streams in the same pass; kEma = false is the code without it.  Three kernels address the bucket differently around
+// them:
 //   adam_clamp_kernel       one float per lane and trip: tails, short and unaligned buckets;
 //   adam_clamp_vec4_kernel  one float4 per lane and trip, seven 16-byte streams: the aligned bulk of a flat bucket;
 //   adam_derive_kernel      one workgroup = one block of the caller's cover of the bucket (include/ick_amd.h,
@@ -30,7 +35,8 @@ namespace ick {
 namespace {
 
 struct AdamHyper {
-    float gscale, clip, b1, b2, c1, c2, eps, step, bc2_sqrt, coef, w;
+    float gscale, clip, b1, b2, c1, c2, eps, step, bc2_sqrt, coef, w, wd, f;
+    bool coupled;
 };
 
 // The moving average's operands (kEma): the array, the device word that holds the decay, the warmup flag.  Passed to
@@ -42,16 +48,37 @@ struct AdamEma {
     int warmup;
 };
 
+// The weight decay's operands (kDecay): the device word that holds wd, one byte (0 / 1) per 64-float granule of the bucket,
+// how many there are, the offset in floats of the kernel's arrays from the bucket's start (the mask is indexed from the
+// bucket's start, not from the address: the scalar tail of a flat launch starts behind the float4 part) and the form.
+// Passed to every instantiation like AdamEma; the ones without kDecay never read it.
+struct AdamDecay {
+    const float* wd;
+    const uint8_t* mask;
+    int64_t granules;
+    int64_t base;
+    int coupled;
+};
+
+constexpr int kGranuleShift = 6;      // log2 of the granule: bucket.ALIGN = 64 floats, where every parameter starts
+
+// Is the decay on for the element at float offset `at` from the bucket's start?  (A granule beyond the table: off.)
+__device__ __forceinline__ bool decay_on(const AdamDecay& dec, int64_t at) {
+    const int64_t gr = at >> kGranuleShift;
+    return gr < dec.granules && dec.mask[gr] != 0;
+}
+
 // The prologue of every Adam kernel.  false: no token contributed to the (global) batch, which then has no mean loss --
 // the kernel leaves parameters, moments, images and the rate word alone instead of spreading 0 * inf = NaN over every
 // weight.  kOpt (ick_adam_opt[_derive]): the step's rate comes from the base rate word and the schedule
 // instead of the literal, h.coef is the global-norm clip's coefficient, and workgroup 0 leaves the rate it used in
 // words[4].  kEma: h.w = 1 - d_t, the weight of the new parameter in the moving average, with d_t = *decay or, with the
 // warmup flag, min(*decay, (1 + t) / (10 + t)) on the step t of the bias correction.
-template <bool kOpt, bool kEma>
+template <bool kOpt, bool kEma, bool kDecay>
 __device__ __forceinline__ bool adam_hyper(AdamHyper& h, float gscale, float clip, float lr, float b1, float b2, float eps,
                                            int step0, const uint32_t* step_ptr, const float* __restrict__ gscale_den,
-                                           float* words, const ick_lr_schedule& sched, const AdamEma& ema) {
+                                           float* words, const ick_lr_schedule& sched, const AdamEma& ema,
+                                           const AdamDecay& dec) {
     if (gscale_den) {
         if (!(gscale_den[0] > 0.f)) return false;
         gscale = gscale / gscale_den[0];
@@ -72,19 +99,36 @@ __device__ __forceinline__ bool adam_hyper(AdamHyper& h, float gscale, float cli
         if (ema.warmup) d = fminf(d, (1.f + t) / (10.f + t));
         h.w = 1.f - d;
     }
+    h.wd = 0.f; h.f = 1.f; h.coupled = false;
+    if (kDecay) {
+        h.wd = dec.wd[0];
+        const float shrink = lr * h.wd;       // lr: the rate this update uses (the scheduled one with kOpt)
+        h.f = 1.f - shrink;
+        h.coupled = dec.coupled != 0;
+    }
     h.gscale = gscale; h.clip = clip; h.b1 = b1; h.b2 = b2; h.c1 = 1.f - b1; h.c2 = 1.f - b2; h.eps = eps;
     return true;
 }
 
 // The update of one element, the only place its arithmetic is written (-ffp-contract=off keeps the operations apart).
 // kOpt: the gradient times the clip coefficient between the scale and the clamp, as an operation of its own -- with
-// coef == 1 and a constant schedule the bits are the plain instantiation's.
-template <bool kOpt>
-__device__ __forceinline__ void adam1(const AdamHyper& h, float& p, float& g, float& m, float& v) {
+// coef == 1 and a constant schedule the bits are the plain instantiation's.  kDecay and `on` (the element's granule is
+// selected): decoupled, the parameter shrinks first and the update is the unchanged one; coupled, the product wd * p and
+// its sum with the clamped gradient feed the moments, behind the gradient's write-back.
+template <bool kOpt, bool kDecay = false>
+__device__ __forceinline__ void adam1(const AdamHyper& h, float& p, float& g, float& m, float& v, bool on = false) {
     float x = g * h.gscale;
     if (kOpt) x = x * h.coef;
     if (h.clip > 0.f) x = fminf(fmaxf(x, -h.clip), h.clip);
     g = x;
+    if (kDecay && on) {
+        if (h.coupled) {
+            const float term = h.wd * p;
+            x = x + term;
+        } else {
+            p = p * h.f;
+        }
+    }
     m = h.b1 * m + h.c1 * x;
     v = h.b2 * v + h.c2 * x * x;
     p -= h.step * m / (sqrtf(v) / h.bc2_sqrt + h.eps);
@@ -103,28 +147,31 @@ __device__ __forceinline__ void ema4(const AdamHyper& h, float4& e, const float4
     ema1(h, e.w, p.w);
 }
 
-template <bool kOpt>
-__device__ __forceinline__ void adam4(const AdamHyper& h, float4& p, float4& g, float4& m, float4& v) {
-    adam1<kOpt>(h, p.x, g.x, m.x, v.x);
-    adam1<kOpt>(h, p.y, g.y, m.y, v.y);
-    adam1<kOpt>(h, p.z, g.z, m.z, v.z);
-    adam1<kOpt>(h, p.w, g.w, m.w, v.w);
+// (a float4 at a multiple of 4 floats from the bucket's start lies inside one granule: one `on` for the four)
+template <bool kOpt, bool kDecay = false>
+__device__ __forceinline__ void adam4(const AdamHyper& h, float4& p, float4& g, float4& m, float4& v, bool on = false) {
+    adam1<kOpt, kDecay>(h, p.x, g.x, m.x, v.x, on);
+    adam1<kOpt, kDecay>(h, p.y, g.y, m.y, v.y, on);
+    adam1<kOpt, kDecay>(h, p.z, g.z, m.z, v.z, on);
+    adam1<kOpt, kDecay>(h, p.w, g.w, m.w, v.w, on);
 }
 
-template <bool kOpt, bool kEma>
+template <bool kOpt, bool kEma, bool kDecay>
 __global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                          float gscale, float clip, float lr, float b1, float b2,
                                                          float eps, int step0, const uint32_t* step_ptr,
                                                          const float* __restrict__ gscale_den, float* words,
-                                                         ick_lr_schedule sched, AdamEma ema) {
+                                                         ick_lr_schedule sched, AdamEma ema, AdamDecay dec) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     AdamHyper h;
-    if (!adam_hyper<kOpt, kEma>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema)) return;
+    if (!adam_hyper<kOpt, kEma, kDecay>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema,
+                                         dec))
+        return;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         float gi = g[i], mi = m[i], vi = v[i], pi = p[i], ei = 0.f;
         if (kEma) ei = ema.e[i];
-        adam1<kOpt>(h, pi, gi, mi, vi);
+        adam1<kOpt, kDecay>(h, pi, gi, mi, vi, kDecay && decay_on(dec, dec.base + i));
         g[i] = gi; m[i] = mi; v[i] = vi; p[i] = pi;
         if (kEma) { ema1(h, ei, pi); ema.e[i] = ei; }
     }
@@ -132,21 +179,23 @@ __global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, 
 
 // The same update on float4: seven 16-byte streams per lane (the scalar form reaches 0.66 of the HBM rate, 320 MB per
 // cfg2 step).  n4 = n / 4 elements of float4; the launcher sends a tail of n % 4 to the scalar kernel.
-template <bool kOpt, bool kEma>
+template <bool kOpt, bool kEma, bool kDecay>
 __global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict__ p, float4* __restrict__ g,
                                                               float4* __restrict__ m, float4* __restrict__ v, int64_t n4,
                                                               float gscale, float clip, float lr, float b1, float b2,
                                                               float eps, int step0, const uint32_t* step_ptr,
                                                               const float* __restrict__ gscale_den, float* words,
-                                                              ick_lr_schedule sched, AdamEma ema) {
+                                                              ick_lr_schedule sched, AdamEma ema, AdamDecay dec) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     AdamHyper h;
-    if (!adam_hyper<kOpt, kEma>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema)) return;
+    if (!adam_hyper<kOpt, kEma, kDecay>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema,
+                                         dec))
+        return;
     float4* __restrict__ e = reinterpret_cast<float4*>(ema.e);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
         float4 gi = g[i], mi = m[i], vi = v[i], pi = p[i], ei;
         if (kEma) ei = e[i];
-        adam4<kOpt>(h, pi, gi, mi, vi);
+        adam4<kOpt, kDecay>(h, pi, gi, mi, vi, kDecay && decay_on(dec, dec.base + 4 * i));
         g[i] = gi; m[i] = mi; v[i] = vi; p[i] = pi;
         if (kEma) { ema4(h, ei, pi); e[i] = ei; }
     }
@@ -155,18 +204,20 @@ __global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict
 constexpr int kT = 64;        // tile edge
 constexpr int kLd = 68;       // LDS row stride of the tile (16-byte aligned rows, 4 banks of skew per row)
 
-template <bool kOpt, bool kEma>
+template <bool kOpt, bool kEma, bool kDecay>
 __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p, float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v,
                                                           const ick_adam_item* __restrict__ items,
                                                           const ick_adam_block* __restrict__ blocks, float gscale,
                                                           float clip, float lr, float b1, float b2, float eps, int step0,
                                                           const uint32_t* step_ptr, const float* __restrict__ gscale_den,
-                                                          float* words, ick_lr_schedule sched, AdamEma ema) {
+                                                          float* words, ick_lr_schedule sched, AdamEma ema, AdamDecay dec) {
     __shared__ __attribute__((aligned(16))) float tile[kT * kLd];
     const ick_adam_block blk = blocks[blockIdx.x];
     AdamHyper h;
-    if (!adam_hyper<kOpt, kEma>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema)) return;
+    if (!adam_hyper<kOpt, kEma, kDecay>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema,
+                                         dec))
+        return;
     const int tid = threadIdx.x;
 
     if (blk.item < 0) {
@@ -177,19 +228,22 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
         float4* v4 = reinterpret_cast<float4*>(v) + blk.off4;
         float4* e4 = reinterpret_cast<float4*>(ema.e) + blk.off4;
         float4 pi[4], gi[4], mi[4], vi[4], ei[4];
+        bool on[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int j = tid + 256 * i;
+            on[i] = false;
             if (j < blk.cnt4) {
                 gi[i] = g4[j]; mi[i] = m4[j]; vi[i] = v4[j]; pi[i] = p4[j];
                 if (kEma) ei[i] = e4[j];
+                if (kDecay) on[i] = decay_on(dec, 4 * ((int64_t)blk.off4 + j));
             }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int j = tid + 256 * i;
             if (j < blk.cnt4) {
-                adam4<kOpt>(h, pi[i], gi[i], mi[i], vi[i]);
+                adam4<kOpt, kDecay>(h, pi[i], gi[i], mi[i], vi[i], on[i]);
                 g4[j] = gi[i]; m4[j] = mi[i]; v4[j] = vi[i]; p4[j] = pi[i];
                 if (kEma) { ema4(h, ei[i], pi[i]); e4[j] = ei[i]; }
                 if (blk.copy) reinterpret_cast<float4*>(blk.copy)[j] = pi[i];
@@ -205,6 +259,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
     {
         float4 pi[4], gi[4], mi[4], vi[4], ei[4];
         int64_t at[4];
+        bool on[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int idx = tid + 256 * i;
@@ -218,6 +273,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
                 pi[i] = *reinterpret_cast<const float4*>(p + at[i]);
                 if (kEma) ei[i] = *reinterpret_cast<const float4*>(ema.e + at[i]);
             }
+            on[i] = kDecay && at[i] >= 0 && decay_on(dec, at[i]);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -225,7 +281,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
             const int row = idx >> 4, c4 = idx & 15;
             float4 out = make_float4(0.f, 0.f, 0.f, 0.f);      // outside the item / the matrix: zeros (the images' padding)
             if (at[i] >= 0) {
-                adam4<kOpt>(h, pi[i], gi[i], mi[i], vi[i]);
+                adam4<kOpt, kDecay>(h, pi[i], gi[i], mi[i], vi[i], on[i]);
                 *reinterpret_cast<float4*>(g + at[i]) = gi[i];
                 *reinterpret_cast<float4*>(m + at[i]) = mi[i];
                 *reinterpret_cast<float4*>(v + at[i]) = vi[i];
@@ -331,52 +387,62 @@ using namespace ick;
 
 // What every entry asks of its arguments (count: the floats of a flat bucket, the blocks of a cover); al16: whether all
 // the arrays lie on 16 bytes, which the float4 kernels need.  kEma: the moving average is one more array, and its decay
-// word must be there.
-template <bool kEma>
+// word must be there.  kDecay: the decay word, the granule mask with at least one granule, a known form.
+template <bool kEma, bool kDecay>
 static int adam_args(const float* p, const float* g, const float* m, const float* v, int64_t count, int32_t step,
-                     const uint32_t* step_ptr, const AdamEma& ema, bool& al16) {
+                     const uint32_t* step_ptr, const AdamEma& ema, const AdamDecay& dec, bool& al16) {
     ICK_CHECK_ARG(p && g && m && v && count > 0 && (step >= 1 || step_ptr != nullptr));
     if (kEma) ICK_CHECK_ARG(ema.e != nullptr && ema.decay != nullptr);
+    if (kDecay)
+        ICK_CHECK_ARG(dec.wd != nullptr && dec.mask != nullptr && dec.granules > 0 &&
+                      (dec.coupled == ICK_DECAY_DECOUPLED || dec.coupled == ICK_DECAY_COUPLED));
     al16 = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
              reinterpret_cast<uintptr_t>(v) | (kEma ? reinterpret_cast<uintptr_t>(ema.e) : 0)) & 15) == 0;
     return ICK_OK;
 }
 
-// ick_adam_clamp, ick_adam_opt and ick_adam_ema: the float4 kernel over the aligned bulk, the scalar kernel over the rest
-template <bool kOpt, bool kEma>
+// ick_adam_clamp, ick_adam_opt, ick_adam_ema and ick_adam_decay: the float4 kernel over the aligned bulk, the scalar kernel
+// over the rest (which tells the mask where it starts: dec.base)
+template <bool kOpt, bool kEma, bool kDecay = false>
 static int launch_adam(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr, float* words,
                        ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                       const float* gscale_den, AdamEma ema, void* stream) {
+                       const float* gscale_den, AdamEma ema, void* stream, AdamDecay dec = AdamDecay{}) {
     bool al16;
-    if (int rc = adam_args<kEma>(p, g, m, v, n, step, step_ptr, ema, al16)) return rc;
+    if (int rc = adam_args<kEma, kDecay>(p, g, m, v, n, step, step_ptr, ema, dec, al16)) return rc;
+    if (kDecay) ICK_CHECK_ARG(dec.granules >= ceil_div(n, (int64_t)1 << kGranuleShift));
     if (kEma && (reinterpret_cast<uintptr_t>(ema.e) & 3)) return ICK_EALIGN;
     int64_t done = 0;
     if (n >= 4096 && al16) {
         const int64_t n4 = n / 4;
-        hipLaunchKernelGGL((adam_clamp_vec4_kernel<kOpt, kEma>), dim3((int)std::min<int64_t>(ceil_div(n4, 256), 4096)),
+        hipLaunchKernelGGL((adam_clamp_vec4_kernel<kOpt, kEma, kDecay>), dim3((int)std::min<int64_t>(ceil_div(n4, 256), 4096)),
                            dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(p), reinterpret_cast<float4*>(g),
                            reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), n4, gscale, clip, lr, beta1, beta2,
-                           eps, step, step_ptr, gscale_den, words, sched, ema);
+                           eps, step, step_ptr, gscale_den, words, sched, ema, dec);
         done = 4 * n4;
         if (done == n) ICK_LAUNCH_RET();
     }
     if (kEma) ema.e += done;
-    hipLaunchKernelGGL((adam_clamp_kernel<kOpt, kEma>), dim3((int)std::min<int64_t>(ceil_div(n - done, 256), 4096)),
+    dec.base = done;
+    hipLaunchKernelGGL((adam_clamp_kernel<kOpt, kEma, kDecay>), dim3((int)std::min<int64_t>(ceil_div(n - done, 256), 4096)),
                        dim3(256), 0, (hipStream_t)stream, p + done, g + done, m + done, v + done, n - done, gscale, clip, lr,
-                       beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema);
+                       beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema, dec);
     ICK_LAUNCH_RET();
 }
 
-template <bool kOpt, bool kEma>
+// (the cover lies on the device, so the granule count cannot be held against it here: the kernel treats a granule beyond
+// the table as not selected)
+template <bool kOpt, bool kEma, bool kDecay = false>
 static int launch_adam_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
                               const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
                               float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                              const uint32_t* step_ptr, const float* gscale_den, AdamEma ema, void* stream) {
+                              const uint32_t* step_ptr, const float* gscale_den, AdamEma ema, void* stream,
+                              AdamDecay dec = AdamDecay{}) {
     bool al16;
-    if (int rc = adam_args<kEma>(p, g, m, v, blocks ? n_blocks : 0, step, step_ptr, ema, al16)) return rc;
+    if (int rc = adam_args<kEma, kDecay>(p, g, m, v, blocks ? n_blocks : 0, step, step_ptr, ema, dec, al16)) return rc;
     if (!al16) return ICK_EALIGN;
-    hipLaunchKernelGGL((adam_derive_kernel<kOpt, kEma>), dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       items, blocks, gscale, clip, lr, beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema);
+    hipLaunchKernelGGL((adam_derive_kernel<kOpt, kEma, kDecay>), dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       items, blocks, gscale, clip, lr, beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema,
+                       dec);
     ICK_LAUNCH_RET();
 }
 
@@ -443,3 +509,63 @@ extern "C" int ick_adam_ema_derive(float* p, float* g, float* m, float* v, float
                                           beta2, eps, step, step_ptr, gscale_den, ema, stream);
 }
 
+
+// The entries with weight decay: words == NULL takes the host rate lr, e == NULL keeps no average -- the
+// four <kOpt, kEma, true> instantiations of each kernel.
+template <typename Plain, typename Opt>
+static int with_rate(const float* words, const ick_lr_schedule& sched, Plain plain, Opt opt) {
+    if (!words) return plain();
+    ICK_CHECK_ARG(lr_schedule_ok(sched));
+    return opt();
+}
+
+extern "C" int ick_adam_decay(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip,
+                              float lr, float* words, ick_lr_schedule sched, float beta1, float beta2, float eps,
+                              int32_t step, const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay,
+                              int32_t ema_warmup, const float* decay, const uint8_t* decay_mask, int64_t n_granules,
+                              int32_t decay_form, void* stream) {
+    const AdamEma ema{e, ema_decay, ema_warmup != 0};
+    const AdamDecay dec{decay, decay_mask, n_granules, 0, decay_form};
+    const ick_lr_schedule none{};
+    if (!e)
+        return with_rate(
+            words, sched,
+            [&] { return launch_adam<false, false, true>(p, g, m, v, n, gscale, clip, lr, nullptr, none, beta1, beta2, eps,
+                                                         step, step_ptr, gscale_den, AdamEma{}, stream, dec); },
+            [&] { return launch_adam<true, false, true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps,
+                                                        step, step_ptr, gscale_den, AdamEma{}, stream, dec); });
+    return with_rate(
+        words, sched,
+        [&] { return launch_adam<false, true, true>(p, g, m, v, n, gscale, clip, lr, nullptr, none, beta1, beta2, eps, step,
+                                                    step_ptr, gscale_den, ema, stream, dec); },
+        [&] { return launch_adam<true, true, true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step,
+                                                   step_ptr, gscale_den, ema, stream, dec); });
+}
+
+extern "C" int ick_adam_decay_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
+                                     const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
+                                     float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                                     const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay,
+                                     int32_t ema_warmup, const float* decay, const uint8_t* decay_mask,
+                                     int64_t n_granules, int32_t decay_form, void* stream) {
+    const AdamEma ema{e, ema_decay, ema_warmup != 0};
+    const AdamDecay dec{decay, decay_mask, n_granules, 0, decay_form};
+    const ick_lr_schedule none{};
+    if (!e)
+        return with_rate(
+            words, sched,
+            [&] { return launch_adam_derive<false, false, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr,
+                                                                nullptr, none, beta1, beta2, eps, step, step_ptr,
+                                                                gscale_den, AdamEma{}, stream, dec); },
+            [&] { return launch_adam_derive<true, false, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words,
+                                                               sched, beta1, beta2, eps, step, step_ptr, gscale_den,
+                                                               AdamEma{}, stream, dec); });
+    return with_rate(
+        words, sched,
+        [&] { return launch_adam_derive<false, true, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr, nullptr,
+                                                           none, beta1, beta2, eps, step, step_ptr, gscale_den, ema, stream,
+                                                           dec); },
+        [&] { return launch_adam_derive<true, true, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words,
+                                                          sched, beta1, beta2, eps, step, step_ptr, gscale_den, ema, stream,
+                                                          dec); });
+}

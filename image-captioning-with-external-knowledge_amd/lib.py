@@ -243,6 +243,10 @@ SIGNATURES = {
     "ick_adam_ema": [vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp, i32, vp],
     "ick_adam_ema_derive": [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp,
                             i32, vp],
+    "ick_adam_decay": [vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp, i32, vp, vp,
+                       i64, i32, vp],
+    "ick_adam_decay_derive": [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp,
+                              i32, vp, vp, i64, i32, vp],
     "ick_conv1_wgrad_plan": [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i64)],
     "ick_conv1_wgrad": [vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
     "ick_counter_add": [vp, u32, vp],

@@ -1575,10 +1575,13 @@ def conv1_wgrad(d_img, feats, dw, db, scratch=None):
 
 _ADAM_ENTRIES = ("ick_adam_clamp", "ick_adam_opt", "ick_adam_clamp_derive", "ick_adam_opt_derive")
 _ADAM_EMA_ENTRIES = ("ick_adam_ema", "ick_adam_ema_derive")      # (both rates: words == NULL selects the host float)
+_ADAM_DECAY_ENTRIES = ("ick_adam_decay", "ick_adam_decay_derive")      # (... and e == NULL selects no average)
+DECAY_DECOUPLED, DECAY_COUPLED = 0, 1                                   # ICK_DECAY_*
 
 
 def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=None, clip=5.0, gscale=1.0, beta1=0.9,
-                beta2=0.999, eps=1e-8, step_tensor=None, gscale_den=None, ema=None, ema_decay_word=None, ema_warmup=False):
+                beta2=0.999, eps=1e-8, step_tensor=None, gscale_den=None, ema=None, ema_decay_word=None, ema_warmup=False,
+                decay_word=None, decay_mask=None, decoupled=True):
     """g = clamp(g * gscale (/ the device scalar gscale_den, if given), +-clip), then Adam's update of p, m, v; step (+ the
     uint32 device counter step_tensor, if given) is Adam's 1-based step count.  Nothing is written while gscale_den is
     given and not > 0.
@@ -1594,29 +1597,50 @@ def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=N
     ema: None, or the exponential moving average of p, a float32 device tensor laid out like p, updated in the same pass
     (ick_adam_ema[_derive]): e += (1 - d) * (p_new - e) with the decay d read from ema_decay_word, a one-float tensor ON THE
     DEVICE (a host scalar is refused: it would be baked into a captured launch); ema_warmup: d = min(d, (1 + t) / (10 + t))
-    on the step count t.  p, g, m, v get the bits they get without ema."""
+    on the step count t.  p, g, m, v get the bits they get without ema.
+    decay_word + decay_mask (both or neither): weight decay in the same pass (ick_adam_decay[_derive]).  decay_word: wd, a
+    one-float tensor ON THE DEVICE (a host scalar is refused for the reason the EMA word is); decay_mask: a uint8 device
+    tensor of at least ceil(p.numel() / 64) granules (bucket.ParamBucket.decay_mask), one per 64 floats from p's start,
+    non-zero where the elements decay.  decoupled: True, torch.optim.AdamW's p *= 1 - lr_t * wd ahead of the update;
+    False, torch.optim.Adam(weight_decay=)'s wd * p added to the clamped gradient the moments see (g is written back
+    without it)."""
     if (lr is None) == (words is None):
         raise L.IckError("adam_update needs exactly one of lr (a host float) and words (the optimizer words)")
     if words is None and schedule is not None:
         raise L.IckError("adam_update: a schedule shapes the rate in the optimizer words; give words, not lr")
     if ema is None and (ema_decay_word is not None or ema_warmup):
         raise L.IckError("adam_update: ema_decay_word / ema_warmup shape a moving average; give ema= as well")
-    if ema is None:
+    if (decay_word is None) != (decay_mask is None):
+        raise L.IckError("adam_update: weight decay needs both decay_word (wd) and decay_mask (which granules decay)")
+    decay = ()
+    if decay_word is not None:
+        granules = (p.numel() + 63) // 64
+        for what, t, dtype, least in (("decay_word", decay_word, torch.float32, 1),
+                                      ("decay_mask", decay_mask, torch.uint8, granules)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or \
+                    t.numel() < least:
+                raise L.IckError("adam_update needs %s as a contiguous %s device tensor of at least %d element(s)"
+                                 % (what, str(dtype).replace("torch.", ""), least))
+        decay = (_p(decay_word), _p(decay_mask), decay_mask.numel(), DECAY_DECOUPLED if decoupled else DECAY_COUPLED)
+    if ema is None and not decay:
         name = _ADAM_ENTRIES[(words is not None) + 2 * (cover is not None)]
         rate = (lr,) if words is None else (_p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule))
         avg, tail = (), ()
     else:
-        for what, t, least in (("ema", ema, p.numel()), ("ema_decay_word", ema_decay_word, 1)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or \
-                    t.numel() < least:
-                raise L.IckError("adam_update needs %s as a contiguous float32 device tensor of at least %d element(s)"
-                                 % (what, least))
-        if ema.data_ptr() % (4 if cover is None else 16):
-            raise L.IckError("adam_update: ema must lie on %d bytes" % (4 if cover is None else 16))
-        name = _ADAM_EMA_ENTRIES[cover is not None]
+        avg, tail = (None,), (None, 0)                                   # (the decay entries: e == NULL, no average)
+        if ema is not None:
+            for what, t, least in (("ema", ema, p.numel()), ("ema_decay_word", ema_decay_word, 1)):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or \
+                        t.numel() < least:
+                    raise L.IckError("adam_update needs %s as a contiguous float32 device tensor of at least %d element(s)"
+                                     % (what, least))
+            if ema.data_ptr() % (4 if cover is None else 16):
+                raise L.IckError("adam_update: ema must lie on %d bytes" % (4 if cover is None else 16))
+            avg, tail = (_p(ema),), (_p(ema_decay_word), int(bool(ema_warmup)))
+        name = (_ADAM_DECAY_ENTRIES if decay else _ADAM_EMA_ENTRIES)[cover is not None]
         rate = (0.0, _p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule)) if words is not None else \
             (lr, None, L.LrSchedule())
-        avg, tail = (_p(ema),), (_p(ema_decay_word), int(bool(ema_warmup)))
+        tail += decay
     if cover is None:
         over = (p.numel(),)
     else:

@@ -140,6 +140,15 @@ def classify(name, args):
     if name == "ick_adam_ema_derive":
         return ("clamp + Adam + EMA + re-laid-out weight copies",
                 float(getattr(L, "ADAM_DERIVE_BYTES", 0)) + 8.0 * getattr(L, "ADAM_DERIVE_FLOATS", 0), "byte")
+    if name == "ick_adam_decay":
+        # args[4]: the average (None: seven streams, else nine); the granule mask adds one byte per 64 floats
+        streams = 9 if args[4] else 7
+        return ("clamp + Adam + weight decay" + (" + EMA" if args[4] else ""),
+                4.0 * args[5] * streams + args[5] / 64.0, "byte")
+    if name == "ick_adam_decay_derive":
+        floats = getattr(L, "ADAM_DERIVE_FLOATS", 0)
+        return ("clamp + Adam + weight decay" + (" + EMA" if args[4] else "") + " + re-laid-out weight copies",
+                float(getattr(L, "ADAM_DERIVE_BYTES", 0)) + (8.0 * floats if args[4] else 0.0) + floats / 64.0, "byte")
     if name == "ick_grad_sqnorm":
         # one read of the gradient bucket (the partials and the words are a few KiB)
         return "gradient norm (global-norm clip)", 4.0 * args[1], "byte"

@@ -25,7 +25,11 @@ join the dict as "geo_js".
 `ema_decay=<float in [0, 1)>`: an exponential moving average of the trained parameters (fused: kept by the optimizer
 launch, TrainStep(ema_decay=); unfused: TorchEma, a lerp_ after optimizer.step()); with `ema_validate` the validation pass
 -- and so early stopping and BEST_ -- runs on the averaged weights, and the checkpoint carries the average under
-"decoder_ema" (utils.load_ema_weights copies it into a loaded checkpoint's modules)."""
+"decoder_ema" (utils.load_ema_weights copies it into a loaded checkpoint's modules).
+`weight_decay=<float >= 0>`: weight decay on the decoder's matrices and embedding tables (ndim >= 2), torch.optim.AdamW's
+(`decoupled_weight_decay=True`) or torch.optim.Adam(weight_decay=)'s -- fused: inside the optimizer launch
+(TrainStep(weight_decay=)); unfused: the torch optimizer itself; on both the checkpoint's `decoder_optimizer` then has one
+param group per parameter, and a resume takes the moments from either layout and the decay from the Config."""
 import contextlib
 import json
 import math
@@ -45,7 +49,8 @@ from .datasets import CaptionDataset
 from .geo_metric import GeoReferenceMetric
 from .metrics import CaptionMetrics
 from .scst import SelfCriticalStep
-from .training import TrainStep, check_ema_decay, check_lr_schedule, check_max_grad_norm, ema_decay_at, lr_at
+from .training import (TrainStep, check_ema_decay, check_lr_schedule, check_max_grad_norm, check_weight_decay,
+                       default_decay_filter, ema_decay_at, lr_at)
 
 
 @dataclass
@@ -123,12 +128,22 @@ class Config:
     ema_warmup: bool = False                           # the decay of step t is min(ema_decay, (1 + t) / (10 + t))
     ema_validate: bool = True                          # with ema_decay: validate (early stopping, BEST_) on the averaged
                                                        # weights instead of the raw ones
+    weight_decay: object = None                        # float >= 0: weight decay on the decoder's parameters with
+                                                       # ndim >= 2 (fused: inside the optimizer launch,
+                                                       # TrainStep(weight_decay=); unfused: the torch optimizer's, over one
+                                                       # param group per parameter); None: off
+    decoupled_weight_decay: bool = True                # True: torch.optim.AdamW; False: torch.optim.Adam(weight_decay=)
+    encoder_weight_decay: object = None                # with train_conv1: the same for Encoder.conv1.weight
 
     def __post_init__(self):
         try:
             check_ema_decay(self.ema_decay)
+            check_weight_decay(self.weight_decay)
+            check_weight_decay(self.encoder_weight_decay)
         except RuntimeError as e:
             raise ValueError(str(e))
+        if self.encoder_weight_decay is not None and not self.train_conv1:
+            raise ValueError("encoder_weight_decay needs train_conv1=True")
 
 
 def _batch_to_device(batch, device, has_facts):
@@ -398,6 +413,37 @@ def train(loader, encoder, decoder, criterion, decoder_optimizer, step, epoch, c
             break
     STATS["last_epoch_steps_per_s"] = n_steps / max(time.time() - t_epoch, 1e-9)
     return losses.avg
+
+
+def _has_decay_groups(opt):
+    return len(opt.param_groups) > 1 or any(g.get("weight_decay", 0) != 0 for g in opt.param_groups)
+
+
+def make_decoder_optimizer(decoder, cfg, old=None):
+    """The unfused path's decoder optimizer.  Without cfg.weight_decay torch.optim.Adam over the trainable parameters, as
+    ever; with it AdamW (or Adam, decoupled_weight_decay=False) over ONE PARAM GROUP PER PARAMETER in the same order, the
+    decay on the parameters training.default_decay_filter selects -- the layout TrainStep.state_dict() reports.  old: a
+    resumed optimizer; its moments, step counts, rate, betas and eps carry over (parameter i of its flattened groups is
+    parameter i here), its decay does not: that comes from cfg."""
+    named = [(n, p) for n, p in decoder.named_parameters() if p.requires_grad]
+    if cfg.weight_decay is None:
+        opt = torch.optim.Adam([p for _, p in named], lr=cfg.decoder_lr)
+    else:
+        cls = torch.optim.AdamW if cfg.decoupled_weight_decay else torch.optim.Adam
+        opt = cls([dict(params=[p], weight_decay=float(cfg.weight_decay) if default_decay_filter(n, p) else 0.0)
+                   for n, p in named], lr=cfg.decoder_lr, weight_decay=0.0)
+    if old is not None:
+        theirs, mine = old.state_dict(), opt.state_dict()
+        ids = [i for g in theirs["param_groups"] for i in g["params"]]
+        if len(ids) != len(named):
+            raise ValueError("the checkpoint's decoder_optimizer holds %d parameters, the decoder trains %d"
+                             % (len(ids), len(named)))
+        keep = {k: v for k, v in theirs["param_groups"][0].items() if k in ("lr", "base_lr", "betas", "eps")}
+        for g in mine["param_groups"]:
+            g.update(keep)
+        mine["state"] = {k: theirs["state"][i] for k, i in enumerate(ids) if i in theirs["state"]}
+        opt.load_state_dict(mine)
+    return opt
 
 
 def _optimizer_steps(opt):
@@ -701,7 +747,8 @@ def main(cfg=None):
                          # Encoder.conv1; _train_fused_pipelined() flushes the last one of an epoch
                          lazy_update=bool(pipelined), label_smoothing=cfg.label_smoothing,
                          max_grad_norm=cfg.max_grad_norm, lr_schedule=cfg.lr_schedule, ema_decay=cfg.ema_decay,
-                         ema_warmup=cfg.ema_warmup)
+                         ema_warmup=cfg.ema_warmup, weight_decay=cfg.weight_decay,
+                         decoupled_weight_decay=cfg.decoupled_weight_decay, encoder_weight_decay=cfg.encoder_weight_decay)
         if decoder_optimizer is not None:
             # resume: Adam moments, step count (bias correction + dropout stream position) and the decayed lr come
             # back from the pickled optimizer (ours or one written by the reference, geo-aware/utils.py:32-46)
@@ -713,7 +760,10 @@ def main(cfg=None):
         # starts from rank 0's copy: every process initialised its own
         dp.broadcast_module_state([encoder, decoder], _bucket_range(step))
     elif decoder_optimizer is None:
-        decoder_optimizer = torch.optim.Adam([p for p in decoder.parameters() if p.requires_grad], lr=cfg.decoder_lr)
+        decoder_optimizer = make_decoder_optimizer(decoder, cfg)
+    elif cfg.weight_decay is not None or _has_decay_groups(decoder_optimizer):
+        # resume across decay on / off: the moments carry over, the decay and the group layout come from the Config
+        decoder_optimizer = make_decoder_optimizer(decoder, cfg, old=decoder_optimizer)
     # the moving average: the fused step keeps its own; the unfused path's is a lerp_ after optimizer.step().  A resumed
     # run takes it from the checkpoint (a checkpoint without one: the average starts at the loaded weights).
     ema = None

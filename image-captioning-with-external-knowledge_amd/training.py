@@ -867,6 +867,22 @@ def ema_decay_at(t, decay, warmup=False):
     return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
 
 
+def check_weight_decay(wd):
+    """None (no weight decay) or a finite float >= 0."""
+    if wd is None:
+        return None
+    wd = float(wd)
+    if not (wd >= 0.0 and math.isfinite(wd)):       # (NaN fails the compare)
+        raise IckError("weight_decay must be a finite float >= 0 (None: off), got %r" % (wd,))
+    return wd
+
+
+def default_decay_filter(name, param):
+    """What weight decay covers by default: matrices and embedding tables (ndim >= 2), not biases, norm scales or the
+    1-element parameters."""
+    return param.ndim >= 2
+
+
 def check_max_grad_norm(m):
     if m is None:
         return None
@@ -898,8 +914,29 @@ class TrainStep:
     def __init__(self, decoder, lr=4e-4, grad_clip=5.0, betas=(0.9, 0.999), eps=1e-8, process_group=None, seed=0,
                  use_graph=True, encoder=None, deterministic=None, lazy_update=False, label_smoothing=0.0,
                  max_grad_norm=None, lr_schedule=None, train_conv1=False, encoder_lr=1e-4, ema_decay=None,
-                 ema_warmup=False):
+                 ema_warmup=False, weight_decay=None, decoupled_weight_decay=True, decay_filter=None,
+                 encoder_weight_decay=None):
         self.dec = decoder
+        # weight_decay (finite float >= 0; None: off): weight decay inside the optimizer launch, on the
+        # decoder's parameters that decay_filter(name, param) selects (default: param.ndim >= 2 -- matrices and embedding
+        # tables, not biases, norm scales or 1-element parameters).  decoupled_weight_decay=True is torch.optim.AdamW
+        # (p *= 1 - lr_t * wd ahead of the update, lr_t the rate the update uses, scheduled or not); False is
+        # torch.optim.Adam(weight_decay=): wd * p joins the clamped gradient the moments see; max_grad_norm keeps
+        # measuring the gradient without the term and flat_g keeps it without the term.  encoder_weight_decay (needs
+        # train_conv1): the same for conv1.weight (never conv1.bias), at encoder_lr.  The values live in one-float device
+        # words (set_weight_decay / set_encoder_weight_decay replay the captured graphs); whether there is decay, its form
+        # and the selection are fixed at construction.  A step without tokens applies no update and so no decay (torch
+        # would decay on such a step; here the step does not exist).  Decay is a function of replicated state: no
+        # collective.  A hyper-parameter like grad_clip: state_dict() reports it per parameter, load_state_dict ignores
+        # stored values.  None: nothing is allocated, the same launches.
+        self.weight_decay = check_weight_decay(weight_decay)
+        self.encoder_weight_decay = check_weight_decay(encoder_weight_decay)
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self._decay_filter = decay_filter if decay_filter is not None else default_decay_filter
+        self._wd_word = self._wd_mask = self._enc_wd_word = self._enc_wd_mask = None
+        self._decayed = []
+        if self.encoder_weight_decay is not None and not train_conv1:
+            raise IckError("encoder_weight_decay needs train_conv1=True: the step trains no encoder parameter without it")
         # ema_decay (float in [0, 1); None: off): an exponential moving average of every trained parameter
         # (conv1's with train_conv1), e += (1 - d_t) (p - e) after each applied update, kept by the optimizer launch itself
         # in flat_e / enc_e, laid out like flat_p / enc_p and starting as copies of them.  d_t = ema_decay, or with
@@ -1013,6 +1050,16 @@ class TrainStep:
             self._eps_word = torch.full((1,), self.label_smoothing, device=dev, dtype=torch.float32)
         if self.ema_decay is not None:
             self._ema_word = torch.full((1,), self.ema_decay, device=dev, dtype=torch.float32)
+        if self.weight_decay is not None:
+            names = {}
+            for name, p in decoder.named_parameters():
+                names.setdefault(id(p), name)
+            self._decayed = [(names[id(p)], p) for p in params if self._decay_filter(names[id(p)], p)]
+            self._wd_word = torch.full((1,), self.weight_decay, device=dev, dtype=torch.float32)
+            self._wd_mask = db.decay_mask(p for _, p in self._decayed)
+        if self.encoder_weight_decay is not None:
+            self._enc_wd_word = torch.full((1,), self.encoder_weight_decay, device=dev, dtype=torch.float32)
+            self._enc_wd_mask = eb.decay_mask([encoder.conv1.weight])
         self._graphs = {}
         # the re-laid-out copies of the weights (packed row-chain images, cross K/V gather, bf16 planes) that the optimizer
         # kernel keeps current itself: built on the first call (DerivedWeights); ICK_ADAM_DERIVE=0 keeps the per-step
@@ -1211,6 +1258,11 @@ class TrainStep:
             return {}
         return dict(ema=e, ema_decay_word=self._ema_word, ema_warmup=self.ema_warmup)
 
+    def _decay_kwargs(self, word, mask):
+        if word is None:
+            return {}
+        return dict(decay_word=word, decay_mask=mask, decoupled=self.decoupled_weight_decay)
+
     def _adam_conv1(self):
         """conv1's own update: the same division by the global token count, the element clamp, Adam with encoder_lr and
         the step counter the decoder's update of the same step reads (so it runs before the counter advances) -- then the
@@ -1218,7 +1270,8 @@ class TrainStep:
         place.  A no-op on the parameters while the token count is zero, as the decoder's update."""
         ops.adam_update(self.enc_p, self.enc_g, self.enc_m, self.enc_v, 1, lr=self.encoder_lr, clip=self.clip, gscale=1.0,
                         beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step_tensor=self.counter,
-                        gscale_den=self.flat_g[self._t + 1:], **self._ema_kwargs(self.enc_e))
+                        gscale_den=self.flat_g[self._t + 1:], **self._ema_kwargs(self.enc_e),
+                        **self._decay_kwargs(self._enc_wd_word, self._enc_wd_mask))
         self._conv1_resplit()
 
     def _conv1_resplit(self):
@@ -1265,7 +1318,8 @@ class TrainStep:
         # (the update runs over flat_p's n floats or the cover: flat_g's two trailing words stay outside without a view)
         ops.adam_update(self.flat_p, self.flat_g, self.flat_m, self.flat_v, 1, cover=self.derived,
                         clip=self.clip, gscale=1.0, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                        step_tensor=self.counter, gscale_den=den, **rate, **self._ema_kwargs(self.flat_e))
+                        step_tensor=self.counter, gscale_den=den, **rate, **self._ema_kwargs(self.flat_e),
+                        **self._decay_kwargs(self._wd_word, self._wd_mask))
 
     # ---- the same step in two halves (several ranks: the early half's all-reduce overlaps the late half) ----
     def _part_a1(self, *inputs):
@@ -1335,11 +1389,31 @@ class TrainStep:
         (geo-aware/utils.py:32-46) and with the fused=False path.  Tensors are copies."""
         self.flush()
         self._check_views()
-        return self._dec_bucket.adam_state(self._adam_order(), self._step(), self.lr, self.betas, self.eps)
+        order = self._adam_order()
+        return self._dec_bucket.adam_state(order, self._step(), self.lr, self.betas, self.eps,
+                                           **self._decay_groups(order, self.weight_decay, self._decayed))
+
+    def _decay_groups(self, order, wd, decayed):
+        """adam_state's decay arguments: with decay on, one value per parameter of `order` (0 where it is not selected)."""
+        if wd is None:
+            return {}
+        chosen = {id(p) for _, p in decayed}
+        return dict(decay=[wd if id(p) in chosen else 0.0 for p in order], decoupled=self.decoupled_weight_decay)
+
+    def _torch_optimizer(self, order, lr, wd, decayed):
+        """torch.optim.Adam over `order`, or with decay on AdamW / Adam over one param group per parameter."""
+        kw = dict(lr=lr, betas=tuple(self.betas), eps=self.eps)
+        if wd is None:
+            return torch.optim.Adam(order, **kw)
+        groups = self._decay_groups(order, wd, decayed)["decay"]
+        cls = torch.optim.AdamW if self.decoupled_weight_decay else torch.optim.Adam
+        return cls([dict(params=[p], weight_decay=w) for p, w in zip(order, groups)], weight_decay=0.0, **kw)
 
     def load_state_dict(self, sd):
         """Restore Adam moments, step count (which also positions the dropout stream) and learning rate from a
-        torch.optim.Adam-layout state dict: ours, the reference's, or the fused=False path's."""
+        torch.optim.Adam-layout state dict: ours, the reference's, or the fused=False path's -- one param group or one per
+        parameter.  Stored weight-decay values are ignored: decay is a hyper-parameter like grad_clip, and the
+        constructor's (or set_weight_decay's) value holds."""
         self.flush()
         self._check_views()
         order = self._adam_order()
@@ -1370,7 +1444,7 @@ class TrainStep:
     def as_torch_optimizer(self):
         """A live torch.optim.Adam over the decoder's parameters carrying this step's state: what goes into the
         checkpoint under 'decoder_optimizer', exactly the kind of object the reference pickles there."""
-        opt = torch.optim.Adam(self._adam_order(), lr=self.lr, betas=tuple(self.betas), eps=self.eps)
+        opt = self._torch_optimizer(self._adam_order(), self.lr, self.weight_decay, self._decayed)
         opt.load_state_dict(self.state_dict())
         return opt
 
@@ -1386,7 +1460,9 @@ class TrainStep:
         feature-file encoder's trainable parameters [conv1.weight, conv1.bias] (geo-aware/train.py:93-100).  Both optimizers
         step together: the step count is the decoder's.  Tensors are copies; state_dict() is unchanged."""
         self._need_conv1("encoder_state_dict")
-        return self._enc_bucket.adam_state(self.enc_params, self._step(), self.encoder_lr, self.betas, self.eps)
+        return self._enc_bucket.adam_state(self.enc_params, self._step(), self.encoder_lr, self.betas, self.eps,
+                                           **self._decay_groups(self.enc_params, self.encoder_weight_decay,
+                                                                self._enc_decayed()))
 
     def load_encoder_state_dict(self, sd):
         """Restore conv1's moments and rate from a torch.optim.Adam-layout state dict over [conv1.weight, conv1.bias].  The
@@ -1406,9 +1482,40 @@ class TrainStep:
         """A live torch.optim.Adam over [conv1.weight, conv1.bias] carrying conv1's state: what goes into the checkpoint
         under 'encoder_optimizer', the kind of object the reference pickles there."""
         sd = self.encoder_state_dict()
-        opt = torch.optim.Adam(self.enc_params, lr=self.encoder_lr, betas=tuple(self.betas), eps=self.eps)
+        opt = self._torch_optimizer(self.enc_params, self.encoder_lr, self.encoder_weight_decay, self._enc_decayed())
         opt.load_state_dict(sd)
         return opt
+
+    # ---- weight decay (weight_decay= / encoder_weight_decay=, DESIGN.md 3.1k) -----------------------
+    def _enc_decayed(self):
+        return [("conv1.weight", self.enc_params[0])] if self.encoder_weight_decay is not None else []
+
+    def decayed_parameter_names(self):
+        """The names of the parameters weight decay covers: the decoder's (named_parameters() names, bucket order), then
+        "encoder.conv1.weight" with encoder_weight_decay.  Empty without decay."""
+        return [n for n, _ in self._decayed] + ["encoder." + n for n, _ in self._enc_decayed()]
+
+    def _set_decay(self, wd, what, attr, word):
+        if (wd is None) != (word is None):
+            raise IckError("weight decay cannot be switched %s after construction: build the TrainStep with%s %s="
+                           % (("off", "out", what) if wd is None else ("on", "", what)))
+        if wd is None:
+            return
+        wd = check_weight_decay(wd)
+        self.flush()
+        setattr(self, attr, wd)
+        word.fill_(wd)
+
+    def set_weight_decay(self, wd):
+        """A new weight-decay value for the decoder's selected parameters, applied from the next update on: only the
+        device word is written, the captured graphs replay.  A pending (lazy_update) update is applied first, under the
+        old value.  Whether there is decay is fixed at construction: None here, or a value for a step built without it,
+        is refused."""
+        self._set_decay(wd, "weight_decay", "weight_decay", self._wd_word)
+
+    def set_encoder_weight_decay(self, wd):
+        """set_weight_decay for conv1.weight's decay (encoder_weight_decay=)."""
+        self._set_decay(wd, "encoder_weight_decay", "encoder_weight_decay", self._enc_wd_word)
 
     # ---- the moving average of the parameters (ema_decay=, DESIGN.md 3.1j) -------------------------
     def _need_ema(self, what):

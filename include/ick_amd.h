@@ -801,6 +801,32 @@ int ick_adam_ema_derive(float* p, float* g, float* m, float* v, float* e, const 
                         const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr, float* words,
                         ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
                         const float* gscale_den, const float* ema_decay, int32_t ema_warmup, void* stream);
+/* The Adam entries above WITH weight decay on a per-parameter selection.  decay: a DEVICE float wd (a
+ * captured graph follows a new value).  decay_mask: n_granules bytes on the device, one per 64 floats of the bucket counted
+ * from the bucket's start (p itself, whatever its address); the elements of a granule whose byte is non-zero decay, the
+ * others get the entries' above bits.  Every parameter of a bucket starts at a multiple of 64 floats, so a granule belongs
+ * to one parameter.  decay_form, in float32 operations kept apart:
+ *   ICK_DECAY_DECOUPLED (torch.optim.AdamW)   once: f = 1 - lr_t * wd, lr_t the rate this update uses (lr, or with words
+ *                                             the scheduled rate);  per element: p = p * f, then the unchanged update;
+ *   ICK_DECAY_COUPLED (Adam(weight_decay=))   per element, x the gradient after scale, clip coefficient and clamp:
+ *                                             x2 = x + wd * p feeds the moments and the update; g is written back as x.
+ * words == NULL: the host rate lr; e == NULL: no moving average (ema_decay / ema_warmup are not read), else as
+ * ick_adam_ema[_derive].  While *gscale_den is not > 0 nothing is written: no decay either.
+ * ICK_EINVAL without a launch: decay or decay_mask NULL, n_granules < ceil(n / 64) (flat form) or < 1 (derive form, whose
+ * cover lies on the device: there the kernel takes a granule beyond the table as not selected), an unknown decay_form,
+ * and what the entries above refuse. */
+#define ICK_DECAY_DECOUPLED 0
+#define ICK_DECAY_COUPLED 1
+int ick_adam_decay(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip, float lr,
+                   float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                   const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
+                   const float* decay, const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form, void* stream);
+int ick_adam_decay_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
+                          const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr, float* words,
+                          ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                          const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
+                          const float* decay, const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form,
+                          void* stream);
 /* The weight and bias gradient of Encoder.conv1 (1x1 convolution) straight from the NCHW feature map:
  *     dw[o, c] = sum over b, p of d_img[b, p, o] * feats[b, c, p],     db[o] = sum over b, p of d_img[b, p, o].
  * d_img (B, P, d): the gradient of the image memory rows; feats (B, C, P): the feature map as it lies; dw (d, C): conv1's
