@@ -18,4 +18,12 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1
     return c;
 }
 
+// The Gumbel noise of a 32-bit draw x (Gumbel-max sampling: sample.hip, sched_sample.hip): -log(-log(u)) in fp32 with the
+// accurate logf, u = min(fl32((x >> 8) + 0.5) * 2^-24, 1 - 2^-24).
+__device__ __forceinline__ float gumbel(uint32_t x) {
+    float u = ((float)(x >> 8) + 0.5f) * 0x1p-24f;
+    u = fminf(u, 0x1.fffffep-1f);
+    return -logf(-logf(u));
+}
+
 }  // namespace ick

@@ -64,12 +64,6 @@ __device__ __forceinline__ uint32_t okey(float f) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
-__device__ __forceinline__ float gumbel(uint32_t x) {
-    float u = ((float)(x >> 8) + 0.5f) * 0x1p-24f;
-    u = fminf(u, 0x1.fffffep-1f);
-    return -logf(-logf(u));
-}
-
 // Wave 0 scans a 256-bin histogram from the top digit down and returns (in LDS) the first digit whose inclusive
 // running total reaches `need` (counts) -- lane l owns digits 255 - 4l .. 252 - 4l.
 template <typename T>

@@ -262,6 +262,8 @@ SIGNATURES = {
     "ick_gather_rows": [vp, i64, vp, vp, vp, i64, i32, i32, vp],
     "ick_row_logprob_rank": [vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "ick_caption_score_sums": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "ick_sched_sample_mix": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp,
+                             vp],
     "ick_caption_metrics": [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, C.c_double, i32, vp, i32, vp,
                             vp, vp, vp, vp, vp, vp, vp, vp],
     "ick_caption_metric_sums": [vp, vp, vp, i32, vp, vp, vp, vp],

@@ -900,6 +900,46 @@ def samples_to_captions(tokens, V, K, has_facts, start, end, pad, out=None):
     return caps, masks, lengths
 
 
+SCHED_SAMPLE_MODES = ("sample", "argmax")
+
+
+def sched_sample_mix(scores, pack, captions, caption_masks, V, K, F, start_token, pad_token, prob, temperature, seed,
+                     step, mode="sample", out=None):
+    """Scheduled sampling's mixed inputs (ick_sched_sample_mix) from the PACKED score rows of a
+    teacher-forced pass (scores (B, L, Vx) as _score_head(pack=) writes them, pack: the HeadRows) and the gold captions /
+    caption_masks (B, L) int64 -> (captions_in, masks_in int64, replaced int32), each (B, L) and written whole.  prob,
+    temperature (float32), seed (int64) and step (int32, read as uint32: TrainStep's counter) are ONE-element device
+    tensors the kernel reads, so a captured launch follows new values; mode ("sample" | "argmax") is fixed at launch.
+    out: the three tensors to write."""
+    B, Lc, Vx = scores.shape
+    dev = scores.device
+    if mode not in SCHED_SAMPLE_MODES:
+        raise L.IckError("sched_sample_mix: unknown mode %r (one of %s)" % (mode, ", ".join(SCHED_SAMPLE_MODES)))
+    if Vx != V + K + F:
+        raise L.IckError("sched_sample_mix: scores have %d columns, V + K + F is %d" % (Vx, V + K + F))
+    for name, t in (("captions", captions), ("caption_masks", caption_masks)):
+        if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (B, Lc):
+            raise L.IckError("sched_sample_mix needs contiguous int64 %s (%d, %d) on the device" % (name, B, Lc))
+    for name, t, dt in (("prob", prob, torch.float32), ("temperature", temperature, torch.float32),
+                        ("seed", seed, torch.int64), ("step", step, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.numel() != 1 or t.dtype != dt or not t.is_cuda:
+            raise L.IckError("sched_sample_mix needs %s as a one-element %s tensor on the device" % (name, dt))
+    # all B * L rows of the buffer exist (the valid ones packed at its top): the kernel's row bound relies on it
+    assert scores.stride(0) == Lc * scores.stride(1) and scores.stride(2) == 1
+    assert pack.B == B and pack.L == Lc
+    if out is None:
+        out = (torch.empty(B, Lc, device=dev, dtype=torch.int64), torch.empty(B, Lc, device=dev, dtype=torch.int64),
+               torch.empty(B, Lc, device=dev, dtype=torch.int32))
+    caps_in, masks_in, replaced = out
+    assert all(tuple(t.shape) == (B, Lc) and t.is_contiguous() for t in out)
+    assert caps_in.dtype == masks_in.dtype == torch.int64 and replaced.dtype == torch.int32
+    L.check(L.load().ick_sched_sample_mix(_p(scores), scores.stride(1), _p(pack.rowstart), _p(pack.decode_len),
+                                          _p(captions), _p(caption_masks), B, Lc, V, K, F, start_token, pad_token,
+                                          _p(prob), _p(temperature), _p(seed), _p(step), int(mode == "argmax"),
+                                          _p(caps_in), _p(masks_in), _p(replaced), _stream()), "ick_sched_sample_mix")
+    return caps_in, masks_in, replaced
+
+
 CIDER_MODES = {None: 0, "greedy": 1, "mean": 2}
 
 

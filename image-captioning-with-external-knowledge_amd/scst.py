@@ -72,6 +72,9 @@ class SelfCriticalStep:
             # reach Encoder.conv1: self-critical training with a trained projection is not supported
             raise IckError("SelfCriticalStep cannot drive a TrainStep built with train_conv1=True (its samples share "
                            "token-major encoder rows through image_index)")
+        if getattr(train_step, "ss", None) is not None:
+            raise IckError("SelfCriticalStep cannot drive a TrainStep built with scheduled_sampling=: it trains on sampled "
+                           "captions already (and weighs them with caption_weights, which such a step refuses)")
         self.ts = train_step
         self.dec = train_step.dec
         self.reward_fn = reward_fn

@@ -29,7 +29,11 @@ launch, TrainStep(ema_decay=); unfused: TorchEma, a lerp_ after optimizer.step()
 `weight_decay=<float >= 0>`: weight decay on the decoder's matrices and embedding tables (ndim >= 2), torch.optim.AdamW's
 (`decoupled_weight_decay=True`) or torch.optim.Adam(weight_decay=)'s -- fused: inside the optimizer launch
 (TrainStep(weight_decay=)); unfused: the torch optimizer itself; on both the checkpoint's `decoder_optimizer` then has one
-param group per parameter, and a resume takes the moments from either layout and the decay from the Config."""
+param group per parameter, and a resume takes the moments from either layout and the decay from the Config.
+`scheduled_sampling_start=<epoch >= 0>`: scheduled sampling in the cross-entropy phase (fused only,
+TrainStep(scheduled_sampling=)): from that epoch on each fed token is replaced with the model's own prediction with the
+probability training.sampling_prob_at gives the epoch (the staircase scheduled_sampling_increase_every /
+_increase_prob / _max_prob), set once per epoch through set_sampling_prob.  Validation is unchanged."""
 import contextlib
 import json
 import math
@@ -49,8 +53,8 @@ from .datasets import CaptionDataset
 from .geo_metric import GeoReferenceMetric
 from .metrics import CaptionMetrics
 from .scst import SelfCriticalStep
-from .training import (TrainStep, check_ema_decay, check_lr_schedule, check_max_grad_norm, check_weight_decay,
-                       default_decay_filter, ema_decay_at, lr_at)
+from .training import (TrainStep, check_ema_decay, check_lr_schedule, check_max_grad_norm, check_scheduled_sampling,
+                       check_weight_decay, default_decay_filter, ema_decay_at, lr_at, sampling_prob_at)
 
 
 @dataclass
@@ -134,14 +138,27 @@ class Config:
                                                        # param group per parameter); None: off
     decoupled_weight_decay: bool = True                # True: torch.optim.AdamW; False: torch.optim.Adam(weight_decay=)
     encoder_weight_decay: object = None                # with train_conv1: the same for Encoder.conv1.weight
+    scheduled_sampling_start: int = -1                 # epoch from which fed tokens are replaced with the model's own
+                                                       # predictions (fused only, TrainStep(scheduled_sampling=)); -1: off
+    scheduled_sampling_increase_every: int = 5         # the probability of epoch e >= start is min(max_prob,
+    scheduled_sampling_increase_prob: float = 0.05     # increase_prob * ((e - start) // increase_every + 1))
+    scheduled_sampling_max_prob: float = 0.25          # (training.sampling_prob_at)
+    scheduled_sampling_mode: str = "sample"            # "sample" (Gumbel-max draw at temperature 1) | "argmax"
 
     def __post_init__(self):
         try:
             check_ema_decay(self.ema_decay)
             check_weight_decay(self.weight_decay)
             check_weight_decay(self.encoder_weight_decay)
+            check_scheduled_sampling(dict(prob=self.scheduled_sampling_max_prob, mode=self.scheduled_sampling_mode))
+            check_scheduled_sampling(dict(prob=self.scheduled_sampling_increase_prob))
+            sampling_prob_at(0, 0, self.scheduled_sampling_increase_every, 0.0, 0.0)
         except RuntimeError as e:
             raise ValueError(str(e))
+        if self.scheduled_sampling_start >= 0 and (self.scst or not self.fused or self.fine_tune_encoder):
+            raise ValueError("scheduled_sampling_start >= 0 needs the fused cross-entropy step (fused=True, "
+                             "fine_tune_encoder=False, scst=False): the package has no route to the packed score rows of "
+                             "the first pass outside TrainStep, and SCST trains on sampled captions already")
         if self.encoder_weight_decay is not None and not self.train_conv1:
             raise ValueError("encoder_weight_decay needs train_conv1=True")
 
@@ -748,7 +765,10 @@ def main(cfg=None):
                          lazy_update=bool(pipelined), label_smoothing=cfg.label_smoothing,
                          max_grad_norm=cfg.max_grad_norm, lr_schedule=cfg.lr_schedule, ema_decay=cfg.ema_decay,
                          ema_warmup=cfg.ema_warmup, weight_decay=cfg.weight_decay,
-                         decoupled_weight_decay=cfg.decoupled_weight_decay, encoder_weight_decay=cfg.encoder_weight_decay)
+                         decoupled_weight_decay=cfg.decoupled_weight_decay, encoder_weight_decay=cfg.encoder_weight_decay,
+                         # (seed None: the step's own, which is offset by the rank above; the probability is set per epoch)
+                         scheduled_sampling=None if cfg.scheduled_sampling_start < 0 else
+                         dict(prob=0.0, mode=cfg.scheduled_sampling_mode))
         if decoder_optimizer is not None:
             # resume: Adam moments, step count (bias correction + dropout stream position) and the decayed lr come
             # back from the pickled optimizer (ours or one written by the reference, geo-aware/utils.py:32-46)
@@ -811,6 +831,10 @@ def main(cfg=None):
         # the epoch's permutation depends on (seed, epoch) only, so a resumed run sees the batches the interrupted
         # one would have seen
         shuffle_gen.manual_seed(cfg.seed * 100003 + epoch)
+        if step is not None and step.ss is not None:
+            step.set_sampling_prob(sampling_prob_at(epoch, cfg.scheduled_sampling_start, cfg.scheduled_sampling_increase_every,
+                                                    cfg.scheduled_sampling_increase_prob, cfg.scheduled_sampling_max_prob))
+            STATS["sampling_prob"] = step.ss["prob"]
         if samplers["TRAIN"] is not None:
             samplers["TRAIN"].set_epoch(epoch)
         if sc is not None:

@@ -893,6 +893,53 @@ def check_max_grad_norm(m):
 
 
 # ----------------------------------------------------------------------------------------------
+# scheduled sampling: the definitions
+# ----------------------------------------------------------------------------------------------
+SAMPLING_MODES = ops.SCHED_SAMPLE_MODES
+
+
+def check_sampling_prob(p):
+    p = float(p)
+    if not 0.0 <= p <= 1.0:           # (NaN fails both compares)
+        raise IckError("scheduled_sampling: prob must lie in [0, 1], got %r" % (p,))
+    return p
+
+
+def check_sampling_temperature(T):
+    T = float(T)
+    if not (T > 0.0 and math.isfinite(T)):
+        raise IckError("scheduled_sampling: temperature must be a finite float > 0, got %r" % (T,))
+    return T
+
+
+def check_scheduled_sampling(ss):
+    """dict(prob=0.25, mode="sample" | "argmax", temperature=1.0, seed=None) -> the same with every key present and
+    checked (None stays None).  0 <= prob <= 1, temperature > 0; seed None: the step's own seed."""
+    if ss is None:
+        return None
+    if not isinstance(ss, dict) or set(ss) - {"prob", "mode", "temperature", "seed"}:
+        raise IckError("scheduled_sampling must be a dict of prob, mode, temperature, seed; got %r" % (ss,))
+    mode = ss.get("mode", "sample")
+    if mode not in SAMPLING_MODES:
+        raise IckError("scheduled_sampling: unknown mode %r (one of %s)" % (mode, ", ".join(SAMPLING_MODES)))
+    seed = ss.get("seed")
+    if seed is not None and (isinstance(seed, bool) or int(seed) != seed or not -2 ** 63 <= seed < 2 ** 64):
+        raise IckError("scheduled_sampling: seed must be an integer of at most 64 bits or None, got %r" % (seed,))
+    return dict(prob=check_sampling_prob(ss.get("prob", 0.25)), mode=mode,
+                temperature=check_sampling_temperature(ss.get("temperature", 1.0)), seed=None if seed is None else int(seed))
+
+
+def sampling_prob_at(epoch, start, increase_every, increase_prob, max_prob):
+    """The usual staircase of the scheduled-sampling probability over the epochs: 0 before `start` (and for start < 0:
+    off), then min(max_prob, increase_prob * ((epoch - start) // increase_every + 1))."""
+    if increase_every < 1:
+        raise IckError("sampling_prob_at: increase_every must be an integer >= 1, got %r" % (increase_every,))
+    if start < 0 or epoch < start:
+        return 0.0
+    return min(float(max_prob), float(increase_prob) * ((int(epoch) - int(start)) // int(increase_every) + 1))
+
+
+# ----------------------------------------------------------------------------------------------
 # fused data-parallel training step
 # ----------------------------------------------------------------------------------------------
 class TrainStep:
@@ -915,8 +962,27 @@ class TrainStep:
                  use_graph=True, encoder=None, deterministic=None, lazy_update=False, label_smoothing=0.0,
                  max_grad_norm=None, lr_schedule=None, train_conv1=False, encoder_lr=1e-4, ema_decay=None,
                  ema_warmup=False, weight_decay=None, decoupled_weight_decay=True, decay_filter=None,
-                 encoder_weight_decay=None):
+                 encoder_weight_decay=None, scheduled_sampling=None):
         self.dec = decoder
+        # scheduled_sampling (dict(prob=0.25, mode="sample" | "argmax", temperature=1.0, seed=None); None: off; DESIGN.md
+        # 3.1l): the two-pass scheduled sampling of a Transformer decoder.  Part A starts with a FIRST PASS -- the inference
+        # layers on the gold captions, without dropout whatever the module's mode (the decoder as it will decode, the
+        # choice score_captions makes), the packed score head over the valid rows and ick_sched_sample_mix, which replaces
+        # each fed token with the model's own prediction for that position with probability prob (drawn through Gumbel
+        # noise at `temperature`, or the argmax).  The existing pass then runs on the mixed captions / masks -- embedding,
+        # context indicators, predicate gate and every backward kernel that reads the fed tokens follow them -- against the
+        # GOLD targets.  prob, temperature and the seed (None: the step's own) live in device words (set_sampling_prob /
+        # set_sampling_temperature replay the captured graphs); the coin and the noise take the step's device counter, so
+        # every replay draws anew; whether there is sampling and its mode are part of the graph key.  sampled_inputs()
+        # hands out the last step's (captions_in, masks_in, replaced).  The first pass has to see the newest weights: such
+        # a step applies its update eagerly, lazy_update does not defer it (_lazy_active is false).  It reads the weight
+        # images the second pass of the same step reads.  The mix is rank-local: no collective changes.  Not with
+        # caption_weights or image_index (SelfCriticalStep trains on sampled captions already).  None: nothing is
+        # allocated, the same launches.
+        self.ss = check_scheduled_sampling(scheduled_sampling)
+        self._ss_words = self._ss_out = None
+        self._ss_bufs, self._ss_first = {}, {}        # (B, L) -> the mix kernel's outputs; graph key -> the first pass's graph
+        self._ss_inline = os.environ.get("ICK_SS_ONE_GRAPH", "0") not in ("", "0")
         # weight_decay (finite float >= 0; None: off): weight decay inside the optimizer launch, on the
         # decoder's parameters that decay_filter(name, param) selects (default: param.ndim >= 2 -- matrices and embedding
         # tables, not biases, norm scales or 1-element parameters).  decoupled_weight_decay=True is torch.optim.AdamW
@@ -1050,6 +1116,11 @@ class TrainStep:
             self._eps_word = torch.full((1,), self.label_smoothing, device=dev, dtype=torch.float32)
         if self.ema_decay is not None:
             self._ema_word = torch.full((1,), self.ema_decay, device=dev, dtype=torch.float32)
+        if self.ss is not None:
+            sd = (self.seed if self.ss["seed"] is None else self.ss["seed"]) & (2 ** 64 - 1)
+            self._ss_words = (torch.full((1,), self.ss["prob"], device=dev, dtype=torch.float32),
+                              torch.full((1,), self.ss["temperature"], device=dev, dtype=torch.float32),
+                              torch.tensor([sd - 2 ** 64 if sd >= 2 ** 63 else sd], device=dev, dtype=torch.int64))
         if self.weight_decay is not None:
             names = {}
             for name, p in decoder.named_parameters():
@@ -1216,7 +1287,13 @@ class TrainStep:
         _part_a1 / _part_a2 in two phases.  The lazy hooks are None in the split step (_lazy_active is false there)."""
         box = {}
         lazy = self._lazy_active(enc_in)
-        scores, tape = forward_with_tape(self.dec, captions, caption_masks, entities, facts, gmap=gmap,
+        fed, fed_masks = captions, caption_masks      # the targets stay `captions`, whatever is fed
+        if self.ss is not None:
+            # the first pass has written the mixed inputs: in a graph of its own in front of this one, or (A/B runs) here
+            if self._ss_inline:
+                self._first_pass(captions, caption_masks, entities, facts, enc_in, gmap, lengths)
+            fed, fed_masks = self._ss_bufs[tuple(captions.shape)][:2]
+        scores, tape = forward_with_tape(self.dec, fed, fed_masks, entities, facts, gmap=gmap,
                                          seed=self.seed * 2654435761 & 0xFFFFFFFF, epoch=self.counter, fresh_pack=True,
                                          overlap=self._overlap("ICK_NO_FWD_OVERLAP"),
                                          side_tail=self._side_tail(box, captions, entities, facts, lengths),
@@ -1230,6 +1307,76 @@ class TrainStep:
         return (self.dec, tape, ce[2], self.grads), dict(self._conv1_bwd_kwargs(enc_in),
                                                          overlap=self._overlap("ICK_NO_BWD_OVERLAP"))
 
+    # ---- scheduled sampling (scheduled_sampling=) ---------------------------------
+    def _first_pass(self, captions, caption_masks, entities, facts, enc_in, gmap, lengths, weights=None):
+        """The first pass of a step with scheduled sampling (part A's argument list), into the step's (captions_in, masks_in,
+        replaced) buffers: the inference layers on the gold prefix (no dropout, nothing saved), a head hook that lists the
+        valid rows, runs the packed score head over them and the mix kernel.  The pass reads the re-laid-out weights
+        through dec.weight_images(), the very buffers the second pass reads: with DerivedWeights the optimizer launch has
+        just written them (they are stamped current, no launch); without, they are filled here from the live parameters,
+        unconditionally -- a launch whose presence must not depend on what the host believes while a graph is captured.
+        Captured steps replay it as a graph of its own in front of graph A, the structure of score_captions' graph (cfg2
+        step 4.95 ms; 5.17 ms with the pass captured inside graph A, which ICK_SS_ONE_GRAPH=1 keeps for A/B runs; DESIGN.md
+        3.1l)."""
+        dec = self.dec
+        B, Lc = captions.shape
+        V, K = dec.vocab_size, entities.shape[1]
+        Fn = facts.shape[1] if dec.has_facts else 0
+        wm = dec.word_map
+        wi = dec.weight_images()
+        groups = ["kv"] + (["chain"] if dec.chain_supported() else []) + (["pred_wt"] if dec.has_facts else [])
+        if ops.gemm_split_mode() != 0:
+            groups += ["kv_ps"] + (["vocab_ps"] if vocab_planes_wanted(B * Lc) else [])
+        if self.derived is not None:
+            wi.adopt(*groups)
+        else:
+            wi.refresh(*groups)
+        out = self._ss_bufs[(B, Lc)]
+
+        def head(x, ee, fe, eib, hv):
+            pack = ops.HeadRows(lengths, B, Lc)
+            Vx = V + K + Fn
+            ld = (Vx + 3) // 4 * 4          # 16-byte aligned rows for the mix kernel's float4 loads
+            scores = torch.empty(B, Lc, ld, device=x.device, dtype=torch.float32)[:, :, :Vx]
+            dec._score_head(x, ee, fe, eib, hv, scores, dec._vocab_presplit(B * Lc), pack=pack)
+            ops.stamp("first pass: packed scores done")
+            prob, temp, seed = self._ss_words
+            return ops.sched_sample_mix(scores, pack, captions, caption_masks, V, K, Fn, wm["<start>"], wm["<pad>"], prob,
+                                        temp, seed, self.counter, mode=self.ss["mode"], out=out)
+
+        with torch.no_grad():
+            # (a feature map goes through Encoder.conv1 here and again in the second pass, which writes the rows straight
+            # into its memory buffer)
+            enc_tok = dec._token_major(self.enc(enc_in)) if enc_in.dim() == 4 else enc_in
+            dec._forward_device(captions, caption_masks, entities, facts, enc_tok, None, head=head)
+        ops.stamp("first pass: mixed inputs done")
+
+    def _need_sampling(self, what):
+        if self.ss is None:
+            raise IckError("%s needs a TrainStep built with scheduled_sampling=" % what)
+
+    def set_sampling_prob(self, p):
+        """A new replacement probability, from the next step on: only the device word is written, the captured graphs
+        replay.  Whether there is scheduled sampling is fixed at construction."""
+        self._need_sampling("set_sampling_prob")
+        self.ss["prob"] = check_sampling_prob(p)
+        self._ss_words[0].fill_(self.ss["prob"])
+
+    def set_sampling_temperature(self, T):
+        """A new temperature of the draw (mode "sample"), from the next step on: only the device word is written."""
+        self._need_sampling("set_sampling_temperature")
+        self.ss["temperature"] = check_sampling_temperature(T)
+        self._ss_words[1].fill_(self.ss["temperature"])
+
+    def sampled_inputs(self):
+        """The last step's (captions_in, masks_in int64, replaced int32), each (B, L) on the device: what its second pass
+        was fed and where the model's own prediction took gold's place.  No synchronisation; the tensors are the step's
+        own buffers, written again by the next step of the same shape (clone() to keep them)."""
+        self._need_sampling("sampled_inputs")
+        if self._ss_out is None:
+            raise IckError("sampled_inputs: no step has run yet")
+        return self._ss_out
+
     def _part_a(self, *inputs):
         ops.stamp("A: start")
         args, kwargs = self._forward_and_loss(*inputs)
@@ -1237,7 +1384,9 @@ class TrainStep:
         ops.stamp("A: end (after join)")
 
     def _lazy_active(self, enc_in):
-        return bool(self.lazy and self.use_graph and self.derived is not None and not self.split and not self.deterministic
+        # (not with scheduled sampling: its first pass has to see this step's weights, so the update is never deferred)
+        return bool(self.lazy and self.ss is None and self.use_graph and self.derived is not None and not self.split
+                    and not self.deterministic
                     and enc_in is not None and enc_in.dim() == 4 and self._overlap("ICK_NO_FWD_OVERLAP"))
 
     def _conv1_bwd_kwargs(self, enc_in):
@@ -1351,17 +1500,23 @@ class TrainStep:
         torch.cuda.current_stream().wait_stream(side)
         return static
 
-    def _capture(self, fn, inputs):
-        static = self._warm_static(fn, inputs)
+    @staticmethod
+    def _after(first, fn):
+        """fn, behind `first` on the same arguments when there is one (the warm-up run of a step with scheduled sampling:
+        part A reads what the first pass wrote)."""
+        return fn if first is None else lambda *s: (first(*s), fn(*s))
+
+    def _capture(self, fn, inputs, first=None):
+        static = self._warm_static(self._after(first, fn), inputs)
         g = torch.cuda.CUDAGraph()
         with ops.capture(g):
             fn(*static)
         return g, static
 
-    def _capture_split(self, inputs):
+    def _capture_split(self, inputs, first=None):
         """Graphs A1 (forward, CE, early backward) and A2 (late backward) over one memory pool: A2 reads what A1 left
         in the tape."""
-        static = self._warm_static(lambda *s: (self._part_a1(*s), self._part_a2()), inputs)
+        static = self._warm_static(self._after(first, lambda *s: (self._part_a1(*s), self._part_a2())), inputs)
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with ops.capture(g1):
             self._part_a1(*static)
@@ -1689,6 +1844,9 @@ class TrainStep:
         dev = encoder_out.device
         if image_index is not None and encoder_out.dim() == 4:
             raise IckError("image_index needs a token-major encoder_out (B, d, P), not a 4-D feature map")
+        if self.ss is not None and (caption_weights is not None or image_index is not None):
+            raise IckError("scheduled_sampling: a step built with it takes no caption_weights and no image_index (its inputs "
+                           "are mixed per caption row; SelfCriticalStep trains on sampled captions already)")
         if self.train_conv1 and (encoder_out.dim() != 4 or image_index is not None):
             raise IckError("train_conv1=True needs the 4-D feature map as encoder_out and no image_index: from a token-major "
                            "encoder_out the step cannot reach Encoder.conv1")
@@ -1717,6 +1875,17 @@ class TrainStep:
         key = tuple(None if t is None else tuple(t.shape) for t in inputs) + (ops.gemm_split_mode(),)
         if self.label_smoothing != 0.0:
             key += ("label_smoothing",)     # another loss kernel; the value itself is read from the device word
+        if self.ss is not None:
+            key += ("scheduled_sampling", self.ss["mode"])      # the first pass; prob / temperature / seed are device words
+            B, Lc = captions.shape
+            if (B, Lc) not in self._ss_bufs:    # the mix kernel's outputs: the step's own, outside every graph's pool
+                if len(self._ss_bufs) >= 4:
+                    self._ss_bufs.clear()
+                    self._graphs.clear()
+                self._ss_bufs[(B, Lc)] = (torch.zeros(B, Lc, device=dev, dtype=torch.int64),
+                                          torch.zeros(B, Lc, device=dev, dtype=torch.int64),
+                                          torch.zeros(B, Lc, device=dev, dtype=torch.int32))
+            self._ss_out = self._ss_bufs[(B, Lc)]
         if not self._derived_tried:
             self._derived_tried = True
             if os.environ.get("ICK_ADAM_DERIVE", "1") != "0":
@@ -1732,11 +1901,19 @@ class TrainStep:
             state = [self.counter] + [t for b in self._buckets for t in b.tensors()]
             snap = [t.clone() for t in state]
             try:
+                first = self._first_pass if self.ss is not None and not self._ss_inline else None
                 if self.split:
-                    ga, static, ga2 = self._capture_split(inputs)
+                    ga, static, ga2 = self._capture_split(inputs, first)
                 else:
-                    ga, static = self._capture(self._part_a, inputs)
+                    ga, static = self._capture(self._part_a, inputs, first)
                     ga2 = None
+                if first is not None:         # the first pass over the same static inputs, a graph of its own
+                    g0 = torch.cuda.CUDAGraph()
+                    with ops.capture(g0):
+                        first(*static)
+                    if not self._graphs:
+                        self._ss_first.clear()
+                    self._ss_first[key] = g0
                 gb, _ = self._capture(self._part_b, [])
                 self._gb = gb
                 self._graphs[key] = (ga, static, gb, ga2)
@@ -1764,9 +1941,13 @@ class TrainStep:
             from .decoder import copy_inputs
             copy_inputs(static, inputs)
             part_a, part_a2, part_b = ga.replay, None if ga2 is None else ga2.replay, gb.replay
+            first = self._ss_first[key].replay if self.ss is not None and not self._ss_inline else None
         else:
             part_a = functools.partial(self._part_a1 if self.split else self._part_a, *inputs)
             part_a2, part_b = self._part_a2 if self.split else None, self._part_b
+            first = functools.partial(self._first_pass, *inputs) if self.ss is not None and not self._ss_inline else None
+        if first is not None:
+            first()
         part_a()
         if part_a2 is None:
             dp.allreduce_bucket(self.flat_g, self.pg)

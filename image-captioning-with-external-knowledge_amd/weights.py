@@ -176,6 +176,15 @@ class WeightImages:
             self.refresh(*stale)
         return self
 
+    def adopt(self, *groups):
+        """Stamp the (allocated) groups as filled from the live parameters without a launch: for the caller that knows
+        another writer has just done so -- TrainStep's optimizer kernel, through DerivedWeights -- and is about to run code
+        that asks current() for them inside the step (the first pass of scheduled sampling)."""
+        for g in groups:
+            if g in self.img:
+                self.stamp[g] = self.key(g)
+        return self
+
     def planes(self, group, rows=None):
         """The current planes of a presplit group for a GEMM over `rows` rows; None where ick_gemm would not read them
         (the exact fp32 product mode, a vocabulary GEMM below vocab_planes_wanted)."""

@@ -927,6 +927,29 @@ int ick_caption_score_sums(const int32_t* rowstart, int32_t R, int32_t L, int32_
                            float* top1_hits, float* topk_hits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Scheduled sampling (csrc/sched_sample.hip): the inputs of a training step's second pass, from the packed
+ * score rows of a teacher-forced first pass (scores (M', ld), rowstart, decode_len: the packed head's and
+ * ick_head_rowmap's).  captions / caption_masks (B, L) int64 are the gold rows; captions_in / masks_in (B, L) int64 and
+ * replaced (B, L) int32 are written whole.  With n_b = clamp(decode_len[b], 0, L - 1), position (b, q) is eligible when
+ * 1 <= q <= n_b - 1; packed row rowstart[b] + q - 1 predicts its token.  Every other position copies gold, replaced = 0.
+ *   coin: x = element 0 of Philox-4x32-10 of counter (0xFFFFFFFF, *step, q - 1, b) under key (lo32(*seed), hi32(*seed));
+ *     the position is replaced iff (x >> 8) + 0.5 < *prob * 2^24 (exact: 0 replaces nothing, 1 every eligible position).
+ *   draw: argmax != 0: the lowest column that holds the row's maximum; else the first maximum of s[c] / *temperature +
+ *     g_c in fp32, g_c the Gumbel noise of ick_decode_select_sample applied to element c & 3 of Philox of counter
+ *     (c >> 2, *step, q - 1, b).  Columns start_token and pad_token never win.
+ *   token: column c < V gives (c, 0), V <= c < V + K gives (c, 1), c >= V + K gives (c, 2) in (captions_in, masks_in):
+ *     the rule of ick_samples_to_captions.
+ * A position that is not replaced does not read its score row.  prob, temperature (float), seed (int64) and step
+ * (uint32) are ONE word each in device memory, read at run time: a captured launch follows new values.  No atomics: the
+ * same words give the same bits on every run.  F = 0 without facts.
+ * ICK_EINVAL, without a launch: a NULL pointer or word, B < 1, L < 2, B * L > 2^31 - 1, V + K + F > 2^24, ld < V + K + F. */
+int ick_sched_sample_mix(const float* scores, int64_t ld, const int32_t* rowstart, const int32_t* decode_len,
+                         const int64_t* captions, const int64_t* caption_masks, int32_t B, int32_t L, int32_t V,
+                         int32_t K, int32_t F, int32_t start_token, int32_t pad_token, const float* prob,
+                         const float* temperature, const int64_t* seed, const uint32_t* step, int32_t argmax,
+                         int64_t* captions_in, int64_t* masks_in, int32_t* replaced, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Geo-reference counts: the histograms of the geo variant's Jensen-Shannon metric (the reference's
  * JSGeoMetric.run / store_data_for_idx), on token ids.  One launch, one wave per caption row.
  *
