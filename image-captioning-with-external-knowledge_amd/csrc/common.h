@@ -237,6 +237,30 @@ inline bool rules_ok(const ick_decode_ctx* c, const ick_decode_rules* rules, boo
     return !beam || (rules->lp && rules->len && c->end_token >= 0 && c->end_token < c->V);
 }
 
+// Column bias of beam search and sampling (ick_decode_bias): a caption's list is 64 (column, value)
+// slots, -1 = an empty slot, read at run time.  Every wave keeps the whole list in one register pair, lane t holding
+// slot t (two coalesced loads), and visits the slots that concern it (a ballot over the lanes: `live`) in order, with
+// the slot's column as a wave-uniform value: no LDS, no barrier, and no work for an empty slot.  Full waves only.
+constexpr int kBiasMax = ICK_BIAS_MAX;
+struct BiasLanes {
+    int col; float val;
+    // the slots whose column lies in [lo, hi), as a bit mask (uniform); walk it with next()
+    __device__ __forceinline__ unsigned long long live(int lo, int hi) const { return __ballot(col >= lo && col < hi); }
+    static __device__ __forceinline__ int next(unsigned long long& mask) {
+        const int slot = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        return slot;
+    }
+    __device__ __forceinline__ int col_of(int slot) const { return __builtin_amdgcn_readlane(col, slot); }
+    __device__ __forceinline__ float val_of(int slot) const {
+        return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(val), slot));
+    }
+};
+__device__ __forceinline__ BiasLanes bias_lanes(const int32_t* cols, const float* vals, int64_t caption) {
+    const int lane = threadIdx.x & (kWave - 1);
+    return BiasLanes{cols[caption * kBiasMax + lane], vals[caption * kBiasMax + lane]};
+}
+
 struct DropArg {
     float p;
     uint32_t seed, site;

@@ -223,11 +223,18 @@ struct BeamPartArgs {
 struct BeamPartForcedArgs : BeamPartArgs {
     const int32_t* force; const int32_t* met;
 };
+// The column-bias variant (BIASED) appends the bias lists (R / k, kBiasMax) in the same way.
+struct BeamPartBiasArgs : BeamPartArgs {
+    const int32_t* bcols; const float* bvals;
+};
+template <bool FORCED, bool BIASED>
+using BeamPartArgsOf = std::conditional_t<FORCED, BeamPartForcedArgs, std::conditional_t<BIASED, BeamPartBiasArgs, BeamPartArgs>>;
 // RULES: the decoding-rules variant (ick_decode_select_beam_rules); FORCED: constrained beam search
-// (ick_decode_select_beam_forced)
-template <bool RULES, bool FORCED = false>
+// (ick_decode_select_beam_forced); BIASED: column bias (ick_decode_select_beam_biased, §3.2k)
+template <bool RULES, bool FORCED = false, bool BIASED = false>
 __global__ __launch_bounds__(256)
-void dec_beam_partial_kernel(std::conditional_t<FORCED, BeamPartForcedArgs, BeamPartArgs> a) {
+void dec_beam_partial_kernel(BeamPartArgsOf<FORCED, BIASED> a) {
+    static_assert(!(FORCED && BIASED), "the column bias does not compose with forced columns");
     if (*a.n_done >= a.n_total) return;
     __shared__ float shv[4];
     __shared__ int shc[4];
@@ -286,6 +293,29 @@ void dec_beam_partial_kernel(std::conditional_t<FORCED, BeamPartForcedArgs, Beam
         for (int q = 0; q < 4; ++q)
             if (unmet_any && idx[q] == a.end_token) { x[q] = -INFINITY; idx[q] = kNone; }
     }
+    if constexpr (BIASED) {
+        // Column bias: the pool holds s + b (the maximum and the sum of exp above stay raw).  The slots that fall in
+        // this chunk -- most chunks have none -- are visited in order with their column as a uniform value and added by
+        // the lane that owns the column (column c of the chunk is x[c >> 8] of thread c & 255), a column's lowest slot
+        // only.  A banned column stays out whatever its bias, and a -inf bias takes its column out as a ban does.
+        const BiasLanes bl = bias_lanes(a.bcols, a.bvals, r / a.k);
+        int done = 0;
+        for (unsigned long long live = bl.live(ch * kBeamChunk, min((ch + 1) * kBeamChunk, Vx)); live != 0;) {
+            const int t = BiasLanes::next(live);
+            const int c = bl.col_of(t) - ch * kBeamChunk;
+            const float b = bl.val_of(t);
+            const int q = c >> 8;
+            if ((c & 255) == tid && !((done >> q) & 1)) {
+                done |= 1 << q;
+#pragma unroll
+                for (int q2 = 0; q2 < 4; ++q2)
+                    if (q2 == q) x[q2] += b;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (x[q] == -INFINITY) idx[q] = kNone;
+    }
     for (int round = 0; round < a.k; ++round) {
         float bv = -INFINITY; int bc = kNone;
 #pragma unroll
@@ -307,6 +337,12 @@ void dec_beam_partial_kernel(std::conditional_t<FORCED, BeamPartForcedArgs, Beam
 struct BeamRows {
     float *cum, *lse;
     int *fin, *len, *parent, *tok, *nfin, *met, *force, *nmet, *xtok;
+    float* bsum;
+};
+// The column-bias variant (BIASED) appends the bias lists (R / k, kBiasMax) and every hypothesis' bias sum (R), for
+// that variant alone (as BeamPartBiasArgs).
+struct BeamBiasArgs : BeamArgs {
+    const int32_t* bcols; const float* bvals; float* bsum;
 };
 
 // One selection round: the block-wide arg-best (bv, bc) of every thread's candidates; the winner leaves the pool.
@@ -327,21 +363,26 @@ __device__ __forceinline__ void beam_round(float (&v)[N], int (&c)[N], float& bv
 
 // The winner of a round (code c, key `key`) becomes hypothesis h: thread 0 decides parent, token and ended-or-not and
 // stores the step's bookkeeping.  cum is the raw summed log-probability: where the key is not that (length penalty,
-// diversity penalty, banks) it is derived again from the step's score row, by the expression that made the key.
-template <bool DIVERSE, bool FORCED>
+// diversity penalty, banks, column bias) it is derived again from the step's score row, by the expression that made the
+// key.  BIASED: bsum_out is the caption's bias sums in global memory and bw the bias of the winner's column; the new
+// hypothesis carries its parent's sum plus bw, a carried one its own.
+template <bool DIVERSE, bool FORCED, bool BIASED = false>
 __device__ __forceinline__ void beam_winner(const BeamArgs& a, const BeamRows& s, int64_t r0, bool lp_on, int h,
-                                            float key, int c) {
+                                            float key, int c, float* bsum_out = nullptr, float bw = 0.f) {
     const int np = a.emb.K + a.emb.F, Vx = a.emb.V + np;
-    const bool rederive = DIVERSE || FORCED || lp_on;
+    const bool rederive = DIVERSE || FORCED || BIASED || lp_on;
     float v = rederive || c == kNone ? -INFINITY : key;         // fewer candidates than beams: a dead slot
     int parent = 0, tok = a.emb.pad_token, nf = 1, len = 0, met = 0;
+    float bsum = 0.f;
     if (c != kNone) {
         parent = c / Vx;
         if constexpr (FORCED) met = s.met[parent];
+        if constexpr (BIASED) bsum = s.bsum[parent];
         if (s.fin[parent]) {                                    // an ended hypothesis is carried as it is
             if (rederive) v = s.cum[parent];
             if (lp_on) len = s.len[parent];
         } else {
+            if constexpr (BIASED) bsum += bw;
             tok = c - parent * Vx; nf = tok == a.end_token;
             if (rederive) {
                 const float x = tok < a.emb.V ? a.scores[(r0 + parent) * a.ld + tok]
@@ -357,6 +398,7 @@ __device__ __forceinline__ void beam_winner(const BeamArgs& a, const BeamRows& s
     if constexpr (FORCED) s.nmet[h] = met;
     if constexpr (DIVERSE) s.xtok[h] = c != kNone && !s.fin[parent] ? tok : -1;
     if (lp_on) a.len[r0 + h] = len;
+    if constexpr (BIASED) bsum_out[h] = bsum;
     a.cum[r0 + h] = v;
     a.fin[r0 + h] = nf;
     const bool live = c != kNone && !nf;
@@ -365,9 +407,10 @@ __device__ __forceinline__ void beam_winner(const BeamArgs& a, const BeamRows& s
 }
 
 // DIVERSE: diverse beam search (ick_decode_select_beam_diverse); FORCED: constrained beam search
-// (ick_decode_select_beam_forced)
-template <bool RULES, bool DIVERSE = false, bool FORCED = false>
-__global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
+// (ick_decode_select_beam_forced); BIASED: column bias (ick_decode_select_beam_biased, §3.2k)
+template <bool RULES, bool DIVERSE = false, bool FORCED = false, bool BIASED = false>
+__global__ __launch_bounds__(256) void dec_select_beam_kernel(std::conditional_t<BIASED, BeamBiasArgs, BeamArgs> a) {
+    static_assert(!(BIASED && (DIVERSE || FORCED)), "the column bias composes with the rules only");
     // No exit on *n_done here: other workgroups of this very launch add to it, and the hypothesis tables are
     // ping-pong buffers -- a step that skipped its carry-copy would leave the previous step's rows (in another
     // order) in the buffer the caller reads.  The decision below only looks at this caption's own state, which no
@@ -381,7 +424,10 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     __shared__ int met_s[FORCED ? kBeamMax : 1], force_s[FORCED ? kForceMax : 1], nmet_s[FORCED ? kBeamMax : 1];
     __shared__ int shp[FORCED ? 4 : 1];
     __shared__ int xtok_s[DIVERSE ? kBeamMax : 1];          // column expanded into slot j at this step, or -1
-    const BeamRows rows{cum_s, lse_s, fin_s, len_s, parent_s, tok_s, nfin_s, met_s, force_s, nmet_s, xtok_s};
+    __shared__ float bsum_s[BIASED ? kBeamMax : 1];         // bias sum of hypothesis j going into this step
+    __shared__ int bcol_s[BIASED ? kBiasMax : 1];           // the caption's bias list
+    __shared__ float bval_s[BIASED ? kBiasMax : 1];
+    const BeamRows rows{cum_s, lse_s, fin_s, len_s, parent_s, tok_s, nfin_s, met_s, force_s, nmet_s, xtok_s, bsum_s};
     const int tid = threadIdx.x, k = a.emb.rows_per_sample;
     const int64_t r0 = (int64_t)blockIdx.x * k;
     const int np = a.emb.K + a.emb.F, Vx = a.emb.V + np;
@@ -396,6 +442,13 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
     if constexpr (FORCED) {
         if (tid < k) met_s[tid] = a.met[r0 + tid];
         if (tid >= 64 && tid < 64 + kForceMax) force_s[tid - 64] = a.force[blockIdx.x * kForceMax + tid - 64];
+    }
+    if constexpr (BIASED) {
+        if (tid < k) bsum_s[tid] = a.bsum[r0 + tid];
+        if (tid >= 64 && tid < 64 + kBiasMax) {
+            bcol_s[tid - 64] = a.bcols[blockIdx.x * kBiasMax + tid - 64];
+            bval_s[tid - 64] = a.bvals[blockIdx.x * kBiasMax + tid - 64];
+        }
     }
     __syncthreads();
     bool live_any = false;
@@ -441,13 +494,15 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
             if (cum_s[j] != -INFINITY) {
                 if (fin_s[j]) {
                     if (rem == 0) {                                      // an ended hypothesis competes as it is
-                        cv[q] = lp_on ? cum_s[j] / lpf_s[j] : cum_s[j]; cc[q] = j * Vx;
+                        const float v = BIASED ? cum_s[j] + bsum_s[j] : cum_s[j];
+                        cv[q] = lp_on ? v / lpf_s[j] : v; cc[q] = j * Vx;
                     }
                 } else {
                     const float* rc = a.rec + ((r0 + j) * nchunk + c) * kBeamRec;
                     const int idx = __float_as_int(rc[3 + 2 * slot]);
                     if (idx != kNone) {
-                        const float v = cum_s[j] - lse_s[j] + rc[2 + 2 * slot];
+                        float v = cum_s[j] - lse_s[j] + rc[2 + 2 * slot];       // (BIASED: the record holds s + b)
+                        if constexpr (BIASED) v += bsum_s[j];
                         cv[q] = lp_on ? v / lp_live : v; cc[q] = j * Vx + idx;
                     }
                 }
@@ -506,6 +561,19 @@ __global__ __launch_bounds__(256) void dec_select_beam_kernel(BeamArgs a) {
         }
         __syncthreads();
         if (tid < k) a.met[r0 + tid] = nmet_s[tid];
+    } else if constexpr (BIASED) {
+        // Column bias: the key holds the hypothesis' bias sum and the column's bias, cum does not (beam_winner derives
+        // it again from the raw score).  Wave 0 finds the winner's bias in the caption's list, the lowest slot first.
+        for (int round = 0; round < k; ++round) {
+            float bv; int bc;
+            beam_round(cv, cc, bv, bc, shv, shc);
+            if (tid < kBiasMax) {
+                const int tok = bc == kNone ? -2 : bc % Vx;
+                const unsigned long long hit = __ballot(bcol_s[tid] == tok);
+                const float bw = hit ? bval_s[__ffsll(hit) - 1] : 0.f;
+                if (tid == 0) beam_winner<false, false, true>(a, rows, r0, lp_on, round, bv, bc, a.bsum + r0, bw);
+            }
+        }
     } else if constexpr (!DIVERSE) {
         for (int round = 0; round < k; ++round) {
             float bv; int bc;
@@ -593,8 +661,8 @@ extern "C" int ick_decode_select_greedy(const ick_decode_ctx* c, int32_t pos, vo
 }
 
 static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, const ick_decode_rules* rules,
-                            const ick_decode_diversity* div, const ick_decode_constraints* fc, int32_t pos,
-                            void* stream) {
+                            const ick_decode_diversity* div, const ick_decode_constraints* fc,
+                            const ick_decode_bias* bias, int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && bs && c->R > 0 && pos >= 0 && pos < c->max_len);
     ICK_CHECK_ARG(c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax && c->R % c->rows_per_sample == 0);
     ICK_CHECK_ARG(c->scores && c->scores_ld >= c->V && c->ptr && c->n_done && c->next_token && c->next_mask &&
@@ -614,6 +682,13 @@ static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, c
         pa.force = fc->force; pa.met = fc->met;
         void (*part)(BeamPartForcedArgs) = rules ? dec_beam_partial_kernel<true, true> : dec_beam_partial_kernel<false, true>;
         hipLaunchKernelGGL(part, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, pa);
+    } else if (bias != nullptr) {
+        // the column bias is instantiated on the rules form only: without rules the rule words read as zero
+        BeamPartBiasArgs ba;
+        static_cast<BeamPartArgs&>(ba) = pa;
+        ba.bcols = bias->cols; ba.bvals = bias->vals;
+        hipLaunchKernelGGL((dec_beam_partial_kernel<true, false, true>), dim3(nchunk, c->R), dim3(256), 0,
+                           (hipStream_t)stream, ba);
     } else {
         void (*part)(BeamPartArgs) = rules ? dec_beam_partial_kernel<true> : dec_beam_partial_kernel<false>;
         hipLaunchKernelGGL(part, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, (const BeamPartArgs&)pa);
@@ -629,6 +704,14 @@ static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, c
     a.groups = div ? div->groups : 1; a.penalty = div ? div->penalty : nullptr;
     a.force = fc ? fc->force : nullptr; a.met = fc ? fc->met : nullptr;
     a.scores = c->scores; a.ld = c->scores_ld; a.ptr = c->ptr;
+    if (bias != nullptr) {
+        BeamBiasArgs ba;
+        static_cast<BeamArgs&>(ba) = a;
+        ba.bcols = bias->cols; ba.bvals = bias->vals; ba.bsum = bias->sum;
+        hipLaunchKernelGGL((dec_select_beam_kernel<true, false, false, true>), dim3(c->R / c->rows_per_sample),
+                           dim3(256), 0, (hipStream_t)stream, ba);
+        ICK_LAUNCH_RET();
+    }
     void (*sel)(BeamArgs) = fc ? (rules ? dec_select_beam_kernel<true, false, true>
                                         : dec_select_beam_kernel<false, false, true>) :
                             div ? (rules ? dec_select_beam_kernel<true, true> : dec_select_beam_kernel<false, true>)
@@ -638,13 +721,13 @@ static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, c
 }
 
 extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_state* bs, int32_t pos, void* stream) {
-    return select_beam_impl(c, bs, nullptr, nullptr, nullptr, pos, stream);
+    return select_beam_impl(c, bs, nullptr, nullptr, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_rules(const ick_decode_ctx* c, const ick_beam_state* bs,
                                             const ick_decode_rules* rules, int32_t pos, void* stream) {
     ICK_CHECK_ARG(rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, nullptr, nullptr, pos, stream);
+    return select_beam_impl(c, bs, rules, nullptr, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_diverse(const ick_decode_ctx* c, const ick_beam_state* bs,
@@ -653,7 +736,7 @@ extern "C" int ick_decode_select_beam_diverse(const ick_decode_ctx* c, const ick
     ICK_CHECK_ARG(c && div && div->penalty && div->groups >= 1 && c->rows_per_sample >= 1 &&
                   c->rows_per_sample % div->groups == 0);
     ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, div, nullptr, pos, stream);
+    return select_beam_impl(c, bs, rules, div, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_forced(const ick_decode_ctx* c, const ick_beam_state* bs,
@@ -661,5 +744,13 @@ extern "C" int ick_decode_select_beam_forced(const ick_decode_ctx* c, const ick_
                                              int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && fc && fc->force && fc->met && c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax);
     ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, nullptr, fc, pos, stream);
+    return select_beam_impl(c, bs, rules, nullptr, fc, nullptr, pos, stream);
+}
+
+extern "C" int ick_decode_select_beam_biased(const ick_decode_ctx* c, const ick_beam_state* bs,
+                                             const ick_decode_rules* rules, const ick_decode_bias* bias, int32_t pos,
+                                             void* stream) {
+    ICK_CHECK_ARG(c && bias && bias->cols && bias->vals && bias->sum);
+    ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
+    return select_beam_impl(c, bs, rules, nullptr, nullptr, bias, pos, stream);
 }

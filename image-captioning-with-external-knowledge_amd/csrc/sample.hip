@@ -16,6 +16,9 @@
 // Decoding rules (ick_decode_select_sample_rules): columns banned by the no-repeat n-gram / min-length
 // rules are absent before top-k and top-p (not counted in k, no mass; the top-p weights are taken relative to the
 // allowed maximum) and from the draw; m, the sum of exp and log_prob still cover every column.
+// Column bias (ick_decode_select_sample_biased): everything that selects -- the top-k threshold, z, the
+// top-p weights and their maximum, the Gumbel arg-max -- runs on s' = s + b; a column with b = -inf is absent like a
+// banned one.  m, the sum of exp and log_prob stay on the raw s, and a column's noise does not change.
 //
 // Determinism: every thread owns the same columns on every launch (lane t of group g: columns 4 (g*1024 + t) + 0..3),
 // float reductions run per lane in column order, then over the wave (DPP / readlane, fixed pattern), then over the 16
@@ -29,6 +32,7 @@
 #include "philox.h"
 
 #include <climits>
+#include <type_traits>
 
 namespace ick {
 namespace {
@@ -56,6 +60,12 @@ struct SampleArgs {
     float emb_scale;
     int n_total;
     const int32_t* words;                  // optional rule words (no-repeat n-gram size, min length)
+};
+
+// The column-bias variant (BIASED) appends the bias lists (R / rows_per_sample, kBiasMax), for that variant alone: the
+// hidden launch arguments the other instantiations read follow the explicit ones, and would move with them.
+struct SampleBiasArgs : SampleArgs {
+    const int32_t* bcols; const float* bvals;
 };
 
 // order-preserving key of a float (larger float -> larger key); -0 is folded onto +0 first (x + 0 = +0 for x = -0)
@@ -91,8 +101,9 @@ __device__ __forceinline__ void scan_desc(const T* hist, T need, T above, int* d
 // NG = groups of 4 columns a lane holds in registers: 4 (Vx <= 16 384, cfg5) keeps them in VGPRs; 16 (cfg4's 50 071)
 // exceeds the 128 registers a lane of a 1024-thread workgroup has and spills part of the row to scratch.
 // RULES: the decoding-rules variant (ick_decode_select_sample_rules); the rule-free one compiles without the ban pass.
-template <int NG, bool RULES>
-__global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
+// BIASED: column bias (ick_decode_select_sample_biased), on the rules form.
+template <int NG, bool RULES, bool BIASED = false>
+__global__ __launch_bounds__(kSNT) void dec_sample_kernel(std::conditional_t<BIASED, SampleBiasArgs, SampleArgs> a) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int64_t r = blockIdx.x;
     const int i = a.step;
@@ -180,9 +191,32 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
         }
         se = wave_sum(se);
         if (lane == 0) red[1][wid] = se;
+        // some column may be absent from the selection (uniform)
+        const bool cut = ban_any || BIASED;
+        if constexpr (BIASED) {
+            // Column bias, after the raw reductions: s becomes s' = s + b in place, no second copy of the row.  The
+            // non-empty slots are visited in order with their column as a uniform value; column c is element
+            // (c >> 12) * 4 + (c & 3) of thread (c >> 2) & 1023, its only owner, and a column's lowest slot counts.
+            // b = -inf: the column is absent like a banned one.
+            const BiasLanes bl = bias_lanes(a.bcols, a.bvals, r / a.rows_per_sample);
+            uint64_t done = 0;
+            for (unsigned long long live = bl.live(0, Vx); live != 0;) {
+                const int t = BiasLanes::next(live);
+                const int c = bl.col_of(t);
+                const float bias = bl.val_of(t);
+                const int e = ((c >> 12) << 2) | (c & 3);
+                if (((c >> 2) & (kSNT - 1)) == tid && !((done >> e) & 1u)) {
+                    done |= 1ull << e;
+                    if (bias == -INFINITY) banned |= 1ull << e;
+#pragma unroll
+                    for (int e2 = 0; e2 < NG * 4; ++e2)
+                        if (e2 == e) s[e2] += bias;
+                }
+            }
+        }
         // the maximum over the allowed columns: the top-p weights are exp(z - its z)
         float mk = m;
-        if (ban_any) {
+        if (cut) {
             mk = -INFINITY;
 #pragma unroll
             for (int e = 0; e < NG * 4; ++e)
@@ -215,7 +249,7 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
                 }
                 __syncthreads();
                 if (wid == 0) {
-                    if (pass == 0 && ban_any) {     // k >= the allowed columns: every allowed column is kept
+                    if (pass == 0 && cut) {         // k >= the allowed columns: every allowed column is kept
                         uint32_t t4 = hist_n[4 * lane] + hist_n[4 * lane + 1] + hist_n[4 * lane + 2] + hist_n[4 * lane + 3];
 #pragma unroll
                         for (int off = 32; off >= 1; off >>= 1) t4 += __shfl_xor(t4, off, 64);
@@ -227,7 +261,7 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
                     if (dig >= 0) { dig_sh = dig; need_sh = need - above_out; }
                 }
                 __syncthreads();
-                if (pass == 0 && ban_any && all_sh) { prefix = 0; break; }     // uniform
+                if (pass == 0 && cut && all_sh) { prefix = 0; break; }         // uniform
                 prefix |= (uint32_t)dig_sh << shift;
                 pmask |= 255u << shift;
                 need = need_sh;
@@ -326,6 +360,9 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgs a) {
                 if (bv_sh[w] > bv || (bv_sh[w] == bv && bc_sh[w] < bc)) { bv = bv_sh[w]; bc = bc_sh[w]; bs = bs_sh[w]; }
             float sum = red[1][0];
             for (int w = 1; w < kSNW; ++w) sum += red[1][w];
+            if constexpr (BIASED) {         // log_prob is the model's: the drawn column's raw score, from the score row
+                if (bc < Vx) bs = bc < a.V ? srow[bc] : prow[bc - a.V];
+            }
             int64_t* o = a.output + r * a.max_len;
             if (a.log_prob != nullptr) a.log_prob[r * a.max_len + i] = (bs - m) - logf(sum);
             o[i] = bc;
@@ -369,7 +406,7 @@ extern "C" int ick_decode_sample_supported(int32_t Vx, int32_t rows_per_sample) 
 }
 
 static int select_sample_impl(const ick_decode_ctx* c, const ick_sample_state* s, const ick_decode_rules* rules,
-                              int32_t pos, void* stream) {
+                              const ick_decode_bias* bias, int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && s && c->R > 0 && c->R <= 65535 && pos >= 0 && pos < c->max_len);
     ICK_CHECK_ARG(c->rows_per_sample >= 1 && c->R % c->rows_per_sample == 0);
     ICK_CHECK_ARG(c->V > 0 && c->K > 0 && c->F >= 0 && c->end_token >= 0 && c->end_token < c->V);
@@ -390,6 +427,15 @@ static int select_sample_impl(const ick_decode_ctx* c, const ick_sample_state* s
     a.emb_scale = c->emb_scale; a.n_total = c->R;
     a.words = rules ? rules->words : nullptr;
     const bool small = c->V + c->K + c->F <= 4 * 4 * kSNT;
+    if (bias != nullptr) {
+        // the column bias is instantiated on the rules form only: without rules the rule words read as zero
+        SampleBiasArgs ba;
+        static_cast<SampleArgs&>(ba) = a;
+        ba.bcols = bias->cols; ba.bvals = bias->vals;
+        void (*kern)(SampleBiasArgs) = small ? dec_sample_kernel<4, true, true> : dec_sample_kernel<kSGMax, true, true>;
+        hipLaunchKernelGGL(kern, dim3(c->R), dim3(kSNT), 0, (hipStream_t)stream, ba);
+        ICK_LAUNCH_RET();
+    }
     void (*kern)(SampleArgs) = rules == nullptr ? (small ? dec_sample_kernel<4, false> : dec_sample_kernel<kSGMax, false>)
                                                 : (small ? dec_sample_kernel<4, true> : dec_sample_kernel<kSGMax, true>);
     hipLaunchKernelGGL(kern, dim3(c->R), dim3(kSNT), 0, (hipStream_t)stream, a);
@@ -397,11 +443,19 @@ static int select_sample_impl(const ick_decode_ctx* c, const ick_sample_state* s
 }
 
 extern "C" int ick_decode_select_sample(const ick_decode_ctx* c, const ick_sample_state* s, int32_t pos, void* stream) {
-    return select_sample_impl(c, s, nullptr, pos, stream);
+    return select_sample_impl(c, s, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_sample_rules(const ick_decode_ctx* c, const ick_sample_state* s,
                                               const ick_decode_rules* rules, int32_t pos, void* stream) {
     ICK_CHECK_ARG(rules_ok(c, rules, false));
-    return select_sample_impl(c, s, rules, pos, stream);
+    return select_sample_impl(c, s, rules, nullptr, pos, stream);
+}
+
+extern "C" int ick_decode_select_sample_biased(const ick_decode_ctx* c, const ick_sample_state* s,
+                                               const ick_decode_rules* rules, const ick_decode_bias* bias, int32_t pos,
+                                               void* stream) {
+    ICK_CHECK_ARG(c && bias && bias->cols && bias->vals);
+    ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, false));
+    return select_sample_impl(c, s, rules, bias, pos, stream);
 }

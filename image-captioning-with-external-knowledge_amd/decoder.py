@@ -220,6 +220,94 @@ def check_force(what, B, Vx, special, force_tokens=None, num_beam_groups=1):
     return out
 
 
+BIAS_MAX = 64
+
+
+def bias_tensors(B, ids, vals):
+    """The device inputs of a column bias as CPU tensors: int32 ids (B, 64) padded with -1 and fp32 values (B, 64), 0 in
+    every empty slot; ids (B, C) or (C,) integer and vals of the same shape, C <= 64 (a (C,) pair goes to every caption)."""
+    ids = torch.as_tensor(ids).to(torch.int64)
+    vals = torch.as_tensor(vals).to(torch.float32)
+    if ids.dim() == 1:
+        ids, vals = ids.view(1, -1).expand(B, -1), vals.view(1, -1).expand(B, -1)
+    out_i = torch.full((B, BIAS_MAX), -1, dtype=torch.int32)
+    out_v = torch.zeros(B, BIAS_MAX, dtype=torch.float32)
+    out_i[:, :ids.shape[1]] = ids.to(torch.int32)
+    out_v[:, :ids.shape[1]] = torch.where(ids >= 0, vals, torch.zeros_like(vals))
+    return out_i, out_v
+
+
+def _bias_input(bias, device):
+    """bias_tensors()' pair as ONE int32 (2, B, 64) device tensor, ids over the values' bits: one host-to-device copy per
+    call, one static input of the decode graph."""
+    return torch.stack([bias[0], bias[1].view(torch.int32)]).to(device)
+
+
+def _bias_views(packed):
+    """The (B, 64) ids and values of a _bias_input()."""
+    return packed[0], packed[1].view(torch.float32)
+
+
+def check_column_bias(what, B, Vx, word_map, column_bias=None, num_beam_groups=1, force_tokens=None):
+    """Validate the column_bias of predict_beam / predict_sample (IckError): None; a dict {column id or word of
+    word_map: value} for every caption; or a pair (ids, values) of an integer tensor / nested list (B, C) or (C,), C in
+    1..64, and a float one of the same shape.  Ids are force_tokens' columns, -1 = an empty slot (its value is ignored);
+    a value is a finite float or -inf.  Returns None or bias_tensors()' padded (B, 64) pair."""
+    if column_bias is None:
+        return None
+    if isinstance(num_beam_groups, int) and num_beam_groups > 1:
+        raise IckError("%s: column_bias does not compose with num_beam_groups > 1" % what)
+    if force_tokens is not None:
+        raise IckError("%s: column_bias does not compose with force_tokens" % what)
+    shape_msg = "%s needs column_bias as a dict {column: value} or a pair (ids, values) of shape (B = %d, 1..%d) or " \
+                "(1..%d,)" % (what, B, BIAS_MAX, BIAS_MAX)
+    if isinstance(column_bias, dict):
+        ids, vals = [], []
+        for key, v in column_bias.items():
+            if isinstance(key, str):
+                if key not in word_map:
+                    raise IckError("%s: column_bias names the unknown word %r" % (what, key))
+                key = word_map[key]
+            if isinstance(key, bool) or not isinstance(key, int) or isinstance(v, bool) or \
+                    not isinstance(v, (int, float)):
+                raise IckError(shape_msg)
+            ids.append(key)
+            vals.append(float(v))
+        if len(set(ids)) != len(ids):
+            raise IckError("%s: column_bias names a column twice" % what)
+        column_bias = (ids, vals)
+    if not isinstance(column_bias, (tuple, list)) or len(column_bias) != 2:
+        raise IckError(shape_msg)
+    ids, vals = column_bias
+    try:
+        ids = ids if torch.is_tensor(ids) else torch.tensor(ids)
+        vals = vals if torch.is_tensor(vals) else torch.tensor(vals, dtype=torch.float32)
+    except (TypeError, ValueError, RuntimeError):
+        raise IckError(shape_msg)
+    if ids.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or \
+            not (vals.dtype.is_floating_point or vals.dtype in (torch.int32, torch.int64)) or \
+            ids.dim() not in (1, 2) or tuple(vals.shape) != tuple(ids.shape) or \
+            (ids.dim() == 2 and ids.shape[0] != B) or not 1 <= ids.shape[-1] <= BIAS_MAX:
+        raise IckError(shape_msg)
+    ids = ids.detach().to("cpu", torch.int64)                # one small read-back per call
+    vals = vals.detach().to("cpu", torch.float32)
+    if bool((ids < -1).any()) or bool((ids >= Vx).any()):
+        raise IckError("%s: column_bias holds column ids in [0, V+K+F = %d) or -1 for an empty slot" % (what, Vx))
+    used = ids >= 0
+    if bool((used & (torch.isnan(vals) | (vals == float("inf")))).any()):
+        raise IckError("%s: a column_bias value is a finite float or -inf" % what)
+    rows = ids.view(1, -1) if ids.dim() == 1 else ids
+    vrows = vals.view(1, -1) if vals.dim() == 1 else vals
+    never = {word_map[w] for w in ("<start>", "<pad>") if w in word_map and 0 <= word_map[w] < Vx}
+    for row, vrow in zip(rows.tolist(), vrows.tolist()):
+        cols = [c for c in row if c >= 0]
+        if len(set(cols)) != len(cols):
+            raise IckError("%s: column_bias names a column twice in one caption's row" % what)
+        if len(never | {c for c, v in zip(row, vrow) if c >= 0 and v == float("-inf")}) >= Vx:
+            raise IckError("%s: column_bias bans every column of a caption" % what)
+    return bias_tensors(B, ids, vals)
+
+
 def check_score_args(what, has_facts, captions, encoder_out, caption_masks, caption_lengths, entities, facts=None,
                      image_index=None, top_k=5):
     """Validate the arguments of score_captions (IckError); shapes only, so it runs on tensors of any device.  Returns
@@ -1347,7 +1435,7 @@ class DecoderTransformer(nn.Module):
         return t["output"]
 
     def _predict_beam_device(self, enc_tok, entities, facts, max_pred_len, beam, attention=False, rules=None, groups=1,
-                             penalty=None, force=None):
+                             penalty=None, force=None, bias=None):
         """Beam search on the fused decode kernels: R = B * beam rows share their caption's cross K/V; the
         self-attention cache is never reordered -- an ancestry table says which cache row holds position p of a
         hypothesis.  Returns a _BeamResult: the best sequence (B, max_len), its log-probability (B), all sequences, all
@@ -1359,7 +1447,9 @@ class DecoderTransformer(nn.Module):
         sequence (B * G, max_len), its log-probability (B * G), and with attention its weights (max_len, B * G, layers,
         H, S).  force: the (B, 8) int32
         device tensor of check_force() (read at run time) or None; with it the search is the constrained one of
-        DESIGN.md §3.2g and the best hypothesis is the best by (met slots, key)."""
+        DESIGN.md §3.2g and the best hypothesis is the best by (met slots, key).  bias: the (B, 64) int32 ids and fp32
+        values of check_column_bias() on the device (read at run time) or None; with it every hypothesis carries the sum
+        of the biases it has emitted and the best hypothesis is the best by the key with that sum."""
         from . import lib as L
         B = enc_tok.shape[0]
         d, V, K = self.emb_dim, self.vocab_size, entities.shape[1]
@@ -1398,6 +1488,11 @@ class DecoderTransformer(nn.Module):
             met = torch.zeros(R, dtype=torch.int32, device=dev)
             fc = L.DecodeConstraints()
             fc.force, fc.met = force.data_ptr(), met.data_ptr()
+        cb = None
+        if bias is not None:
+            bsum = torch.zeros(R, dtype=torch.float32, device=dev)
+            cb = L.DecodeBias()
+            cb.cols, cb.vals, cb.sum = bias[0].data_ptr(), bias[1].data_ptr(), bsum.data_ptr()
         for i in range(max_pred_len):
             cur, nxt = i & 1, (i + 1) & 1
             c.anc = anc[cur].data_ptr()
@@ -1406,14 +1501,14 @@ class DecoderTransformer(nn.Module):
             self._decode_step(c, t, cap and cap[cur], facts_r, K, i, attn)
             bs.seq_in, bs.seq_out = seq[cur].data_ptr(), seq[nxt].data_ptr()
             bs.anc_in, bs.anc_out = anc[cur].data_ptr(), anc[nxt].data_ptr()
-            ops.decode_select_beam(c, bs, i, rs, dv, fc)
+            ops.decode_select_beam(c, bs, i, rs, dv, fc, cb)
         final = seq[max_pred_len & 1].view(B, beam, max_pred_len)
+        key = cum if bias is None else cum + bsum.view(B, beam)       # the kernel's ranking key
         if rules is None:
-            key = cum
-            best = cum.argmax(dim=1)                      # ties: the lower hypothesis
-        else:                                             # the kernel's ranking key; ties: the lower hypothesis
+            best = key.argmax(dim=1)                      # ties: the lower hypothesis
+        else:                                             # over the length penalty; ties: the lower hypothesis
             lp = rules[4:].view(torch.float32)
-            key = cum / lp[lens.view(B, beam).long()]
+            key = key / lp[lens.view(B, beam).long()]
             best = key.argmax(dim=1)
         if force is not None:                             # bank first: the key ranks among the most-met hypotheses
             bank = ((met.view(B, beam, 1) >> torch.arange(FORCE_MAX, device=dev, dtype=torch.int32)) & 1).sum(dim=2)
@@ -1440,7 +1535,7 @@ class DecoderTransformer(nn.Module):
     @torch.no_grad()
     def predict_beam(self, encoder_out, max_pred_len, entities, facts=None, beam_size=5, return_all=False,
                      return_attention=False, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0, num_beam_groups=1,
-                     diversity_penalty=0.0, return_groups=False, force_tokens=None):
+                     diversity_penalty=0.0, return_groups=False, force_tokens=None, column_bias=None):
         """Beam-search decode (north_star cfg5: beam 5, batch 32).  The reference decodes greedily only
         (geo-aware/eval.py:61,83), so beam > 1 has no reference output to pin against ("parity-unpinned"); the tests
         check it against a CPU beam search written to the same rules.  beam_size == 1 IS predict(): the pinned greedy path with
@@ -1479,14 +1574,27 @@ class DecoderTransformer(nn.Module):
         returned caption contains every forced column whenever max_pred_len >= their number.  The ids are a device
         input of the captured graph (new ids, or another C, replay it); scores stay the model's log-probabilities, the
         rules compose, and return shapes do not change.  A caption whose slots are all empty gets the plain search, bit
-        for bit; None, the default, is the call without the argument.  Not with num_beam_groups > 1."""
+        for bit; None, the default, is the call without the argument.  Not with num_beam_groups > 1.
+
+        Column bias: column_bias adds a value to chosen score columns, -inf meaning "never".  It is a
+        dict {column: value} for every caption (a key is a column id or a word of word_map, e.g. {"<unk>":
+        float("-inf")}), or a pair (ids, values) of an integer tensor or nested list (B, C) and a float one of the same
+        shape, C in 1..64 (a (C,) pair goes to every caption); columns are force_tokens' and -1 is an empty slot.  A
+        hypothesis carries the sum of the biases of the columns it has emitted, and candidates are ranked by the key
+        above plus that sum (an expansion with its column's bias); a -inf column leaves the candidate pool as a banned
+        one does, and a rule ban wins over a bias.  Every returned score stays the model's log-probability.  Ids and
+        values are device inputs of the captured graph (new values, ids or another C replay it); all slots empty or all
+        values 0 give the bits of the call without the argument.  The rules compose; not with num_beam_groups > 1 or
+        force_tokens.  beam_size == 1 with a bias runs the beam kernels with one hypothesis."""
         P_ = entities.shape[1] + (facts.shape[1] if facts is not None else 0)
         rules_on = check_rules("predict_beam", max_pred_len, self.vocab_size + P_, length_penalty,
                                no_repeat_ngram_size, min_len)
         diverse = check_diversity("predict_beam", beam_size, num_beam_groups, diversity_penalty)
         force = check_force("predict_beam", encoder_out.shape[0], self.vocab_size + P_,
                             [self.word_map[w] for w in ("<start>", "<end>", "<pad>")], force_tokens, num_beam_groups)
-        if beam_size == 1 and not rules_on and force is None:
+        bias = check_column_bias("predict_beam", encoder_out.shape[0], self.vocab_size + P_, self.word_map, column_bias,
+                                 num_beam_groups, force_tokens)
+        if beam_size == 1 and not rules_on and force is None and bias is None:
             return DecoderTransformer.predict(self, encoder_out, max_pred_len, entities, facts,
                                               return_attention=return_attention)
         enc_tok, entities, facts, _, _ = self._decode_front(
@@ -1501,15 +1609,19 @@ class DecoderTransformer(nn.Module):
         extra = force.to(enc_tok.device) if forced else \
             torch.tensor([diversity_penalty], dtype=torch.float32).to(enc_tok.device) if diverse else None
         inputs = [enc_tok, entities, facts] + ([rules, extra] if extra is not None else [rules] if rules_on else [])
+        if bias is not None:
+            inputs = [enc_tok, entities, facts, rules, _bias_input(bias, enc_tok.device)]
 
         def run(t, e, f, r=None, x=None):
             return self._predict_beam_device(t, e, f, max_pred_len, beam_size, return_attention, r, G,
-                                             x if diverse else None, x if forced else None)
+                                             x if diverse else None, x if forced else None,
+                                             _bias_views(x) if bias is not None else None)
 
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, beam_size) + self._enc_key(enc_tok) + ((G,) if diverse else ())
-            kind = "beam" + ("_force" if forced else "_div" if diverse else "") + ("_rules" if rules_on else "") + \
+            kind = "beam" + ("_force" if forced else "_div" if diverse else "_bias" if bias is not None else "") + \
+                ("_rules" if rules_on else "") + \
                 ("_attn" if return_attention else "")
             res = self._graphed(kind, key, run, inputs)
         else:
@@ -1524,11 +1636,13 @@ class DecoderTransformer(nn.Module):
             return out, score, res.all, res.all_scores, attn.clone(), res.all_attn.clone()
         return out, attn.clone()
 
-    def _predict_sample_device(self, enc_tok, entities, facts, knobs, max_pred_len, n, attention=False, rules=None):
+    def _predict_sample_device(self, enc_tok, entities, facts, knobs, max_pred_len, n, attention=False, rules=None,
+                               bias=None):
         """Sampled decode on the fused decode kernels: R = B * n rows, the n samples of a caption share its cross K/V
         and keep their own self-attention caches.  knobs: int64 (3) device tensor [seed, temperature | top_p << 32
         (two fp32 words), top_k] -- read by the selection kernel, so a replay sees whatever was copied into it.
-        rules: a rules_tensor() (read the same way) or None.  Returns (tokens (R, max_len), log-probabilities (R, max_len)[, cross-attention weights (max_len, R, layers, H,
+        rules: a rules_tensor() (read the same way) or None; bias: the (B, 64) ids and values of check_column_bias() on
+        the device (read the same way) or None.  Returns (tokens (R, max_len), log-probabilities (R, max_len)[, cross-attention weights (max_len, R, layers, H,
         S)])."""
         from . import lib as L
         dev = enc_tok.device
@@ -1543,9 +1657,13 @@ class DecoderTransformer(nn.Module):
         st.seed, st.temp_top_p, st.top_k, st.log_prob = base, base + 8, base + 16, log_prob.data_ptr()
         attn = torch.zeros(max_pred_len, c.R, c.layers, c.H, c.S, device=dev) if attention else None
         rs = None if rules is None else _rules_struct(rules)
+        cb = None
+        if bias is not None:
+            cb = L.DecodeBias()
+            cb.cols, cb.vals = bias[0].data_ptr(), bias[1].data_ptr()
         for i in range(max_pred_len):
             self._decode_step(c, t, t.get("cap_buf"), facts_r, K, i, attn)
-            ops.decode_select_sample(c, st, i, rs)
+            ops.decode_select_sample(c, st, i, rs, cb)
         if attention:
             return t["output"], log_prob, _zero_after_end(attn, t["output"], self.word_map["<end>"])
         return t["output"], log_prob
@@ -1553,7 +1671,7 @@ class DecoderTransformer(nn.Module):
     @torch.no_grad()
     def predict_sample(self, encoder_out, max_pred_len, entities, facts=None, num_samples=1, temperature=1.0, top_k=0,
                        top_p=1.0, seed=None, return_log_probs=False, return_attention=False, no_repeat_ngram_size=0,
-                       min_len=0):
+                       min_len=0, column_bias=None):
         """Stochastic decode: `num_samples` captions per image drawn from the model's distribution, with temperature,
         top-k and nucleus (top-p) truncation.  Per row and step over the V+K+F raw scores s: z = s / temperature;
         top-k keeps s >= the k-th largest s (ties at the boundary all kept); top-p then keeps the tokens whose
@@ -1574,9 +1692,17 @@ class DecoderTransformer(nn.Module):
         Decoding rules (as predict_beam; 0 = off, the default): no_repeat_ngram_size = n in 0..8 bans every token that
         would repeat an n-gram of the row, min_len = m bans <end> before step m.  A banned token is absent before top-k
         and top-p (not counted in k, no mass); its Gumbel noise is unchanged, so a step where no ban fires draws the
-        same token as without rules.  return_log_probs stays the untruncated log-probability."""
+        same token as without rules.  return_log_probs stays the untruncated log-probability.
+
+        Column bias (as predict_beam's column_bias): everything that selects runs on s' = s + b -- the
+        top-k threshold, z = s' / temperature, the top-p weights and the Gumbel arg-max; a -inf column is absent like a
+        banned one.  The noise of a column does not change, so a step at which no biased column is near the draw draws
+        the token it drew before; return_log_probs stays log_softmax of the raw scores.  A bias on <end> is the length
+        control of sampling.  Ids and values are inputs of the captured graph."""
         P_ = entities.shape[1] + (facts.shape[1] if facts is not None else 0)
         rules_on = check_rules("predict_sample", max_pred_len, self.vocab_size + P_, 0.0, no_repeat_ngram_size, min_len)
+        bias = check_column_bias("predict_sample", encoder_out.shape[0], self.vocab_size + P_, self.word_map,
+                                 column_bias)
         if not (isinstance(num_samples, int) and num_samples >= 1):
             raise IckError("predict_sample needs num_samples >= 1")
         if not (math.isfinite(temperature) and temperature > 0):
@@ -1597,14 +1723,18 @@ class DecoderTransformer(nn.Module):
         knobs = torch.tensor([seed, tp, min(top_k, 2 ** 31 - 1)], dtype=torch.int64).to(enc_tok.device)
         rules = rules_tensor(max_pred_len, 0.0, no_repeat_ngram_size, min_len, enc_tok.device) if rules_on else None
         inputs = [enc_tok, entities, facts, knobs] + ([rules] if rules_on else [])
+        if bias is not None:
+            inputs = [enc_tok, entities, facts, knobs, rules, _bias_input(bias, enc_tok.device)]
 
-        def run(t, e, f, k, r=None):
-            return self._predict_sample_device(t, e, f, k, max_pred_len, num_samples, return_attention, r)
+        def run(t, e, f, k, r=None, x=None):
+            return self._predict_sample_device(t, e, f, k, max_pred_len, num_samples, return_attention, r,
+                                               None if x is None else _bias_views(x))
 
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, num_samples) + self._enc_key(enc_tok)
-            kind = "sample" + ("_rules" if rules_on else "") + ("_attn" if return_attention else "")
+            kind = "sample" + ("_bias" if bias is not None else "") + ("_rules" if rules_on else "") + \
+                ("_attn" if return_attention else "")
             res = self._graphed(kind, key, run, inputs)
         else:
             res = run(*inputs)

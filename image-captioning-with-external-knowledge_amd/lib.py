@@ -168,6 +168,10 @@ class DecodeConstraints(C.Structure):   # ick_decode_constraints: forced columns
     _fields_ = [("force", vp), ("met", vp)]
 
 
+class DecodeBias(C.Structure):      # ick_decode_bias: column ids (B, 64) int32, values (B, 64) fp32, beam bias sums (R) fp32
+    _fields_ = [(n, vp) for n in ("cols", "vals", "sum")]
+
+
 # name -> argtypes; every entry returns int (0 ok, <0 ICK_E*, >0 hipError_t)
 SIGNATURES = {
     "ick_version": [],
@@ -221,6 +225,10 @@ SIGNATURES = {
                                        C.POINTER(DecodeDiversity), i32, vp],
     "ick_decode_select_beam_forced": [C.POINTER(DecodeCtx), C.POINTER(BeamState), C.POINTER(DecodeRules),
                                       C.POINTER(DecodeConstraints), i32, vp],
+    "ick_decode_select_beam_biased": [C.POINTER(DecodeCtx), C.POINTER(BeamState), C.POINTER(DecodeRules),
+                                      C.POINTER(DecodeBias), i32, vp],
+    "ick_decode_select_sample_biased": [C.POINTER(DecodeCtx), C.POINTER(SampleState), C.POINTER(DecodeRules),
+                                        C.POINTER(DecodeBias), i32, vp],
     "ick_attention_bwd": [C.POINTER(AttnBwdArgs), vp],
     "ick_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, f32, u32, u32, vp, vp, vp],
     "ick_layernorm_bwd_rows_per_block": [],

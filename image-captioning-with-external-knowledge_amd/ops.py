@@ -693,11 +693,16 @@ def _ref(s):
     return None if s is None else C.byref(s)
 
 
-def decode_select_beam(ctx, beam_state, pos, rules=None, diversity=None, constraints=None):
+def decode_select_beam(ctx, beam_state, pos, rules=None, diversity=None, constraints=None, bias=None):
     """Beam selection of step `pos` (ick_decode_select_beam), under decoding rules (lib.DecodeRules: n-gram / min-length
     bans, length penalty) or none, as plain, diverse (lib.DecodeDiversity: groups, penalty: ick_..._diverse) or
-    constrained beam search (lib.DecodeConstraints: force, met: ick_..._forced)."""
-    if constraints is not None:
+    constrained beam search (lib.DecodeConstraints: force, met: ick_..._forced), or with a column bias (lib.DecodeBias:
+    cols, vals, sum: ick_..._biased; not with groups or forced columns)."""
+    if bias is not None:
+        if diversity is not None or constraints is not None:
+            raise L.IckError("decode_select_beam: a column bias does not compose with beam groups or forced columns")
+        name, extra = "ick_decode_select_beam_biased", (_ref(rules), C.byref(bias))
+    elif constraints is not None:
         name, extra = "ick_decode_select_beam_forced", (_ref(rules), C.byref(constraints))
     elif diversity is not None:
         name, extra = "ick_decode_select_beam_diverse", (_ref(rules), C.byref(diversity))
@@ -710,10 +715,15 @@ def decode_select_beam_forced(ctx, beam_state, rules, constraints, pos):
     decode_select_beam(ctx, beam_state, pos, rules, constraints=constraints)
 
 
-def decode_select_sample(ctx, sample_state, pos, rules=None):
+def decode_select_sample(ctx, sample_state, pos, rules=None, bias=None):
     """Sampled token of step `pos` for every live row (ick_decode_select_sample); sample_state: lib.SampleState; rules:
-    lib.DecodeRules (n-gram / min-length bans: ick_decode_select_sample_rules) or None."""
-    name, extra = ("ick_decode_select_sample", ()) if rules is None else ("ick_decode_select_sample_rules", (_ref(rules),))
+    lib.DecodeRules (n-gram / min-length bans: ick_decode_select_sample_rules) or None; bias: lib.DecodeBias (cols, vals:
+    ick_decode_select_sample_biased) or None."""
+    if bias is not None:
+        name, extra = "ick_decode_select_sample_biased", (_ref(rules), C.byref(bias))
+    else:
+        name, extra = ("ick_decode_select_sample", ()) if rules is None else \
+            ("ick_decode_select_sample_rules", (_ref(rules),))
     L.check(getattr(L.load(), name)(C.byref(ctx), C.byref(sample_state), *extra, pos, _stream()), name)
 
 

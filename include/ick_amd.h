@@ -521,6 +521,35 @@ int ick_decode_select_beam_forced(const ick_decode_ctx* ctx, const ick_beam_stat
                                   const ick_decode_rules* rules /* NULL: no rules */,
                                   const ick_decode_constraints* constraints, int32_t pos, void* stream);
 
+/* Column bias: up to 64 (column, value) slots per caption, ids as ick_decode_constraints numbers
+ * them, -1 = an empty slot (its value is not used); a value is a finite float or -inf.  If one id sits in two slots of a
+ * row, the lowest slot counts.  cols and vals are read at run time, so a captured decode graph replays with new ids and
+ * values.  The supported sizes are those of ick_decode_beam_supported / ick_decode_sample_supported.
+ *   Beam: every hypothesis carries sum[r], the bias sum of the columns it has emitted.  Hypothesis j expanded with
+ *     column w is ranked by (cum_j - lse_j + s_w + b_w) + sum_j, an ended hypothesis by cum_j + sum_j (each over its
+ *     own lp[L] under a length penalty); lse runs over the raw scores of every column and cum stays the model's raw
+ *     summed log-probability.  A column with b = -inf leaves the candidate pool as a banned column does, and a rule ban
+ *     wins over any bias.  The caller zeroes sum before step 0 and picks the final best by the same key.
+ *   Sampling: top-k, z = s' / T, the top-p weights (relative to the allowed maximum of s') and the Gumbel arg-max run on
+ *     s' = s + b; a -inf column is absent like a rule-banned one (not counted in k, no mass).  The noise of a column and
+ *     log_prob (log_softmax of the raw scores) do not change.
+ * With every slot empty, or every value 0, the results are the bits of ick_decode_select_beam_rules /
+ * ick_decode_select_sample_rules (rules == NULL: of the entries without rules).  Argument errors (a NULL pointer, sum
+ * missing for the beam entry) return ICK_EINVAL without a launch. */
+#define ICK_BIAS_MAX 64
+typedef struct {
+    const int32_t* cols;          /* (R / rows_per_sample, 64) column ids, -1 = empty slot; device memory */
+    const float*   vals;          /* same shape; finite or -inf */
+    float*         sum;           /* beam: (R) bias sum of every hypothesis, zeroed by the caller before step 0;
+                                   * sampling: NULL */
+} ick_decode_bias;
+int ick_decode_select_beam_biased(const ick_decode_ctx* ctx, const ick_beam_state* beam,
+                                  const ick_decode_rules* rules /* NULL: no rules */, const ick_decode_bias* bias,
+                                  int32_t pos, void* stream);
+int ick_decode_select_sample_biased(const ick_decode_ctx* ctx, const ick_sample_state* s,
+                                    const ick_decode_rules* rules /* NULL: no rules */, const ick_decode_bias* bias,
+                                    int32_t pos, void* stream);
+
 /* fused token-mean cross entropy over the packed rows of train.py
  * (pack_padded_sequence + CrossEntropyLoss(ignore_index=<pad>), geo-aware/train.py:275-281):
  * rows (b,t) with t < decode_len[b] and target != pad contribute.  Writes loss_sum[0] (sum of
