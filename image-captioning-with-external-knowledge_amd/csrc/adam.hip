@@ -60,6 +60,25 @@ struct AdamDecay {
     int coupled;
 };
 
+// The step counter's advance inside the optimizer launch (ick_adam_step[_derive]): ticket == nullptr is
+// the code without it.  Every workgroup has read the counter in adam_hyper() before it draws its ticket; the workgroup
+// that draws the last one adds inc to the counter -- nobody of this launch reads it any more -- and sets the ticket word
+// back to 0 for the next launch.  A launch that returns from adam_hyper() (no token) draws no ticket and adds nothing.
+struct AdamBump {
+    uint32_t* counter;
+    uint32_t inc;
+    uint32_t* ticket;
+};
+__device__ __forceinline__ void adam_bump(const AdamBump& b) {
+    if (b.ticket == nullptr) return;      // uniform
+    __syncthreads();                      // every wave of the workgroup is past its read of the counter
+    if (threadIdx.x == 0 &&
+        __hip_atomic_fetch_add(b.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) {
+        *b.counter += b.inc;
+        __hip_atomic_store(b.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 constexpr int kGranuleShift = 6;      // log2 of the granule: bucket.ALIGN = 64 floats, where every parameter starts
 
 // Is the decay on for the element at float offset `at` from the bucket's start?  (A granule beyond the table: off.)
@@ -162,7 +181,7 @@ __global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, 
                                                          float gscale, float clip, float lr, float b1, float b2,
                                                          float eps, int step0, const uint32_t* step_ptr,
                                                          const float* __restrict__ gscale_den, float* words,
-                                                         ick_lr_schedule sched, AdamEma ema, AdamDecay dec) {
+                                                         ick_lr_schedule sched, AdamEma ema, AdamDecay dec, AdamBump bump) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     AdamHyper h;
     if (!adam_hyper<kOpt, kEma, kDecay>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema,
@@ -175,6 +194,7 @@ __global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, 
         g[i] = gi; m[i] = mi; v[i] = vi; p[i] = pi;
         if (kEma) { ema1(h, ei, pi); ema.e[i] = ei; }
     }
+    adam_bump(bump);
 }
 
 // The same update on float4: seven 16-byte streams per lane (the scalar form reaches 0.66 of the HBM rate, 320 MB per
@@ -185,7 +205,7 @@ __global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict
                                                               float gscale, float clip, float lr, float b1, float b2,
                                                               float eps, int step0, const uint32_t* step_ptr,
                                                               const float* __restrict__ gscale_den, float* words,
-                                                              ick_lr_schedule sched, AdamEma ema, AdamDecay dec) {
+                                                              ick_lr_schedule sched, AdamEma ema, AdamDecay dec, AdamBump bump) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     AdamHyper h;
     if (!adam_hyper<kOpt, kEma, kDecay>(h, gscale, clip, lr, b1, b2, eps, step0, step_ptr, gscale_den, words, sched, ema,
@@ -199,6 +219,7 @@ __global__ __launch_bounds__(256) void adam_clamp_vec4_kernel(float4* __restrict
         g[i] = gi; m[i] = mi; v[i] = vi; p[i] = pi;
         if (kEma) { ema4(h, ei, pi); e[i] = ei; }
     }
+    adam_bump(bump);
 }
 
 constexpr int kT = 64;        // tile edge
@@ -211,7 +232,8 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
                                                           const ick_adam_block* __restrict__ blocks, float gscale,
                                                           float clip, float lr, float b1, float b2, float eps, int step0,
                                                           const uint32_t* step_ptr, const float* __restrict__ gscale_den,
-                                                          float* words, ick_lr_schedule sched, AdamEma ema, AdamDecay dec) {
+                                                          float* words, ick_lr_schedule sched, AdamEma ema, AdamDecay dec,
+                                                          AdamBump bump) {
     __shared__ __attribute__((aligned(16))) float tile[kT * kLd];
     const ick_adam_block blk = blocks[blockIdx.x];
     AdamHyper h;
@@ -249,6 +271,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
                 if (blk.copy) reinterpret_cast<float4*>(blk.copy)[j] = pi[i];
             }
         }
+        adam_bump(bump);
         return;
     }
 
@@ -378,6 +401,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
             if (nl >= rlo && nl < rhi && k0 + kl < K) it.tr[(int64_t)(k0 + kl) * it.tr_ld + n0 + nl] = tile[nl * kLd + kl];
         }
     }
+    adam_bump(bump);
 }
 
 }  // namespace
@@ -406,18 +430,22 @@ static int adam_args(const float* p, const float* g, const float* m, const float
 template <bool kOpt, bool kEma, bool kDecay = false>
 static int launch_adam(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr, float* words,
                        ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                       const float* gscale_den, AdamEma ema, void* stream, AdamDecay dec = AdamDecay{}) {
+                       const float* gscale_den, AdamEma ema, void* stream, AdamDecay dec = AdamDecay{},
+                       AdamBump bump = AdamBump{}) {
     bool al16;
     if (int rc = adam_args<kEma, kDecay>(p, g, m, v, n, step, step_ptr, ema, dec, al16)) return rc;
+    if (bump.ticket) ICK_CHECK_ARG(step_ptr != nullptr);
+    bump.counter = const_cast<uint32_t*>(step_ptr);
     if (kDecay) ICK_CHECK_ARG(dec.granules >= ceil_div(n, (int64_t)1 << kGranuleShift));
     if (kEma && (reinterpret_cast<uintptr_t>(ema.e) & 3)) return ICK_EALIGN;
     int64_t done = 0;
     if (n >= 4096 && al16) {
         const int64_t n4 = n / 4;
+        const AdamBump here = n % 4 == 0 ? bump : AdamBump{};       // the counter moves in the bucket's LAST launch
         hipLaunchKernelGGL((adam_clamp_vec4_kernel<kOpt, kEma, kDecay>), dim3((int)std::min<int64_t>(ceil_div(n4, 256), 4096)),
                            dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(p), reinterpret_cast<float4*>(g),
                            reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), n4, gscale, clip, lr, beta1, beta2,
-                           eps, step, step_ptr, gscale_den, words, sched, ema, dec);
+                           eps, step, step_ptr, gscale_den, words, sched, ema, dec, here);
         done = 4 * n4;
         if (done == n) ICK_LAUNCH_RET();
     }
@@ -425,7 +453,7 @@ static int launch_adam(float* p, float* g, float* m, float* v, int64_t n, float 
     dec.base = done;
     hipLaunchKernelGGL((adam_clamp_kernel<kOpt, kEma, kDecay>), dim3((int)std::min<int64_t>(ceil_div(n - done, 256), 4096)),
                        dim3(256), 0, (hipStream_t)stream, p + done, g + done, m + done, v + done, n - done, gscale, clip, lr,
-                       beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema, dec);
+                       beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema, dec, bump);
     ICK_LAUNCH_RET();
 }
 
@@ -436,13 +464,15 @@ static int launch_adam_derive(float* p, float* g, float* m, float* v, const ick_
                               const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
                               float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
                               const uint32_t* step_ptr, const float* gscale_den, AdamEma ema, void* stream,
-                              AdamDecay dec = AdamDecay{}) {
+                              AdamDecay dec = AdamDecay{}, AdamBump bump = AdamBump{}) {
     bool al16;
     if (int rc = adam_args<kEma, kDecay>(p, g, m, v, blocks ? n_blocks : 0, step, step_ptr, ema, dec, al16)) return rc;
     if (!al16) return ICK_EALIGN;
+    if (bump.ticket) ICK_CHECK_ARG(step_ptr != nullptr);
+    bump.counter = const_cast<uint32_t*>(step_ptr);
     hipLaunchKernelGGL((adam_derive_kernel<kOpt, kEma, kDecay>), dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                        items, blocks, gscale, clip, lr, beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema,
-                       dec);
+                       dec, bump);
     ICK_LAUNCH_RET();
 }
 
@@ -568,4 +598,67 @@ extern "C" int ick_adam_decay_derive(float* p, float* g, float* m, float* v, flo
         [&] { return launch_adam_derive<true, true, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words,
                                                           sched, beta1, beta2, eps, step, step_ptr, gscale_den, ema, stream,
                                                           dec); });
+}
+
+// The general entries: every option by its pointer -- e == NULL keeps no average, words == NULL takes the
+// host rate lr, decay == NULL decays nothing -- on the instantiation the entry above of the same options launches, and
+// the step counter's advance in the same launch: ticket != NULL (one uint32 in device memory, 0 before the first launch
+// and after every one) makes step_ptr[0] += bump_inc once every workgroup has read it, iff the update ran (gscale_den ==
+// NULL or gscale_den[0] > 0): ick_counter_add_if's rule.  ticket == NULL: the counter is only read.
+template <bool kDerive, typename... Over>
+static int adam_step(float* p, float* g, float* m, float* v, float* e, float gscale, float clip, float lr, float* words,
+                     ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, uint32_t* step_ptr,
+                     const float* gscale_den, const float* ema_decay, int32_t ema_warmup, const float* decay,
+                     const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form, uint32_t bump_inc,
+                     uint32_t* ticket, void* stream, Over... over) {
+    const AdamEma ema = e ? AdamEma{e, ema_decay, ema_warmup != 0} : AdamEma{};
+    const AdamDecay dec{decay, decay_mask, n_granules, 0, decay_form};
+    const AdamBump bump{nullptr, bump_inc, ticket};
+    if (words) ICK_CHECK_ARG(lr_schedule_ok(sched));
+    if (!words) sched = ick_lr_schedule{};
+    auto go = [&](auto opt, auto avg, auto wd) {
+        constexpr bool kOpt = decltype(opt)::value, kEma = decltype(avg)::value, kDecay = decltype(wd)::value;
+        const float rate = kOpt ? 0.f : lr;
+        if constexpr (kDerive)
+            return launch_adam_derive<kOpt, kEma, kDecay>(p, g, m, v, over..., gscale, clip, rate, words, sched, beta1, beta2,
+                                                          eps, step, step_ptr, gscale_den, ema, stream,
+                                                          kDecay ? dec : AdamDecay{}, bump);
+        else
+            return launch_adam<kOpt, kEma, kDecay>(p, g, m, v, over..., gscale, clip, rate, words, sched, beta1, beta2, eps,
+                                                   step, step_ptr, gscale_den, ema, stream, kDecay ? dec : AdamDecay{},
+                                                   bump);
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    const int which = (words ? 1 : 0) | (e ? 2 : 0) | (decay ? 4 : 0);
+    switch (which) {
+        case 0: return go(F{}, F{}, F{});
+        case 1: return go(T{}, F{}, F{});
+        case 2: return go(F{}, T{}, F{});
+        case 3: return go(T{}, T{}, F{});
+        case 4: return go(F{}, F{}, T{});
+        case 5: return go(T{}, F{}, T{});
+        case 6: return go(F{}, T{}, T{});
+        default: return go(T{}, T{}, T{});
+    }
+}
+
+extern "C" int ick_adam_step(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip, float lr,
+                             float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                             uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
+                             const float* decay, const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form,
+                             uint32_t bump_inc, uint32_t* ticket, void* stream) {
+    return adam_step<false>(p, g, m, v, e, gscale, clip, lr, words, sched, beta1, beta2, eps, step, step_ptr, gscale_den,
+                            ema_decay, ema_warmup, decay, decay_mask, n_granules, decay_form, bump_inc, ticket, stream, n);
+}
+
+extern "C" int ick_adam_step_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
+                                    const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
+                                    float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                                    uint32_t* step_ptr, const float* gscale_den, const float* ema_decay,
+                                    int32_t ema_warmup, const float* decay, const uint8_t* decay_mask, int64_t n_granules,
+                                    int32_t decay_form, uint32_t bump_inc, uint32_t* ticket, void* stream) {
+    return adam_step<true>(p, g, m, v, e, gscale, clip, lr, words, sched, beta1, beta2, eps, step, step_ptr, gscale_den,
+                           ema_decay, ema_warmup, decay, decay_mask, n_granules, decay_form, bump_inc, ticket, stream,
+                           items, blocks, n_blocks);
 }

@@ -279,16 +279,17 @@ __global__ __launch_bounds__(256) void fact_encode_bwd_kernel(const float* __res
 // their logical rows.  The dh kernel's workgroup m takes packed row m (logical row rowmap[m]) and exits past the row count
 // rowstart[B]; the dctx kernel reads a zero gradient for the positions beyond a sample's rows.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pointer_bwd_dh_kernel(const float* __restrict__ ds, int64_t ds_ld, int col0,
-                                                             const float* __restrict__ ctx, const float* __restrict__ w,
-                                                             const float* __restrict__ ind, float* __restrict__ dh,
-                                                             int T, int Kc, int d, const int32_t* __restrict__ rowmap,
-                                                             const int32_t* __restrict__ count) {
-    chain_priority();
-    int b = blockIdx.y, t = blockIdx.x;
+// (the roles are written once, as functions of the workgroup's place in its role's own grid: the two-launch entry points
+// run each as a kernel of its own, the fused ones as workgroup ranges of one launch)
+__device__ __forceinline__ void pointer_bwd_dh_role(int bx, int by, int B, const float* __restrict__ ds, int64_t ds_ld,
+                                                    int col0, const float* __restrict__ ctx, const float* __restrict__ w,
+                                                    const float* __restrict__ ind, float* __restrict__ dh, int T, int Kc,
+                                                    int d, const int32_t* __restrict__ rowmap,
+                                                    const int32_t* __restrict__ count) {
+    int b = by, t = bx;
     int64_t dsrow = (int64_t)b * T + t;
     if (rowmap != nullptr) {     // uniform
-        if (dsrow >= device_bound((int)gridDim.y * T, count)) return;
+        if (dsrow >= device_bound(B * T, count)) return;
         const int lr = rowmap[dsrow];
         b = lr / T;
         t = lr - b * T;
@@ -318,24 +319,34 @@ __global__ __launch_bounds__(256) void pointer_bwd_dh_kernel(const float* __rest
     }
 }
 
+__global__ __launch_bounds__(256) void pointer_bwd_dh_kernel(const float* __restrict__ ds, int64_t ds_ld, int col0,
+                                                             const float* __restrict__ ctx, const float* __restrict__ w,
+                                                             const float* __restrict__ ind, float* __restrict__ dh,
+                                                             int T, int Kc, int d, const int32_t* __restrict__ rowmap,
+                                                             const int32_t* __restrict__ count) {
+    chain_priority();
+    pointer_bwd_dh_role(blockIdx.x, blockIdx.y, gridDim.y, ds, ds_ld, col0, ctx, w, ind, dh, T, Kc, d, rowmap, count);
+}
+
 // One workgroup per (sample, 64 columns): the (T x Kc) score gradients of the sample sit in LDS, lane <-> column,
 // the four waves share the Kc context rows.  d w and d bias leave the workgroup as one float atomic per column /
 // one per sample (a workgroup per (sample, row) made 1280 workgroups fight over the same 300 addresses: 59 us).
 // SEQ (deterministic mode): one workgroup per column block walks the samples in order and adds its d w / d bias terms
 // with plain read-modify-writes instead of one float atomic per sample.
-template <bool SEQ>
-__global__ __launch_bounds__(256) void pointer_bwd_dctx_kernel(const float* __restrict__ ds, int64_t ds_ld, int col0,
-                                                               const float* __restrict__ h, const float* __restrict__ ctx,
-                                                               const float* __restrict__ w, const float* __restrict__ ind,
-                                                               float* __restrict__ dctx, float* __restrict__ dw,
-                                                               float* __restrict__ dbias, int B, int T, int Kc, int d,
-                                                               const int32_t* __restrict__ rowstart) {
-    chain_priority();
-    extern __shared__ float gs[];   // T * Kc gradients (indicator applied), 4 floats of scratch, 4 x 64 partial d w
+// kBatch (the fused launch): a lane's T hidden values are loaded eight at a time into registers before the first of
+// them is used; the products enter acc in the same order, t = 0 .. T - 1.
+template <bool SEQ, bool kBatch>
+__device__ __forceinline__ void pointer_bwd_dctx_role(int bx, int by, float* gs, const float* __restrict__ ds,
+                                                      int64_t ds_ld, int col0, const float* __restrict__ h,
+                                                      const float* __restrict__ ctx, const float* __restrict__ w,
+                                                      const float* __restrict__ ind, float* __restrict__ dctx,
+                                                      float* __restrict__ dw, float* __restrict__ dbias, int B, int T,
+                                                      int Kc, int d, const int32_t* __restrict__ rowstart) {
+    // gs: T * Kc gradients (indicator applied), 4 floats of scratch, 4 x 64 partial d w
     float* red = gs + T * Kc;
     float* dwp = red + 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int b = SEQ ? 0 : blockIdx.x; b < (SEQ ? B : (int)blockIdx.x + 1); ++b) {
+  for (int b = SEQ ? 0 : bx; b < (SEQ ? B : bx + 1); ++b) {
     float bsum = 0.f;
     // packed score gradients: the sample's nrow rows start at row0; the positions beyond them contribute exact zeros
     const int64_t row0 = rowstart ? rowstart[b] : (int64_t)b * T;
@@ -348,15 +359,27 @@ __global__ __launch_bounds__(256) void pointer_bwd_dctx_kernel(const float* __re
         gs[idx] = g;
     }
     bsum = block_sum<4>(bsum, red);   // contains the barriers that publish gs
-    if (threadIdx.x == 0 && blockIdx.y == 0) { if (SEQ) dbias[0] += bsum; else atomicAdd(dbias, bsum); }
-    const int c = blockIdx.y * 64 + lane;
+    if (threadIdx.x == 0 && by == 0) { if (SEQ) dbias[0] += bsum; else atomicAdd(dbias, bsum); }
+    const int c = by * 64 + lane;
     const bool ok = c < d;
     const float* hb = h + (int64_t)b * T * d + (ok ? c : 0);
     const float wc = ok ? w[c] : 0.f;
     float dwl = 0.f;
     for (int k = wave; k < Kc; k += 4) {
         float acc = 0.f;
-        for (int t = 0; t < T; ++t) acc = fmaf(gs[t * Kc + k], hb[(int64_t)t * d], acc);
+        if (kBatch) {
+            int t = 0;
+            for (; t + 8 <= T; t += 8) {
+                float hv[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) hv[q] = hb[(int64_t)(t + q) * d];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc = fmaf(gs[(t + q) * Kc + k], hv[q], acc);
+            }
+            for (; t < T; ++t) acc = fmaf(gs[t * Kc + k], hb[(int64_t)t * d], acc);
+        } else {
+            for (int t = 0; t < T; ++t) acc = fmaf(gs[t * Kc + k], hb[(int64_t)t * d], acc);
+        }
         if (ok) {
             const int64_t o = ((int64_t)b * Kc + k) * d + c;
             dctx[o] += acc * wc;
@@ -371,6 +394,45 @@ __global__ __launch_bounds__(256) void pointer_bwd_dctx_kernel(const float* __re
     }
     if (SEQ) __syncthreads();          // the LDS buffers are rewritten for the next sample
   }
+}
+
+template <bool SEQ>
+__global__ __launch_bounds__(256) void pointer_bwd_dctx_kernel(const float* __restrict__ ds, int64_t ds_ld, int col0,
+                                                               const float* __restrict__ h, const float* __restrict__ ctx,
+                                                               const float* __restrict__ w, const float* __restrict__ ind,
+                                                               float* __restrict__ dctx, float* __restrict__ dw,
+                                                               float* __restrict__ dbias, int B, int T, int Kc, int d,
+                                                               const int32_t* __restrict__ rowstart) {
+    chain_priority();
+    extern __shared__ float gs[];
+    pointer_bwd_dctx_role<SEQ, false>(blockIdx.x, blockIdx.y, gs, ds, ds_ld, col0, h, ctx, w, ind, dctx, dw, dbias, B, T, Kc,
+                                      d, rowstart);
+}
+
+// Both roles in one launch (ick_pointer_scores_bwd_fused[_packed]): the two write disjoint outputs and read only what
+// earlier launches wrote, so their workgroups run beside each other.  Workgroups [0, n_ctx) take the dctx role -- the
+// longer one, dispatched first -- as (x = id % ctx_x, y = id / ctx_x) of its own grid; the rest take the dh role as
+// (t = id % T, b = id / T).
+template <bool SEQ>
+__global__ __launch_bounds__(256) void pointer_bwd_fused_kernel(const float* __restrict__ ds, int64_t ds_ld, int col0,
+                                                                const float* __restrict__ h, const float* __restrict__ ctx,
+                                                                const float* __restrict__ w, const float* __restrict__ ind,
+                                                                float* __restrict__ dh, float* __restrict__ dctx,
+                                                                float* __restrict__ dw, float* __restrict__ dbias, int B,
+                                                                int T, int Kc, int d, const int32_t* __restrict__ rowmap,
+                                                                const int32_t* __restrict__ rowstart, int ctx_x,
+                                                                int n_ctx) {
+    chain_priority();
+    extern __shared__ float gs[];
+    const int id = blockIdx.x;      // uniform
+    if (id < n_ctx) {
+        pointer_bwd_dctx_role<SEQ, true>(id % ctx_x, id / ctx_x, gs, ds, ds_ld, col0, h, ctx, w, ind, dctx, dw, dbias, B, T,
+                                         Kc, d, rowstart);
+    } else {
+        const int r = id - n_ctx;
+        pointer_bwd_dh_role(r % T, r / T, B, ds, ds_ld, col0, ctx, w, ind, dh, T, Kc, d, rowmap,
+                            rowstart ? rowstart + B : nullptr);
+    }
 }
 
 // Predicate-gate backward (knowledge variants): gate[b,p,:] = bias + sum_{distinct active preds} W[:, pred]
@@ -510,6 +572,37 @@ extern "C" int ick_pointer_scores_bwd_packed(const float* ds, int64_t ds_ld, int
         hipLaunchKernelGGL(pointer_bwd_dctx_kernel<false>, dim3(B, ceil_div(d, 64)), dim3(256), smem, s, ds, ds_ld, col0, h,
                            ctx, w, ind, dctx, dw, dbias, B, T, Kc, d, rowstart);
     ICK_LAUNCH_RET();
+}
+
+// The pair of launches above as ONE: the same sums in the same order, bit for bit.
+extern "C" int ick_pointer_scores_bwd_fused_packed(const float* ds, int64_t ds_ld, int32_t col0, const float* h,
+                                                   const float* ctx, const float* w, const float* ind, float* dh,
+                                                   float* dctx, float* dw, float* dbias, int32_t B, int32_t T, int32_t Kc,
+                                                   int32_t d, const int32_t* rowmap, const int32_t* rowstart,
+                                                   void* stream) {
+    ICK_CHECK_ARG(ds && h && ctx && w && dh && dctx && dw && dbias && B > 0 && B <= 65535 && T > 0 && Kc > 0 && d > 0);
+    ICK_CHECK_ARG((rowmap == nullptr) == (rowstart == nullptr) && (int64_t)B * T <= INT32_MAX);
+    const size_t smem = ((size_t)T * Kc + 4 + 256) * sizeof(float);
+    ICK_CHECK_ARG(smem <= 64 * 1024);
+    const int ctx_x = deterministic() ? 1 : B;
+    const int64_t n_ctx = (int64_t)ctx_x * ceil_div(d, 64);
+    ICK_CHECK_ARG(n_ctx + (int64_t)B * T <= INT32_MAX);
+    const dim3 grid((unsigned)(n_ctx + (int64_t)B * T));
+    hipStream_t s = (hipStream_t)stream;
+    if (deterministic())
+        hipLaunchKernelGGL(pointer_bwd_fused_kernel<true>, grid, dim3(256), smem, s, ds, ds_ld, col0, h, ctx, w, ind, dh,
+                           dctx, dw, dbias, B, T, Kc, d, rowmap, rowstart, ctx_x, (int)n_ctx);
+    else
+        hipLaunchKernelGGL(pointer_bwd_fused_kernel<false>, grid, dim3(256), smem, s, ds, ds_ld, col0, h, ctx, w, ind, dh,
+                           dctx, dw, dbias, B, T, Kc, d, rowmap, rowstart, ctx_x, (int)n_ctx);
+    ICK_LAUNCH_RET();
+}
+
+extern "C" int ick_pointer_scores_bwd_fused(const float* ds, int64_t ds_ld, int32_t col0, const float* h, const float* ctx,
+                                            const float* w, const float* ind, float* dh, float* dctx, float* dw,
+                                            float* dbias, int32_t B, int32_t T, int32_t Kc, int32_t d, void* stream) {
+    return ick_pointer_scores_bwd_fused_packed(ds, ds_ld, col0, h, ctx, w, ind, dh, dctx, dw, dbias, B, T, Kc, d, nullptr,
+                                               nullptr, stream);
 }
 
 extern "C" int ick_entity_encode_bwd(int32_t variant, const float* dee, const float* entities, int32_t ent_cols,

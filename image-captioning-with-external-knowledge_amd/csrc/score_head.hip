@@ -407,12 +407,14 @@ __global__ __launch_bounds__(256) void packed_ce_rows_kernel(const float* __rest
 // Fixed-order reduction of the per-row losses (deterministic, unlike float atomics); kWeighted: row i belongs to caption
 // i / L and its loss enters the sum times that caption's weight (the count stays the number of rows).
 // rowmap / nrows (the packed form): the first *nrows of the n rows exist, row i belongs to caption rowmap[i] / L.
+// mean (ick_packed_ce_*_mean; else nullptr): also mean[0] = loss_sum / count, 0 when no row counts.
 template <bool kWeighted>
 __global__ __launch_bounds__(256) void packed_ce_reduce_kernel(const float* __restrict__ row_loss, int n, int L,
                                                                const float* __restrict__ weight,
                                                                float* __restrict__ loss_sum, float* __restrict__ count,
                                                                const int32_t* __restrict__ rowmap,
-                                                               const int32_t* __restrict__ nrows) {
+                                                               const int32_t* __restrict__ nrows,
+                                                               float* __restrict__ mean) {
     __shared__ float red[4];
     float s = 0.f, c = 0.f;
     n = device_bound(n, nrows);
@@ -422,7 +424,11 @@ __global__ __launch_bounds__(256) void packed_ce_reduce_kernel(const float* __re
     }
     s = block_sum<4>(s, red);
     c = block_sum<4>(c, red);
-    if (threadIdx.x == 0) { loss_sum[0] = s; count[0] = c; }
+    if (threadIdx.x == 0) {
+        loss_sum[0] = s;
+        count[0] = c;
+        if (mean) mean[0] = c > 0.f ? s / c : 0.f;
+    }
 }
 
 // Caption scoring (ick_row_logprob_rank): what a scorer needs of one packed score row -- the target's
@@ -727,9 +733,9 @@ extern "C" int ick_greedy_select(const float* scores, int64_t ld, int32_t B, int
     ICK_LAUNCH_RET();
 }
 
-extern "C" int ick_packed_ce(const float* scores, int64_t ld, const int64_t* captions_sorted,
+static int packed_ce_impl(const float* scores, int64_t ld, const int64_t* captions_sorted,
                              const int32_t* decode_len, int32_t B, int32_t L, int32_t Vx, int32_t pad_token,
-                             float* row_loss, float* loss_sum, float* count, float* dscores, void* stream) {
+                             float* row_loss, float* loss_sum, float* count, float* dscores, float* mean, void* stream) {
     using namespace ick;
     ICK_CHECK_ARG(scores && captions_sorted && decode_len && row_loss && loss_sum && count);
     ICK_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Vx > 0 && ld >= Vx);
@@ -737,14 +743,14 @@ extern "C" int ick_packed_ce(const float* scores, int64_t ld, const int64_t* cap
     hipLaunchKernelGGL(packed_ce_rows_kernel<false>, dim3(L, B), dim3(256), 0, s, scores, ld, captions_sorted, decode_len,
                        L, Vx, pad_token, row_loss, dscores, nullptr, nullptr, CeEps<false>{});
     hipLaunchKernelGGL(packed_ce_reduce_kernel<false>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, nullptr, loss_sum,
-                       count, nullptr, nullptr);
+                       count, nullptr, nullptr, mean);
     ICK_LAUNCH_RET();
 }
 
-extern "C" int ick_packed_ce_packed(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+static int packed_ce_packed_impl(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
                                     const int32_t* count, const float* weights, int32_t B, int32_t L, int32_t Vx,
                                     int32_t pad_token, float* row_loss, float* loss_sum, float* count_out, float* dscores,
-                                    void* stream) {
+                                    float* mean, void* stream) {
     using namespace ick;
     ICK_CHECK_ARG(scores && captions && rowmap && count && row_loss && loss_sum && count_out);
     ICK_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Vx > 0 && ld >= Vx && (int64_t)B * L <= INT32_MAX);
@@ -753,20 +759,21 @@ extern "C" int ick_packed_ce_packed(const float* scores, int64_t ld, const int64
         hipLaunchKernelGGL((packed_ce_rows_kernel<true, true>), dim3(L, B), dim3(256), 0, s, scores, ld, captions, count, L,
                            Vx, pad_token, row_loss, dscores, weights, rowmap, CeEps<false>{});
         hipLaunchKernelGGL(packed_ce_reduce_kernel<true>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, weights, loss_sum,
-                           count_out, rowmap, count);
+                           count_out, rowmap, count, mean);
     } else {
         hipLaunchKernelGGL((packed_ce_rows_kernel<false, true>), dim3(L, B), dim3(256), 0, s, scores, ld, captions, count, L,
                            Vx, pad_token, row_loss, dscores, nullptr, rowmap, CeEps<false>{});
         hipLaunchKernelGGL(packed_ce_reduce_kernel<false>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, nullptr, loss_sum,
-                           count_out, rowmap, count);
+                           count_out, rowmap, count, mean);
     }
     ICK_LAUNCH_RET();
 }
 
-extern "C" int ick_packed_ce_smooth(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+static int packed_ce_smooth_impl(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
                                     const int32_t* count, const int32_t* decode_len, const float* weights,
                                     const float* eps, int32_t B, int32_t L, int32_t Vx, int32_t pad_token,
-                                    float* row_loss, float* loss_sum, float* count_out, float* dscores, void* stream) {
+                                    float* row_loss, float* loss_sum, float* count_out, float* dscores, float* mean,
+                                    void* stream) {
     using namespace ick;
     ICK_CHECK_ARG(scores && captions && eps && row_loss && loss_sum && count_out);
     ICK_CHECK_ARG((rowmap != nullptr) == (count != nullptr) && (rowmap != nullptr || decode_len != nullptr));
@@ -780,11 +787,11 @@ extern "C" int ick_packed_ce_smooth(const float* scores, int64_t ld, const int64
     if (weights != nullptr) {
         if (rowmap) { ICK_CE_SMOOTH(true, true); } else { ICK_CE_SMOOTH(true, false); }
         hipLaunchKernelGGL(packed_ce_reduce_kernel<true>, dim3(1), block, 0, s, row_loss, B * L, L, weights, loss_sum,
-                           count_out, rowmap, count);
+                           count_out, rowmap, count, mean);
     } else {
         if (rowmap) { ICK_CE_SMOOTH(false, true); } else { ICK_CE_SMOOTH(false, false); }
         hipLaunchKernelGGL(packed_ce_reduce_kernel<false>, dim3(1), block, 0, s, row_loss, B * L, L, nullptr, loss_sum,
-                           count_out, rowmap, count);
+                           count_out, rowmap, count, mean);
     }
 #undef ICK_CE_SMOOTH
     ICK_LAUNCH_RET();
@@ -816,10 +823,10 @@ extern "C" int ick_caption_score_sums(const int32_t* rowstart, int32_t R, int32_
     ICK_LAUNCH_RET();
 }
 
-extern "C" int ick_packed_ce_weighted(const float* scores, int64_t ld, const int64_t* captions_sorted,
+static int packed_ce_weighted_impl(const float* scores, int64_t ld, const int64_t* captions_sorted,
                                       const int32_t* decode_len, const float* weights, int32_t B, int32_t L, int32_t Vx,
                                       int32_t pad_token, float* row_loss, float* loss_sum, float* count, float* dscores,
-                                      void* stream) {
+                                      float* mean, void* stream) {
     using namespace ick;
     ICK_CHECK_ARG(scores && captions_sorted && decode_len && weights && row_loss && loss_sum && count);
     ICK_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Vx > 0 && ld >= Vx && (int64_t)B * L <= INT32_MAX);
@@ -827,6 +834,71 @@ extern "C" int ick_packed_ce_weighted(const float* scores, int64_t ld, const int
     hipLaunchKernelGGL(packed_ce_rows_kernel<true>, dim3(L, B), dim3(256), 0, s, scores, ld, captions_sorted, decode_len,
                        L, Vx, pad_token, row_loss, dscores, weights, nullptr, CeEps<false>{});
     hipLaunchKernelGGL(packed_ce_reduce_kernel<true>, dim3(1), dim3(256), 0, s, row_loss, B * L, L, weights, loss_sum,
-                       count, nullptr, nullptr);
+                       count, nullptr, nullptr, mean);
     ICK_LAUNCH_RET();
+}
+
+// ---- the C entries of the packed cross entropy: the two-launch forms, and the same with the mean loss written by the
+// reduction (ick_packed_ce_*_mean) -----------------------------------------------------------------
+extern "C" int ick_packed_ce(const float* scores, int64_t ld, const int64_t* captions_sorted, const int32_t* decode_len,
+                             int32_t B, int32_t L, int32_t Vx, int32_t pad_token, float* row_loss, float* loss_sum,
+                             float* count, float* dscores, void* stream) {
+    return packed_ce_impl(scores, ld, captions_sorted, decode_len, B, L, Vx, pad_token, row_loss, loss_sum, count, dscores,
+                          nullptr, stream);
+}
+
+extern "C" int ick_packed_ce_weighted(const float* scores, int64_t ld, const int64_t* captions_sorted,
+                                      const int32_t* decode_len, const float* weights, int32_t B, int32_t L, int32_t Vx,
+                                      int32_t pad_token, float* row_loss, float* loss_sum, float* count, float* dscores,
+                                      void* stream) {
+    return packed_ce_weighted_impl(scores, ld, captions_sorted, decode_len, weights, B, L, Vx, pad_token, row_loss, loss_sum,
+                                   count, dscores, nullptr, stream);
+}
+
+extern "C" int ick_packed_ce_packed(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                                    const int32_t* count, const float* weights, int32_t B, int32_t L, int32_t Vx,
+                                    int32_t pad_token, float* row_loss, float* loss_sum, float* count_out, float* dscores,
+                                    void* stream) {
+    return packed_ce_packed_impl(scores, ld, captions, rowmap, count, weights, B, L, Vx, pad_token, row_loss, loss_sum,
+                                 count_out, dscores, nullptr, stream);
+}
+
+extern "C" int ick_packed_ce_smooth(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                                    const int32_t* count, const int32_t* decode_len, const float* weights,
+                                    const float* eps, int32_t B, int32_t L, int32_t Vx, int32_t pad_token,
+                                    float* row_loss, float* loss_sum, float* count_out, float* dscores, void* stream) {
+    return packed_ce_smooth_impl(scores, ld, captions, rowmap, count, decode_len, weights, eps, B, L, Vx, pad_token, row_loss,
+                                 loss_sum, count_out, dscores, nullptr, stream);
+}
+
+// (weights == NULL: the plain entry, ick_packed_ce)
+extern "C" int ick_packed_ce_weighted_mean(const float* scores, int64_t ld, const int64_t* captions_sorted,
+                                           const int32_t* decode_len, const float* weights, int32_t B, int32_t L,
+                                           int32_t Vx, int32_t pad_token, float* row_loss, float* loss_sum, float* count,
+                                           float* dscores, float* mean, void* stream) {
+    ICK_CHECK_ARG(mean != nullptr);
+    if (weights == nullptr)
+        return packed_ce_impl(scores, ld, captions_sorted, decode_len, B, L, Vx, pad_token, row_loss, loss_sum, count,
+                              dscores, mean, stream);
+    return packed_ce_weighted_impl(scores, ld, captions_sorted, decode_len, weights, B, L, Vx, pad_token, row_loss, loss_sum,
+                                   count, dscores, mean, stream);
+}
+
+extern "C" int ick_packed_ce_packed_mean(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                                         const int32_t* count, const float* weights, int32_t B, int32_t L, int32_t Vx,
+                                         int32_t pad_token, float* row_loss, float* loss_sum, float* count_out,
+                                         float* dscores, float* mean, void* stream) {
+    ICK_CHECK_ARG(mean != nullptr);
+    return packed_ce_packed_impl(scores, ld, captions, rowmap, count, weights, B, L, Vx, pad_token, row_loss, loss_sum,
+                                 count_out, dscores, mean, stream);
+}
+
+extern "C" int ick_packed_ce_smooth_mean(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                                         const int32_t* count, const int32_t* decode_len, const float* weights,
+                                         const float* eps, int32_t B, int32_t L, int32_t Vx, int32_t pad_token,
+                                         float* row_loss, float* loss_sum, float* count_out, float* dscores, float* mean,
+                                         void* stream) {
+    ICK_CHECK_ARG(mean != nullptr);
+    return packed_ce_smooth_impl(scores, ld, captions, rowmap, count, decode_len, weights, eps, B, L, Vx, pad_token, row_loss,
+                                 loss_sum, count_out, dscores, mean, stream);
 }

@@ -255,6 +255,10 @@ SIGNATURES = {
                        i64, i32, vp],
     "ick_adam_decay_derive": [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp,
                               i32, vp, vp, i64, i32, vp],
+    "ick_adam_step": [vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp, i32, vp, vp,
+                      i64, i32, u32, vp, vp],
+    "ick_adam_step_derive": [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp,
+                             i32, vp, vp, i64, i32, u32, vp, vp],
     "ick_conv1_wgrad_plan": [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i64)],
     "ick_conv1_wgrad": [vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
     "ick_counter_add": [vp, u32, vp],
@@ -268,6 +272,11 @@ SIGNATURES = {
     "ick_packed_ce_smooth": [vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "ick_pointer_scores_bwd_packed": [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],
     "ick_gather_rows": [vp, i64, vp, vp, vp, i64, i32, i32, vp],
+    "ick_packed_ce_weighted_mean": [vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "ick_packed_ce_packed_mean": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "ick_packed_ce_smooth_mean": [vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "ick_pointer_scores_bwd_fused": [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "ick_pointer_scores_bwd_fused_packed": [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],
     "ick_row_logprob_rank": [vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "ick_caption_score_sums": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "ick_sched_sample_mix": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp,

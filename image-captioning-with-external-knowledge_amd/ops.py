@@ -757,9 +757,11 @@ def gather_rows(x2, pack):
     return out
 
 
-def packed_ce_rows(scores, captions, pack, pad_token, weights=None, want_grad=False, out_sum=None, out_count=None):
+def packed_ce_rows(scores, captions, pack, pad_token, weights=None, want_grad=False, out_sum=None, out_count=None,
+                   mean=None):
     """packed_ce / packed_ce_weighted over PACKED score rows (scores (B, L, Vx): the first M' rows of its B * L hold the
-    valid positions in pack.rowmap's order): -> (loss_sum, count, dscores packed alike; rows from M' on are not written)."""
+    valid positions in pack.rowmap's order): -> (loss_sum, count, dscores packed alike; rows from M' on are not written).
+    mean: see _ce_mean."""
     B, Lc, Vx = scores.shape
     dev = scores.device
     if weights is not None and (weights.shape != (B,) or weights.dtype != torch.float32 or not weights.is_cuda or
@@ -772,10 +774,21 @@ def packed_ce_rows(scores, captions, pack, pad_token, weights=None, want_grad=Fa
     assert scores.stride(0) == Lc * scores.stride(1) and scores.stride(2) == 1
     if want_grad:
         dscores = torch.empty(B, Lc, scores.stride(1), device=dev, dtype=torch.float32)[:, :, :Vx]
-    L.check(L.load().ick_packed_ce_packed(_p(scores), scores.stride(1), _p(captions), _p(pack.rowmap), _p(pack.count),
-                                          _p(weights), B, Lc, Vx, pad_token, _p(row_loss), _p(loss_sum), _p(count),
-                                          _p(dscores), _stream()), "ick_packed_ce_packed")
+    name, tail = _ce_mean("ick_packed_ce_packed", mean)
+    L.check(getattr(L.load(), name)(_p(scores), scores.stride(1), _p(captions), _p(pack.rowmap), _p(pack.count),
+                                    _p(weights), B, Lc, Vx, pad_token, _p(row_loss), _p(loss_sum), _p(count), _p(dscores),
+                                    *tail, _stream()), name)
     return loss_sum, count, dscores
+
+
+def _ce_mean(name, mean):
+    """The entry a loss wrapper calls and its extra argument.  mean: a one-element float32 device tensor; the reduction
+    launch then also writes the token-mean loss into it (ick_*_mean; 0 for a batch without a token)."""
+    if mean is None:
+        return name, ()
+    if mean.numel() != 1 or mean.dtype != torch.float32 or not mean.is_cuda:
+        raise L.IckError("the loss's mean must be one float32 on the device")
+    return name + "_mean", (_p(mean),)
 
 
 def row_logprob_rank(scores, captions, pack, pad_token, out=None):
@@ -818,9 +831,10 @@ def caption_score_sums(pack, tlp, rank, best, top_k=5, out=None):
     return log_prob, tokens, totals[0:1], totals[1:2], totals[2:3], totals[3:4]
 
 
-def packed_ce(scores, captions_sorted, decode_len, pad_token, want_grad=False, out_sum=None, out_count=None):
+def packed_ce(scores, captions_sorted, decode_len, pad_token, want_grad=False, out_sum=None, out_count=None, mean=None):
     """Returns (loss_sum (1,), count (1,), dscores or None): token-mean loss = loss_sum / count.  out_sum / out_count:
-    one-element float tensors to receive the two scalars (the tail of TrainStep's gradient bucket)."""
+    one-element float tensors to receive the two scalars (the tail of TrainStep's gradient bucket).  mean: see _ce_mean
+    (the weighted entry's form with no weights)."""
     B, Lc, Vx = scores.shape
     dev = scores.device
     row_loss = torch.empty(B * Lc, device=dev, dtype=torch.float32)
@@ -830,6 +844,12 @@ def packed_ce(scores, captions_sorted, decode_len, pad_token, want_grad=False, o
     if want_grad:     # same (possibly padded) row stride as the scores: the kernel takes one leading dimension
         dscores = torch.empty(B, Lc, scores.stride(1), device=dev, dtype=torch.float32)[:, :, :Vx]
         assert scores.stride(0) == Lc * scores.stride(1) and scores.stride(2) == 1
+    if mean is not None:
+        name, tail = _ce_mean("ick_packed_ce_weighted", mean)
+        L.check(getattr(L.load(), name)(_p(scores), scores.stride(1), _p(captions_sorted), _p(decode_len), None, B, Lc, Vx,
+                                        pad_token, _p(row_loss), _p(loss_sum), _p(count), _p(dscores), *tail, _stream()),
+                name)
+        return loss_sum, count, dscores
     L.check(L.load().ick_packed_ce(_p(scores), scores.stride(1), _p(captions_sorted), _p(decode_len), B, Lc, Vx,
                                    pad_token, _p(row_loss), _p(loss_sum), _p(count), _p(dscores), _stream()),
             "ick_packed_ce")
@@ -837,7 +857,7 @@ def packed_ce(scores, captions_sorted, decode_len, pad_token, want_grad=False, o
 
 
 def packed_ce_weighted(scores, captions_sorted, decode_len, weights, pad_token, want_grad=False, out_sum=None,
-                       out_count=None):
+                       out_count=None, mean=None):
     """packed_ce with one fp32 weight per caption (weights (B,) on the device, any sign): loss_sum = sum over captions
     of weight * (sum of its token losses), count = the number of tokens (unweighted), dscores = weight * (softmax -
     onehot).  Weights of 1 give packed_ce's bits exactly (ick_packed_ce_weighted)."""
@@ -852,15 +872,15 @@ def packed_ce_weighted(scores, captions_sorted, decode_len, weights, pad_token, 
     if want_grad:
         dscores = torch.empty(B, Lc, scores.stride(1), device=dev, dtype=torch.float32)[:, :, :Vx]
         assert scores.stride(0) == Lc * scores.stride(1) and scores.stride(2) == 1
-    L.check(L.load().ick_packed_ce_weighted(_p(scores), scores.stride(1), _p(captions_sorted), _p(decode_len),
-                                            _p(weights), B, Lc, Vx, pad_token, _p(row_loss), _p(loss_sum), _p(count),
-                                            _p(dscores), _stream()),
-            "ick_packed_ce_weighted")
+    name, tail = _ce_mean("ick_packed_ce_weighted", mean)
+    L.check(getattr(L.load(), name)(_p(scores), scores.stride(1), _p(captions_sorted), _p(decode_len), _p(weights), B, Lc,
+                                    Vx, pad_token, _p(row_loss), _p(loss_sum), _p(count), _p(dscores), *tail, _stream()),
+            name)
     return loss_sum, count, dscores
 
 
 def packed_ce_smooth(scores, captions, decode_len_or_pack, pad_token, eps, weights=None, want_grad=False, out_sum=None,
-                     out_count=None):
+                     out_count=None, mean=None):
     """The packed cross entropy with label smoothing (ick_packed_ce_smooth; torch's CrossEntropyLoss(label_smoothing=)):
     row loss (1 - eps) * (lse - x[t]) + eps * (lse - mean(x)), gradient w * (softmax - (1 - eps) * onehot - eps / Vx).
     decode_len_or_pack: the int32 decode lengths (scores are the (B, L) rows, as packed_ce / packed_ce_weighted take them)
@@ -884,9 +904,10 @@ def packed_ce_smooth(scores, captions, decode_len_or_pack, pad_token, eps, weigh
     if want_grad:
         dscores = torch.empty(B, Lc, scores.stride(1), device=dev, dtype=torch.float32)[:, :, :Vx]
     rowmap, rows, dl = (pack.rowmap, pack.count, None) if pack is not None else (None, None, decode_len_or_pack)
-    L.check(L.load().ick_packed_ce_smooth(_p(scores), scores.stride(1), _p(captions), _p(rowmap), _p(rows), _p(dl),
-                                          _p(weights), _p(eps), B, Lc, Vx, pad_token, _p(row_loss), _p(loss_sum),
-                                          _p(count), _p(dscores), _stream()), "ick_packed_ce_smooth")
+    name, tail = _ce_mean("ick_packed_ce_smooth", mean)
+    L.check(getattr(L.load(), name)(_p(scores), scores.stride(1), _p(captions), _p(rowmap), _p(rows), _p(dl), _p(weights),
+                                    _p(eps), B, Lc, Vx, pad_token, _p(row_loss), _p(loss_sum), _p(count), _p(dscores),
+                                    *tail, _stream()), name)
     return loss_sum, count, dscores
 
 
@@ -1508,18 +1529,17 @@ def caption_embed_bwd(dx, captions, masks, dword, dee, dfe, V, pad_token, scale,
                                            V, d, pad_token, scale, *_dargs(drop), _stream()), "ick_caption_embed_bwd")
 
 
-def pointer_scores_bwd(dscores, col0, h, ctx, w, ind, dh, dctx, dw, dbias, pack=None):
-    """pack (HeadRows): dscores holds the packed rows of the valid positions (ick_pointer_scores_bwd_packed)."""
+def pointer_scores_bwd(dscores, col0, h, ctx, w, ind, dh, dctx, dw, dbias, pack=None, fused=False):
+    """pack (HeadRows): dscores holds the packed rows of the valid positions (ick_pointer_scores_bwd_packed).  fused: both
+    roles in one launch (ick_pointer_scores_bwd_fused[_packed]), the same bits."""
     B, T, d = h.shape
     Kc = ctx.shape[1]
+    name = "ick_pointer_scores_bwd_fused" if fused else "ick_pointer_scores_bwd"
+    tail = ()
     if pack is not None:
-        L.check(L.load().ick_pointer_scores_bwd_packed(_p(dscores), dscores.stride(-2), col0, _p(h), _p(ctx), _p(w), _p(ind),
-                                                       _p(dh), _p(dctx), _p(dw), _p(dbias), B, T, Kc, d, _p(pack.rowmap),
-                                                       _p(pack.rowstart), _stream()), "ick_pointer_scores_bwd_packed")
-        return
-    L.check(L.load().ick_pointer_scores_bwd(_p(dscores), dscores.stride(-2), col0, _p(h), _p(ctx), _p(w), _p(ind),
-                                            _p(dh), _p(dctx), _p(dw), _p(dbias), B, T, Kc, d, _stream()),
-            "ick_pointer_scores_bwd")
+        name, tail = name + "_packed", (_p(pack.rowmap), _p(pack.rowstart))
+    L.check(getattr(L.load(), name)(_p(dscores), dscores.stride(-2), col0, _p(h), _p(ctx), _p(w), _p(ind), _p(dh),
+                                    _p(dctx), _p(dw), _p(dbias), B, T, Kc, d, *tail, _stream()), name)
 
 
 def entity_encode_bwd(variant, dee, entities, ee, dtype_emb, word_emb=None, dword=None):
@@ -1631,7 +1651,7 @@ DECAY_DECOUPLED, DECAY_COUPLED = 0, 1                                   # ICK_DE
 
 def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=None, clip=5.0, gscale=1.0, beta1=0.9,
                 beta2=0.999, eps=1e-8, step_tensor=None, gscale_den=None, ema=None, ema_decay_word=None, ema_warmup=False,
-                decay_word=None, decay_mask=None, decoupled=True):
+                decay_word=None, decay_mask=None, decoupled=True, bump=None):
     """g = clamp(g * gscale (/ the device scalar gscale_den, if given), +-clip), then Adam's update of p, m, v; step (+ the
     uint32 device counter step_tensor, if given) is Adam's 1-based step count.  Nothing is written while gscale_den is
     given and not > 0.
@@ -1653,7 +1673,10 @@ def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=N
     tensor of at least ceil(p.numel() / 64) granules (bucket.ParamBucket.decay_mask), one per 64 floats from p's start,
     non-zero where the elements decay.  decoupled: True, torch.optim.AdamW's p *= 1 - lr_t * wd ahead of the update;
     False, torch.optim.Adam(weight_decay=)'s wd * p added to the clamped gradient the moments see (g is written back
-    without it)."""
+    without it).
+    bump = (inc, ticket): the launch also advances step_tensor by inc once all of it has read the counter, iff the update
+    ran (counter_add_if's rule on gscale_den) -- ick_adam_step[_derive], the same bits; ticket: a one-element int32 device
+    tensor holding 0 (ops.adam_ticket), the launch's own between calls."""
     if (lr is None) == (words is None):
         raise L.IckError("adam_update needs exactly one of lr (a host float) and words (the optimizer words)")
     if words is None and schedule is not None:
@@ -1672,6 +1695,27 @@ def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=N
                 raise L.IckError("adam_update needs %s as a contiguous %s device tensor of at least %d element(s)"
                                  % (what, str(dtype).replace("torch.", ""), least))
         decay = (_p(decay_word), _p(decay_mask), decay_mask.numel(), DECAY_DECOUPLED if decoupled else DECAY_COUPLED)
+    if bump is not None:
+        inc, ticket = bump
+        if step_tensor is None or ticket.numel() != 1 or ticket.dtype != torch.int32 or not ticket.is_cuda:
+            raise L.IckError("adam_update: bump needs step_tensor and a one-element int32 device ticket")
+        if ema is not None:
+            for what, t, least in (("ema", ema, p.numel()), ("ema_decay_word", ema_decay_word, 1)):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or \
+                        t.numel() < least:
+                    raise L.IckError("adam_update needs %s as a contiguous float32 device tensor of at least %d element(s)"
+                                     % (what, least))
+        if cover is None:
+            name, over = "ick_adam_step", (p.numel(),)
+        else:
+            L.ADAM_DERIVE_BYTES, L.ADAM_DERIVE_FLOATS = cover.nbytes, p.numel()
+            name, over = "ick_adam_step_derive", (_p(cover.items_dev), _p(cover.blocks_dev), cover.n_blocks)
+        rate = (0.0, _p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule)) if words is not None else \
+            (lr, None, L.LrSchedule())
+        L.check(getattr(L.load(), name)(_p(p), _p(g), _p(m), _p(v), _p(ema), *over, gscale, clip, *rate, beta1, beta2, eps,
+                                        step, _p(step_tensor), _p(gscale_den), _p(ema_decay_word), int(bool(ema_warmup)),
+                                        *(decay or (None, None, 0, 0)), int(inc), _p(ticket), _stream()), name)
+        return
     if ema is None and not decay:
         name = _ADAM_ENTRIES[(words is not None) + 2 * (cover is not None)]
         rate = (lr,) if words is None else (_p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule))
@@ -1698,6 +1742,11 @@ def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=N
         over = (_p(cover.items_dev), _p(cover.blocks_dev), cover.n_blocks)
     L.check(getattr(L.load(), name)(_p(p), _p(g), _p(m), _p(v), *avg, *over, gscale, clip, *rate, beta1, beta2, eps, step,
                                     _p(step_tensor), _p(gscale_den), *tail, _stream()), name)
+
+
+def adam_ticket(device):
+    """The ticket word of adam_update(bump=): zero now, and zero again after every launch."""
+    return torch.zeros(1, device=device, dtype=torch.int32)
 
 
 def counter_add(counter, inc=1):

@@ -117,13 +117,17 @@ def classify(name, args):
     if name == "ick_packed_ce_weighted":
         B, Lc, Vx = args[5], args[6], args[7]
         return "weighted packed cross entropy (+ gradient)", 4.0 * B * Lc * Vx * (2 if args[12] else 1), "byte"
-    if name == "ick_packed_ce_packed":
+    if name == "ick_packed_ce_weighted_mean":      # (weights may be absent: the plain entry's form)
+        B, Lc, Vx = args[5], args[6], args[7]
+        return (("weighted " if args[4] else "") + "packed cross entropy (+ gradient)",
+                4.0 * B * Lc * Vx * (2 if args[12] else 1), "byte")
+    if name in ("ick_packed_ce_packed", "ick_packed_ce_packed_mean"):
         # the packed score head: the row count lives on the device, so the launch is priced at all B * L rows -- the achieved
         # rate of this class then overstates what the kernel moves
         B, Lc, Vx = args[6], args[7], args[8]
         return (("weighted " if args[5] else "") + "packed cross entropy (+ gradient)",
                 4.0 * B * Lc * Vx * (2 if args[13] else 1), "byte")
-    if name == "ick_packed_ce_smooth":
+    if name in ("ick_packed_ce_smooth", "ick_packed_ce_smooth_mean"):
         # the same bytes as its plain siblings: one read of the scores, one write of the gradient (packed rows: priced
         # at all B * L, as above)
         B, Lc, Vx = args[8], args[9], args[10]
@@ -149,6 +153,15 @@ def classify(name, args):
         floats = getattr(L, "ADAM_DERIVE_FLOATS", 0)
         return ("clamp + Adam + weight decay" + (" + EMA" if args[4] else "") + " + re-laid-out weight copies",
                 float(getattr(L, "ADAM_DERIVE_BYTES", 0)) + (8.0 * floats if args[4] else 0.0) + floats / 64.0, "byte")
+    if name in ("ick_adam_step", "ick_adam_step_derive"):      # the entry of the same options, by its pointers
+        e, decay = args[4], args[19 if name == "ick_adam_step" else 21]
+        label = "clamp + Adam" + (" + weight decay" if decay else "") + (" + EMA" if e else "")
+        if name == "ick_adam_step":
+            return label, 4.0 * args[5] * (9 if e else 7) + (args[5] / 64.0 if decay else 0.0), "byte"
+        floats = getattr(L, "ADAM_DERIVE_FLOATS", 0)
+        return (label + " + re-laid-out weight copies",
+                float(getattr(L, "ADAM_DERIVE_BYTES", 0)) + (8.0 * floats if e else 0.0) + (floats / 64.0 if decay else 0.0),
+                "byte")
     if name == "ick_grad_sqnorm":
         # one read of the gradient bucket (the partials and the words are a few KiB)
         return "gradient norm (global-norm clip)", 4.0 * args[1], "byte"
@@ -167,6 +180,8 @@ def classify(name, args):
         return ("fused decode step (3 kernels / layer + head + vocabulary)", first if args[2] == 1 else kv + w - first, "byte")
     if name == "ick_decode_select_greedy":
         return "greedy selection + next-token embedding", None, None
+    if name in ("ick_pointer_scores_bwd_fused", "ick_pointer_scores_bwd_fused_packed"):
+        return "pointer scores bwd" + (" packed" if name.endswith("_packed") else ""), None, None
     return name[4:].replace("_", " "), None, None
 
 

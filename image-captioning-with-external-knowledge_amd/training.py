@@ -681,10 +681,10 @@ def _backward_phases(dec, tape, dscores, grads, want_image_grad=False, image_gra
         return _g(grads, param)
 
     ops.pointer_scores_bwd(dscores, V, h, ee, _p(dec.fc_entity.weight), None, dh, dee, gbuf(dec.fc_entity.weight),
-                           gbuf(dec.fc_entity.bias), pack=pack)
+                           gbuf(dec.fc_entity.bias), pack=pack, fused=True)
     if dec.has_facts:
         ops.pointer_scores_bwd(dscores, V + K, h, fe, _p(dec.fc_fact.weight), m["eib"], dh, dfe,
-                               gbuf(dec.fc_fact.weight), gbuf(dec.fc_fact.bias), pack=pack)
+                               gbuf(dec.fc_fact.weight), gbuf(dec.fc_fact.bias), pack=pack, fused=True)
     # ---- decoder stack
     layers = list(dec.transformer_decoder.layers)
     nseg = 2 * len(layers)
@@ -1109,6 +1109,10 @@ class TrainStep:
             eg = eb.grad_views(self.enc_g)
             self._c1_gw, self._c1_gb = eg[id(c1.weight)].view(c1.weight.shape[0], -1), eg[id(c1.bias)]
         self.counter = torch.zeros(1, device=dev, dtype=torch.int32)   # steps done (read as uint32 by the kernels)
+        # this rank's token-mean loss, written by the loss's reduction launch: __call__ returns it at world
+        # size 1 -- the step's own buffer, written again by the next step (clone() to keep a value)
+        self._mean = torch.zeros(1, device=dev, dtype=torch.float32)
+        self._adam_ticket = ops.adam_ticket(dev)      # the deferred update's (it runs on the side stream: a word of its own)
         self.one = torch.ones(1, device=dev, dtype=torch.float32)
         if self.max_grad_norm is not None or self.lr_schedule is not None:
             self._make_words()
@@ -1254,7 +1258,8 @@ class TrainStep:
         those two floats); with per-caption weights (SelfCriticalStep's advantages) the weighted form.  pack: the scores
         are the packed rows of the valid positions, and so are the score gradients.  With label smoothing on, the
         smoothed entry in the same layout."""
-        tail = dict(want_grad=True, out_sum=self.flat_g[self._t:self._t + 1], out_count=self.flat_g[self._t + 1:])
+        tail = dict(want_grad=True, out_sum=self.flat_g[self._t:self._t + 1], out_count=self.flat_g[self._t + 1:],
+                    mean=self._mean)
         pad = self.dec.word_map["<pad>"]
         if self.label_smoothing != 0.0:
             return ops.packed_ce_smooth(scores, captions, pack if pack is not None else decode_len, pad, self._eps_word,
@@ -1433,8 +1438,7 @@ class TrainStep:
         """The previous step's clamp + Adam and step counter, at the head of this step's graph.  Both are no-ops while the
         token count in the gradient bucket's tail is zero: the very first step, and the step after a flush().  (A trained
         conv1's update has run on the main stream by now: forward_with_tape's pre_main.)"""
-        self._adam()
-        ops.counter_add_if(self.counter, 1, self.flat_g[self._t + 1:])
+        self._adam(bump=(1, self._adam_ticket))       # (the counter moves inside the launch, by counter_add_if's rule)
 
     def flush(self):
         """Apply a pending (lazy_update) optimizer update now; afterwards the parameters, moments, step counter and weight
@@ -1451,7 +1455,7 @@ class TrainStep:
         if self.derived is not None:
             self.derived.mark_current()
 
-    def _adam(self):
+    def _adam(self, bump=None):
         # divide by the global token count (device-resident), clamp, Adam with the device step counter -- and, with
         # self.derived, the re-laid-out copies of the updated weights in the same pass (the cover runs over the whole
         # bucket).  With the optimizer words the rate comes from them and the schedule, else from self.lr.
@@ -1468,7 +1472,7 @@ class TrainStep:
         ops.adam_update(self.flat_p, self.flat_g, self.flat_m, self.flat_v, 1, cover=self.derived,
                         clip=self.clip, gscale=1.0, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
                         step_tensor=self.counter, gscale_den=den, **rate, **self._ema_kwargs(self.flat_e),
-                        **self._decay_kwargs(self._wd_word, self._wd_mask))
+                        **self._decay_kwargs(self._wd_word, self._wd_mask), bump=bump)
 
     # ---- the same step in two halves (several ranks: the early half's all-reduce overlaps the late half) ----
     def _part_a1(self, *inputs):
@@ -1830,7 +1834,9 @@ class TrainStep:
 
     def __call__(self, captions, encoder_out, caption_masks, caption_lengths, entities, facts=None,
                  caption_weights=None, image_index=None):
-        """One training step; returns the token-mean loss (device scalar).  caption_weights (R,) fp32: per-caption
+        """One training step; returns the token-mean loss (device scalar; at world size 1 the step's own one-element buffer,
+        which the next step writes again: .item() or .clone() it to keep a value; 0 for a batch without a token).
+        caption_weights (R,) fp32: per-caption
         weights of the loss (the weighted packed cross entropy; SelfCriticalStep's advantages), still divided by the
         token count.  image_index (R,) int: caption row r reads row image_index[r] of a token-major encoder_out with
         fewer rows (several captions of one image share its encoder output); not with a 4-D feature map.  Both are
@@ -1967,5 +1973,8 @@ class TrainStep:
         dec.invalidate_caches()   # the update went around torch's version counters
         if self.derived is not None:
             self.derived.mark_current()
-        # token-mean loss of the global batch, still on the device
+        # token-mean loss of the global batch, still on the device: at world size 1 the loss launch has written it (0 for a
+        # batch without a token); several ranks divide the all-reduced sums
+        if dp.world_size(self.pg) == 1:
+            return self._mean
         return self.flat_g[self._t:self._t + 1] / self.flat_g[self._t + 1:]

@@ -856,6 +856,24 @@ int ick_adam_decay_derive(float* p, float* g, float* m, float* v, float* e, cons
                           const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
                           const float* decay, const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form,
                           void* stream);
+/* The general entries, which can also advance the step counter in the optimizer's own launch.  Every
+ * option goes by its pointer: e == NULL keeps no average, words == NULL takes the host rate lr, decay == NULL decays
+ * nothing; each combination runs the kernel of the entry above with the same options and leaves the same bits.
+ * ticket != NULL (ONE uint32 in device memory, 0 before the first launch; the launch leaves it 0 again): once every
+ * workgroup has read step_ptr[0], the last one to finish does step_ptr[0] += bump_inc -- iff the update ran, that is
+ * gscale_den == NULL or gscale_den[0] > 0, ick_counter_add_if's rule.  step_ptr is then required.  ticket == NULL: the
+ * counter is only read, as by the entries above. */
+int ick_adam_step(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip, float lr,
+                  float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
+                  uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
+                  const float* decay, const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form,
+                  uint32_t bump_inc, uint32_t* ticket, void* stream);
+int ick_adam_step_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
+                         const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr, float* words,
+                         ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, uint32_t* step_ptr,
+                         const float* gscale_den, const float* ema_decay, int32_t ema_warmup, const float* decay,
+                         const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form, uint32_t bump_inc,
+                         uint32_t* ticket, void* stream);
 /* The weight and bias gradient of Encoder.conv1 (1x1 convolution) straight from the NCHW feature map:
  *     dw[o, c] = sum over b, p of d_img[b, p, o] * feats[b, c, p],     db[o] = sum over b, p of d_img[b, p, o].
  * d_img (B, P, d): the gradient of the image memory rows; feats (B, C, P): the feature map as it lies; dw (d, C): conv1's
@@ -933,6 +951,34 @@ int ick_pointer_scores_bwd_packed(const float* ds, int64_t ds_ld, int32_t col0, 
  * product modes; the pre-split kernel gathers in ick_presplit_weights instead). */
 int ick_gather_rows(const float* src, int64_t src_rs, const int32_t* rowmap, const int32_t* count, float* dst,
                     int64_t dst_rs, int32_t max_rows, int32_t d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The lean step's entries.  Every output has the bits of the entry it stands in for.
+ *
+ * ick_packed_ce_weighted_mean (weights may be NULL: ick_packed_ce), ick_packed_ce_packed_mean,
+ * ick_packed_ce_smooth_mean: the reduction launch also writes mean[0] = loss_sum / count_out (0 when count_out is 0),
+ *   so that a training step needs no launch of its own for the division.  NULL mean: ICK_EINVAL.
+ * ick_pointer_scores_bwd_fused[_packed]: the dh and the dctx / dw / dbias workgroups of ick_pointer_scores_bwd[_packed]
+ *   as ranges of ONE grid instead of two launches in series. */
+int ick_packed_ce_weighted_mean(const float* scores, int64_t ld, const int64_t* captions, const int32_t* decode_len,
+                                const float* weights, int32_t B, int32_t L, int32_t Vx, int32_t pad_token,
+                                float* row_loss, float* loss_sum, float* count_out, float* dscores, float* mean,
+                                void* stream);
+int ick_packed_ce_packed_mean(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                              const int32_t* count, const float* weights, int32_t B, int32_t L, int32_t Vx,
+                              int32_t pad_token, float* row_loss, float* loss_sum, float* count_out, float* dscores,
+                              float* mean, void* stream);
+int ick_packed_ce_smooth_mean(const float* scores, int64_t ld, const int64_t* captions, const int32_t* rowmap,
+                              const int32_t* count, const int32_t* decode_len, const float* weights, const float* eps,
+                              int32_t B, int32_t L, int32_t Vx, int32_t pad_token, float* row_loss, float* loss_sum,
+                              float* count_out, float* dscores, float* mean, void* stream);
+int ick_pointer_scores_bwd_fused(const float* ds, int64_t ds_ld, int32_t col0, const float* h, const float* ctx,
+                                 const float* w, const float* ind, float* dh, float* dctx, float* dw, float* dbias,
+                                 int32_t B, int32_t T, int32_t Kc, int32_t d, void* stream);
+int ick_pointer_scores_bwd_fused_packed(const float* ds, int64_t ds_ld, int32_t col0, const float* h, const float* ctx,
+                                        const float* w, const float* ind, float* dh, float* dctx, float* dw,
+                                        float* dbias, int32_t B, int32_t T, int32_t Kc, int32_t d, const int32_t* rowmap,
+                                        const int32_t* rowstart, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Caption scoring: how likely a GIVEN caption is, from the packed score rows of the head above.
