@@ -9,18 +9,18 @@
 //   g = clamp(g * gscale [/ *gscale_den], -clip, clip);  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // (default betas / eps, no amsgrad.)  The update is written once: adam_hyper() is the prologue, adam1() the arithmetic of
-// one element.  kDecay (ick_adam_decay[_derive]): weight decay on the elements whose 64-float granule of
+// one element.  kDecay (decay != NULL): weight decay on the elements whose 64-float granule of
 // the bucket has its byte of the caller's mask set -- decoupled (torch.optim.AdamW), p = p * (1 - lr_t * wd) ahead of
 // the unchanged update, or coupled (torch.optim.Adam(weight_decay=), L2), wd * p added to the clamped gradient that the
 // moments and the update see, while the gradient written back stays without the term; wd is read from a device word.
-// kDecay = false is the code without it.  kEma (ick_adam_ema[_derive]): the lane that holds the new p
+// kDecay = false is the code without it.  kEma (e != NULL): the lane that holds the new p
 // also keeps an exponential moving average of it in a fourth array, e += (1 - d_t) (p - e) (ema1()), two more 16-byte
 // streams in the same pass; kEma = false is the code without it.  Three kernels address the bucket differently around
 // them:
 //   adam_clamp_kernel       one float per lane and trip: tails, short and unaligned buckets;
 //   adam_clamp_vec4_kernel  one float4 per lane and trip, seven 16-byte streams: the aligned bulk of a flat bucket;
 //   adam_derive_kernel      one workgroup = one block of the caller's cover of the bucket (include/ick_amd.h,
-//                           ick_adam_clamp_derive):
+//                           ick_adam_step_derive):
 //     flat run   <= 1024 float4, the seven 16-byte streams of adam_clamp_vec4_kernel (+ an optional plain copy);
 //     tile       64 rows x 64 columns of a 2-D parameter (row segments of 256 contiguous bytes): updated in registers,
 //                written back, the new values staged in LDS and read out once per image in that image's own order, so
@@ -89,7 +89,7 @@ __device__ __forceinline__ bool decay_on(const AdamDecay& dec, int64_t at) {
 
 // The prologue of every Adam kernel.  false: no token contributed to the (global) batch, which then has no mean loss --
 // the kernel leaves parameters, moments, images and the rate word alone instead of spreading 0 * inf = NaN over every
-// weight.  kOpt (ick_adam_opt[_derive]): the step's rate comes from the base rate word and the schedule
+// weight.  kOpt (words != NULL): the step's rate comes from the base rate word and the schedule
 // instead of the literal, h.coef is the global-norm clip's coefficient, and workgroup 0 leaves the rate it used in
 // words[4].  kEma: h.w = 1 - d_t, the weight of the new parameter in the moving average, with d_t = *decay or, with the
 // warmup flag, min(*decay, (1 + t) / (10 + t)) on the step t of the bias correction.
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(256) void adam_derive_kernel(float* __restrict__ p,
 
 using namespace ick;
 
-// What every entry asks of its arguments (count: the floats of a flat bucket, the blocks of a cover); al16: whether all
+// What both entries ask of their arguments (count: the floats of a flat bucket, the blocks of a cover); al16: whether all
 // the arrays lie on 16 bytes, which the float4 kernels need.  kEma: the moving average is one more array, and its decay
 // word must be there.  kDecay: the decay word, the granule mask with at least one granule, a known form.
 template <bool kEma, bool kDecay>
@@ -425,17 +425,14 @@ static int adam_args(const float* p, const float* g, const float* m, const float
     return ICK_OK;
 }
 
-// ick_adam_clamp, ick_adam_opt, ick_adam_ema and ick_adam_decay: the float4 kernel over the aligned bulk, the scalar kernel
-// over the rest (which tells the mask where it starts: dec.base)
-template <bool kOpt, bool kEma, bool kDecay = false>
+// ick_adam_step: the float4 kernel over the aligned bulk, the scalar kernel over the rest (which tells the mask where it
+// starts: dec.base)
+template <bool kOpt, bool kEma, bool kDecay>
 static int launch_adam(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr, float* words,
                        ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                       const float* gscale_den, AdamEma ema, void* stream, AdamDecay dec = AdamDecay{},
-                       AdamBump bump = AdamBump{}) {
+                       const float* gscale_den, AdamEma ema, void* stream, AdamDecay dec, AdamBump bump) {
     bool al16;
     if (int rc = adam_args<kEma, kDecay>(p, g, m, v, n, step, step_ptr, ema, dec, al16)) return rc;
-    if (bump.ticket) ICK_CHECK_ARG(step_ptr != nullptr);
-    bump.counter = const_cast<uint32_t*>(step_ptr);
     if (kDecay) ICK_CHECK_ARG(dec.granules >= ceil_div(n, (int64_t)1 << kGranuleShift));
     if (kEma && (reinterpret_cast<uintptr_t>(ema.e) & 3)) return ICK_EALIGN;
     int64_t done = 0;
@@ -457,181 +454,55 @@ static int launch_adam(float* p, float* g, float* m, float* v, int64_t n, float 
     ICK_LAUNCH_RET();
 }
 
-// (the cover lies on the device, so the granule count cannot be held against it here: the kernel treats a granule beyond
-// the table as not selected)
-template <bool kOpt, bool kEma, bool kDecay = false>
+// ick_adam_step_derive (the cover lies on the device, so the granule count cannot be held against it here: the kernel
+// treats a granule beyond the table as not selected)
+template <bool kOpt, bool kEma, bool kDecay>
 static int launch_adam_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
                               const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
                               float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                              const uint32_t* step_ptr, const float* gscale_den, AdamEma ema, void* stream,
-                              AdamDecay dec = AdamDecay{}, AdamBump bump = AdamBump{}) {
+                              const uint32_t* step_ptr, const float* gscale_den, AdamEma ema, void* stream, AdamDecay dec,
+                              AdamBump bump) {
     bool al16;
     if (int rc = adam_args<kEma, kDecay>(p, g, m, v, blocks ? n_blocks : 0, step, step_ptr, ema, dec, al16)) return rc;
     if (!al16) return ICK_EALIGN;
-    if (bump.ticket) ICK_CHECK_ARG(step_ptr != nullptr);
-    bump.counter = const_cast<uint32_t*>(step_ptr);
     hipLaunchKernelGGL((adam_derive_kernel<kOpt, kEma, kDecay>), dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                        items, blocks, gscale, clip, lr, beta1, beta2, eps, step, step_ptr, gscale_den, words, sched, ema,
                        dec, bump);
     ICK_LAUNCH_RET();
 }
 
-extern "C" int ick_adam_clamp(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr,
-                              float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                              const float* gscale_den, void* stream) {
-    return launch_adam<false, false>(p, g, m, v, n, gscale, clip, lr, nullptr, ick_lr_schedule{}, beta1, beta2, eps, step,
-                                     step_ptr, gscale_den, AdamEma{}, stream);
-}
-
-extern "C" int ick_adam_opt(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float* words,
-                            ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                            const uint32_t* step_ptr, const float* gscale_den, void* stream) {
-    ICK_CHECK_ARG(words != nullptr && lr_schedule_ok(sched));
-    return launch_adam<true, false>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step, step_ptr,
-                                    gscale_den, AdamEma{}, stream);
-}
-
-extern "C" int ick_adam_clamp_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
-                                     const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
-                                     float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                                     const float* gscale_den, void* stream) {
-    return launch_adam_derive<false, false>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr, nullptr,
-                                            ick_lr_schedule{}, beta1, beta2, eps, step, step_ptr, gscale_den, AdamEma{},
-                                            stream);
-}
-
-extern "C" int ick_adam_opt_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
-                                   const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float* words,
-                                   ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                                   const uint32_t* step_ptr, const float* gscale_den, void* stream) {
-    ICK_CHECK_ARG(words != nullptr && lr_schedule_ok(sched));
-    return launch_adam_derive<true, false>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words, sched, beta1,
-                                           beta2, eps, step, step_ptr, gscale_den, AdamEma{}, stream);
-}
-
-// The entries with the moving average: words == NULL takes the plain instantiation and the host rate lr, else the
-// optimizer words' one (lr is then not read).
-extern "C" int ick_adam_ema(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip, float lr,
-                            float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                            const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
-                            void* stream) {
-    const AdamEma ema{e, ema_decay, ema_warmup != 0};
-    if (!words)
-        return launch_adam<false, true>(p, g, m, v, n, gscale, clip, lr, nullptr, ick_lr_schedule{}, beta1, beta2, eps,
-                                        step, step_ptr, gscale_den, ema, stream);
-    ICK_CHECK_ARG(lr_schedule_ok(sched));
-    return launch_adam<true, true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step, step_ptr,
-                                   gscale_den, ema, stream);
-}
-
-extern "C" int ick_adam_ema_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
-                                   const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
-                                   float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                                   const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay,
-                                   int32_t ema_warmup, void* stream) {
-    const AdamEma ema{e, ema_decay, ema_warmup != 0};
-    if (!words)
-        return launch_adam_derive<false, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr, nullptr,
-                                               ick_lr_schedule{}, beta1, beta2, eps, step, step_ptr, gscale_den, ema,
-                                               stream);
-    ICK_CHECK_ARG(lr_schedule_ok(sched));
-    return launch_adam_derive<true, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words, sched, beta1,
-                                          beta2, eps, step, step_ptr, gscale_den, ema, stream);
-}
-
-
-// The entries with weight decay: words == NULL takes the host rate lr, e == NULL keeps no average -- the
-// four <kOpt, kEma, true> instantiations of each kernel.
-template <typename Plain, typename Opt>
-static int with_rate(const float* words, const ick_lr_schedule& sched, Plain plain, Opt opt) {
-    if (!words) return plain();
-    ICK_CHECK_ARG(lr_schedule_ok(sched));
-    return opt();
-}
-
-extern "C" int ick_adam_decay(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip,
-                              float lr, float* words, ick_lr_schedule sched, float beta1, float beta2, float eps,
-                              int32_t step, const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay,
-                              int32_t ema_warmup, const float* decay, const uint8_t* decay_mask, int64_t n_granules,
-                              int32_t decay_form, void* stream) {
-    const AdamEma ema{e, ema_decay, ema_warmup != 0};
-    const AdamDecay dec{decay, decay_mask, n_granules, 0, decay_form};
-    const ick_lr_schedule none{};
-    if (!e)
-        return with_rate(
-            words, sched,
-            [&] { return launch_adam<false, false, true>(p, g, m, v, n, gscale, clip, lr, nullptr, none, beta1, beta2, eps,
-                                                         step, step_ptr, gscale_den, AdamEma{}, stream, dec); },
-            [&] { return launch_adam<true, false, true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps,
-                                                        step, step_ptr, gscale_den, AdamEma{}, stream, dec); });
-    return with_rate(
-        words, sched,
-        [&] { return launch_adam<false, true, true>(p, g, m, v, n, gscale, clip, lr, nullptr, none, beta1, beta2, eps, step,
-                                                    step_ptr, gscale_den, ema, stream, dec); },
-        [&] { return launch_adam<true, true, true>(p, g, m, v, n, gscale, clip, 0.f, words, sched, beta1, beta2, eps, step,
-                                                   step_ptr, gscale_den, ema, stream, dec); });
-}
-
-extern "C" int ick_adam_decay_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
-                                     const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
-                                     float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                                     const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay,
-                                     int32_t ema_warmup, const float* decay, const uint8_t* decay_mask,
-                                     int64_t n_granules, int32_t decay_form, void* stream) {
-    const AdamEma ema{e, ema_decay, ema_warmup != 0};
-    const AdamDecay dec{decay, decay_mask, n_granules, 0, decay_form};
-    const ick_lr_schedule none{};
-    if (!e)
-        return with_rate(
-            words, sched,
-            [&] { return launch_adam_derive<false, false, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr,
-                                                                nullptr, none, beta1, beta2, eps, step, step_ptr,
-                                                                gscale_den, AdamEma{}, stream, dec); },
-            [&] { return launch_adam_derive<true, false, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words,
-                                                               sched, beta1, beta2, eps, step, step_ptr, gscale_den,
-                                                               AdamEma{}, stream, dec); });
-    return with_rate(
-        words, sched,
-        [&] { return launch_adam_derive<false, true, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, lr, nullptr,
-                                                           none, beta1, beta2, eps, step, step_ptr, gscale_den, ema, stream,
-                                                           dec); },
-        [&] { return launch_adam_derive<true, true, true>(p, g, m, v, items, blocks, n_blocks, gscale, clip, 0.f, words,
-                                                          sched, beta1, beta2, eps, step, step_ptr, gscale_den, ema, stream,
-                                                          dec); });
-}
-
-// The general entries: every option by its pointer -- e == NULL keeps no average, words == NULL takes the
-// host rate lr, decay == NULL decays nothing -- on the instantiation the entry above of the same options launches, and
-// the step counter's advance in the same launch: ticket != NULL (one uint32 in device memory, 0 before the first launch
-// and after every one) makes step_ptr[0] += bump_inc once every workgroup has read it, iff the update ran (gscale_den ==
-// NULL or gscale_den[0] > 0): ick_counter_add_if's rule.  ticket == NULL: the counter is only read.
+// The optimizer's two entries (include/ick_amd.h): every option by its pointer -- words == NULL takes the host rate lr
+// (kOpt off), e == NULL keeps no average (kEma off), decay == NULL decays nothing (kDecay off) -- picks one of the eight
+// <kOpt, kEma, kDecay> instantiations; ticket != NULL makes the launch advance the step counter as well (AdamBump).  An
+// option's other arguments without the pointer that selects it are refused here, the rest of an option's arguments by
+// adam_args and the launchers, all of it before any launch.
 template <bool kDerive, typename... Over>
 static int adam_step(float* p, float* g, float* m, float* v, float* e, float gscale, float clip, float lr, float* words,
                      ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, uint32_t* step_ptr,
                      const float* gscale_den, const float* ema_decay, int32_t ema_warmup, const float* decay,
                      const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form, uint32_t bump_inc,
                      uint32_t* ticket, void* stream, Over... over) {
-    const AdamEma ema = e ? AdamEma{e, ema_decay, ema_warmup != 0} : AdamEma{};
-    const AdamDecay dec{decay, decay_mask, n_granules, 0, decay_form};
-    const AdamBump bump{nullptr, bump_inc, ticket};
     if (words) ICK_CHECK_ARG(lr_schedule_ok(sched));
+    if (!e) ICK_CHECK_ARG(ema_decay == nullptr && ema_warmup == 0);
+    ICK_CHECK_ARG((decay == nullptr) == (decay_mask == nullptr));
+    if (ticket) ICK_CHECK_ARG(step_ptr != nullptr);
     if (!words) sched = ick_lr_schedule{};
+    const AdamEma ema = e ? AdamEma{e, ema_decay, ema_warmup != 0} : AdamEma{};
+    const AdamDecay dec = decay ? AdamDecay{decay, decay_mask, n_granules, 0, decay_form} : AdamDecay{};
+    const AdamBump bump{step_ptr, bump_inc, ticket};
     auto go = [&](auto opt, auto avg, auto wd) {
         constexpr bool kOpt = decltype(opt)::value, kEma = decltype(avg)::value, kDecay = decltype(wd)::value;
         const float rate = kOpt ? 0.f : lr;
         if constexpr (kDerive)
             return launch_adam_derive<kOpt, kEma, kDecay>(p, g, m, v, over..., gscale, clip, rate, words, sched, beta1, beta2,
-                                                          eps, step, step_ptr, gscale_den, ema, stream,
-                                                          kDecay ? dec : AdamDecay{}, bump);
+                                                          eps, step, step_ptr, gscale_den, ema, stream, dec, bump);
         else
             return launch_adam<kOpt, kEma, kDecay>(p, g, m, v, over..., gscale, clip, rate, words, sched, beta1, beta2, eps,
-                                                   step, step_ptr, gscale_den, ema, stream, kDecay ? dec : AdamDecay{},
-                                                   bump);
+                                                   step, step_ptr, gscale_den, ema, stream, dec, bump);
     };
     using T = std::true_type;
     using F = std::false_type;
-    const int which = (words ? 1 : 0) | (e ? 2 : 0) | (decay ? 4 : 0);
-    switch (which) {
+    switch ((words ? 1 : 0) | (e ? 2 : 0) | (decay ? 4 : 0)) {
         case 0: return go(F{}, F{}, F{});
         case 1: return go(T{}, F{}, F{});
         case 2: return go(F{}, T{}, F{});

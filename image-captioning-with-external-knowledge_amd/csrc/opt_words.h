@@ -1,5 +1,5 @@
-// The optimizer words and the learning-rate schedule of ick_adam_opt / ick_adam_opt_derive (include/ick_amd.h, DESIGN.md
-// 3.1h): what the three Adam kernels share when they are instantiated with kOpt.
+// The optimizer words and the learning-rate schedule of ick_adam_step / ick_adam_step_derive (include/ick_amd.h, DESIGN.md
+// 3.1h): what the three Adam kernels share when they are instantiated with kOpt, which words != NULL selects.
 #pragma once
 #include "common.h"
 
@@ -19,7 +19,7 @@ inline bool lr_schedule_ok(const ick_lr_schedule& s) {
 }
 
 // The rate of the 1-based step t (an integer held in a float, as the Adam kernels' bias correction has it).  A constant
-// schedule without warmup returns `base` itself, so that entry's step size is ick_adam_clamp's float.
+// schedule without warmup returns `base` itself, so the step size is then the float words == NULL gets from lr.
 __device__ __forceinline__ float lr_schedule(float base, const ick_lr_schedule s, float t) {
     const float W = (float)s.warmup;
     if (s.kind == ICK_LR_INVERSE_SQRT) return base * fminf(t / W, sqrtf(W / t));

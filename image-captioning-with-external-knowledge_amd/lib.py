@@ -93,11 +93,11 @@ class AdamItem(C.Structure):      # ick_adam_item: a 2-D block of the bucket + t
                 ("copy", vp), ("ps", vp), ("ps_t", vp), ("tr", vp), ("copy_ld", i64), ("tr_ld", i64)]
 
 
-class AdamBlock(C.Structure):     # ick_adam_block: the work of one workgroup of ick_adam_clamp_derive
+class AdamBlock(C.Structure):     # ick_adam_block: the work of one workgroup of ick_adam_step_derive
     _fields_ = [("item", i32), ("tn", i32), ("tk", i32), ("cnt4", i32), ("off4", i64), ("copy", vp)]
 
 
-class LrSchedule(C.Structure):    # ick_lr_schedule: passed BY VALUE to ick_adam_opt[_derive]
+class LrSchedule(C.Structure):    # ick_lr_schedule: passed BY VALUE to ick_adam_step[_derive]
     _fields_ = [("kind", i32), ("warmup", i32), ("total", i32), ("min_ratio", f32)]
 
 
@@ -242,19 +242,8 @@ SIGNATURES = {
     "ick_entity_encode_bwd": [i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp],
     "ick_fact_encode_bwd": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "ick_context_gate_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-    "ick_adam_clamp": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp],
-    "ick_adam_clamp_derive": [vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp],
     "ick_grad_sqnorm_plan": [i64, C.POINTER(i32)],
     "ick_grad_sqnorm": [vp, i64, f32, vp, vp, i64, vp, vp],
-    "ick_adam_opt": [vp, vp, vp, vp, i64, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp],
-    "ick_adam_opt_derive": [vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp],
-    "ick_adam_ema": [vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp, i32, vp],
-    "ick_adam_ema_derive": [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp,
-                            i32, vp],
-    "ick_adam_decay": [vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp, i32, vp, vp,
-                       i64, i32, vp],
-    "ick_adam_decay_derive": [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp,
-                              i32, vp, vp, i64, i32, vp],
     "ick_adam_step": [vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp, i32, vp, vp,
                       i64, i32, u32, vp, vp],
     "ick_adam_step_derive": [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, LrSchedule, f32, f32, f32, i32, vp, vp, vp,

@@ -1643,9 +1643,6 @@ def conv1_wgrad(d_img, feats, dw, db, scratch=None):
     return dw, db
 
 
-_ADAM_ENTRIES = ("ick_adam_clamp", "ick_adam_opt", "ick_adam_clamp_derive", "ick_adam_opt_derive")
-_ADAM_EMA_ENTRIES = ("ick_adam_ema", "ick_adam_ema_derive")      # (both rates: words == NULL selects the host float)
-_ADAM_DECAY_ENTRIES = ("ick_adam_decay", "ick_adam_decay_derive")      # (... and e == NULL selects no average)
 DECAY_DECOUPLED, DECAY_COUPLED = 0, 1                                   # ICK_DECAY_*
 
 
@@ -1656,26 +1653,26 @@ def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=N
     uint32 device counter step_tensor, if given) is Adam's 1-based step count.  Nothing is written while gscale_den is
     given and not > 0.
     The rate is exactly one of
-      lr     a host float (ick_adam_clamp[_derive]);
-      words  the optimizer words ON THE DEVICE -- a host scalar is refused (ick_adam_opt[_derive]): the base rate in
+      lr     a host float (the entry's words == NULL);
+      words  the optimizer words ON THE DEVICE -- a host scalar is refused (the kOpt instantiation): the base rate in
              words[0] shaped by `schedule` (lr_schedule_struct) on the step count, the gradient multiplied by words[3] (the
              global-norm clip's coefficient) between the scale and the clamp; words[4] receives the rate used.
     cover: None for the p.numel() floats of a flat bucket; otherwise the owner of a cover of the WHOLE bucket
     (weights.DerivedWeights: items_dev / blocks_dev, device arrays of ick_adam_item / ick_adam_block, n_blocks, and nbytes,
     the launch's algorithmic bytes for profiling.py), read at call time: the same pass then also writes the re-laid-out
-    copies of the updated weights (the *_derive entries).
+    copies of the updated weights (ick_adam_step_derive instead of ick_adam_step).
     ema: None, or the exponential moving average of p, a float32 device tensor laid out like p, updated in the same pass
-    (ick_adam_ema[_derive]): e += (1 - d) * (p_new - e) with the decay d read from ema_decay_word, a one-float tensor ON THE
+    (kEma, e != NULL): e += (1 - d) * (p_new - e) with the decay d read from ema_decay_word, a one-float tensor ON THE
     DEVICE (a host scalar is refused: it would be baked into a captured launch); ema_warmup: d = min(d, (1 + t) / (10 + t))
     on the step count t.  p, g, m, v get the bits they get without ema.
-    decay_word + decay_mask (both or neither): weight decay in the same pass (ick_adam_decay[_derive]).  decay_word: wd, a
+    decay_word + decay_mask (both or neither): weight decay in the same pass (kDecay, decay != NULL).  decay_word: wd, a
     one-float tensor ON THE DEVICE (a host scalar is refused for the reason the EMA word is); decay_mask: a uint8 device
     tensor of at least ceil(p.numel() / 64) granules (bucket.ParamBucket.decay_mask), one per 64 floats from p's start,
     non-zero where the elements decay.  decoupled: True, torch.optim.AdamW's p *= 1 - lr_t * wd ahead of the update;
     False, torch.optim.Adam(weight_decay=)'s wd * p added to the clamped gradient the moments see (g is written back
     without it).
     bump = (inc, ticket): the launch also advances step_tensor by inc once all of it has read the counter, iff the update
-    ran (counter_add_if's rule on gscale_den) -- ick_adam_step[_derive], the same bits; ticket: a one-element int32 device
+    ran (counter_add_if's rule on gscale_den) -- ticket != NULL, the same bits; ticket: a one-element int32 device
     tensor holding 0 (ops.adam_ticket), the launch's own between calls."""
     if (lr is None) == (words is None):
         raise L.IckError("adam_update needs exactly one of lr (a host float) and words (the optimizer words)")
@@ -1685,63 +1682,36 @@ def adam_update(p, g, m, v, step, lr=None, *, words=None, schedule=None, cover=N
         raise L.IckError("adam_update: ema_decay_word / ema_warmup shape a moving average; give ema= as well")
     if (decay_word is None) != (decay_mask is None):
         raise L.IckError("adam_update: weight decay needs both decay_word (wd) and decay_mask (which granules decay)")
-    decay = ()
+    checks = []                                                          # (name, tensor, dtype, least elements)
     if decay_word is not None:
-        granules = (p.numel() + 63) // 64
-        for what, t, dtype, least in (("decay_word", decay_word, torch.float32, 1),
-                                      ("decay_mask", decay_mask, torch.uint8, granules)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or \
-                    t.numel() < least:
-                raise L.IckError("adam_update needs %s as a contiguous %s device tensor of at least %d element(s)"
-                                 % (what, str(dtype).replace("torch.", ""), least))
-        decay = (_p(decay_word), _p(decay_mask), decay_mask.numel(), DECAY_DECOUPLED if decoupled else DECAY_COUPLED)
-    if bump is not None:
-        inc, ticket = bump
-        if step_tensor is None or ticket.numel() != 1 or ticket.dtype != torch.int32 or not ticket.is_cuda:
-            raise L.IckError("adam_update: bump needs step_tensor and a one-element int32 device ticket")
-        if ema is not None:
-            for what, t, least in (("ema", ema, p.numel()), ("ema_decay_word", ema_decay_word, 1)):
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or \
-                        t.numel() < least:
-                    raise L.IckError("adam_update needs %s as a contiguous float32 device tensor of at least %d element(s)"
-                                     % (what, least))
-        if cover is None:
-            name, over = "ick_adam_step", (p.numel(),)
-        else:
-            L.ADAM_DERIVE_BYTES, L.ADAM_DERIVE_FLOATS = cover.nbytes, p.numel()
-            name, over = "ick_adam_step_derive", (_p(cover.items_dev), _p(cover.blocks_dev), cover.n_blocks)
-        rate = (0.0, _p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule)) if words is not None else \
-            (lr, None, L.LrSchedule())
-        L.check(getattr(L.load(), name)(_p(p), _p(g), _p(m), _p(v), _p(ema), *over, gscale, clip, *rate, beta1, beta2, eps,
-                                        step, _p(step_tensor), _p(gscale_den), _p(ema_decay_word), int(bool(ema_warmup)),
-                                        *(decay or (None, None, 0, 0)), int(inc), _p(ticket), _stream()), name)
-        return
-    if ema is None and not decay:
-        name = _ADAM_ENTRIES[(words is not None) + 2 * (cover is not None)]
-        rate = (lr,) if words is None else (_p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule))
-        avg, tail = (), ()
-    else:
-        avg, tail = (None,), (None, 0)                                   # (the decay entries: e == NULL, no average)
-        if ema is not None:
-            for what, t, least in (("ema", ema, p.numel()), ("ema_decay_word", ema_decay_word, 1)):
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or \
-                        t.numel() < least:
-                    raise L.IckError("adam_update needs %s as a contiguous float32 device tensor of at least %d element(s)"
-                                     % (what, least))
-            if ema.data_ptr() % (4 if cover is None else 16):
-                raise L.IckError("adam_update: ema must lie on %d bytes" % (4 if cover is None else 16))
-            avg, tail = (_p(ema),), (_p(ema_decay_word), int(bool(ema_warmup)))
-        name = (_ADAM_DECAY_ENTRIES if decay else _ADAM_EMA_ENTRIES)[cover is not None]
-        rate = (0.0, _p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule)) if words is not None else \
-            (lr, None, L.LrSchedule())
-        tail += decay
+        checks += [("decay_word", decay_word, torch.float32, 1),
+                   ("decay_mask", decay_mask, torch.uint8, (p.numel() + 63) // 64)]
+    if ema is not None:
+        checks += [("ema", ema, torch.float32, p.numel()), ("ema_decay_word", ema_decay_word, torch.float32, 1)]
+    if bump is not None and (step_tensor is None or bump[1].numel() != 1 or bump[1].dtype != torch.int32 or
+                             not bump[1].is_cuda):
+        raise L.IckError("adam_update: bump needs step_tensor and a one-element int32 device ticket")
+    for what, t, dtype, least in checks:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or \
+                t.numel() < least:
+            raise L.IckError("adam_update needs %s as a contiguous %s device tensor of at least %d element(s)"
+                             % (what, str(dtype).replace("torch.", ""), least))
+    if ema is not None and ema.data_ptr() % (4 if cover is None else 16):
+        raise L.IckError("adam_update: ema must lie on %d bytes" % (4 if cover is None else 16))
     if cover is None:
-        over = (p.numel(),)
+        name, over = "ick_adam_step", (p.numel(),)
     else:
         L.ADAM_DERIVE_BYTES, L.ADAM_DERIVE_FLOATS = cover.nbytes, p.numel()     # (profiling.py's byte model)
-        over = (_p(cover.items_dev), _p(cover.blocks_dev), cover.n_blocks)
-    L.check(getattr(L.load(), name)(_p(p), _p(g), _p(m), _p(v), *avg, *over, gscale, clip, *rate, beta1, beta2, eps, step,
-                                    _p(step_tensor), _p(gscale_den), *tail, _stream()), name)
+        name, over = "ick_adam_step_derive", (_p(cover.items_dev), _p(cover.blocks_dev), cover.n_blocks)
+    rate = (0.0, _p(_opt_words(words, "adam_update")), lr_schedule_struct(schedule)) if words is not None else \
+        (lr, None, L.LrSchedule())
+    # every option by its pointer: None is the update without it
+    avg = (_p(ema_decay_word), int(bool(ema_warmup)))
+    decay = (None, None, 0, 0) if decay_word is None else \
+        (_p(decay_word), _p(decay_mask), decay_mask.numel(), DECAY_DECOUPLED if decoupled else DECAY_COUPLED)
+    inc, ticket = (0, None) if bump is None else bump
+    L.check(getattr(L.load(), name)(_p(p), _p(g), _p(m), _p(v), _p(ema), *over, gscale, clip, *rate, beta1, beta2, eps, step,
+                                    _p(step_tensor), _p(gscale_den), *avg, *decay, int(inc), _p(ticket), _stream()), name)
 
 
 def adam_ticket(device):

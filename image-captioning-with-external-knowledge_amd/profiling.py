@@ -133,31 +133,14 @@ def classify(name, args):
         B, Lc, Vx = args[8], args[9], args[10]
         return (("weighted " if args[6] else "") + "packed cross entropy, label smoothing (+ gradient)",
                 4.0 * B * Lc * Vx * (2 if args[15] else 1), "byte")
-    if name in ("ick_adam_clamp", "ick_adam_opt"):
-        return "clamp + Adam", 4.0 * args[4] * 7, "byte"
-    if name in ("ick_adam_clamp_derive", "ick_adam_opt_derive"):
-        # the seven streams of the update + every image of the updated weights (packed, transposed, bf16 planes)
-        return "clamp + Adam + re-laid-out weight copies", float(getattr(L, "ADAM_DERIVE_BYTES", 0)), "byte"
-    if name == "ick_adam_ema":
-        # the moving average is read and written in the same pass: nine streams
-        return "clamp + Adam + EMA", 4.0 * args[5] * 9, "byte"
-    if name == "ick_adam_ema_derive":
-        return ("clamp + Adam + EMA + re-laid-out weight copies",
-                float(getattr(L, "ADAM_DERIVE_BYTES", 0)) + 8.0 * getattr(L, "ADAM_DERIVE_FLOATS", 0), "byte")
-    if name == "ick_adam_decay":
-        # args[4]: the average (None: seven streams, else nine); the granule mask adds one byte per 64 floats
-        streams = 9 if args[4] else 7
-        return ("clamp + Adam + weight decay" + (" + EMA" if args[4] else ""),
-                4.0 * args[5] * streams + args[5] / 64.0, "byte")
-    if name == "ick_adam_decay_derive":
-        floats = getattr(L, "ADAM_DERIVE_FLOATS", 0)
-        return ("clamp + Adam + weight decay" + (" + EMA" if args[4] else "") + " + re-laid-out weight copies",
-                float(getattr(L, "ADAM_DERIVE_BYTES", 0)) + (8.0 * floats if args[4] else 0.0) + floats / 64.0, "byte")
-    if name in ("ick_adam_step", "ick_adam_step_derive"):      # the entry of the same options, by its pointers
+    if name in ("ick_adam_step", "ick_adam_step_derive"):      # one row per kind of work: the options, by their pointers
         e, decay = args[4], args[19 if name == "ick_adam_step" else 21]
         label = "clamp + Adam" + (" + weight decay" if decay else "") + (" + EMA" if e else "")
         if name == "ick_adam_step":
+            # seven streams of the update, nine with the moving average (read and written in the same pass); the
+            # granule mask adds one byte per 64 floats
             return label, 4.0 * args[5] * (9 if e else 7) + (args[5] / 64.0 if decay else 0.0), "byte"
+        # ... + every image of the updated weights (packed, transposed, bf16 planes)
         floats = getattr(L, "ADAM_DERIVE_FLOATS", 0)
         return (label + " + re-laid-out weight copies",
                 float(getattr(L, "ADAM_DERIVE_BYTES", 0)) + (8.0 * floats if e else 0.0) + (floats / 64.0 if decay else 0.0),

@@ -1206,7 +1206,7 @@ class TrainStep:
     # ---- global-norm clip and learning-rate schedule: the optimizer words --------
     def _make_words(self):
         """The optimizer words (include/ick_amd.h: base lr, max_norm, norm, coef, lr used, sum of squares) and the norm
-        pass's scratch.  From here on _adam() launches ick_adam_opt[_derive], which read the rate from the words."""
+        pass's scratch.  From here on _adam() gives ick_adam_step[_derive] the words, which then hold the rate."""
         dev = self.flat_p.device
         if self._words is None:
             w = [0.0] * 8

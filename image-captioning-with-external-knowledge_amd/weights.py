@@ -1,6 +1,6 @@
 """Re-laid-out copies of the decoder's weights.  Every fast path reads the
 weights through such copies; WeightImages owns all of them -- one object per decoder, the only code that allocates or fills
-one -- and DerivedWeights is the table that lets the optimizer kernel (ick_adam_clamp_derive, csrc/adam.hip) write
+one -- and DerivedWeights is the table that lets the optimizer kernel (ick_adam_step_derive, csrc/adam.hip) write
 them in the same pass as the update: the reference's optimizer.step() (geo-aware/train.py:292) is the only writer of the
 parameters, so nothing has to re-pack a weight in front of the next forward pass."""
 import weakref
@@ -205,7 +205,7 @@ class WeightImages:
 
 
 class DerivedWeights:
-    """The optimizer kernel's view of a decoder's WeightImages (ops.adam_update(cover=) / ick_adam_clamp_derive): the item
+    """The optimizer kernel's view of a decoder's WeightImages (ops.adam_update(cover=) / ick_adam_step_derive): the item
     table that names, for every trainable weight with an image, where in TrainStep's flat bucket it lives and which buffers
     of the owner its updated values go to, and the block table that covers the bucket.
 

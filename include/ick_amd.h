@@ -718,50 +718,6 @@ int ick_fact_encode_bwd(const float* dfe, const int64_t* facts, float* dee, floa
 int ick_context_gate_bwd(const int64_t* captions, const int64_t* facts, const float* dgate, float* dw,
                          float* dbias, int32_t B, int32_t L, int32_t T, int32_t K, int32_t F, int32_t V,
                          int32_t num_pred, int32_t d, int32_t mode, void* stream);
-/* g = clamp(g*gscale, +-clip) (clip <= 0: no clamp) followed by torch.optim.Adam's update, one flat
- * fp32 bucket; the 1-based step count is step + *step_ptr (step_ptr may be NULL; a device-resident counter
- * lets a captured graph advance the bias correction on every replay).  With gscale_den (device scalar, may be
- * NULL) the gradient scale is gscale / *gscale_den: the token-mean normalisation by the all-reduced token
- * count without a host round trip or a separate pass over the bucket. */
-int ick_adam_clamp(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float lr,
-                   float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                   const float* gscale_den, void* stream);
-/* ick_adam_clamp over the whole bucket which ALSO keeps the re-laid-out copies of the weights current that the
- * next step's kernels read (geo-aware/train.py:292 optimizer.step() is the only writer of the parameters, so the
- * packed / transposed / bf16-plane images need no launches of their own: round 4 spent 126 us of kernel time per cfg2
- * step on ick_pack_weights + ick_presplit_weights).  The bucket is cut into workgroup-sized `blocks`:
- *   - a flat run of <= 1024 float4 (item < 0), optionally mirrored into a plain copy (the gathered cross K/V bias);
- *   - a 64 x 64 tile of an `item`: `rows` x K floats, row-major with row stride K, starting `off` floats into the
- *     bucket, which are rows drow0 .. drow0 + rows - 1 of a logical (Nd, K) matrix W.  The tile (tn, tk) covers rows
- *     64 tn .. 64 tn + 63 of W and columns 64 tk .. 64 tk + 63; after the update its new values are written to every
- *     non-NULL image of W: `pack` = ick_pack_weights(W), `pack_t` = ick_pack_weights(W^T), `copy` = W with row stride
- *     copy_ld, `ps` = ick_presplit_weights(W), `ps_t` = ick_presplit_weights(W^T), `tr` = W^T with row stride tr_ld.
- *     The images must have been filled once by those entry points (their zero padding is never rewritten).
- *     Constraints: K % 4 == 0, off % 4 == 0; pack_t needs drow0 % 4 == 0 and rows % 4 == 0; ps_t needs drow0 % 8 == 0
- *     and rows % 8 == 0; copy_ld % 4 == 0.
- * Every float of [0, n) must lie in exactly one block (the caller builds the cover).  items / blocks are DEVICE arrays.
- * Arithmetic: ick_adam_clamp's own (one function, csrc/adam.hip: bit-identical parameters, moments, clamped gradients). */
-typedef struct ick_adam_item {
-    int64_t off;
-    int32_t rows, K, drow0, Nd;
-    float* pack;
-    float* pack_t;
-    float* copy;
-    void* ps;
-    void* ps_t;
-    float* tr;
-    int64_t copy_ld, tr_ld;
-} ick_adam_item;
-typedef struct ick_adam_block {
-    int32_t item, tn, tk, cnt4;
-    int64_t off4;
-    float* copy;
-} ick_adam_block;
-int ick_adam_clamp_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items,
-                          const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr,
-                          float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                          const float* gscale_den, void* stream);
-
 /* ------------------------------------------------------------------------------------------
  * Global-norm gradient clipping and a learning-rate schedule on the device.
  *
@@ -772,7 +728,7 @@ int ick_adam_clamp_derive(float* p, float* g, float* m, float* v, const ick_adam
  *   [2] norm: the L2 norm of the token-mean gradient g * gscale / *gscale_den over the whole bucket, before any clip
  *   [3] coef = min(1, max_norm / (norm + 1e-6)), 1 while max_norm <= 0 (torch.nn.utils.clip_grad_norm_, norm_type 2,
  *       error_if_nonfinite=False: a NaN norm gives a NaN coef)           ([2], [3], [5]: written by ick_grad_sqnorm)
- *   [4] the learning rate the last applied update used   (written by ick_adam_opt[_derive])
+ *   [4] the learning rate the last applied update used   (written by ick_adam_step[_derive] with words)
  *   [5] the sum of squares of the raw bucket g[0, n) that [2] was made from
  *   [6], [7] unused.
  * The schedule's shape is an argument (baked into a captured graph), defined on the 1-based step count t that the
@@ -798,71 +754,84 @@ int ick_grad_sqnorm_plan(int64_t n, int32_t* plan);
  * entries.  g 16-byte aligned; scratch_floats >= plan[2]. */
 int ick_grad_sqnorm(const float* g, int64_t n, float gscale, const float* gscale_den, float* scratch,
                     int64_t scratch_floats, float* words, void* stream);
-/* ick_adam_clamp / ick_adam_clamp_derive with the learning rate of the step taken from words[0] and the schedule, and
- * the gradient multiplied by words[3] between the scale and the clamp:
- *   x = g * gscale [/ *gscale_den];  x = x * coef;  clamp;  m, v, p as ick_adam_clamp with lr = schedule(words[0], t).
- * words[4] receives that lr.  With coef == 1 and ICK_LR_CONSTANT, warmup 0, the results are ick_adam_clamp[_derive]'s
- * bit for bit.  The gradient written back is the clipped one. */
-int ick_adam_opt(float* p, float* g, float* m, float* v, int64_t n, float gscale, float clip, float* words,
-                 ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                 const float* gscale_den, void* stream);
-int ick_adam_opt_derive(float* p, float* g, float* m, float* v, const ick_adam_item* items, const ick_adam_block* blocks,
-                        int32_t n_blocks, float gscale, float clip, float* words, ick_lr_schedule sched, float beta1,
-                        float beta2, float eps, int32_t step, const uint32_t* step_ptr, const float* gscale_den,
-                        void* stream);
-/* The Adam entries above which ALSO keep an exponential moving average of the parameters.  e: a fourth
- * array laid out like p (n floats, or the bucket the cover runs over).  The lane that has made the new p updates e at the
- * same offset, in this order of float32 operations:
- *     w = 1 - d_t;   e = e + w * (p_new - e)
- * with d_t = *ema_decay (a DEVICE float: a captured graph follows a new value), or, with ema_warmup != 0,
- * d_t = min(*ema_decay, (1 + t) / (10 + t)) on the step count t = step + *step_ptr of the bias correction.
- * words == NULL: the rate is the host float lr, sched is not read, and p, g, m, v get ick_adam_clamp[_derive]'s bits;
- * words != NULL: the optimizer words as in ick_adam_opt[_derive] (lr is not read) and their bits.  While *gscale_den is
- * not > 0 nothing is written, e included.  The re-laid-out images of the derive form stay images of p.
- * ICK_EINVAL without a launch: e or ema_decay NULL (and what the entries above refuse); ICK_EALIGN without a launch: e not
- * on 4 bytes (flat form; like p, g, m, v it need not lie on 16: the scalar kernel then runs), e not on 16 bytes (derive
- * form). */
-int ick_adam_ema(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip, float lr,
-                 float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                 const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
-                 void* stream);
-int ick_adam_ema_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
-                        const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr, float* words,
-                        ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step, const uint32_t* step_ptr,
-                        const float* gscale_den, const float* ema_decay, int32_t ema_warmup, void* stream);
-/* The Adam entries above WITH weight decay on a per-parameter selection.  decay: a DEVICE float wd (a
- * captured graph follows a new value).  decay_mask: n_granules bytes on the device, one per 64 floats of the bucket counted
- * from the bucket's start (p itself, whatever its address); the elements of a granule whose byte is non-zero decay, the
- * others get the entries' above bits.  Every parameter of a bucket starts at a multiple of 64 floats, so a granule belongs
- * to one parameter.  decay_form, in float32 operations kept apart:
- *   ICK_DECAY_DECOUPLED (torch.optim.AdamW)   once: f = 1 - lr_t * wd, lr_t the rate this update uses (lr, or with words
- *                                             the scheduled rate);  per element: p = p * f, then the unchanged update;
- *   ICK_DECAY_COUPLED (Adam(weight_decay=))   per element, x the gradient after scale, clip coefficient and clamp:
- *                                             x2 = x + wd * p feeds the moments and the update; g is written back as x.
- * words == NULL: the host rate lr; e == NULL: no moving average (ema_decay / ema_warmup are not read), else as
- * ick_adam_ema[_derive].  While *gscale_den is not > 0 nothing is written: no decay either.
- * ICK_EINVAL without a launch: decay or decay_mask NULL, n_granules < ceil(n / 64) (flat form) or < 1 (derive form, whose
- * cover lies on the device: there the kernel takes a granule beyond the table as not selected), an unknown decay_form,
- * and what the entries above refuse. */
+/* The optimizer: two entries, ick_adam_step over a flat fp32 bucket of n floats and ick_adam_step_derive over a cover
+ * of the whole bucket (below).  The base update, with every option pointer NULL:
+ *     g = clamp(g * gscale [/ *gscale_den], +-clip)   (clip <= 0: no clamp),  then torch.optim.Adam's update of p, m, v
+ * with the host rate lr (default betas / eps semantics, no amsgrad).  The 1-based step count is t = step + *step_ptr
+ * (step_ptr may be NULL; a device-resident counter lets a captured graph advance the bias correction on every replay).
+ * With gscale_den (device scalar, may be NULL) the gradient scale is gscale / *gscale_den: the token-mean normalisation
+ * by the all-reduced token count without a host round trip or a separate pass over the bucket.  While *gscale_den is not
+ * > 0 nothing at all is written, whatever the options.  The gradient written back is the clamped one.
+ *
+ * The cover (ick_adam_step_derive): the same update, one function in csrc/adam.hip and the same bits in p, g, m, v,
+ * which ALSO keeps the re-laid-out copies of the weights current that the next step's kernels read (geo-aware/train.py:292
+ * optimizer.step() is the only writer of the parameters, so the packed / transposed / bf16-plane images need no launches
+ * of their own: round 4 spent 126 us of kernel time per cfg2 step on ick_pack_weights + ick_presplit_weights).  The
+ * bucket is cut into workgroup-sized `blocks`:
+ *   - a flat run of <= 1024 float4 (item < 0), optionally mirrored into a plain copy (the gathered cross K/V bias);
+ *   - a 64 x 64 tile of an `item`: `rows` x K floats, row-major with row stride K, starting `off` floats into the
+ *     bucket, which are rows drow0 .. drow0 + rows - 1 of a logical (Nd, K) matrix W.  The tile (tn, tk) covers rows
+ *     64 tn .. 64 tn + 63 of W and columns 64 tk .. 64 tk + 63; after the update its new values are written to every
+ *     non-NULL image of W: `pack` = ick_pack_weights(W), `pack_t` = ick_pack_weights(W^T), `copy` = W with row stride
+ *     copy_ld, `ps` = ick_presplit_weights(W), `ps_t` = ick_presplit_weights(W^T), `tr` = W^T with row stride tr_ld.
+ *     The images must have been filled once by those entry points (their zero padding is never rewritten).
+ *     Constraints: K % 4 == 0, off % 4 == 0; pack_t needs drow0 % 4 == 0 and rows % 4 == 0; ps_t needs drow0 % 8 == 0
+ *     and rows % 8 == 0; copy_ld % 4 == 0.
+ * Every float of the bucket must lie in exactly one block (the caller builds the cover).  items / blocks are DEVICE
+ * arrays.  The images stay images of p under every option.
+ *
+ * The options, each selected by one pointer and independent of the others; an option that is off leaves the bits of
+ * the update without it:
+ *   words != NULL  the optimizer words above: the rate is schedule(words[0], t) instead of lr (which is
+ *       not read), and the gradient is multiplied by coef = words[3] between the scale and the clamp, as an operation of
+ *       its own:  x = g * gscale [/ *gscale_den];  x = x * coef;  clamp.  words[4] receives the rate used.  With coef == 1
+ *       and ICK_LR_CONSTANT, warmup 0, p, g, m, v are those of words == NULL with lr = words[0], bit for bit.  words ==
+ *       NULL: sched is not read.
+ *   e != NULL  an exponential moving average of the parameters in a fourth array laid out like p.  The
+ *       lane that has made the new p updates e at the same offset, in this order of float32 operations:
+ *           w = 1 - d_t;   e = e + w * (p_new - e)
+ *       with d_t = *ema_decay (a DEVICE float: a captured graph follows a new value), or, with ema_warmup != 0,
+ *       d_t = min(*ema_decay, (1 + t) / (10 + t)).  p, g, m, v keep the bits they have with e == NULL.
+ *   decay != NULL, with decay_mask  weight decay on a per-parameter selection.  decay: a DEVICE float
+ *       wd.  decay_mask: n_granules bytes on the device, one per 64 floats of the bucket counted from the bucket's start
+ *       (p itself, whatever its address); the elements of a granule whose byte is non-zero decay, the others keep the
+ *       bits they have with decay == NULL.  Every parameter of a bucket starts at a multiple of 64 floats, so a granule
+ *       belongs to one parameter.  decay_form, in float32 operations kept apart:
+ *         ICK_DECAY_DECOUPLED (torch.optim.AdamW)   once: f = 1 - lr_t * wd, lr_t the rate this update uses (lr, or with
+ *                                                   words the scheduled rate);  per element: p = p * f, then the
+ *                                                   unchanged update;
+ *         ICK_DECAY_COUPLED (Adam(weight_decay=))   per element, x the gradient after scale, clip coefficient and clamp:
+ *                                                   x2 = x + wd * p feeds the moments and the update; g is written back
+ *                                                   as x.
+ *   ticket != NULL  the launch also advances the step counter.  ticket: ONE uint32 in device memory, 0
+ *       before the first launch; the launch leaves it 0 again.  Once every workgroup has read step_ptr[0], the last one
+ *       to finish does step_ptr[0] += bump_inc -- iff the update ran, that is gscale_den == NULL or gscale_den[0] > 0,
+ *       ick_counter_add_if's rule.  Everything else keeps the bits it has with ticket == NULL, where the counter is only
+ *       read and bump_inc is not.
+ * ICK_EINVAL without a launch: p, g, m or v NULL; n < 1, or blocks NULL or n_blocks < 1; step < 1 with step_ptr NULL;
+ * words with an unknown schedule kind; e without ema_decay; ema_decay or a non-zero ema_warmup without e; decay and
+ * decay_mask one without the other; with decay, an unknown decay_form, n_granules < ceil(n / 64) (flat form) or < 1
+ * (derive form, whose cover lies on the device: there the kernel takes a granule beyond the table as not selected);
+ * ticket without step_ptr.  ICK_EALIGN without a launch: e not on 4 bytes (flat form; like p, g, m, v it need not lie on
+ * 16: the scalar kernel then runs); p, g, m, v or e not on 16 bytes (derive form). */
+typedef struct ick_adam_item {
+    int64_t off;
+    int32_t rows, K, drow0, Nd;
+    float* pack;
+    float* pack_t;
+    float* copy;
+    void* ps;
+    void* ps_t;
+    float* tr;
+    int64_t copy_ld, tr_ld;
+} ick_adam_item;
+typedef struct ick_adam_block {
+    int32_t item, tn, tk, cnt4;
+    int64_t off4;
+    float* copy;
+} ick_adam_block;
 #define ICK_DECAY_DECOUPLED 0
 #define ICK_DECAY_COUPLED 1
-int ick_adam_decay(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip, float lr,
-                   float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                   const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
-                   const float* decay, const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form, void* stream);
-int ick_adam_decay_derive(float* p, float* g, float* m, float* v, float* e, const ick_adam_item* items,
-                          const ick_adam_block* blocks, int32_t n_blocks, float gscale, float clip, float lr, float* words,
-                          ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
-                          const uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
-                          const float* decay, const uint8_t* decay_mask, int64_t n_granules, int32_t decay_form,
-                          void* stream);
-/* The general entries, which can also advance the step counter in the optimizer's own launch.  Every
- * option goes by its pointer: e == NULL keeps no average, words == NULL takes the host rate lr, decay == NULL decays
- * nothing; each combination runs the kernel of the entry above with the same options and leaves the same bits.
- * ticket != NULL (ONE uint32 in device memory, 0 before the first launch; the launch leaves it 0 again): once every
- * workgroup has read step_ptr[0], the last one to finish does step_ptr[0] += bump_inc -- iff the update ran, that is
- * gscale_den == NULL or gscale_den[0] > 0, ick_counter_add_if's rule.  step_ptr is then required.  ticket == NULL: the
- * counter is only read, as by the entries above. */
 int ick_adam_step(float* p, float* g, float* m, float* v, float* e, int64_t n, float gscale, float clip, float lr,
                   float* words, ick_lr_schedule sched, float beta1, float beta2, float eps, int32_t step,
                   uint32_t* step_ptr, const float* gscale_den, const float* ema_decay, int32_t ema_warmup,
@@ -891,7 +860,7 @@ int ick_conv1_wgrad(const float* d_img, const float* feats, float* dw, float* db
 /* *counter += inc on the stream (step / dropout-epoch counter of captured training graphs). */
 int ick_counter_add(uint32_t* counter, uint32_t inc, void* stream);
 /* ... only if *flag > 0 (device scalar): the step counter of a training step whose optimizer update is deferred into the
- * next step's graph advances exactly when that update is applied -- ick_adam_clamp[_derive] with gscale_den = flag is a
+ * next step's graph advances exactly when that update is applied -- ick_adam_step[_derive] with gscale_den = flag is a
  * no-op under the same condition (no pending gradients: first call, or the update was flushed). */
 int ick_counter_add_if(uint32_t* counter, uint32_t inc, const float* flag, void* stream);
 /* n <= 8 device-to-device copies (src[i] -> dst[i], bytes[i]) in one launch; host arrays of device pointers. */

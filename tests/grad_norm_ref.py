@@ -1,5 +1,5 @@
 """float64 numpy restatement of the fused optimizer update with the global-norm clip: what
-ick_grad_sqnorm + ick_adam_opt[_derive] compute, in torch's order --
+ick_grad_sqnorm + ick_adam_step[_derive] (with the words) compute, in torch's order --
     norm = sqrt(sum over every parameter of sum(g^2))            torch.nn.utils.clip_grad_norm_(params, m, norm_type=2)
     coef = min(1, max_norm / (norm + 1e-6))                      (max_norm None: 1)
     g    = clamp(g * coef, -clip, clip)                          (clip None or <= 0: no clamp)

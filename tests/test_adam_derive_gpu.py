@@ -1,7 +1,7 @@
-"""The optimizer kernel that keeps the re-laid-out weight copies current (ick_adam_clamp_derive, csrc/adam.hip;
+"""The optimizer kernel that keeps the re-laid-out weight copies current (ick_adam_step_derive, csrc/adam.hip;
 VERDICT r4 item 6): the reference's optimizer.step() (geo-aware/train.py:292, clip at :287-288) is the only writer of the
 parameters, so the packed / transposed / bf16-plane images the next step's kernels read are written in the same pass.
-  * the update itself is ick_adam_clamp's, bit for bit (parameters, moments, clamped gradients), on the real bucket of all
+  * the update itself is ick_adam_step's, bit for bit (parameters, moments, clamped gradients), on the real bucket of all
     three variants: the kernels share one adam1 and differ in how they address the bucket;
   * every image equals what the stand-alone packing kernels (ick_pack_weights, ick_presplit_weights) make of the updated
     weights, bit for bit, padding included;

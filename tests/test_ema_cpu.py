@@ -72,17 +72,24 @@ def test_decay_hand_values():
     assert decay_at64(1, 0.1, True) == 0.1
 
 
+# the eight entries, one pair per optimizer feature, that ick_adam_step[_derive] replaced
+REMOVED = ["ick_adam_" + kind + form for kind in ("clamp", "opt", "ema", "decay") for form in ("", "_derive")]
+
+
 def test_header_and_binding_hold_both_entries():
+    import ick_amd.build as build
     src = open(os.path.join(ROOT, "include", "ick_amd.h")).read()
     declared = set(re.findall(r"^int\s+(ick_[a-z0-9_]+)\s*\(", src, flags=re.M))
-    for name, nargs in (("ick_adam_ema", 20), ("ick_adam_ema_derive", 22)):
+    for name, nargs in (("ick_adam_step", 26), ("ick_adam_step_derive", 28)):
         assert name in declared and name in L.SIGNATURES
         assert len(L.SIGNATURES[name]) == nargs and L.SIGNATURES[name][-1] is L.vp
         decl = re.search(r"^int\s+%s\s*\(([^;]*)\);" % name, src, flags=re.M | re.S).group(1)
         assert len(decl.split(",")) == nargs
-    # the existing entries keep their argument counts
-    assert [len(L.SIGNATURES[n]) for n in ("ick_adam_clamp", "ick_adam_opt", "ick_adam_clamp_derive",
-                                           "ick_adam_opt_derive")] == [15, 16, 17, 18]
+    # the two are the optimizer's only entries: the others are gone from the binding, the header and the library
+    exported = ctypes.CDLL(build.build())
+    for name in REMOVED:
+        assert name not in L.SIGNATURES and not re.search(r"\b%s\b" % name, src) and not hasattr(exported, name), name
+    assert hasattr(exported, "ick_adam_step") and hasattr(exported, "ick_adam_step_derive")
 
 
 def test_entries_refuse_bad_arguments_without_a_launch():
@@ -94,25 +101,40 @@ def test_entries_refuse_bad_arguments_without_a_launch():
     p = ctypes.addressof(buf)
     p = p + (-p) % 16
     sch = L.LrSchedule()
-    flat = [p, p, p, p, p, 8, 1.0, 5.0, 4e-4, None, sch, 0.9, 0.999, 1e-8, 1, None, None, p, 0, None]
+    #       p  g  m  v  e  n  gscale clip lr   words sched b1  b2     eps   step sp    den   ema_d w
+    flat = [p, p, p, p, p, 8, 1.0, 5.0, 4e-4, None, sch, 0.9, 0.999, 1e-8, 1, None, None, p, 0,
+            None, None, 0, 0, 0, None, None]                       # decay, mask, granules, form, bump_inc, ticket, stream
     for i, want in ((4, -1), (17, -1), (0, -1), (5, -1)):          # no average, no decay word, no parameters, no floats
         a = list(flat)
         a[i] = 0 if i == 5 else None
-        assert lib.ick_adam_ema(*a) == want, i
+        assert lib.ick_adam_step(*a) == want, i
+    a = list(flat)
+    a[4], a[17], a[18] = None, None, 1                              # a warmup without an average
+    assert lib.ick_adam_step(*a) == -1
     a = list(flat)
     a[4] = p + 2                                                    # not on a float
-    assert lib.ick_adam_ema(*a) == -2
+    assert lib.ick_adam_step(*a) == -2
     a = list(flat)
     a[9], a[10] = p, L.LrSchedule(7, 0, 0, 0.0)                     # with the words: an unknown schedule kind
-    assert lib.ick_adam_ema(*a) == -1
-    cover = [p, p, p, p, p, p, p, 1, 1.0, 5.0, 4e-4, None, sch, 0.9, 0.999, 1e-8, 1, None, None, p, 0, None]
+    assert lib.ick_adam_step(*a) == -1
+    a = list(flat)
+    a[23], a[24] = 1, p                                             # a ticket without the counter it advances
+    assert lib.ick_adam_step(*a) == -1
+    cover = [p, p, p, p, p, p, p, 1, 1.0, 5.0, 4e-4, None, sch, 0.9, 0.999, 1e-8, 1, None, None, p, 0,
+             None, None, 0, 0, 0, None, None]
     for i in (4, 19, 6):                                            # no average, no decay word, no blocks
         a = list(cover)
         a[i] = None
-        assert lib.ick_adam_ema_derive(*a) == -1, i
+        assert lib.ick_adam_step_derive(*a) == -1, i
+    a = list(cover)
+    a[4], a[19], a[20] = None, None, 1
+    assert lib.ick_adam_step_derive(*a) == -1
     a = list(cover)
     a[4] = p + 4                                                    # the cover's float4 accesses need 16 bytes
-    assert lib.ick_adam_ema_derive(*a) == -2
+    assert lib.ick_adam_step_derive(*a) == -2
+    a = list(cover)
+    a[25], a[26] = 1, p
+    assert lib.ick_adam_step_derive(*a) == -1
 
 
 def test_wrapper_errors_come_before_the_library(monkeypatch):

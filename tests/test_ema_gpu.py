@@ -1,7 +1,7 @@
 """The exponential moving average of the parameters inside the fused Adam pass on the GPU:
-  * ick_adam_ema alone on raw buckets: p, g, m, v are ick_adam_clamp's / ick_adam_opt's bits, e is the float32
+  * ick_adam_step with e alone on raw buckets: p, g, m, v are the bits of the call without e, e is the float32
     restatement (tests/ema_ref.py) of the new p, at every size where a kernel path begins or ends;
-  * ick_adam_ema_derive over a real decoder's cover: the flat form's bits, ick_adam_clamp_derive's images;
+  * ick_adam_step_derive with e over a real decoder's cover: the flat form's bits, the images of the call without e;
   * TrainStep(ema_decay=) against a twin without it: the same loss, parameters and moments, and the average of every
     parameter is the restatement folded over the twin's parameter snapshots;
   * set_ema_decay replays, lazy_update, ema_weights(), the state round trip, and the training script.
@@ -141,7 +141,7 @@ def test_derive_form_has_the_flat_forms_bits_and_the_plain_covers_images(variant
     ts.flat_e.copy_(ts.flat_p + rnd() * 0.01)
     ts.counter.fill_(4)
     start = [t.clone() for t in (ts.flat_p, ts.flat_g, ts.flat_m, ts.flat_v, ts.flat_e)]
-    ts._adam()                                                                   # ick_adam_ema_derive
+    ts._adam()                                                                   # ick_adam_step_derive, e != NULL
     torch.cuda.synchronize()
     mine = [t.clone() for t in (ts.flat_p, ts.flat_g, ts.flat_m, ts.flat_v, ts.flat_e)]
     images = {k: v.clone() for k, v in _images(dw).items()}

@@ -1,7 +1,7 @@
 """Global-norm gradient clipping and the device-side learning-rate schedule on the GPU:
   * ick_grad_sqnorm alone: exact on buckets whose every partial sum is an fp32 number, at the sizes where a path of the
     kernel begins or ends; against float64 on normal data; the same bits twice; the token-count rule; the coefficient;
-  * ick_adam_opt / ick_adam_opt_derive against ick_adam_clamp / ick_adam_clamp_derive, bit for bit, with a coefficient
+  * ick_adam_step / ick_adam_step_derive with the words against the same entry without, bit for bit, with a coefficient
     of 1 and of 0.25; the scalar kernel against the float4 kernel on the same elements (csrc/adam.hip: one adam1, three
     kernels that address differently);
   * one TrainStep(max_grad_norm=) step against the CPU oracle with torch's clip_grad_norm_ and clamp_, in every product
@@ -254,7 +254,7 @@ def test_adam_opt_derive_is_adam_clamp_derive_bit_for_bit(coef):
 
 @pytest.mark.parametrize("kind", ["constant", "inverse_sqrt", "cosine", "linear"])
 def test_adam_opt_rate_word_follows_the_schedule(kind):
-    """The rate ick_adam_opt reports over the steps 1 .. N + 3 of each kind: 1e-6 relative (a few fp32 roundings) plus
+    """The rate the kOpt instantiation reports over the steps 1 .. N + 3 of each kind: 1e-6 relative (a few fp32 roundings) plus
     1e-6 * lr absolute (the cosine near its zero)."""
     sch = dict(kind=kind, warmup_steps=3, total_steps=9, min_lr_ratio=0.1)
     t4 = [torch.zeros(256, device="cuda") for _ in range(4)]

@@ -11,11 +11,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NEW = ["ick_packed_ce_weighted_mean", "ick_packed_ce_packed_mean", "ick_packed_ce_smooth_mean",
        "ick_pointer_scores_bwd_fused", "ick_pointer_scores_bwd_fused_packed", "ick_adam_step", "ick_adam_step_derive"]
-# each new entry takes the arguments of the entry it replaces plus these
+# each new entry takes the arguments of the entry it replaces plus these; the two Adam entries replaced every older one (none
+# is left to compare with): their own argument counts
 EXTRA = {"ick_packed_ce_weighted_mean": ("ick_packed_ce_weighted", 1), "ick_packed_ce_packed_mean": ("ick_packed_ce_packed", 1),
          "ick_packed_ce_smooth_mean": ("ick_packed_ce_smooth", 1), "ick_pointer_scores_bwd_fused": ("ick_pointer_scores_bwd", 0),
-         "ick_pointer_scores_bwd_fused_packed": ("ick_pointer_scores_bwd_packed", 0), "ick_adam_step": ("ick_adam_decay", 2),
-         "ick_adam_step_derive": ("ick_adam_decay_derive", 2)}
+         "ick_pointer_scores_bwd_fused_packed": ("ick_pointer_scores_bwd_packed", 0)}
+ADAM_ARGS = {"ick_adam_step": 26, "ick_adam_step_derive": 28}
 
 
 @pytest.fixture(scope="module")
@@ -40,9 +41,15 @@ def test_header_binding_and_library_agree(built_lib):
         assert name in L.SIGNATURES, "lib.py does not bind %s" % name
         assert len(L.SIGNATURES[name]) == len(protos[name]), (name, len(L.SIGNATURES[name]), len(protos[name]))
         assert hasattr(lib, name), "libick_amd.so does not export %s" % name
+        if name in ADAM_ARGS:
+            assert len(L.SIGNATURES[name]) == ADAM_ARGS[name], name
+            continue
         old, extra = EXTRA[name]
         assert len(L.SIGNATURES[name]) == len(L.SIGNATURES[old]) + extra, name
         assert L.SIGNATURES[name][:len(L.SIGNATURES[old]) - 1] == L.SIGNATURES[old][:-1], name
+    # the flat and the derive form differ in what they run over only: n | items, blocks, n_blocks
+    flat, derive = L.SIGNATURES["ick_adam_step"], L.SIGNATURES["ick_adam_step_derive"]
+    assert flat[:5] == derive[:5] and flat[5:6] == [L.i64] and derive[5:8] == [L.vp, L.vp, L.i32] and flat[6:] == derive[8:]
     assert sorted(L.SIGNATURES) == sorted(protos)
 
 
@@ -65,4 +72,13 @@ def test_profiling_classifies_the_new_entries():
     a = list(args)
     assert prof.classify("ick_packed_ce_packed_mean", a)[0] == prof.classify("ick_packed_ce_packed", a)[0]
     assert prof.classify("ick_packed_ce_smooth_mean", a)[0] == prof.classify("ick_packed_ce_smooth", a)[0]
-    assert prof.classify("ick_adam_step_derive", a)[0] == prof.classify("ick_adam_decay_derive", a)[0]
+    # the Adam entries: one class per set of options, (e, decay) by their pointers, in the flat and in the derive form
+    labels = {(0, 0): "clamp + Adam", (0, 1): "clamp + Adam + weight decay", (1, 0): "clamp + Adam + EMA",
+              (1, 1): "clamp + Adam + weight decay + EMA"}
+    for (e, decay), label in labels.items():
+        a = list(args)
+        a[4], a[19] = e or None, decay or None
+        assert prof.classify("ick_adam_step", a)[0] == label
+        a = list(args)
+        a[4], a[21] = e or None, decay or None
+        assert prof.classify("ick_adam_step_derive", a)[0] == label + " + re-laid-out weight copies"

@@ -190,18 +190,20 @@ def test_load_adam_state_round_trips_both_layouts():
 
 
 def test_header_and_binding_hold_both_entries():
+    import ick_amd.build as build
     src = open(os.path.join(ROOT, "include", "ick_amd.h")).read()
     declared = set(re.findall(r"^int\s+(ick_[a-z0-9_]+)\s*\(", src, flags=re.M))
-    for name, nargs in (("ick_adam_decay", 24), ("ick_adam_decay_derive", 26)):
+    for name, nargs in (("ick_adam_step", 26), ("ick_adam_step_derive", 28)):
         assert name in declared and name in L.SIGNATURES
         assert len(L.SIGNATURES[name]) == nargs and L.SIGNATURES[name][-1] is L.vp
         decl = re.search(r"^int\s+%s\s*\(([^;]*)\);" % name, src, flags=re.M | re.S).group(1)
         assert len(decl.split(",")) == nargs
     assert re.search(r"#define ICK_DECAY_DECOUPLED 0\b", src) and re.search(r"#define ICK_DECAY_COUPLED 1\b", src)
     assert (ops.DECAY_DECOUPLED, ops.DECAY_COUPLED) == (0, 1)
-    # the existing entries keep their argument counts
-    assert [len(L.SIGNATURES[n]) for n in ("ick_adam_clamp", "ick_adam_opt", "ick_adam_clamp_derive", "ick_adam_opt_derive",
-                                           "ick_adam_ema", "ick_adam_ema_derive")] == [15, 16, 17, 18, 20, 22]
+    # the entries these two replaced are gone: from the binding, from the header, from the built library
+    exported = ctypes.CDLL(build.build())
+    for name in ["ick_adam_" + kind + form for kind in ("clamp", "opt", "ema", "decay") for form in ("", "_derive")]:
+        assert name not in L.SIGNATURES and not re.search(r"\b%s\b" % name, src) and not hasattr(exported, name), name
 
 
 def test_entries_refuse_bad_arguments_without_a_launch():
@@ -214,23 +216,27 @@ def test_entries_refuse_bad_arguments_without_a_launch():
     p = p + (-p) % 16
     sch = L.LrSchedule()
     #       p  g  m  v  e     n    gscale clip lr   words sched b1  b2     eps   step sp    den   ema_d w  wd mask gr form
-    flat = [p, p, p, p, None, 130, 1.0, 5.0, 4e-4, None, sch, 0.9, 0.999, 1e-8, 1, None, None, None, 0, p, p, 3, 0, None]
+    flat = [p, p, p, p, None, 130, 1.0, 5.0, 4e-4, None, sch, 0.9, 0.999, 1e-8, 1, None, None, None, 0, p, p, 3, 0,
+            0, None, None]                                          # (... bump_inc, ticket, stream)
     for i, bad in ((19, None), (20, None), (21, 2), (21, 0), (22, 2), (22, -1), (0, None), (5, 0)):
-        a = list(flat)          # no decay word, no mask, granules below ceil(130 / 64), an unknown form, no p, no floats
-        a[i] = bad
-        assert lib.ick_adam_decay(*a) == -1, (i, bad)
+        a = list(flat)          # mask without word, word without mask, granules below ceil(130 / 64), an unknown form,
+        a[i] = bad              # no p, no floats
+        assert lib.ick_adam_step(*a) == -1, (i, bad)
     a = list(flat)
     a[4] = p                                                        # with an average: its decay word must be there
-    assert lib.ick_adam_decay(*a) == -1
+    assert lib.ick_adam_step(*a) == -1
     a = list(flat)
     a[9], a[10] = p, L.LrSchedule(7, 0, 0, 0.0)                     # with the words: an unknown schedule kind
-    assert lib.ick_adam_decay(*a) == -1
+    assert lib.ick_adam_step(*a) == -1
+    a = list(flat)
+    a[23], a[24] = 1, p                                             # a ticket without the counter it advances
+    assert lib.ick_adam_step(*a) == -1
     cover = [p, p, p, p, None, p, p, 1, 1.0, 5.0, 4e-4, None, sch, 0.9, 0.999, 1e-8, 1, None, None, None, 0, p, p, 3, 0,
-             None]
+             0, None, None]
     for i, bad in ((21, None), (22, None), (23, 0), (24, 2), (6, None)):
         a = list(cover)
         a[i] = bad
-        assert lib.ick_adam_decay_derive(*a) == -1, (i, bad)
+        assert lib.ick_adam_step_derive(*a) == -1, (i, bad)
 
 
 def test_wrapper_errors_come_before_the_library(monkeypatch):

@@ -1,8 +1,8 @@
 """Weight decay inside the fused Adam pass on the GPU:
-  * ick_adam_decay alone on raw buckets, bit for bit against the plain entries run on inputs prepared with the float32
+  * ick_adam_step with decay alone on raw buckets, bit for bit against the same entry without it run on inputs prepared with the float32
     restatement (tests/weight_decay_ref.py), at every size where a kernel path begins or ends and for masks that cross
     them;
-  * ick_adam_decay_derive over a real decoder's cover: the flat form's bits, and images of the updated parameters;
+  * ick_adam_step_derive with decay over a real decoder's cover: the flat form's bits, and images of the updated parameters;
   * TrainStep(weight_decay=) against a twin without it (deterministic mode: bit for bit), and against the float64 oracle
     with torch.optim.AdamW / Adam(weight_decay=) over the same per-parameter groups;
   * the setters, lazy_update, the default step, the state round trip, SelfCriticalStep and the training script."""
@@ -167,7 +167,7 @@ def test_derive_form_has_the_flat_forms_bits_and_images_of_the_new_parameters(va
         ts.flat_e.copy_(ts.flat_p + rnd() * 0.01)
     ts.counter.fill_(4)
     start = [t.clone() for t in state]
-    ts._adam()                                                                   # ick_adam_decay_derive
+    ts._adam()                                                                   # ick_adam_step_derive, decay != NULL
     torch.cuda.synchronize()
     mine = [t.clone() for t in state]
     images = {k: v.clone() for k, v in _images(dw).items()}
@@ -273,15 +273,20 @@ def test_without_the_cover_and_inside_ema_weights(monkeypatch, det_off_after):
 
 
 def test_weight_decay_none_is_todays_step(det_off_after):
-    """Nothing allocated, the previous entries launched, the twin's bits over four steps, and the setters refuse."""
+    """Nothing allocated, every launch the plain instantiation's (no option pointer given), the twin's bits over four steps, and the setters refuse."""
     launched = []
     real = ops.L.load
 
     class Spy:
         def __getattr__(self, name):
-            if name.startswith("ick_adam"):
-                launched.append(name)
-            return getattr(real(), name)
+            fn = getattr(real(), name)
+            if not name.startswith("ick_adam"):
+                return fn
+
+            def record(*a):
+                launched.append((name, a))
+                return fn(*a)
+            return record
 
     ts, dec, args = build_step("geo", weight_decay=None)
     twin, _, _ = build_step("geo")
@@ -292,7 +297,12 @@ def test_weight_decay_none_is_todays_step(det_off_after):
         losses = [ts(*args).clone() for _ in range(4)]
     finally:
         ops.L.load = real
-    assert launched and set(launched) == {"ick_adam_clamp_derive" if ts.derived is not None else "ick_adam_clamp"}
+    assert launched and {name for name, _ in launched} == \
+        {"ick_adam_step_derive" if ts.derived is not None else "ick_adam_step"}
+    for name, a in launched:                 # every launch selects <kOpt, kEma, kDecay> = <0, 0, 0>: the plain instantiation
+        over = 2 if name == "ick_adam_step_derive" else 0
+        e, words, (decay, mask, granules) = a[4], a[9 + over], a[19 + over:22 + over]
+        assert e is None and words is None and decay is None and mask is None and granules == 0, (name, a)
     losses0 = [twin(*args).clone() for _ in range(4)]
     assert all(same_bits(a, b) for a, b in zip(losses, losses0))
     assert same_bits(ts.flat_p, twin.flat_p) and same_bits(ts.flat_m, twin.flat_m) and same_bits(ts.flat_v, twin.flat_v)

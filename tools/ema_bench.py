@@ -2,8 +2,8 @@
 comparison INTERLEAVED in one run, HIP-event times of repeated blocks, the median over the blocks and their spread
 (min .. max) for each side.
 
-  * the Adam launch alone over a flat bucket of cfg2's and of cfg4's size: plain (ick_adam_clamp, 7 streams), with the
-    average (ick_adam_ema, 9 streams), and plain followed by a separate flat_e.lerp_(flat_p, w) (two launches, 10
+  * the Adam launch alone over a flat bucket of cfg2's and of cfg4's size: plain (ick_adam_step, 7 streams), with the
+    average (e != NULL, 9 streams), and plain followed by a separate flat_e.lerp_(flat_p, w) (two launches, 10
     streams) -- over ONE set of arrays ("warm") and rotating over enough sets to exceed the 256 MB last-level cache
     ("cold"); as us and as a share of the 8 TB/s HBM rate for the streams each side moves.  Only the cold rows are HBM
     figures: cfg2's warm set (five arrays, 228 MB) fits the last-level cache, so its share says how the launch compares

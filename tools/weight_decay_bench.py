@@ -1,8 +1,8 @@
 """What weight decay inside the optimizer launch costs -- the sides of every comparison INTERLEAVED in
 one run, HIP-event times of repeated blocks, the median over the blocks and their spread (min .. max) for each side.
 
-  * the optimizer launch alone over cfg2's and cfg4's bucket, in the flat form (ick_adam_clamp / ick_adam_decay) and in
-    the derive form over the decoder's cover (ick_adam_clamp_derive / ick_adam_decay_derive): plain, with decay (the
+  * the optimizer launch alone over cfg2's and cfg4's bucket, in the flat form (ick_adam_step) and in the derive
+    form over the decoder's cover (ick_adam_step_derive), each without and with decay != NULL: plain, with decay (the
     TrainStep's own mask: parameters with ndim >= 2), and plain followed by a separate torch mul_ over the decayed
     extents -- what a user has today, one more launch per decayed parameter.  Over ONE set of arrays ("warm") and
     rotating over enough sets to exceed the 256 MB last-level cache ("cold"; the derive form rotates p, g, m, v under one
