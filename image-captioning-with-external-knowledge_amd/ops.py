@@ -519,10 +519,17 @@ def project_heads(x, w, bias, nseg, H, S, out=None, s0=0, grp=None, a_gmap=None,
     return out
 
 
+# test hook: a list that receives (direction, T, S, dh, causal) of every head-major attention launch while it is set
+# (attention_plan(direction, T, S, dh) then names the kernels that launch took)
+ATTN_LOG = None
+
+
 def attention_heads(q, kv, O, H, dh, T, S, q_seg=0, k_seg=0, v_seg=1, causal=False, kv_len=None, q_pos0=0, q_t0=0,
                     lse=None, drop=None):
     """Attention over head-major buffers: q (B, nq, H, Tq_alloc, DHP), kv (B, nkv, H, S_alloc, DHP);
     the first T query rows starting at q_t0 attend to the first S key rows."""
+    if ATTN_LOG is not None:
+        ATTN_LOG.append(("fwd", T, S, dh, bool(causal)))
     B = q.shape[0]
     Tq, Sa, hp = q.shape[3], kv.shape[3], q.shape[4]
     assert kv.shape[4] == hp
@@ -1168,6 +1175,8 @@ def attention_heads_bwd(q, kv, O, dO, lse, dQ, dK, dV, H, dh, T, S, q_seg=0, k_s
     """Backward of attention_heads.  q (B,nq,H,Tq,DHP), kv (B,nkv,H,Sa,DHP); O/dO (B,T,d) row-major;
     dQ (B,T,*) / dK, dV (B,S,*) row-major views (last-dim stride 1; their column offset selects the
     segment), written as [h*dh + j].  The head-major buffers' row stride is DHP (dh <= 32) or 2 DHP."""
+    if ATTN_LOG is not None:
+        ATTN_LOG.append(("bwd", T, S, dh, bool(causal)))
     B = q.shape[0]
     Tq, Sa = q.shape[3], kv.shape[3]
     hp = q.shape[4]

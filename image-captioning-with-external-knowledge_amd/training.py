@@ -1489,7 +1489,10 @@ class TrainStep:
         self._adam()
         if self.train_conv1:
             self._adam_conv1()
-        ops.counter_add(self.counter, 1)
+        # the counter counts APPLIED updates: a batch without a token leaves it, as it leaves the parameters and moments
+        # (the deferred update's rule, _deferred_update) -- else Adam's bias correction, the schedule's position and
+        # state_dict()'s step run ahead of the moments, and lazy_update and the eager order part ways
+        ops.counter_add_if(self.counter, 1, self.flat_g[self._t + 1:])
         ops.stamp("B: end")
 
     @staticmethod

@@ -182,13 +182,14 @@ def _forward_loss(cfg, Pr, batch, enc_out, f64):
     return scores, caps, dl, R.packed_ce_loss(cfg, scores, caps, dl)
 
 
-def oracle_step(c, f64, P=None):
+def oracle_step(c, f64, P=None, inputs=None):
     """One oracle step of case c -- R.forward, R.packed_ce_loss, backward -- in float32, as
-    tests/test_bench_sizes_gpu.py::reference_train_step runs it, or in float64.  -> dict(loss, scores (B, L, Vx) in
-    length order, valid (B, L) bool, grads by name)."""
+    tests/test_bench_sizes_gpu.py::reference_train_step runs it, or in float64.  inputs: a (batch, enc_out) in place of
+    the case's own (tests/batch_cases.py).  -> dict(loss, scores (B, L, Vx) in length order, valid (B, L) bool, grads by
+    name)."""
     P = make_params(c) if P is None else P
     cfg = oracle_config(c)
-    batch, enc_out = make_inputs(c)
+    batch, enc_out = make_inputs(c) if inputs is None else inputs
     with (float64_default() if f64 else contextlib.nullcontext()):
         Pr = _trainable(P, f64)
         scores, caps, dl, loss = _forward_loss(cfg, Pr, batch, enc_out, f64)
@@ -199,19 +200,22 @@ def oracle_step(c, f64, P=None):
     return dict(loss=loss.item(), scores=scores.detach(), valid=valid, grads=grads, decode_lengths=dl)
 
 
-def oracle_loss_sequence(c, P=None):
-    """The float64 oracle's losses over STEP_SEEDS' batches with torch Adam (lr 4e-4) on gradients clamped to +-5."""
+def oracle_loss_sequence(c, P=None, inputs=None, f64=True):
+    """The float64 oracle's losses over STEP_SEEDS' batches with torch Adam (lr 4e-4) on gradients clamped to +-5.
+    inputs: a list of (batch, enc_out), of any shapes, in place of those batches; f64=False: the same sequence in float32
+    (the reference's own noise over a sequence, tests/test_batch_geometry_cpu.py)."""
     P = make_params(c) if P is None else P
     cfg = oracle_config(c)
     losses = []
-    inputs = [make_inputs(c, seed) for seed in STEP_SEEDS]      # (drawn in float32: synth draws with the default dtype)
-    with float64_default():
-        Pr = _trainable(P, True)
+    if inputs is None:
+        inputs = [make_inputs(c, seed) for seed in STEP_SEEDS]  # (drawn in float32: synth draws with the default dtype)
+    with (float64_default() if f64 else contextlib.nullcontext()):
+        Pr = _trainable(P, f64)
         uniq = [v for k, v in Pr.items() if not k.startswith("fact_encoder.")]
         opt = torch.optim.Adam(uniq, lr=LR)
         for batch, enc_out in inputs:
             opt.zero_grad()
-            loss = _forward_loss(cfg, Pr, batch, enc_out, True)[3]
+            loss = _forward_loss(cfg, Pr, batch, enc_out, f64)[3]
             loss.backward()
             for p in uniq:
                 if p.grad is not None:

@@ -94,8 +94,11 @@ def reference_train_step(cfg, P, batch, enc_out, lr=4e-4, clip=5.0, float64=Fals
     return loss.item(), grads, {k: v.detach() for k, v in Pr.items()}
 
 
-def run_train_step_vs_oracle(variant, B, L, K, V, Fn, seed, plan_log, geometry=None, float64=False, reference=None):
-    """geometry: dict(d, H, decoder_dim, encoder_dim, num_layers, P) of a model other than build_decoder's (None: 300 / 10 /
+def run_train_step_vs_oracle(variant, B, L, K, V, Fn, seed, plan_log, geometry=None, float64=False, reference=None,
+                             inputs=None, params=None):
+    """inputs: a pre-built (batch, enc_out) in place of synth's batch of (B, L, K, Fn, seed); params: the parameters in
+    place of synth's of (V, seed) (tests/batch_cases.py: hand-built caption lengths, parameters shared between cases).
+    geometry: dict(d, H, decoder_dim, encoder_dim, num_layers, P) of a model other than build_decoder's (None: 300 / 10 /
     512 / 512 / 3 layers over 196 image rows); float64: the oracle's step in float64; reference: (cfg, P, batch, enc_out)
     -> (loss, gradients, parameters after the step) in place of reference_train_step_cached (tests/model_cases.py's cases
     share one oracle step among their tests)."""
@@ -112,9 +115,14 @@ def run_train_step_vs_oracle(variant, B, L, K, V, Fn, seed, plan_log, geometry=N
         cfg = R.config_from_word_map(variant, wm, emb_dim=g["d"], num_heads=g["H"], num_layers=g["num_layers"])
         enc_out = synth.make_enc_out(B, seed, emb_dim=g["d"], P=g["P"])
     batch = synth.make_batch(variant, B, L, K, V, Fn, seed)
+    if params is not None:
+        P = params
+    if inputs is not None:
+        batch, enc_out = inputs
+        assert tuple(batch["captions"].shape) == (B, L) and batch["entities"].shape[1] == K and enc_out.shape[0] == B
     if reference is not None:
         loss_ref, grads_ref, P_after = reference(cfg, P, batch, enc_out)
-    elif geometry is None and not float64:
+    elif geometry is None and not float64 and inputs is None and params is None:
         loss_ref, grads_ref, P_after = reference_train_step_cached((variant, B, L, K, V, Fn, seed), cfg, P, batch, enc_out)
     else:
         loss_ref, grads_ref, P_after = reference_train_step(cfg, P, batch, enc_out, float64=float64)
