@@ -227,14 +227,26 @@ struct BeamPartForcedArgs : BeamPartArgs {
 struct BeamPartBiasArgs : BeamPartArgs {
     const int32_t* bcols; const float* bvals;
 };
-template <bool FORCED, bool BIASED>
-using BeamPartArgsOf = std::conditional_t<FORCED, BeamPartForcedArgs, std::conditional_t<BIASED, BeamPartBiasArgs, BeamPartArgs>>;
+// The caption-prefix variant (PREFIX) appends the forced column of every step (R / k, max_len), -1 = a free step, to the
+// plain and to the biased arguments, again for its own instantiations alone.
+struct BeamPartPrefixArgs : BeamPartArgs {
+    const int32_t* pcols;
+};
+struct BeamPartBiasPrefixArgs : BeamPartBiasArgs {
+    const int32_t* pcols;
+};
+template <bool FORCED, bool BIASED, bool PREFIX>
+using BeamPartArgsOf = std::conditional_t<
+    PREFIX, std::conditional_t<BIASED, BeamPartBiasPrefixArgs, BeamPartPrefixArgs>,
+    std::conditional_t<FORCED, BeamPartForcedArgs, std::conditional_t<BIASED, BeamPartBiasArgs, BeamPartArgs>>>;
 // RULES: the decoding-rules variant (ick_decode_select_beam_rules); FORCED: constrained beam search
-// (ick_decode_select_beam_forced); BIASED: column bias (ick_decode_select_beam_biased, §3.2k)
-template <bool RULES, bool FORCED = false, bool BIASED = false>
+// (ick_decode_select_beam_forced); BIASED: column bias (ick_decode_select_beam_biased, §3.2k); PREFIX:
+// caption prefixes (ick_decode_select_beam_prefix, §3.2l)
+template <bool RULES, bool FORCED = false, bool BIASED = false, bool PREFIX = false>
 __global__ __launch_bounds__(256)
-void dec_beam_partial_kernel(BeamPartArgsOf<FORCED, BIASED> a) {
+void dec_beam_partial_kernel(BeamPartArgsOf<FORCED, BIASED, PREFIX> a) {
     static_assert(!(FORCED && BIASED), "the column bias does not compose with forced columns");
+    static_assert(!(FORCED && PREFIX), "a caption prefix does not compose with forced columns");
     if (*a.n_done >= a.n_total) return;
     __shared__ float shv[4];
     __shared__ int shc[4];
@@ -266,6 +278,30 @@ void dec_beam_partial_kernel(BeamPartArgsOf<FORCED, BIASED> a) {
     e = block_sum<4>(e, red);
     float* rec = a.rec + (r * a.nchunk + ch) * kBeamRec;
     if (tid == 0) { rec[0] = m; rec[1] = e; }
+    if constexpr (PREFIX) {
+        // A forced step (uniform: one column per caption and step): the row's pool is that column alone, whatever the
+        // rules ban, so neither the ban pass nor the k arg-best rounds run.  The chunk that holds the column records
+        // it in slot 0 -- its raw score, plus its bias in the biased form -- and every other slot of every chunk is
+        // written as empty: stage 2 reads all k of them.  The maximum and the sum of exp above cover every raw column.
+        const int fc = __builtin_amdgcn_readfirstlane(a.pcols[(r / a.k) * a.max_len + a.step]);
+        if (fc >= 0) {
+            float fb = 0.f;
+            if constexpr (BIASED) {                         // the bias of the column's lowest slot, as in the pool
+                const BiasLanes bl = bias_lanes(a.bcols, a.bvals, r / a.k);
+                const unsigned long long hit = __ballot(bl.col == fc);
+                if (hit) fb = bl.val_of(__ffsll((long long)hit) - 1);
+            }
+            if (tid < a.k) {
+                float v = -INFINITY; int c = kNone;
+                if (tid == 0 && fc < Vx && fc / kBeamChunk == ch) {
+                    v = (fc < a.V ? row[fc] : pr[fc - a.V]) + fb;
+                    c = v == -INFINITY ? kNone : fc;
+                }
+                rec[2 + 2 * tid] = v; rec[3 + 2 * tid] = __int_as_float(c);
+            }
+            return;
+        }
+    }
     if (RULES && (nrep > 0 || a.step < mlen)) {             // uniform: the banned columns leave the pool (not the sums)
         mark_bans(a.seq + r * a.max_len, a.step, nrep, mlen, a.end_token, ban, ch * kBeamChunk, kBeamChunk / 32, hs);
 #pragma unroll
@@ -662,7 +698,7 @@ extern "C" int ick_decode_select_greedy(const ick_decode_ctx* c, int32_t pos, vo
 
 static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, const ick_decode_rules* rules,
                             const ick_decode_diversity* div, const ick_decode_constraints* fc,
-                            const ick_decode_bias* bias, int32_t pos, void* stream) {
+                            const ick_decode_bias* bias, const ick_decode_prefix* px, int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && bs && c->R > 0 && pos >= 0 && pos < c->max_len);
     ICK_CHECK_ARG(c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax && c->R % c->rows_per_sample == 0);
     ICK_CHECK_ARG(c->scores && c->scores_ld >= c->V && c->ptr && c->n_done && c->next_token && c->next_mask &&
@@ -678,7 +714,23 @@ static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, c
     pa.n_done = c->n_done; pa.n_total = c->R;
     pa.seq = bs->seq_in; pa.words = rules ? rules->words : nullptr;
     pa.step = pos; pa.max_len = c->max_len; pa.end_token = c->end_token;
-    if (fc != nullptr) {
+    if (px != nullptr) {
+        // caption prefixes are instantiated on the rules form only, plain and biased (as the column bias is); beam
+        // groups differ in stage 2 alone
+        if (bias != nullptr) {
+            BeamPartBiasPrefixArgs xa;
+            static_cast<BeamPartArgs&>(xa) = pa;
+            xa.bcols = bias->cols; xa.bvals = bias->vals; xa.pcols = px->cols;
+            hipLaunchKernelGGL((dec_beam_partial_kernel<true, false, true, true>), dim3(nchunk, c->R), dim3(256), 0,
+                               (hipStream_t)stream, xa);
+        } else {
+            BeamPartPrefixArgs xa;
+            static_cast<BeamPartArgs&>(xa) = pa;
+            xa.pcols = px->cols;
+            hipLaunchKernelGGL((dec_beam_partial_kernel<true, false, false, true>), dim3(nchunk, c->R), dim3(256), 0,
+                               (hipStream_t)stream, xa);
+        }
+    } else if (fc != nullptr) {
         pa.force = fc->force; pa.met = fc->met;
         void (*part)(BeamPartForcedArgs) = rules ? dec_beam_partial_kernel<true, true> : dec_beam_partial_kernel<false, true>;
         hipLaunchKernelGGL(part, dim3(nchunk, c->R), dim3(256), 0, (hipStream_t)stream, pa);
@@ -721,13 +773,13 @@ static int select_beam_impl(const ick_decode_ctx* c, const ick_beam_state* bs, c
 }
 
 extern "C" int ick_decode_select_beam(const ick_decode_ctx* c, const ick_beam_state* bs, int32_t pos, void* stream) {
-    return select_beam_impl(c, bs, nullptr, nullptr, nullptr, nullptr, pos, stream);
+    return select_beam_impl(c, bs, nullptr, nullptr, nullptr, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_rules(const ick_decode_ctx* c, const ick_beam_state* bs,
                                             const ick_decode_rules* rules, int32_t pos, void* stream) {
     ICK_CHECK_ARG(rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, nullptr, nullptr, nullptr, pos, stream);
+    return select_beam_impl(c, bs, rules, nullptr, nullptr, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_diverse(const ick_decode_ctx* c, const ick_beam_state* bs,
@@ -736,7 +788,7 @@ extern "C" int ick_decode_select_beam_diverse(const ick_decode_ctx* c, const ick
     ICK_CHECK_ARG(c && div && div->penalty && div->groups >= 1 && c->rows_per_sample >= 1 &&
                   c->rows_per_sample % div->groups == 0);
     ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, div, nullptr, nullptr, pos, stream);
+    return select_beam_impl(c, bs, rules, div, nullptr, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_forced(const ick_decode_ctx* c, const ick_beam_state* bs,
@@ -744,7 +796,7 @@ extern "C" int ick_decode_select_beam_forced(const ick_decode_ctx* c, const ick_
                                              int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && fc && fc->force && fc->met && c->rows_per_sample >= 1 && c->rows_per_sample <= kBeamMax);
     ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, nullptr, fc, nullptr, pos, stream);
+    return select_beam_impl(c, bs, rules, nullptr, fc, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_beam_biased(const ick_decode_ctx* c, const ick_beam_state* bs,
@@ -752,5 +804,17 @@ extern "C" int ick_decode_select_beam_biased(const ick_decode_ctx* c, const ick_
                                              void* stream) {
     ICK_CHECK_ARG(c && bias && bias->cols && bias->vals && bias->sum);
     ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
-    return select_beam_impl(c, bs, rules, nullptr, nullptr, bias, pos, stream);
+    return select_beam_impl(c, bs, rules, nullptr, nullptr, bias, nullptr, pos, stream);
+}
+
+extern "C" int ick_decode_select_beam_prefix(const ick_decode_ctx* c, const ick_beam_state* bs,
+                                             const ick_decode_rules* rules, const ick_decode_diversity* div,
+                                             const ick_decode_bias* bias, const ick_decode_prefix* px, int32_t pos,
+                                             void* stream) {
+    ICK_CHECK_ARG(c && px && px->cols && !(div && bias));
+    ICK_CHECK_ARG(div == nullptr || (div->penalty && div->groups >= 1 && c->rows_per_sample >= 1 &&
+                                     c->rows_per_sample % div->groups == 0));
+    ICK_CHECK_ARG(bias == nullptr || (bias->cols && bias->vals && bias->sum));
+    ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, true));
+    return select_beam_impl(c, bs, rules, div, nullptr, bias, px, pos, stream);
 }

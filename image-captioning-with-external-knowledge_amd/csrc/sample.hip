@@ -98,12 +98,61 @@ __device__ __forceinline__ void scan_desc(const T* hist, T need, T above, int* d
     }
 }
 
+// The caption-prefix variant (PREFIX) appends the forced column of every step (R / rows_per_sample, max_len), -1 = a free
+// step, to the plain and to the biased arguments, again for its own instantiations alone.
+struct SamplePrefixArgs : SampleArgs {
+    const int32_t* pcols;
+};
+struct SampleBiasPrefixArgs : SampleBiasArgs {
+    const int32_t* pcols;
+};
+template <bool BIASED, bool PREFIX>
+using SampleArgsOf = std::conditional_t<PREFIX, std::conditional_t<BIASED, SampleBiasPrefixArgs, SamplePrefixArgs>,
+                                        std::conditional_t<BIASED, SampleBiasArgs, SampleArgs>>;
+
+// Thread 0 records the token of step i of row r: column bc with raw score bs, under the row's raw maximum m and sum of
+// exp(s - m).  tok_sh receives the next input token and its mask.
+__device__ __forceinline__ void record_token(const SampleArgs& a, int64_t r, int i, int bc, float bs, float m, float sum,
+                                             int64_t* tok_sh) {
+    int64_t* o = a.output + r * a.max_len;
+    if (a.log_prob != nullptr) a.log_prob[r * a.max_len + i] = (bs - m) - logf(sum);
+    o[i] = bc;
+    int64_t tok = 0, msk = 0;
+    if (bc == a.end_token) {
+        a.finished[r] = 1;
+        atomicAdd(a.n_done, 1);
+    } else {
+        tok = bc;
+        msk = token_kind(bc, a.V, a.K, a.has_facts);
+    }
+    tok_sh[0] = tok;
+    tok_sh[1] = msk;
+}
+
+// After the step's token is in tok_sh (and a barrier): the row's next input token and mask, its caption buffer, and
+// CaptionEmbedder + sqrt(d) scale + PositionEncoder of the next input token (as dec_select_kernel).
+__device__ __forceinline__ void feed_next(const SampleArgs& a, int64_t r, int i, const int64_t* tok_sh) {
+    const int tid = threadIdx.x;
+    const int64_t tok = tok_sh[0], msk = tok_sh[1];
+    if (tid == 0) {
+        a.next_token[r] = tok;
+        a.next_mask[r] = msk;
+        if (a.cap_buf != nullptr && i + 1 < a.max_len) a.cap_buf[r * a.max_len + i + 1] = tok;
+    }
+    if (i + 1 >= a.max_len) return;
+    const float* src = token_row(tok, (int)msk, r / a.rows_per_sample, a.word_emb, a.ee, a.fe, a.V, a.K, a.F, a.d,
+                                 a.pad_token);
+    const float* pe = a.pe + (int64_t)(i + 1) * a.d;
+    for (int c = tid; c < a.d; c += kSNT) a.x0[r * a.d + c] = fmaf(src[c], a.emb_scale, pe[c]);
+}
+
 // NG = groups of 4 columns a lane holds in registers: 4 (Vx <= 16 384, cfg5) keeps them in VGPRs; 16 (cfg4's 50 071)
 // exceeds the 128 registers a lane of a 1024-thread workgroup has and spills part of the row to scratch.
 // RULES: the decoding-rules variant (ick_decode_select_sample_rules); the rule-free one compiles without the ban pass.
 // BIASED: column bias (ick_decode_select_sample_biased), on the rules form.
-template <int NG, bool RULES, bool BIASED = false>
-__global__ __launch_bounds__(kSNT) void dec_sample_kernel(std::conditional_t<BIASED, SampleBiasArgs, SampleArgs> a) {
+// PREFIX: caption prefixes (ick_decode_select_sample_prefix), on the rules form, plain and biased.
+template <int NG, bool RULES, bool BIASED = false, bool PREFIX = false>
+__global__ __launch_bounds__(kSNT) void dec_sample_kernel(SampleArgsOf<BIASED, PREFIX> a) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int64_t r = blockIdx.x;
     const int i = a.step;
@@ -140,6 +189,51 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(std::conditional_t<BIA
     __shared__ int hs[kRuleHistMax];
     __shared__ int all_sh;
 
+    // A forced step of a caption prefix (uniform: one caption per workgroup, so the barriers below are met by every
+    // thread): the token is the given column, whatever the rules ban -- no ban pass, bias, top-k, top-p or noise.  The
+    // raw maximum and sum of exp are formed as below, over the same columns per lane and in the same order, but
+    // streamed from the score row (it is read twice, from cache the second time) instead of held in registers; thread 0
+    // then records the column with its raw score as it records a drawn one, and the step ends as every step does.
+    if constexpr (PREFIX) {
+        const int fcol = __builtin_amdgcn_readfirstlane(a.pcols[(r / a.rows_per_sample) * a.max_len + i]);
+        const int np = a.K + a.F, Vx = a.V + np;
+        if (!fin && fcol >= 0 && fcol < Vx) {
+            const int ng = (Vx + 4 * kSNT - 1) / (4 * kSNT);
+            const float* srow = a.scores + r * a.ld;
+            const float* prow = a.ptr + r * np;
+            float m = -INFINITY;
+            for (int g = 0; g < ng; ++g)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c = (g * kSNT + tid) * 4 + q;
+                    if (c < Vx) m = fmaxf(m, c < a.V ? srow[c] : prow[c - a.V]);
+                }
+            m = wave_max(m);
+            if (lane == 0) red[0][wid] = m;
+            __syncthreads();
+            m = red[0][0];
+#pragma unroll
+            for (int w = 1; w < kSNW; ++w) m = fmaxf(m, red[0][w]);
+            float se = 0.f;
+            for (int g = 0; g < ng; ++g)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c = (g * kSNT + tid) * 4 + q;
+                    if (c < Vx) se += expf((c < a.V ? srow[c] : prow[c - a.V]) - m);
+                }
+            se = wave_sum(se);
+            if (lane == 0) red[1][wid] = se;
+            __syncthreads();
+            if (tid == 0) {
+                float sum = red[1][0];
+                for (int w = 1; w < kSNW; ++w) sum += red[1][w];
+                record_token(a, r, i, fcol, fcol < a.V ? srow[fcol] : prow[fcol - a.V], m, sum, tok_sh);
+            }
+            __syncthreads();
+            feed_next(a, r, i, tok_sh);
+            return;
+        }
+    }
     const uint4 rw = RULES ? rule_words(a.words) : make_uint4(0u, 0u, 0u, 0u);
     const int nrep = (int)rw.x, mlen = (int)rw.y;
     // decoding rules (uniform): banned columns are absent from top-k, top-p and the draw -- not from the log-softmax
@@ -363,37 +457,14 @@ __global__ __launch_bounds__(kSNT) void dec_sample_kernel(std::conditional_t<BIA
             if constexpr (BIASED) {         // log_prob is the model's: the drawn column's raw score, from the score row
                 if (bc < Vx) bs = bc < a.V ? srow[bc] : prow[bc - a.V];
             }
-            int64_t* o = a.output + r * a.max_len;
-            if (a.log_prob != nullptr) a.log_prob[r * a.max_len + i] = (bs - m) - logf(sum);
-            o[i] = bc;
-            int64_t tok = 0, msk = 0;
-            if (bc == a.end_token) {
-                a.finished[r] = 1;
-                atomicAdd(a.n_done, 1);
-            } else {
-                tok = bc;
-                msk = token_kind(bc, a.V, a.K, a.has_facts);
-            }
-            tok_sh[0] = tok;
-            tok_sh[1] = msk;
+            record_token(a, r, i, bc, bs, m, sum, tok_sh);
         }
     } else if (tid == 0) {
         tok_sh[0] = 0;
         tok_sh[1] = 0;
     }
     __syncthreads();
-    const int64_t tok = tok_sh[0], msk = tok_sh[1];
-    if (tid == 0) {
-        a.next_token[r] = tok;
-        a.next_mask[r] = msk;
-        if (a.cap_buf != nullptr && i + 1 < a.max_len) a.cap_buf[r * a.max_len + i + 1] = tok;
-    }
-    if (i + 1 >= a.max_len) return;
-    // CaptionEmbedder + sqrt(d) scale + PositionEncoder of the next input token (as dec_select_kernel)
-    const float* src = token_row(tok, (int)msk, r / a.rows_per_sample, a.word_emb, a.ee, a.fe, a.V, a.K, a.F, a.d,
-                                 a.pad_token);
-    const float* pe = a.pe + (int64_t)(i + 1) * a.d;
-    for (int c = tid; c < a.d; c += kSNT) a.x0[r * a.d + c] = fmaf(src[c], a.emb_scale, pe[c]);
+    feed_next(a, r, i, tok_sh);
 }
 
 }  // namespace
@@ -406,7 +477,7 @@ extern "C" int ick_decode_sample_supported(int32_t Vx, int32_t rows_per_sample) 
 }
 
 static int select_sample_impl(const ick_decode_ctx* c, const ick_sample_state* s, const ick_decode_rules* rules,
-                              const ick_decode_bias* bias, int32_t pos, void* stream) {
+                              const ick_decode_bias* bias, const ick_decode_prefix* px, int32_t pos, void* stream) {
     ICK_CHECK_ARG(c && s && c->R > 0 && c->R <= 65535 && pos >= 0 && pos < c->max_len);
     ICK_CHECK_ARG(c->rows_per_sample >= 1 && c->R % c->rows_per_sample == 0);
     ICK_CHECK_ARG(c->V > 0 && c->K > 0 && c->F >= 0 && c->end_token >= 0 && c->end_token < c->V);
@@ -429,11 +500,29 @@ static int select_sample_impl(const ick_decode_ctx* c, const ick_sample_state* s
     const bool small = c->V + c->K + c->F <= 4 * 4 * kSNT;
     if (bias != nullptr) {
         // the column bias is instantiated on the rules form only: without rules the rule words read as zero
+        if (px != nullptr) {            // caption prefixes: on the rules form only as well, plain (below) and biased
+            SampleBiasPrefixArgs xa;
+            static_cast<SampleArgs&>(xa) = a;
+            xa.bcols = bias->cols; xa.bvals = bias->vals; xa.pcols = px->cols;
+            void (*kern)(SampleBiasPrefixArgs) = small ? dec_sample_kernel<4, true, true, true>
+                                                       : dec_sample_kernel<kSGMax, true, true, true>;
+            hipLaunchKernelGGL(kern, dim3(c->R), dim3(kSNT), 0, (hipStream_t)stream, xa);
+            ICK_LAUNCH_RET();
+        }
         SampleBiasArgs ba;
         static_cast<SampleArgs&>(ba) = a;
         ba.bcols = bias->cols; ba.bvals = bias->vals;
         void (*kern)(SampleBiasArgs) = small ? dec_sample_kernel<4, true, true> : dec_sample_kernel<kSGMax, true, true>;
         hipLaunchKernelGGL(kern, dim3(c->R), dim3(kSNT), 0, (hipStream_t)stream, ba);
+        ICK_LAUNCH_RET();
+    }
+    if (px != nullptr) {
+        SamplePrefixArgs xa;
+        static_cast<SampleArgs&>(xa) = a;
+        xa.pcols = px->cols;
+        void (*kern)(SamplePrefixArgs) = small ? dec_sample_kernel<4, true, false, true>
+                                               : dec_sample_kernel<kSGMax, true, false, true>;
+        hipLaunchKernelGGL(kern, dim3(c->R), dim3(kSNT), 0, (hipStream_t)stream, xa);
         ICK_LAUNCH_RET();
     }
     void (*kern)(SampleArgs) = rules == nullptr ? (small ? dec_sample_kernel<4, false> : dec_sample_kernel<kSGMax, false>)
@@ -443,13 +532,13 @@ static int select_sample_impl(const ick_decode_ctx* c, const ick_sample_state* s
 }
 
 extern "C" int ick_decode_select_sample(const ick_decode_ctx* c, const ick_sample_state* s, int32_t pos, void* stream) {
-    return select_sample_impl(c, s, nullptr, nullptr, pos, stream);
+    return select_sample_impl(c, s, nullptr, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_sample_rules(const ick_decode_ctx* c, const ick_sample_state* s,
                                               const ick_decode_rules* rules, int32_t pos, void* stream) {
     ICK_CHECK_ARG(rules_ok(c, rules, false));
-    return select_sample_impl(c, s, rules, nullptr, pos, stream);
+    return select_sample_impl(c, s, rules, nullptr, nullptr, pos, stream);
 }
 
 extern "C" int ick_decode_select_sample_biased(const ick_decode_ctx* c, const ick_sample_state* s,
@@ -457,5 +546,14 @@ extern "C" int ick_decode_select_sample_biased(const ick_decode_ctx* c, const ic
                                                void* stream) {
     ICK_CHECK_ARG(c && bias && bias->cols && bias->vals);
     ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, false));
-    return select_sample_impl(c, s, rules, bias, pos, stream);
+    return select_sample_impl(c, s, rules, bias, nullptr, pos, stream);
+}
+
+extern "C" int ick_decode_select_sample_prefix(const ick_decode_ctx* c, const ick_sample_state* s,
+                                               const ick_decode_rules* rules, const ick_decode_bias* bias,
+                                               const ick_decode_prefix* px, int32_t pos, void* stream) {
+    ICK_CHECK_ARG(c && px && px->cols);
+    ICK_CHECK_ARG(bias == nullptr || (bias->cols && bias->vals));
+    ICK_CHECK_ARG(rules == nullptr || rules_ok(c, rules, false));
+    return select_sample_impl(c, s, rules, bias, px, pos, stream);
 }

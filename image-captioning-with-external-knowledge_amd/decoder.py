@@ -308,6 +308,62 @@ def check_column_bias(what, B, Vx, word_map, column_bias=None, num_beam_groups=1
     return bias_tensors(B, ids, vals)
 
 
+def check_prefix(what, B, Vx, max_len, word_map, prefix=None, force_tokens=None, bias=None):
+    """Validate the prefix of predict_beam / predict_sample (IckError): None, or an integer tensor / nested list (B, Pn) or
+    (Pn,), 1 <= Pn <= max_len (a (Pn,) value goes to every caption), of column ids in [0, Vx) numbered as force_tokens
+    numbers them, -1 padding a shorter prefix at its end; in nested lists a string is a word of word_map, and rows of
+    unequal length are padded.  <start>, <end> and <pad> cannot be given.  bias: check_column_bias()'s pair or None -- a
+    -inf bias on a column of the same caption's prefix is refused.  Returns None, or the device form as a CPU tensor:
+    int32 (B, max_len), the forced column of every step and -1 for a free step (its shape does not depend on Pn)."""
+    if prefix is None:
+        return None
+    if force_tokens is not None:
+        raise IckError("%s: prefix does not compose with force_tokens" % what)
+    shape_msg = "%s needs prefix as an integer tensor or nested list (B = %d, 1..max_pred_len = %d) or " \
+                "(1..%d,)" % (what, B, max_len, max_len)
+    px = prefix
+    if not torch.is_tensor(px):
+        def word(v):
+            if isinstance(v, str):
+                if v not in word_map:
+                    raise IckError("%s: prefix names the unknown word %r" % (what, v))
+                return word_map[v]
+            return v
+        if isinstance(px, (list, tuple)) and len(px) > 0 and all(isinstance(r, (list, tuple)) for r in px):
+            width = max(len(r) for r in px)
+            px = [[word(v) for v in r] + [-1] * (width - len(r)) for r in px]
+        elif isinstance(px, (list, tuple)):
+            px = [word(v) for v in px]
+        try:
+            px = torch.tensor(px)
+        except (TypeError, ValueError, RuntimeError):
+            raise IckError(shape_msg)
+    if px.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or px.dim() not in (1, 2) or \
+            (px.dim() == 2 and px.shape[0] != B) or not 1 <= px.shape[-1] <= max_len:
+        raise IckError(shape_msg)
+    px = px.detach().to("cpu", torch.int64)                  # one small read-back per call
+    if px.dim() == 1:
+        px = px.view(1, -1).expand(B, -1)
+    if bool((px < -1).any()) or bool((px >= Vx).any()):
+        raise IckError("%s: prefix holds column ids in [0, V+K+F = %d), or -1 behind a shorter prefix" % (what, Vx))
+    for w in ("<start>", "<end>", "<pad>"):
+        if w in word_map and bool((px == word_map[w]).any()):
+            raise IckError("%s: %s cannot be part of a prefix" % (what, w))
+    free = px < 0
+    if bool((free[:, :-1] & ~free[:, 1:]).any()):
+        raise IckError("%s: prefix holds a column id behind a -1 (-1 only pads a prefix at its end)" % what)
+    if bias is not None:
+        never = torch.where(bias[1] == float("-inf"), bias[0].to(torch.int64), torch.full_like(bias[0], -2, dtype=torch.int64))
+        clash = (px.unsqueeze(2) == never.unsqueeze(1)).any(dim=2)                          # (B, Pn)
+        if bool(clash.any()):
+            b, t = [int(v) for v in clash.nonzero()[0]]
+            raise IckError("%s: column_bias bans (-inf) column %d, which caption %d's prefix holds at step %d"
+                           % (what, int(px[b, t]), b, t))
+    out = torch.full((B, max_len), -1, dtype=torch.int32)
+    out[:, :px.shape[1]] = px.to(torch.int32)
+    return out
+
+
 def check_score_args(what, has_facts, captions, encoder_out, caption_masks, caption_lengths, entities, facts=None,
                      image_index=None, top_k=5):
     """Validate the arguments of score_captions (IckError); shapes only, so it runs on tensors of any device.  Returns
@@ -1435,7 +1491,7 @@ class DecoderTransformer(nn.Module):
         return t["output"]
 
     def _predict_beam_device(self, enc_tok, entities, facts, max_pred_len, beam, attention=False, rules=None, groups=1,
-                             penalty=None, force=None, bias=None):
+                             penalty=None, force=None, bias=None, prefix=None):
         """Beam search on the fused decode kernels: R = B * beam rows share their caption's cross K/V; the
         self-attention cache is never reordered -- an ancestry table says which cache row holds position p of a
         hypothesis.  Returns a _BeamResult: the best sequence (B, max_len), its log-probability (B), all sequences, all
@@ -1449,7 +1505,10 @@ class DecoderTransformer(nn.Module):
         device tensor of check_force() (read at run time) or None; with it the search is the constrained one of
         DESIGN.md §3.2g and the best hypothesis is the best by (met slots, key).  bias: the (B, 64) int32 ids and fp32
         values of check_column_bias() on the device (read at run time) or None; with it every hypothesis carries the sum
-        of the biases it has emitted and the best hypothesis is the best by the key with that sum."""
+        of the biases it has emitted and the best hypothesis is the best by the key with that sum.
+        prefix: the (B, max_len) int32 table of check_prefix() on the device (read at run time) or None; with it a caption
+        keeps one live hypothesis (one per group) through its forced steps, and a slot that was never
+        used is returned with a -inf score and a <pad> row."""
         from . import lib as L
         B = enc_tok.shape[0]
         d, V, K = self.emb_dim, self.vocab_size, entities.shape[1]
@@ -1493,6 +1552,10 @@ class DecoderTransformer(nn.Module):
             bsum = torch.zeros(R, dtype=torch.float32, device=dev)
             cb = L.DecodeBias()
             cb.cols, cb.vals, cb.sum = bias[0].data_ptr(), bias[1].data_ptr(), bsum.data_ptr()
+        px = None
+        if prefix is not None:
+            px = L.DecodePrefix()
+            px.cols = prefix.data_ptr()
         for i in range(max_pred_len):
             cur, nxt = i & 1, (i + 1) & 1
             c.anc = anc[cur].data_ptr()
@@ -1501,8 +1564,10 @@ class DecoderTransformer(nn.Module):
             self._decode_step(c, t, cap and cap[cur], facts_r, K, i, attn)
             bs.seq_in, bs.seq_out = seq[cur].data_ptr(), seq[nxt].data_ptr()
             bs.anc_in, bs.anc_out = anc[cur].data_ptr(), anc[nxt].data_ptr()
-            ops.decode_select_beam(c, bs, i, rs, dv, fc, cb)
+            ops.decode_select_beam(c, bs, i, rs, dv, fc, cb, px)
         final = seq[max_pred_len & 1].view(B, beam, max_pred_len)
+        if prefix is not None:                            # a slot no hypothesis ever filled: a <pad> row
+            final = final.masked_fill((cum == float("-inf")).view(B, beam, 1), self.word_map["<pad>"])
         key = cum if bias is None else cum + bsum.view(B, beam)       # the kernel's ranking key
         if rules is None:
             best = key.argmax(dim=1)                      # ties: the lower hypothesis
@@ -1535,7 +1600,7 @@ class DecoderTransformer(nn.Module):
     @torch.no_grad()
     def predict_beam(self, encoder_out, max_pred_len, entities, facts=None, beam_size=5, return_all=False,
                      return_attention=False, length_penalty=0.0, no_repeat_ngram_size=0, min_len=0, num_beam_groups=1,
-                     diversity_penalty=0.0, return_groups=False, force_tokens=None, column_bias=None):
+                     diversity_penalty=0.0, return_groups=False, force_tokens=None, column_bias=None, prefix=None):
         """Beam-search decode (north_star cfg5: beam 5, batch 32).  The reference decodes greedily only
         (geo-aware/eval.py:61,83), so beam > 1 has no reference output to pin against ("parity-unpinned"); the tests
         check it against a CPU beam search written to the same rules.  beam_size == 1 IS predict(): the pinned greedy path with
@@ -1585,7 +1650,32 @@ class DecoderTransformer(nn.Module):
         one does, and a rule ban wins over a bias.  Every returned score stays the model's log-probability.  Ids and
         values are device inputs of the captured graph (new values, ids or another C replay it); all slots empty or all
         values 0 give the bits of the call without the argument.  The rules compose; not with num_beam_groups > 1 or
-        force_tokens.  beam_size == 1 with a bias runs the beam kernels with one hypothesis."""
+        force_tokens.  beam_size == 1 with a bias runs the beam kernels with one hypothesis.
+
+        Caption prefixes (elsewhere decoder_input_ids or a forced prefix): prefix starts every caption
+        from tokens the caller already has.  It is an integer tensor or nested list (B, Pn), 1 <= Pn <= max_pred_len, of
+        columns numbered as force_tokens numbers them (a word id, V + k for entity slot k, V + K + j for fact j); -1
+        pads a shorter prefix at its end, a (Pn,) value goes to every caption, and in nested lists a string is a word of
+        word_map (rows of unequal length are padded).  <start>, <end> and <pad> cannot be given.  With p_b the number of
+        leading non-negative entries of caption b: at step t < p_b the only candidate of a live hypothesis is column
+        prefix[b][t] -- it wins over the rule bans and over finite biases -- while the log-softmax still runs over every
+        raw column, so a returned score is the model's log-probability of the WHOLE returned caption, prefix included,
+        and score_tokens() of the result agrees with it.  Through its prefix a caption has one live hypothesis (one
+        per group); step p_b fans out from it as step 0 of the plain search does, and from there on the call is the
+        call without a prefix.  The prefix tokens count as generated tokens everywhere: n-gram history, min_len, the
+        length L of the length penalty, the bias sum, the fact-aware caption buffer and the attention maps.  With
+        p_b = max_pred_len nothing fans out: under return_all the other beam_size - 1 (beam_size - G) slots come back
+        unused, with a -inf score and a <pad> row.  The table is a device input of the captured graph and its shape
+        does not depend on Pn: new ids and new lengths replay it.  A caption whose row is all -1 gets the search
+        without a prefix, bit for bit; None, the default, is the call without the argument.  It composes with the
+        rules, num_beam_groups / return_groups, column_bias (a -inf bias on a column of the same caption's prefix is
+        refused), return_all and return_attention; not with force_tokens.  beam_size == 1 with a prefix runs the beam
+        kernels with one hypothesis; predict() does not take the argument.  "One caption per entity" is
+        prefix=[[V + k]] for k in turn.  The attention maps of a GIVEN caption -- where the model looks for each
+        of its words -- are a whole-caption prefix with return_attention:
+            toks = caption[:, 1:1 + max_pred_len]            # the tokens after <start>, before <end>
+            _, attn = decoder.predict_beam(enc, max_pred_len, entities, beam_size=1, prefix=toks, return_attention=True)
+        (attn[t, b] belongs to the step that produced toks[b][t]; split_attention() splits its S axis)."""
         P_ = entities.shape[1] + (facts.shape[1] if facts is not None else 0)
         rules_on = check_rules("predict_beam", max_pred_len, self.vocab_size + P_, length_penalty,
                                no_repeat_ngram_size, min_len)
@@ -1594,7 +1684,9 @@ class DecoderTransformer(nn.Module):
                             [self.word_map[w] for w in ("<start>", "<end>", "<pad>")], force_tokens, num_beam_groups)
         bias = check_column_bias("predict_beam", encoder_out.shape[0], self.vocab_size + P_, self.word_map, column_bias,
                                  num_beam_groups, force_tokens)
-        if beam_size == 1 and not rules_on and force is None and bias is None:
+        ptab = check_prefix("predict_beam", encoder_out.shape[0], self.vocab_size + P_, max_pred_len, self.word_map,
+                            prefix, force_tokens, bias)
+        if beam_size == 1 and not rules_on and force is None and bias is None and ptab is None:
             return DecoderTransformer.predict(self, encoder_out, max_pred_len, entities, facts,
                                               return_attention=return_attention)
         enc_tok, entities, facts, _, _ = self._decode_front(
@@ -1611,16 +1703,18 @@ class DecoderTransformer(nn.Module):
         inputs = [enc_tok, entities, facts] + ([rules, extra] if extra is not None else [rules] if rules_on else [])
         if bias is not None:
             inputs = [enc_tok, entities, facts, rules, _bias_input(bias, enc_tok.device)]
+        if ptab is not None:        # (rules and the variant's input may be None: every prefix call has the same arity)
+            inputs = [enc_tok, entities, facts, rules, inputs[4] if len(inputs) > 4 else None, ptab.to(enc_tok.device)]
 
-        def run(t, e, f, r=None, x=None):
+        def run(t, e, f, r=None, x=None, p=None):
             return self._predict_beam_device(t, e, f, max_pred_len, beam_size, return_attention, r, G,
                                              x if diverse else None, x if forced else None,
-                                             _bias_views(x) if bias is not None else None)
+                                             _bias_views(x) if bias is not None else None, p)
 
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, beam_size) + self._enc_key(enc_tok) + ((G,) if diverse else ())
-            kind = "beam" + ("_force" if forced else "_div" if diverse else "_bias" if bias is not None else "") + \
+            kind = "beam" + ("_prefix" if ptab is not None else "") + ("_force" if forced else "_div" if diverse else "_bias" if bias is not None else "") + \
                 ("_rules" if rules_on else "") + \
                 ("_attn" if return_attention else "")
             res = self._graphed(kind, key, run, inputs)
@@ -1637,12 +1731,13 @@ class DecoderTransformer(nn.Module):
         return out, attn.clone()
 
     def _predict_sample_device(self, enc_tok, entities, facts, knobs, max_pred_len, n, attention=False, rules=None,
-                               bias=None):
+                               bias=None, prefix=None):
         """Sampled decode on the fused decode kernels: R = B * n rows, the n samples of a caption share its cross K/V
         and keep their own self-attention caches.  knobs: int64 (3) device tensor [seed, temperature | top_p << 32
         (two fp32 words), top_k] -- read by the selection kernel, so a replay sees whatever was copied into it.
         rules: a rules_tensor() (read the same way) or None; bias: the (B, 64) ids and values of check_column_bias() on
-        the device (read the same way) or None.  Returns (tokens (R, max_len), log-probabilities (R, max_len)[, cross-attention weights (max_len, R, layers, H,
+        the device (read the same way) or None; prefix: the (B, max_len) int32 table of check_prefix() on the device (read
+        the same way) or None.  Returns (tokens (R, max_len), log-probabilities (R, max_len)[, cross-attention weights (max_len, R, layers, H,
         S)])."""
         from . import lib as L
         dev = enc_tok.device
@@ -1661,9 +1756,13 @@ class DecoderTransformer(nn.Module):
         if bias is not None:
             cb = L.DecodeBias()
             cb.cols, cb.vals = bias[0].data_ptr(), bias[1].data_ptr()
+        px = None
+        if prefix is not None:
+            px = L.DecodePrefix()
+            px.cols = prefix.data_ptr()
         for i in range(max_pred_len):
             self._decode_step(c, t, t.get("cap_buf"), facts_r, K, i, attn)
-            ops.decode_select_sample(c, st, i, rs, cb)
+            ops.decode_select_sample(c, st, i, rs, cb, px)
         if attention:
             return t["output"], log_prob, _zero_after_end(attn, t["output"], self.word_map["<end>"])
         return t["output"], log_prob
@@ -1671,7 +1770,7 @@ class DecoderTransformer(nn.Module):
     @torch.no_grad()
     def predict_sample(self, encoder_out, max_pred_len, entities, facts=None, num_samples=1, temperature=1.0, top_k=0,
                        top_p=1.0, seed=None, return_log_probs=False, return_attention=False, no_repeat_ngram_size=0,
-                       min_len=0, column_bias=None):
+                       min_len=0, column_bias=None, prefix=None):
         """Stochastic decode: `num_samples` captions per image drawn from the model's distribution, with temperature,
         top-k and nucleus (top-p) truncation.  Per row and step over the V+K+F raw scores s: z = s / temperature;
         top-k keeps s >= the k-th largest s (ties at the boundary all kept); top-p then keeps the tokens whose
@@ -1698,11 +1797,22 @@ class DecoderTransformer(nn.Module):
         top-k threshold, z = s' / temperature, the top-p weights and the Gumbel arg-max; a -inf column is absent like a
         banned one.  The noise of a column does not change, so a step at which no biased column is near the draw draws
         the token it drew before; return_log_probs stays log_softmax of the raw scores.  A bias on <end> is the length
-        control of sampling.  Ids and values are inputs of the captured graph."""
+        control of sampling.  Ids and values are inputs of the captured graph.
+
+        Caption prefixes (as predict_beam's prefix): every sample of caption b starts with prefix[b].
+        A forced step draws nothing -- no top-k, no top-p, no noise -- and wins over the rule bans and the bias;
+        return_log_probs holds the model's log-probability of the prefix tokens as well.  The noise is keyed by (seed,
+        caption, sample, step, column), so the later steps draw what they would have drawn: feeding back the first p
+        tokens of a sample with the seed it was drawn with reproduces that sample.  num_samples continuations of one
+        opening are prefix=opening with num_samples > 1.  The table is an input of the captured graph (new ids and
+        lengths replay it); a row of -1 gets the draw without a prefix, bit for bit.  The attention maps of a given
+        caption are a whole-caption prefix with return_attention (see predict_beam)."""
         P_ = entities.shape[1] + (facts.shape[1] if facts is not None else 0)
         rules_on = check_rules("predict_sample", max_pred_len, self.vocab_size + P_, 0.0, no_repeat_ngram_size, min_len)
         bias = check_column_bias("predict_sample", encoder_out.shape[0], self.vocab_size + P_, self.word_map,
                                  column_bias)
+        ptab = check_prefix("predict_sample", encoder_out.shape[0], self.vocab_size + P_, max_pred_len, self.word_map,
+                            prefix, None, bias)
         if not (isinstance(num_samples, int) and num_samples >= 1):
             raise IckError("predict_sample needs num_samples >= 1")
         if not (math.isfinite(temperature) and temperature > 0):
@@ -1725,15 +1835,18 @@ class DecoderTransformer(nn.Module):
         inputs = [enc_tok, entities, facts, knobs] + ([rules] if rules_on else [])
         if bias is not None:
             inputs = [enc_tok, entities, facts, knobs, rules, _bias_input(bias, enc_tok.device)]
+        if ptab is not None:
+            inputs = [enc_tok, entities, facts, knobs, rules, inputs[5] if bias is not None else None,
+                      ptab.to(enc_tok.device)]
 
-        def run(t, e, f, k, r=None, x=None):
+        def run(t, e, f, k, r=None, x=None, p=None):
             return self._predict_sample_device(t, e, f, k, max_pred_len, num_samples, return_attention, r,
-                                               None if x is None else _bias_views(x))
+                                               None if x is None else _bias_views(x), p)
 
         if self.use_hip_graphs:
             key = (tuple(enc_tok.shape), tuple(entities.shape), None if facts is None else tuple(facts.shape),
                    max_pred_len, num_samples) + self._enc_key(enc_tok)
-            kind = "sample" + ("_bias" if bias is not None else "") + ("_rules" if rules_on else "") + \
+            kind = "sample" + ("_prefix" if ptab is not None else "") + ("_bias" if bias is not None else "") + ("_rules" if rules_on else "") + \
                 ("_attn" if return_attention else "")
             res = self._graphed(kind, key, run, inputs)
         else:

@@ -52,7 +52,8 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
     row per (image, group) with the columns image, group, generated_caption, the best hypothesis of each group;
     force_tokens (constrained beam search) is a callable fn(batch_index, batch) -> the (B, C) forced column ids of
     that batch, since one tensor cannot fit every batch; column_bias (in beam or sample) is predict_beam's value -- a
-    dict or a pair for every batch -- or such a callable; beam and sample together are a ValueError.
+    dict or a pair for every batch -- or such a callable, and prefix (in beam or sample) is predict_beam's value or such a
+    callable; beam and sample together are a ValueError.
     attention_out: a path for one .npz of the decoder's cross-attention (return_attention of predict / predict_sample):
     "attention" float16 (N, max_len, S), the last decoder layer's weights averaged over its heads, one row per CSV row;
     "tokens" int64 (N, max_len); "P", "K", "F": how the S memory rows split into image, entity and fact rows.  With
@@ -109,6 +110,8 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
                 kw["force_tokens"] = kw["force_tokens"](bi, batch)
             if callable(kw.get("column_bias")):              # the bias of this batch
                 kw["column_bias"] = kw["column_bias"](bi, batch)
+            if callable(kw.get("prefix")):                   # the caption prefixes of this batch
+                kw["prefix"] = kw["prefix"](bi, batch)
             seq = decoder.predict_beam(enc_in, max_caption_len, ent, *extra, return_attention=want_attn, **kw)
         elif sample is None:
             seq = decoder.predict(enc_in, max_caption_len, ent, *extra, return_attention=want_attn)  # (max_len, B)
@@ -119,6 +122,8 @@ def evaluate(encoder, decoder, loader, word_map, max_caption_len=30, out_csv="ge
             kw.pop("return_log_probs", None)
             if callable(kw.get("column_bias")):
                 kw["column_bias"] = kw["column_bias"](bi, batch)
+            if callable(kw.get("prefix")):
+                kw["prefix"] = kw["prefix"](bi, batch)
             seq = decoder.predict_sample(enc_in, max_caption_len, ent, *extra, return_attention=want_attn, **kw)
         if want_attn:
             seq, attn = seq

@@ -172,6 +172,10 @@ class DecodeBias(C.Structure):      # ick_decode_bias: column ids (B, 64) int32,
     _fields_ = [(n, vp) for n in ("cols", "vals", "sum")]
 
 
+class DecodePrefix(C.Structure):    # ick_decode_prefix: forced column of every step (B, max_len) int32, -1 = a free step
+    _fields_ = [("cols", vp)]
+
+
 # name -> argtypes; every entry returns int (0 ok, <0 ICK_E*, >0 hipError_t)
 SIGNATURES = {
     "ick_version": [],
@@ -229,6 +233,10 @@ SIGNATURES = {
                                       C.POINTER(DecodeBias), i32, vp],
     "ick_decode_select_sample_biased": [C.POINTER(DecodeCtx), C.POINTER(SampleState), C.POINTER(DecodeRules),
                                         C.POINTER(DecodeBias), i32, vp],
+    "ick_decode_select_beam_prefix": [C.POINTER(DecodeCtx), C.POINTER(BeamState), C.POINTER(DecodeRules),
+                                      C.POINTER(DecodeDiversity), C.POINTER(DecodeBias), C.POINTER(DecodePrefix), i32, vp],
+    "ick_decode_select_sample_prefix": [C.POINTER(DecodeCtx), C.POINTER(SampleState), C.POINTER(DecodeRules),
+                                        C.POINTER(DecodeBias), C.POINTER(DecodePrefix), i32, vp],
     "ick_attention_bwd": [C.POINTER(AttnBwdArgs), vp],
     "ick_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, f32, u32, u32, vp, vp, vp],
     "ick_layernorm_bwd_rows_per_block": [],

@@ -700,12 +700,19 @@ def _ref(s):
     return None if s is None else C.byref(s)
 
 
-def decode_select_beam(ctx, beam_state, pos, rules=None, diversity=None, constraints=None, bias=None):
+def decode_select_beam(ctx, beam_state, pos, rules=None, diversity=None, constraints=None, bias=None, prefix=None):
     """Beam selection of step `pos` (ick_decode_select_beam), under decoding rules (lib.DecodeRules: n-gram / min-length
     bans, length penalty) or none, as plain, diverse (lib.DecodeDiversity: groups, penalty: ick_..._diverse) or
     constrained beam search (lib.DecodeConstraints: force, met: ick_..._forced), or with a column bias (lib.DecodeBias:
-    cols, vals, sum: ick_..._biased; not with groups or forced columns)."""
-    if bias is not None:
+    cols, vals, sum: ick_..._biased; not with groups or forced columns).  prefix: lib.DecodePrefix (cols: the forced column
+    of every step, ick_..._prefix), with the rules, groups or a bias; not with forced columns."""
+    if prefix is not None:
+        if constraints is not None:
+            raise L.IckError("decode_select_beam: a caption prefix does not compose with forced columns")
+        if diversity is not None and bias is not None:
+            raise L.IckError("decode_select_beam: a column bias does not compose with beam groups or forced columns")
+        name, extra = "ick_decode_select_beam_prefix", (_ref(rules), _ref(diversity), _ref(bias), C.byref(prefix))
+    elif bias is not None:
         if diversity is not None or constraints is not None:
             raise L.IckError("decode_select_beam: a column bias does not compose with beam groups or forced columns")
         name, extra = "ick_decode_select_beam_biased", (_ref(rules), C.byref(bias))
@@ -722,11 +729,14 @@ def decode_select_beam_forced(ctx, beam_state, rules, constraints, pos):
     decode_select_beam(ctx, beam_state, pos, rules, constraints=constraints)
 
 
-def decode_select_sample(ctx, sample_state, pos, rules=None, bias=None):
+def decode_select_sample(ctx, sample_state, pos, rules=None, bias=None, prefix=None):
     """Sampled token of step `pos` for every live row (ick_decode_select_sample); sample_state: lib.SampleState; rules:
     lib.DecodeRules (n-gram / min-length bans: ick_decode_select_sample_rules) or None; bias: lib.DecodeBias (cols, vals:
-    ick_decode_select_sample_biased) or None."""
-    if bias is not None:
+    ick_decode_select_sample_biased) or None; prefix: lib.DecodePrefix (cols: the forced column of every step,
+    ick_decode_select_sample_prefix) or None."""
+    if prefix is not None:
+        name, extra = "ick_decode_select_sample_prefix", (_ref(rules), _ref(bias), C.byref(prefix))
+    elif bias is not None:
         name, extra = "ick_decode_select_sample_biased", (_ref(rules), C.byref(bias))
     else:
         name, extra = ("ick_decode_select_sample", ()) if rules is None else \

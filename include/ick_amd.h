@@ -550,6 +550,38 @@ int ick_decode_select_sample_biased(const ick_decode_ctx* ctx, const ick_sample_
                                     const ick_decode_rules* rules /* NULL: no rules */, const ick_decode_bias* bias,
                                     int32_t pos, void* stream);
 
+/* Caption prefixes: cols[b][t] >= 0 is the column that every live row of caption b takes at step t (a
+ * forced step), numbered as ick_decode_constraints numbers columns; -1 leaves step t free.  The table has max_len
+ * columns whatever the prefixes' lengths and is read at run time, so a captured decode graph replays with new ids and
+ * lengths.  The caller keeps <start>, <end> and <pad> out of it and fills a row's forced steps from step 0 on.
+ *   A forced step: the only candidate of a live row is the forced column.  It wins over the rule bans (no n-gram or
+ *     min-length ban is applied at that step) and over finite biases; the log-softmax normaliser still runs over every
+ *     raw column, so cum (beam) and log_prob (sampling) hold the model's log-probability of the forced token.  The
+ *     token counts as a generated one everywhere: n-gram history, length, the hypothesis' bias sum, the caption buffer,
+ *     the embedding of the next step.  A -inf bias on a forced column is a contradiction the caller refuses: the row
+ *     then has no candidate.
+ *   Beam: a row offers one candidate, so a caption that starts from one live hypothesis (one per group with
+ *     ick_decode_diversity) keeps one through its forced steps; the other slots stay unused (cum = -inf, counted in
+ *     n_done), and the first free step fans out from that one parent as step 0 of a plain search does.  An ended
+ *     hypothesis competes as it is.  The ban pass and the k arg-best rounds of stage 1 do not run at a forced step.
+ *   Sampling: a forced step draws nothing (no top-k, top-p or noise).  The noise is keyed by (seed, caption, sample,
+ *     step, column), so later steps draw what they would have drawn.
+ * At a free step, and with a table that is all -1, the results are the bits of ick_decode_select_beam_rules / _diverse /
+ * _biased and of ick_decode_select_sample_rules / _biased with the same arguments (rules == NULL: of the entries without
+ * rules).  diversity and bias together, a NULL table and unsupported sizes return ICK_EINVAL without a launch. */
+typedef struct {
+    const int32_t* cols;   /* (R / rows_per_sample, max_len) forced column of step t, -1 = free; device memory */
+} ick_decode_prefix;
+int ick_decode_select_beam_prefix(const ick_decode_ctx* ctx, const ick_beam_state* beam,
+                                  const ick_decode_rules* rules /* NULL: no rules */,
+                                  const ick_decode_diversity* diversity /* NULL: one group */,
+                                  const ick_decode_bias* bias /* NULL: no bias */, const ick_decode_prefix* prefix,
+                                  int32_t pos, void* stream);
+int ick_decode_select_sample_prefix(const ick_decode_ctx* ctx, const ick_sample_state* s,
+                                    const ick_decode_rules* rules /* NULL: no rules */,
+                                    const ick_decode_bias* bias /* NULL: no bias */, const ick_decode_prefix* prefix,
+                                    int32_t pos, void* stream);
+
 /* fused token-mean cross entropy over the packed rows of train.py
  * (pack_padded_sequence + CrossEntropyLoss(ignore_index=<pad>), geo-aware/train.py:275-281):
  * rows (b,t) with t < decode_len[b] and target != pad contribute.  Writes loss_sum[0] (sum of
